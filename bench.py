@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""bench.py -- cine frames/s (seg + flow) at 256x256 on N MI355X, with the roofline of the dominant kernel, the
-correlation kernels' HBM rooflines and the CPU baseline timed beside it.
+"""bench.py -- cine frames/s (seg + flow) at 256x256 on N MI355X; with --full also the roofline of the dominant kernel, the
+correlation kernels' HBM rooflines, the nested RAFT measurement and the CPU baseline timed beside it.
 
 A "step" is one pass of the hot path over one batch of synthetic cine slices (BASELINE.json config 4):
   B slices x T=30 frames x 256x256  ->  2-D U-Net segmentation of every frame (4-flip TTA)  +  SegFlowGaussian
@@ -9,13 +9,19 @@ A "step" is one pass of the hot path over one batch of synthetic cine slices (BA
 Inputs and weights are resident in HBM before the timed region; outputs stay in HBM.  frames/s = N*B*T*K / time.
 
 BASELINE config 3 (RAFT: all-pairs correlation pyramid + 12 update iterations per 256x256 frame pair,
-SegFlowGaussian.py:875-969) is measured by the same command as a nested object `config3_raft` of the ONE JSON line
+SegFlowGaussian.py:875-969) is measured by `--full` as a nested object `config3_raft` of the ONE JSON line
 (`--variant raft` makes it the headline of the line instead; `--no-raft` skips it).
 Other variants: `successive` = config 4 with its other dispatch (successive.yaml: OpticalFlowModelSuccessive x 2 in ModelWrap, d_model 512,
 8 heads); `warp` = BASELINE config 2 (VoxelMorph warp of frame pairs); `api` = the file-level API end to end (`predict_from_folder` on
 synthetic patients in a tmpfs folder: NIfTI read + preprocessing, device, NIfTI / NPZ export) with the wall-time split.
 
-Usage (driver contract):  python bench.py --gpus N --steps K --warmup W
+Usage (driver contract):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  * a plain run sets up, runs W untimed steps, times exactly K steps, writes the outputs if asked and prints the JSON line (`value`,
+    `ms_per_step` = wall time of one timed step).  Everything else is measured only with --full: the rooflines (per-launch event pairs
+    recorded during the timed steps on rank 0), the nested `config3_raft`, the CPU baseline and the `--seg-precision f16` parity figures.
+  * --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned as DIR/<name>.npy (float32, float64 where the
+    output is float64; a fixed seeded sample of each large output, see dump_outputs).  Inputs and weights are seeded, so two runs or two builds
+    with the same arguments compute on identical inputs.
   * N > 1 without WORLD_SIZE in the environment: this process starts N ranks of itself (RANK / LOCAL_RANK / WORLD_SIZE /
     MASTER_* set, one per GPU) BEFORE anything touches the GPU, relays rank 0's JSON line and exits non-zero if a rank
     fails.  Under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` it is one of the ranks.
@@ -340,14 +346,15 @@ def conv_roofline(h, dt):
             "launches": n, "avg_launch_us": round(ms * 1e3 / n, 2), "share_of_step_time": round(ms * 1e-3 / dt, 3)}
 
 
-def timed(fn, steps, warmup, h, dev, what):
-    """W untimed steps, then exactly K steps between barrier + synchronize pairs; returns the MAX over ranks"""
+def timed(fn, steps, warmup, h, dev, what, profile=False):
+    """W untimed steps, then exactly K steps between barrier + synchronize pairs; returns the MAX over ranks and the last step's output.
+    profile (--full): per-launch event pairs recorded during the timed steps, the rooflines' source"""
     from cineflow import parallel, _lib
     for _ in range(warmup):
         fn()
         torch.cuda.synchronize()
         log("%s: warm-up step done" % what)
-    if RANK == 0:      # per-launch event pairs (the roofline's source) on rank 0 only: the other ranks of an N-GPU run just do the work
+    if profile and RANK == 0:      # per-launch event pairs on rank 0 only: the other ranks of an N-GPU run just do the work
         _lib.check(h.cf_profile_enable(60000), "cf_profile_enable")
     parallel.barrier()
     torch.cuda.synchronize()
@@ -358,10 +365,27 @@ def timed(fn, steps, warmup, h, dev, what):
     mine = time.perf_counter() - t0
     parallel.barrier()
     dt = time.perf_counter() - t0
-    del out
     dt = parallel.max_over_ranks(dt, dev)
     log("%s: rank %d: %d steps in %.3f s (max over ranks incl. barrier: %.3f s)" % (what, RANK, steps, mine, dt))
-    return dt
+    return dt, out
+
+
+DUMP_MAX_ELEMS = 1 << 21     # per output: 8 MiB as float32, 16 MiB as float64; no variant returns more than four outputs (<= 64 MB in all)
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: the outputs of the last timed step as outdir/<name>.npy, float32 (float64 stays float64).  An output of more than
+    DUMP_MAX_ELEMS elements is written as a fixed sample: the flattened output at DUMP_MAX_ELEMS sorted positions drawn from a generator
+    seeded with 0, so runs with the same arguments write the same positions."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            pos = torch.randint(t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[pos.to(t.device)]
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu()
+        np.save(os.path.join(outdir, name + ".npy"), t.numpy())
+    log("outputs of the last timed step written to %s (%s)" % (outdir, ", ".join(sorted(arrays))))
 
 
 def bench_joint(args, dev, h, world, rank):
@@ -374,16 +398,21 @@ def bench_joint(args, dev, h, world, rank):
     ed_labels = ring_labels(B, S).to(dev)
     log("joint: weights + inputs resident (rank %d/%d, B=%d, T=%d)" % (rank, world, B, T))
     mp = args.seg_precision == "f16"
-    parity = seg_precision_parity(fnet, snet, frames, ed_labels) if (mp and rank == 0) else None
-    dt = timed(lambda: run_step(fnet, snet, frames, ed_labels, mp), args.steps, args.warmup, h, dev, "joint")
-    roofline = conv_roofline(h, dt)
-    corr = [read_profile(h, k) for k in (3, 4, 5)]
-    tot = tuple(sum(c[i] for c in corr) for i in range(3))
-    roofline_corr = hbm_roofline("corr_volume_mfma_kernel<1|2|4> (persistent; 2-D banded f16-MFMA products of hi/lo-split operands, fp32 accumulate)", tot, pmc="corr")
-    if roofline_corr:
-        roofline_corr["per_level"] = {"s%d" % s: {"GB/s": round(c[1] / (c[0] * 1e-3) / 1e9, 1), "avg_launch_us": round(c[0] * 1e3 / c[2], 2)}
-                                      for s, c in zip((1, 2, 4), corr) if c[2]}
-    h.cf_profile_enable(0)
+    parity = seg_precision_parity(fnet, snet, frames, ed_labels) if (mp and args.full and rank == 0) else None
+    dt, out = timed(lambda: run_step(fnet, snet, frames, ed_labels, mp), args.steps, args.warmup, h, dev, "joint", profile=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    del out
+    extra = {}
+    if args.full:
+        corr = [read_profile(h, k) for k in (3, 4, 5)]
+        tot = tuple(sum(c[i] for c in corr) for i in range(3))
+        roofline_corr = hbm_roofline("corr_volume_mfma_kernel<1|2|4> (persistent; 2-D banded f16-MFMA products of hi/lo-split operands, fp32 accumulate)", tot, pmc="corr")
+        if roofline_corr:
+            roofline_corr["per_level"] = {"s%d" % s: {"GB/s": round(c[1] / (c[0] * 1e-3) / 1e9, 1), "avg_launch_us": round(c[0] * 1e3 / c[2], 2)}
+                                          for s, c in zip((1, 2, 4), corr) if c[2]}
+        extra = {"roofline": conv_roofline(h, dt), "roofline_corr": roofline_corr}
+        h.cf_profile_enable(0)
     frames_total = world * B * T * args.steps
     return {
         "metric": "cine frames/sec (seg+flow) at 256x256",
@@ -396,23 +425,34 @@ def bench_joint(args, dev, h, world, rank):
                                % (T, "ModelWrap(OpticalFlowModelSuccessive x 2, successive.yaml: d_model 512, 8 heads)" if args.variant == "successive"
                                   else "SegFlowGaussian(%s.yaml)" % args.variant),
                    "slices_per_step_per_gpu": B, "frames_per_slice": T, "image": "256x256", "sharding": "patients, rank = part_id"},
-        "roofline": roofline, "roofline_corr": roofline_corr,
+        **extra,
         **({"seg_precision": "f16: the segmentation U-Net's convolutions in the one-term product mode (operands rounded to fp16, fp32 accumulate / norms) = "
                              "the reference's mixed_precision=True on that path; the flow network stays f32-class.  NOT the headline configuration "
-                             "(default: --seg-precision f32)", "seg_precision_parity": parity} if mp else {}),
+                             "(default: --seg-precision f32)"} if mp else {}),
+        **({"seg_precision_parity": parity} if mp and args.full else {}),
     }
 
 
-def bench_raft(args, dev, h, world, rank, steps, warmup):
+def bench_raft(args, dev, h, world, rank, steps, warmup, dump_dir=None):
     """BASELINE config 3: RAFT flow, 12 update iterations per 256x256 frame pair (fmaps [B,256,32,32]); a step = B pairs"""
     B, S = args.pairs, 256
     (fnet,) = load_nets(make_nets("raft", with_seg=False), dev, 1234, world, rank)
     frames = synthetic_cine(B, 2, S, 4321 + rank).to(dev)
     log("raft: weights + inputs resident (rank %d/%d, B=%d pairs)" % (rank, world, B))
-    dt = timed(lambda: fnet(frames)["backward_flow"], steps, warmup, h, dev, "raft")
-    roofline = conv_roofline(h, dt)
-    allp, look, up = (read_profile(h, k) for k in (7, 8, 9))
-    h.cf_profile_enable(0)
+    dt, out = timed(lambda: fnet(frames)["backward_flow"], steps, warmup, h, dev, "raft", profile=args.full)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, {"backward_flow": out})
+    del out
+    extra = {}
+    if args.full:
+        allp, look, up = (read_profile(h, k) for k in (7, 8, 9))
+        extra = {
+            "roofline": conv_roofline(h, dt),
+            "roofline_allpairs": hbm_roofline("allpairs_pyramid_kernel (f16-split MFMA product, the 4 pyramid levels from one set of accumulators); 7.67 MB / pair", allp),
+            "roofline_lookup": hbm_roofline("corr_lookup_tiled_kernel (324 channels written once per iteration; gathers are cache traffic)", look),
+            "roofline_upsample": hbm_roofline("convex_upsample_rows_kernel (576-channel mask read once per iteration, eight adjacent outputs per thread)", up),
+        }
+        h.cf_profile_enable(0)
     pairs = world * B * steps
     return {
         "metric": "RAFT frame pairs/sec (12 update iterations) at 256x256", "value": round(pairs / dt, 2), "unit": "frame pairs/s",
@@ -422,10 +462,7 @@ def bench_raft(args, dev, h, world, rank, steps, warmup):
         "config": {"workload": "BASELINE config 3: SegFlowGaussian(raft=True, raft_iters=12) on 256x256 frame pairs: two encoders, all-pairs "
                                "correlation pyramid (fmaps [B,256,32,32], 4 levels), 12 x (lookup r=4 -> motion encoder -> SepConvGRU -> flow / mask "
                                "heads -> convex upsampling), memory-encoder refresh", "pairs_per_step_per_gpu": B, "image": "256x256"},
-        "roofline": roofline,
-        "roofline_allpairs": hbm_roofline("allpairs_pyramid_kernel (f16-split MFMA product, the 4 pyramid levels from one set of accumulators); 7.67 MB / pair", allp),
-        "roofline_lookup": hbm_roofline("corr_lookup_tiled_kernel (324 channels written once per iteration; gathers are cache traffic)", look),
-        "roofline_upsample": hbm_roofline("convex_upsample_rows_kernel (576-channel mask read once per iteration, eight adjacent outputs per thread)", up),
+        **extra,
     }
 
 
@@ -455,14 +492,20 @@ def bench_warp(args, dev, h, world, rank, steps, warmup):
     def step():
         return ops.warp_bilinear(flow, img), ops.warp_labels(fl5, lab), ops.jacobian_det(flow)
 
-    dt = timed(step, steps, warmup, h, dev, "warp")
-    recs = [read_profile(h, k) for k in (11, 12, 13)]
-    h.cf_profile_enable(0)
-    names = ["warp_bilinear_2d_v4_kernel (flow 8 B + image 4 B read, 4 B written per pixel)",
-             "warp_labels_2d_v4_kernel (flow 8 B + label 1 B read, 1 B written per pixel)",
-             "jacobian_det_2d_v4_kernel (displacement 8 B read, float64 determinant 8 B written per pixel)"]
-    roofs = [hbm_roofline(n, r) for n, r in zip(names, recs)]
-    dom = max(range(3), key=lambda i: recs[i][0])
+    dt, out = timed(step, steps, warmup, h, dev, "warp", profile=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("warped_image", "registered", "jacobian_det"), out)))
+    del out
+    extra = {}
+    if args.full:
+        recs = [read_profile(h, k) for k in (11, 12, 13)]
+        h.cf_profile_enable(0)
+        names = ["warp_bilinear_2d_v4_kernel (flow 8 B + image 4 B read, 4 B written per pixel)",
+                 "warp_labels_2d_v4_kernel (flow 8 B + label 1 B read, 1 B written per pixel)",
+                 "jacobian_det_2d_v4_kernel (displacement 8 B read, float64 determinant 8 B written per pixel)"]
+        roofs = [hbm_roofline(n, r) for n, r in zip(names, recs)]
+        dom = max(range(3), key=lambda i: recs[i][0])
+        extra = {"roofline": roofs[dom], "roofline_other": [r for i, r in enumerate(roofs) if i != dom]}
     pairs = world * B * steps
     return {
         "metric": "VoxelMorph warp frame pairs/sec at 256x256", "value": round(pairs / dt, 1), "unit": "frame pairs/s", "n_gpus": world,
@@ -471,7 +514,7 @@ def bench_warp(args, dev, h, world, rank, steps, warmup):
         "config": {"workload": "BASELINE config 2: per 256x256 frame pair, SpatialTransformer warp of the moving image, warp_linear label "
                                "propagation (4 classes) and the Jacobian determinant of the displacement", "pairs_per_step_per_gpu": B,
                    "image": "256x256"},
-        "roofline": roofs[dom], "roofline_other": [r for i, r in enumerate(roofs) if i != dom],
+        **extra,
     }
 
 
@@ -607,7 +650,15 @@ def main():
                          "(the reference's mixed_precision=True on the segmentation path), reported as a second, labelled line with its parity figures")
     ap.add_argument("--cpu-frames", type=int, default=30, help="frames of the one-slice CPU baseline sample (30 = one whole cine slice, ~15 s on 16 cores)")
     ap.add_argument("--dry-run", action="store_true", help="exercise the multi-rank path on gloo / CPU tensors without GPU work")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: rooflines, the nested config3_raft, the CPU baseline, --seg-precision f16 parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64; a fixed seeded sample of large outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.variant == "api":
+        ap.error("--dump-outputs: the api variant's outputs are NIfTI / NPZ files, not arrays of the timed call")
     if args.pairs is None:
         args.pairs = 960 if args.variant == "warp" else 128      # RAFT: 64 / 128 / 256 pairs per step measured 995 / 1033 / 1036 pairs/s
     if args.slices is None:
@@ -638,7 +689,7 @@ def main():
     _ops.set_conv_mode(args.conv_mode)
 
     if args.variant == "raft":
-        line = bench_raft(args, dev, h, world, rank, args.steps, args.warmup)
+        line = bench_raft(args, dev, h, world, rank, args.steps, args.warmup, args.dump_outputs)
     elif args.variant == "warp":
         line = bench_warp(args, dev, h, world, rank, args.steps, args.warmup)
     elif args.variant == "api":
@@ -646,11 +697,11 @@ def main():
         args.no_cpu_baseline = True       # the CPU path of this metric is the default variant's cpu_baseline (the oracle has no file-level API)
     else:
         line = bench_joint(args, dev, h, world, rank)
-        if not args.no_raft and args.variant != "successive":
+        if args.full and not args.no_raft and args.variant != "successive":
             torch.cuda.empty_cache()
             line["config3_raft"] = bench_raft(args, dev, h, world, rank, max(1, args.steps), 1)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("timing the CPU baseline (oracle, %d threads) ..." % host_threads())
             line["cpu_baseline"] = cpu_baseline(args.variant, 1234, args.cpu_frames)
             log("CPU baseline done")

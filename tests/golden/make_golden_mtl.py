@@ -40,6 +40,17 @@ def pin(name, ref, ora, tol=0.0):
     assert d <= tol, name
 
 
+def run64(module, *xs):
+    """the same module (already filled) on the same inputs in float64: vectors that do not depend on the host CPU's float32 summation order"""
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    try:
+        with torch.no_grad():
+            return module.double()(*(x.double() for x in xs))
+    finally:
+        torch.set_default_dtype(prev)
+
+
 def build_reference(image_size, window_size, num_classes, in_dims, out_dims, heads, bottleneck_heads):
     from nnunet.network_architecture.MTL_model import MTLmodel
     from nnunet.lib.utils import ConvBlocks2DGroup
@@ -67,7 +78,9 @@ def main():
     with torch.no_grad():
         r, o = ref(x, skip), ora(x, skip)
     pin("SwinFilterBlock (window 8, shifted second block)", r, o, 1e-6)
-    np.savez_compressed(os.path.join(HERE, "mtl_filter.npz"), x=x.numpy(), skip=skip.numpy(), out=r.numpy())
+    r64 = run64(ref, x, skip)
+    pin("SwinFilterBlock (window 8, shifted second block), float64", r64, run64(ora, x, skip), 1e-12)
+    np.savez_compressed(os.path.join(HERE, "mtl_filter.npz"), x=x.numpy(), skip=skip.numpy(), out=r.numpy(), out64=r64.numpy())
     # ---- window 7 on a 28x28 map (the ACDC setting: image 224, window 7)
     ref = fill_module_(SwinFilterBlock(in_dim=8, out_dim=8, input_resolution=(28, 28), num_heads=2, norm=torch.nn.BatchNorm2d, device="cpu",
                                        rpe_mode="bias", rpe_contextual_tensor="qkv", window_size=7, depth=2, add_absolute_pos=False, init_weights=None), 62).eval()
@@ -88,7 +101,9 @@ def main():
         with torch.no_grad():
             r, o = ref(x)["pred"], ora(x)["pred"]
         pin("MTLmodel %d classes (adversarial_acdc.yaml, reduced)" % ncls, r, o, 2e-6)
-        np.savez_compressed(os.path.join(HERE, "mtl_%s.npz" % tag), x=x.numpy(), pred=r.numpy())
+        r64 = run64(ref, x)["pred"]
+        pin("MTLmodel %d classes (adversarial_acdc.yaml, reduced), float64" % ncls, r64, run64(ora, x)["pred"], 1e-12)
+        np.savez_compressed(os.path.join(HERE, "mtl_%s.npz" % tag), x=x.numpy(), pred=r.numpy(), pred64=r64.numpy())
     with open(os.path.join(HERE, "PIN_REPORT_mtl.txt"), "w") as f:
         f.write("oracle/mtl.py vs the reference (tests/golden/make_golden_mtl.py)\n")
         for name, d, tol in REPORT:

@@ -128,6 +128,29 @@ def test_bench_successive_and_api_variants_dry_run():
         assert d["config"]["variant"] == variant and d["weights_identical_on_all_ranks"] is True
 
 
+def test_bench_dump_outputs_writes_a_fixed_sample(tmp_path):
+    """--dump-outputs: small outputs keep their shape, larger ones become the same seeded sample on every call; uint8 -> float32,
+    float64 stays float64; the options are checked before anything runs"""
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    big = torch.arange(bench.DUMP_MAX_ELEMS + 1000, dtype=torch.float32)
+    outs = {"big": big, "labels": torch.ones(3, 4, dtype=torch.uint8), "jac": torch.zeros(5, dtype=torch.float64)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs)
+    a = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in outs}
+    b = np.load(str(tmp_path / "b" / "big.npy"))
+    assert a["big"].shape == (bench.DUMP_MAX_ELEMS,) and a["big"].dtype == np.float32 and np.array_equal(a["big"], b)
+    assert np.all(np.diff(a["big"]) >= 0) and a["big"].max() < big.numel()          # sorted positions of the flattened output
+    assert a["labels"].shape == (3, 4) and a["labels"].dtype == np.float32 and a["jac"].dtype == np.float64
+    assert sum(os.path.getsize(str(tmp_path / "a" / (k + ".npy"))) for k in outs) < 64e6
+    for args in (("--steps", "0"), ("--variant", "api", "--dump-outputs", str(tmp_path / "c"))):
+        r = _run_bench(*args)
+        assert r.returncode == 2 and not r.stdout.strip(), r.stderr[-2000:]
+
+
 def _api_worker(rank, world, port, q, folders):
     """cineflow.predict.load_model_and_checkpoint_files in a 2-rank job: rank 1's model folder holds plans.json ONLY"""
     import sys

@@ -15,19 +15,31 @@ def _gold(name):
     return np.load(os.path.join(GOLD, name + ".npz"))
 
 
+def _run64(module, *xs):
+    """float64 forward (make_golden_mtl.run64): float32 results depend on the host CPU's summation order (oneDNN kernels, thread count)
+    by a few 1e-6 on this network, float64 ones do not"""
+    prev = torch.get_default_dtype()
+    torch.set_default_dtype(torch.float64)
+    try:
+        with torch.no_grad():
+            return module.double()(*(torch.from_numpy(x).double() for x in xs))
+    finally:
+        torch.set_default_dtype(prev)
+
+
 def test_oracle_mtl_matches_reference_outputs():
+    """the oracle against the reference's own float64 outputs on the same seeded weights and inputs"""
     from oracle import mtl as OMTL
     from cineflow.weights import fill_module_
     for tag, ncls, seed in (("crop", 2, 63), ("seg", 4, 64)):
         g = _gold("mtl_" + tag)
         m = fill_module_(OMTL.MTLmodel(64, 8, ncls, **RED), seed).eval()
-        with torch.no_grad():
-            out = m(torch.from_numpy(g["x"]))["pred"]
-        assert float((out - torch.from_numpy(g["pred"])).abs().max()) <= 1e-6
+        out = _run64(m, g["x"])["pred"]
+        assert out.dtype == torch.float64 and float((out - torch.from_numpy(g["pred64"])).abs().max()) <= 1e-6
     g = _gold("mtl_filter")
     f = fill_module_(OMTL.SwinFilterBlock(16, 16, (32, 32), 2, 8), 61).eval()
-    with torch.no_grad():
-        assert float((f(torch.from_numpy(g["x"]), torch.from_numpy(g["skip"])) - torch.from_numpy(g["out"])).abs().max()) <= 1e-6
+    out = _run64(f, g["x"], g["skip"])
+    assert out.dtype == torch.float64 and float((out - torch.from_numpy(g["out64"])).abs().max()) <= 1e-6
 
 
 def test_mtl_state_dict_layout_matches_oracle():
