@@ -8,11 +8,13 @@ layout the downstream scripts read (`<out>/<patient>/{Segmentation,Registered}/<
 Differences that are deliberate and documented in DESIGN.md:
   * every patient folder is processed (the reference `return`s from inside its patient loop, predict.py:743);
   * the model folder holds `plans.json` + `fold_X/<chk>.model` written by `save_model_folder` below (a plain tensor
-    dict, loaded with `torch.load(weights_only=True)`); the reference's `plans.pkl` / `*.model.pkl` are pickles of
-    trainer objects whose classes cannot be imported here, and nothing on this path un-pickles;
-  * preprocessing is the z-score of the volume at native spacing (crop-to-nonzero and resampling are the "next" rows
-    of SURVEY.md section 8f), so the exporter needs no resampling either; the heart centroid of `Processor` comes from
-    the image centre because the reference's 2-class cropping network is outside this path (SURVEY row a20);
+    dict, loaded with `torch.load(weights_only=True)`), one folder for both networks; the folders the reference's trainers
+    write (`plans.pkl`, `fold_X/<chk>.model` + `.model.pkl`, the flow trainer's `config.yaml` + `<task>/fold_X/`) are turned
+    into one by `cineflow.reference_models` (restricted unpickler, tensor names and shapes checked), never read here;
+  * preprocessing is the reference's test-time chain driven by the plan entries (crop to non-zero, resampling to the
+    stage spacing, the plans' normalisation schemes: `CineTrainer.preprocess_patient`, cineflow.preprocessing) and the
+    exporter resamples back; the heart centroid of `Processor` comes from the cropping network of plans['cropping_net']
+    when the folder has one (the reference's MTLmodel cropper), else from the patch centre;
   * when no ED label map is supplied the ED segmentation predicted by the U-Net is the one propagated;
   * `predict_from_folder` loads the model once and fills the device batch ACROSS patients: the cropped slices of as many patients as fit
     `MAX_SLICES_PER_LAUNCH` (64) go through the networks as one batch (`CineTrainer.predict_patients_flow`), the next group's files are

@@ -1,0 +1,324 @@
+"""Import of the model folders the reference's trainers write, into the `plans.json` + `fold_X/<chk>.model` format of cineflow.predict.
+
+The reference trains its two networks separately and writes
+
+    <seg_folder>/plans.pkl                              nnU-Net 2-D plans (predict.py:691-694)
+    <seg_folder>/fold_X/<chk>.model                     torch.save({epoch, state_dict, optimizer_state_dict, lr_scheduler_state_dict,
+                                                        plot_stuff, best_stuff[, amp_grad_scaler]})  (network_trainer.py:305-335)
+    <seg_folder>/fold_X/<chk>.model.pkl                 {init, name, class (a str), plans}  (nnUNetTrainer.py:4302-4310)
+    <flow_weights>/config.yaml                          the flow network's YAML (run_training.py:191)
+    <flow_weights>/<task>/fold_X/<chk>.model[.pkl]      the flow trainer's checkpoint (run_training.py:283)
+
+`import_reference_model_folder` pairs one segmentation folder with one flow folder and writes a folder that `predict_from_folder(model=...)`
+and `python -m cineflow.predict -m ...` take unchanged (save_model_folder).  Nothing here imports or calls a global named by a file:
+`.pkl` files go through a restricted unpickler (cineflow.safe_pickle, widened only by plain-data globals), `.model` files through
+`torch.load(weights_only=True)` with numpy's scalar / array / dtype reconstructors admitted (the losses in `plot_stuff` / `best_stuff` are
+`np.mean(...)` results, which plain `weights_only=True` refuses).  Every tensor is checked against the networks the new plans build before
+anything is written.  Values the build cannot honour raise `NotImplementedError` naming the key, as cineflow.config does.
+
+Command line:  python -m cineflow.reference_models -s SEG -w FLOW -o OUT [--crop_weights F --crop_config Y] [-f FOLDS] [-chk NAME]
+"""
+import argparse
+import os
+import re
+import shutil
+
+import numpy as np
+import torch
+
+from .safe_pickle import PlainUnpickler, load_plain_pickle
+
+join = os.path.join
+
+_DROPPED_CHECKPOINT_KEYS = ("optimizer_state_dict", "lr_scheduler_state_dict", "amp_grad_scaler")
+# buffers the networks rebuild from their constructor arguments and never load: SpatialTransformer grids (predict._broadcast_params),
+# BatchNorm step counters, Swin relative-position indices and shift masks (the MTLmodel cropper's state_dict holds all three)
+_DERIVED_BUFFERS = ("grid", "num_batches_tracked", "relative_position_index", "attn_mask")
+
+
+# ------------------------------------------------------------------------------------------------ safe readers
+class ReferencePickleUnpickler(PlainUnpickler):
+    """PlainUnpickler plus the plain-data globals nnU-Net's `plans.pkl` / `<chk>.model.pkl` need: `set` / `frozenset` (a GLOBAL under
+    pickle protocols <= 3, `__builtin__` under protocol 2) and numpy's dtype classes."""
+
+    _ALLOWED = PlainUnpickler._ALLOWED | {
+        ("builtins", "set"), ("builtins", "frozenset"), ("__builtin__", "set"), ("__builtin__", "frozenset"),
+    } | {("numpy.dtypes", type(np.dtype(c)).__name__) for c in "?bBhHiIlLqQefdg"}
+    _WHAT = "a reference pickle"
+
+
+def load_reference_pickle(path):
+    """`plans.pkl` / `<chk>.model.pkl` -> plain Python / numpy values; any other global raises pickle.UnpicklingError."""
+    return load_plain_pickle(path, ReferencePickleUnpickler)
+
+
+def _numpy_safe_globals():
+    """numpy's scalar / array reconstructors and the dtype classes torch's weights-only unpickler must be told about"""
+    try:
+        from numpy._core import multiarray as ma
+    except ImportError:                                                       # numpy < 2
+        from numpy.core import multiarray as ma
+    dtypes = sorted({type(np.dtype(c)) for c in "?bBhHiIlLqQefdg"}, key=lambda t: t.__name__)
+    return [ma.scalar, ma._reconstruct, np.ndarray, np.dtype] + [t for t in dtypes if t is not np.dtype]
+
+
+def strip_module_prefix(state_dict, expected=None):
+    """network_trainer.py:418-440: a key that the network does not have and that starts with `module.` (nn.DataParallel) loses the prefix.
+    Without `expected` every `module.` prefix is dropped."""
+    out = {}
+    for k, v in state_dict.items():
+        if k.startswith("module.") and (expected is None or k not in expected):
+            k = k[len("module."):]
+        out[k] = v
+    return out
+
+
+def load_reference_checkpoint(path, expected=None):
+    """`<chk>.model` of a reference trainer -> the checkpoint dict without its optimizer / scheduler / grad-scaler entries, `state_dict`
+    with the `module.` prefix stripped (`expected`: the network's key names, for the reference's exact rule).  torch.load runs with
+    weights_only=True; numpy's scalar / array / dtype reconstructors are the only globals added."""
+    with torch.serialization.safe_globals(_numpy_safe_globals()):
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(ck, dict) or "state_dict" not in ck:
+        raise KeyError("%s holds no 'state_dict' entry (not a checkpoint written by NetworkTrainer.save_checkpoint)" % path)
+    out = {k: v for k, v in ck.items() if k not in _DROPPED_CHECKPOINT_KEYS}
+    out["state_dict"] = strip_module_prefix(ck["state_dict"], expected)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ plans
+def _plain(obj):
+    """numpy values / tuples / sets / non-string keys -> what json.dump writes"""
+    if isinstance(obj, dict):
+        return {str(_plain(k)) if not isinstance(k, str) else k: _plain(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return [_plain(v) for v in obj]
+    if isinstance(obj, (set, frozenset)):
+        return sorted(_plain(v) for v in obj)
+    if isinstance(obj, np.ndarray):
+        return obj.tolist()
+    if isinstance(obj, np.generic):
+        return obj.item()
+    return obj
+
+
+def _refuse(key, value, built):
+    raise NotImplementedError("plans_from_reference: %s = %r is outside what the build implements (built: %s)" % (key, value, built))
+
+
+def plans_from_reference(plans, stage=None):
+    """The reference's 2-D nnU-Net plans (experiment_planner_baseline_2DUNet.py:148-160) -> the plans dict CineTrainer reads.
+
+    The stage is chosen as nnUNetTrainer.py:478-482 does (None: the plans must have exactly one); the segmentation network is the
+    Generic_UNet nnUNetTrainerV2.py:147-169 builds from it (num_classes + 1 outputs, one pooling stage per pool_op_kernel_sizes entry,
+    3x3 convolutions, conv_per_stage 2).  crop_size / image_size / flow_net are the flow trainer's and are added by the importer."""
+    stages = plans["plans_per_stage"]
+    if stage is None:
+        if len(stages) != 1:
+            raise ValueError("plans_from_reference: the plans have %d stages %s; pass stage= (nnUNetTrainer.py:479-481)" % (len(stages), sorted(stages)))
+        stage = list(stages.keys())[0]
+    if stage not in stages:
+        raise KeyError("plans_from_reference: stage %r is not in plans_per_stage %s" % (stage, sorted(stages)))
+    sp = stages[stage]
+    patch = [int(v) for v in np.asarray(sp["patch_size"]).ravel()]
+    if len(patch) != 2:
+        _refuse("plans_per_stage[%r]['patch_size']" % stage, patch, "2-D stages")
+    if "pool_op_kernel_sizes" in sp:
+        pool = [[int(v) for v in p_] for p_ in sp["pool_op_kernel_sizes"]]
+    else:                                                                      # nnUNetTrainer.py:489-501: old plans
+        per_axis = [int(v) for v in sp["num_pool_per_axis"]]
+        pool = [[2 if max(per_axis) - j <= i else 1 for j in per_axis] for i in range(max(per_axis))]
+    if any(len(p_) != 2 or tuple(p_) not in ((2, 2), (2, 1), (1, 2)) for p_ in pool):
+        _refuse("plans_per_stage[%r]['pool_op_kernel_sizes']" % stage, pool, "(2, 2), (2, 1), (1, 2)")
+    conv = sp.get("conv_kernel_sizes")
+    conv = [[int(v) for v in k] for k in ([[3, 3]] * (len(pool) + 1) if conv is None else conv)]
+    if any(k != [3, 3] for k in conv):
+        _refuse("plans_per_stage[%r]['conv_kernel_sizes']" % stage, conv, "3x3 everywhere")
+    conv_per_stage = plans.get("conv_per_stage", 2)
+    if conv_per_stage != 2:
+        _refuse("conv_per_stage", conv_per_stage, "2")
+    dp = plans.get("dataset_properties") or {}
+    tf, tb = plans.get("transpose_forward"), plans.get("transpose_backward")
+    if tf is None or tb is None:                                               # nnUNetTrainer.py:526-531
+        tf, tb = [0, 1, 2], [0, 1, 2]
+    return _plain({
+        "num_modalities": int(plans["num_modalities"]),
+        "num_classes": int(plans["num_classes"]) + 1,                            # nnUNetTrainer.py:520: background is not in num_classes
+        "patch_size": patch,
+        "mirror_axes": [0, 1],
+        "seg_net": {"base_num_features": int(plans["base_num_features"]), "num_pool": len(pool), "pool_op_kernel_sizes": pool},
+        "transpose_forward": [int(v) for v in tf], "transpose_backward": [int(v) for v in tb],
+        "normalization_schemes": plans.get("normalization_schemes"),
+        "use_mask_for_norm": plans.get("use_mask_for_norm"),
+        "dataset_properties": {"intensityproperties": dp.get("intensityproperties")},
+        "preprocessor_name": plans.get("preprocessor_name"),
+        "plans_per_stage": stages,
+        "stage": stage,
+    })
+
+
+def crop_and_image_size(task, successive=False):
+    """(crop_size, image_size, window_size) of the flow trainers from the task folder name, substring rule for substring rule:
+    SegFlowGaussian.py:117-135 (31 / 35 -> 128, 224, 7; 39 -> 192, 224, 7; else 192, 384, 8) and nnMTLTrainerV2FlowSuccessive.py:117-126
+    for the successive family (which has no task-39 branch)."""
+    if any(x in task for x in ("31", "35")):
+        return 128, 224, 7
+    if "39" in task and not successive:
+        return 192, 224, 7
+    return 192, 384, 8
+
+
+# ------------------------------------------------------------------------------------------------ folders
+def _checkpoint_folds(folder, checkpoint_name):
+    """{fold number: fold directory} of the fold_<n> sub-folders that hold <checkpoint_name>.model"""
+    out = {}
+    for d in sorted(os.listdir(folder)):
+        m = re.fullmatch(r"fold_(\d+)", d)
+        if m and os.path.isfile(join(folder, d, checkpoint_name + ".model")):
+            out[int(m.group(1))] = join(folder, d)
+    return out
+
+
+def _has_fold_dirs(folder):
+    return os.path.isdir(folder) and any(re.fullmatch(r"fold_\d+", d) for d in os.listdir(folder))
+
+
+def resolve_flow_folder(flow_weight_folder):
+    """The `-w` folder of run_training.py (config.yaml + one <task>/fold_X/ tree) or that <task> folder itself -> (config path, task dir)."""
+    w = os.path.abspath(flow_weight_folder)
+    if os.path.isfile(join(w, "config.yaml")) and not _has_fold_dirs(w):
+        tasks = [d for d in sorted(os.listdir(w)) if _has_fold_dirs(join(w, d))]
+        if len(tasks) != 1:
+            raise ValueError("%s holds config.yaml and %d task folders with fold_X/ inside (%s); pass the task folder itself"
+                             % (w, len(tasks), ", ".join(tasks) or "none"))
+        return join(w, "config.yaml"), join(w, tasks[0])
+    if _has_fold_dirs(w) and os.path.isfile(join(os.path.dirname(w), "config.yaml")):
+        return join(os.path.dirname(w), "config.yaml"), w
+    raise FileNotFoundError("%s is neither a flow weight folder (config.yaml + <task>/fold_X/) nor a <task> folder under one" % w)
+
+
+def _first(names, n=5):
+    names = sorted(names)
+    return ", ".join(names[:n]) + (" ... (%d in all)" % len(names) if len(names) > n else "")
+
+
+def check_state_dict(sd, shapes, what):
+    """Every tensor the network needs, no surplus, every shape equal; derived buffers (`*.grid`, `num_batches_tracked`, Swin
+    `relative_position_index` / `attn_mask`) are ignored on both sides.  Missing -> KeyError, surplus or mis-shaped -> ValueError."""
+    need = {k: tuple(v) for k, v in shapes.items() if not k.endswith(_DERIVED_BUFFERS)}
+    have = {k: tuple(v.shape) for k, v in sd.items() if not k.endswith(_DERIVED_BUFFERS)}
+    missing = set(need) - set(have)
+    if missing:
+        raise KeyError("%s: checkpoint lacks %d tensors the network needs: %s" % (what, len(missing), _first(missing)))
+    surplus = set(have) - set(need)
+    if surplus:
+        raise ValueError("%s: checkpoint holds %d tensors the network does not have: %s" % (what, len(surplus), _first(surplus)))
+    bad = ["%s %s (network %s)" % (k, have[k], need[k]) for k in need if have[k] != need[k]]
+    if bad:
+        raise ValueError("%s: %d tensors have another shape: %s" % (what, len(bad), _first(bad)))
+
+
+def _trainer_info(fold_dir, checkpoint_name):
+    p = join(fold_dir, checkpoint_name + ".model.pkl")
+    return load_reference_pickle(p) if os.path.isfile(p) else None
+
+
+def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, crop_weights=None, crop_config=None, folds=None,
+                                  checkpoint_name="model_final_checkpoint", crop_size=None, image_size=None, window_size=None):
+    """seg_folder: output folder of a 2-D nnU-Net trainer (plans.pkl, fold_X/); flow_weight_folder: the `-w` folder of run_training.py
+    (config.yaml, <task>/fold_X/) or its <task> folder; crop_weights / crop_config: optionally the MTLmodel cropper's checkpoint and its
+    YAML (nnMTLTrainerV2FlowSuccessive.py:482-484, adversarial_acdc.yaml).  Writes `out_folder` in the plans.json format (save_model_folder):
+    plans.json, config.yaml (+ cropping_config.yaml), one fold_X per fold, postprocessing.json when the seg folder has one.
+
+    folds: None takes every fold, and the two folders must hold the same ones; a list selects folds that both must hold.  crop_size /
+    image_size / window_size override the task-number rule (crop_and_image_size) applied to the flow trainer's dataset directory
+    (`.model.pkl` init[3]; the task folder's name when that file is absent).  The flow trainer predicts on [image_size, image_size]
+    patches (SegFlowGaussian.py:366), which become plans['patch_size']; the segmentation stage's own patch stays in plans_per_stage.
+    Returns the plans written."""
+    from . import config as C
+    from .predict import CineTrainer, save_model_folder
+    if not os.path.isfile(join(seg_folder, "plans.pkl")):
+        raise FileNotFoundError("%s has no plans.pkl (not the output folder of an nnU-Net trainer)" % seg_folder)
+    config_path, task_dir = resolve_flow_folder(flow_weight_folder)
+    seg_folds, flow_folds = _checkpoint_folds(seg_folder, checkpoint_name), _checkpoint_folds(task_dir, checkpoint_name)
+    if folds is None or folds == "None":
+        if set(seg_folds) != set(flow_folds) or not seg_folds:
+            raise ValueError("the two trained folders hold different folds of %s.model: segmentation %s, flow %s (pass folds=)"
+                             % (checkpoint_name, sorted(seg_folds), sorted(flow_folds)))
+        folds = sorted(seg_folds)
+    folds = [int(f) for f in ([folds] if isinstance(folds, (int, str)) else folds)]
+    for f in folds:
+        for name, have, where in (("segmentation", seg_folds, seg_folder), ("flow", flow_folds, task_dir)):
+            if f not in have:
+                raise FileNotFoundError("fold_%d/%s.model is missing from the %s folder %s" % (f, checkpoint_name, name, where))
+
+    seg_info = _trainer_info(seg_folds[folds[0]], checkpoint_name)
+    flow_info = _trainer_info(flow_folds[folds[0]], checkpoint_name)
+    stage = seg_info["init"][5] if seg_info and len(seg_info.get("init") or ()) > 5 else None
+    plans = plans_from_reference(load_reference_pickle(join(seg_folder, "plans.pkl")), stage)
+    flow_cfg = C.with_defaults(C.read_config_video(config_path), prediction=False)
+    successive = "no_error" in flow_cfg and "d_model" not in flow_cfg          # config.build_flow_net's dispatch
+    task = os.path.basename(str(flow_info["init"][3]).rstrip("/\\")) if flow_info and len(flow_info.get("init") or ()) > 3 else os.path.basename(task_dir)
+    cs, im, win = crop_and_image_size(task, successive)
+    cs, im, win = crop_size or cs, image_size or im, window_size or win
+    plans.update(crop_size=int(cs), image_size=int(im), patch_size=[int(im), int(im)])
+    if (crop_weights is None) != (crop_config is None):
+        raise ValueError("crop_weights and crop_config go together (the MTLmodel cropper's checkpoint and its YAML)")
+    crop_sd = None
+    if crop_config is not None:
+        plans["cropping_net"] = {"type": "mtl", "config": C.read_config(crop_config, False, False), "window_size": int(win)}
+    plans["flow_net"] = {"config": flow_cfg}
+    trainer = CineTrainer(plans, torch.device("cpu"))                           # builds the three networks' key / shape lists, no device work
+
+    # every tensor of every fold is checked before anything is written
+    if crop_weights is not None:
+        shapes = trainer.crop_net.state_shapes()
+        crop_sd = load_reference_checkpoint(crop_weights, shapes)["state_dict"]
+        check_state_dict(crop_sd, shapes, "cropping network %s" % crop_weights)
+        crop_sd = {k: v for k, v in crop_sd.items() if not k.endswith(_DERIVED_BUFFERS)}
+    params = {}
+    for f in folds:
+        parts = []
+        for net, fold_dir, what in ((trainer.seg_net, seg_folds[f], "segmentation"), (trainer.flow_net, flow_folds[f], "flow")):
+            path = join(fold_dir, checkpoint_name + ".model")
+            shapes = net.state_shapes()
+            sd = load_reference_checkpoint(path, shapes)["state_dict"]
+            check_state_dict(sd, shapes, "%s network %s" % (what, path))
+            parts.append({k: v for k, v in sd.items() if not k.endswith(_DERIVED_BUFFERS)})
+        params[f] = parts
+
+    os.makedirs(out_folder, exist_ok=True)
+    shutil.copy(config_path, join(out_folder, "config.yaml"))
+    plans["flow_net"] = {"config": "config.yaml"}
+    if crop_config is not None:
+        shutil.copy(crop_config, join(out_folder, "cropping_config.yaml"))
+        plans["cropping_net"]["config"] = "cropping_config.yaml"
+    for f in folds:
+        save_model_folder(out_folder, trainer.seg_net, trainer.flow_net, plans, fold=f, checkpoint_name=checkpoint_name,
+                          seg_sd=params[f][0], flow_sd=params[f][1], crop_sd=crop_sd)
+    if os.path.isfile(join(seg_folder, "postprocessing.json")):
+        shutil.copy(join(seg_folder, "postprocessing.json"), join(out_folder, "postprocessing.json"))
+    return plans
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description="Write a cineflow model folder (plans.json + fold_X/<chk>.model) from the folders the "
+                                                 "reference's trainers wrote; predict_from_folder / cineflow.predict -m take it unchanged.")
+    parser.add_argument("-s", "--seg_folder", required=True, help="output folder of the 2-D nnU-Net trainer (plans.pkl, fold_X/)")
+    parser.add_argument("-w", "--flow_weight_folder", required=True, help="the -w folder of run_training.py (config.yaml, <task>/fold_X/) or its <task> folder")
+    parser.add_argument("-o", "--output_folder", required=True)
+    parser.add_argument("--crop_weights", default=None, help="the MTLmodel cropper's model_final_checkpoint.model")
+    parser.add_argument("--crop_config", default=None, help="the cropper's YAML (adversarial_acdc.yaml)")
+    parser.add_argument("-f", "--folds", nargs="+", default="None")
+    parser.add_argument("-chk", default="model_final_checkpoint", required=False)
+    parser.add_argument("--crop_size", type=int, default=None)
+    parser.add_argument("--image_size", type=int, default=None)
+    parser.add_argument("--window_size", type=int, default=None)
+    a = parser.parse_args(argv)
+    plans = import_reference_model_folder(a.seg_folder, a.flow_weight_folder, a.output_folder, a.crop_weights, a.crop_config,
+                                          None if a.folds == "None" else a.folds, a.chk, a.crop_size, a.image_size, a.window_size)
+    print("wrote %s (crop %d, image %d, %d classes)" % (a.output_folder, plans["crop_size"], plans["image_size"], plans["num_classes"]))
+
+
+if __name__ == "__main__":
+    main()

@@ -39,34 +39,12 @@ from . import ops
 from .inference import Processor
 from .nifti import read_nifti, write_nifti
 from .predict import load_remove_save, save_segmentation_nifti_from_softmax, subfiles
+from .safe_pickle import PlainUnpickler as _PlainUnpickler, load_plain_pickle  # noqa: F401  (shared with cineflow.reference_models)
 
 join = os.path.join
 
 
 # ------------------------------------------------------------------------------------------------ small pieces
-class _PlainUnpickler(pickle.Unpickler):
-    """pickle.Unpickler that can only rebuild plain containers and numpy values (what nnU-Net property dicts hold).  `pkl_path` is a free
-    CLI argument and its natural input is a tree another pipeline wrote, so no global outside this list is ever resolved."""
-
-    _ALLOWED = {
-        ("collections", "OrderedDict"),
-        ("numpy", "ndarray"), ("numpy", "dtype"),
-        ("numpy.core.multiarray", "_reconstruct"), ("numpy._core.multiarray", "_reconstruct"),
-        ("numpy.core.multiarray", "scalar"), ("numpy._core.multiarray", "scalar"),
-        ("numpy.core.numeric", "_frombuffer"), ("numpy._core.numeric", "_frombuffer"),
-    }
-
-    def find_class(self, module, name):
-        if (module, name) in self._ALLOWED:
-            return super().find_class(module, name)
-        raise pickle.UnpicklingError("refusing to load global %s.%s from a properties .pkl (plain containers and numpy values only)" % (module, name))
-
-
-def load_plain_pickle(path):
-    with open(path, "rb") as f:
-        return _PlainUnpickler(f).load()
-
-
 def delete_if_exist(folder_name):
     """voxelmorph_saver_Lib.py:279-282."""
     if os.path.isdir(folder_name):
