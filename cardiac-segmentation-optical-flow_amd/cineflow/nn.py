@@ -118,7 +118,7 @@ class Conv2d(Module):
     def prenorm_ok(self, x):
         """can this convolution take the RAW convolution output x with its normalisation + activation deferred (applied while the tile is
         staged)?  3x3 / stride 1 only; on the Winograd kernel where that takes the shape, else on conv_f16s' vector-staging shapes"""
-        if not (self.ks == (3, 3) and self.stride == 1 and self.sub is None and getattr(self, "_f16s", False) and ops.PRENORM and x.data_ptr() % 16 == 0):
+        if not (self.ks == (3, 3) and self.stride == 1 and self.sub is None and getattr(self, "_f16s", False) and x.data_ptr() % 16 == 0):
             return False
         B, C, H, W = x.shape
         return (self._wino and ops.wino_ok(B, C, 0, H, W, self.cout, prenorm=True)) or ops.prenorm_ok(x, self.cout)
@@ -380,9 +380,6 @@ class InstanceNorm3d(Module):
         return y.view(B, C, D, H, W)
 
 # --------------------------------------------------------------------------------------------- lib/utils.py blocks
-PRENORM_GELU = os.environ.get("CF_PRENORM_GELU", "1") != "0"       # 0: GELU(GN1(conv1)) is materialised by its own apply pass (A/B knob)
-FUSE_RES_NORM = os.environ.get("CF_FUSE_RES_NORM", "1") != "0"     # 0: the downsample branch's GroupNorm runs as its own pass (A/B knob)
-
 
 class DoubleConv(Module):
     """nnunet/lib/utils.py:1182-1215: GELU(GN(conv)) twice, residual (optionally 1x1 conv + GN) added after the
@@ -408,7 +405,7 @@ class DoubleConv(Module):
     def forward(self, x, x2=None):
         kw1 = {} if x2 is None else {"x2": x2}
         t, ws1 = self.conv1(x, stats_groups=self.norm1.groups, **kw1)
-        pre = PRENORM_GELU and ws1 is not None and ops.CONV_MODE == "f16s" and self.conv2.prenorm_ok(t)
+        pre = ws1 is not None and ops.CONV_MODE == "f16s" and self.conv2.prenorm_ok(t)
         if pre:
             y2, ws2 = self._conv2(t, ws1)
             conv2 = lambda **k: self.norm2(y2, act="gelu", ws=ws2, **k)                       # noqa: E731
@@ -421,13 +418,9 @@ class DoubleConv(Module):
             # the branch's GroupNorm rides in the final apply pass: GELU(GN2(conv2(t))) + GN_ds(conv1x1(x)) in one kernel
             kw = {} if x2 is None else {"x2": x2}
             r, ws_r = self.downsample[0](x, stats_groups=self.downsample[1].groups, **kw)
-            if FUSE_RES_NORM:
-                return conv2(res=r, res_mode="after_act", res_norm=(ws_r, self.downsample[1]))
-            r = self.downsample[1](r, ws=ws_r)
-        else:
-            assert x2 is None
-            r = x
-        return conv2(res=r, res_mode="after_act")
+            return conv2(res=r, res_mode="after_act", res_norm=(ws_r, self.downsample[1]))
+        assert x2 is None
+        return conv2(res=x, res_mode="after_act")
 
 
 class SingleConv(Module):

@@ -377,15 +377,12 @@ def conv2d_f16s(x1, wpk, wscale, bias, cout, kh, kw, stride=1, pad=(0, 0), x2=No
     return (out, ws) if stats_groups else out
 
 
-DIRECT_STEM = os.environ.get("CF_CONV_DIRECT", "1") != "0"      # 0: the stems go through the MFMA kernels like every other layer (A/B knob)
-
-
 def small_cin_supported(cin, kh, kw, stride, pad, stats_groups=None):
     """layers routed to cf_conv2d_small_cin: 1 or 2 input channels (3x3 pad 1 or 1x1) and 6 input channels 1x1, stride 1, <= 64
     statistics groups.  Measured at 256x256 (tools/microbench.py --only stem): 1 -> 32 B120 209 us vs 641 us on the MFMA kernel,
     1 -> 64 106 vs 238, 6 -> 64 1x1 120 vs 194; the 6 -> 64 3x3 layer is FMA-bound in the direct kernel (304 vs 257 us) and stays
     on the MFMA kernel."""
-    if not DIRECT_STEM or stride != 1 or (stats_groups and stats_groups > 64):
+    if stride != 1 or (stats_groups and stats_groups > 64):
         return False
     k3, k1 = (kh, kw, tuple(pad)) == (3, 3, (1, 1)), (kh, kw, tuple(pad)) == (1, 1, (0, 0))
     return (cin in (1, 2) and (k3 or k1)) or (cin == 6 and k1)
@@ -407,7 +404,7 @@ def conv2d_small_cin(x, weight, bias, stats_groups=None):
 def small_cout_supported(cout, kh, kw, stride, pad):
     """layers routed to cf_conv2d_small_cout: 3x3 / pad 1 / stride 1 with at most 4 output channels (the flow heads).  Measured at
     128 x 64 x 256 x 256 -> 2: see DESIGN.md (the MFMA kernel fills 2 of its 32 rows: 16 TF)."""
-    return DIRECT_STEM and cout <= 4 and (kh, kw, tuple(pad)) == (3, 3, (1, 1)) and stride == 1
+    return cout <= 4 and (kh, kw, tuple(pad)) == (3, 3, (1, 1)) and stride == 1
 
 
 def conv2d_small_cout(x, weight, bias, res=None):
@@ -422,13 +419,10 @@ def conv2d_small_cout(x, weight, bias, res=None):
     return out
 
 
-PRENORM = os.environ.get("CF_PRENORM", "1") != "0"        # 0: every normalisation runs as its own apply pass (A/B knob)
-
-
 def prenorm_ok(x, cout):
     """can cf_conv2d_f16s_prenorm take this input (raw conv output [B,C,H,W]) for a 3x3 / stride 1 convolution to `cout` channels?"""
     B, C, H, W = x.shape
-    return bool(PRENORM and CONV_MODE == "f16s" and x.data_ptr() % 16 == 0 and lib().cf_conv2d_f16s_prenorm_ok(B, C, H, W, cout) == 1)
+    return bool(CONV_MODE == "f16s" and x.data_ptr() % 16 == 0 and lib().cf_conv2d_f16s_prenorm_ok(B, C, H, W, cout) == 1)
 
 
 def group_norm_coef(ws, gamma, beta, groups, B, C, HW, eps=1e-5):

@@ -328,12 +328,10 @@ extern "C" int cf_attention_cf_masked(const float* q, long q_bs, const float* k,
     const float scale = (float)(1.0 / sqrt((double)d));
     dim3 grid((unsigned)(B * heads * ((Nq + 127) / 128)));
     hipStream_t s = as_stream(stream);
-    // head dims >= 16 run on the f16 hi/lo-split kernel (CF_ATTN_F32=1 keeps the exact fp32-MFMA kernel); it reads V with 16-byte
-    // loads: 8-key groups must be 16-byte aligned
-    static int f32_only = -1;
-    if (f32_only < 0) { const char* e = getenv("CF_ATTN_F32"); f32_only = e ? atoi(e) : 0; }
+    // head dims >= 16 run on the f16 hi/lo-split kernel; it reads V with 16-byte loads: 8-key groups must be 16-byte aligned.  The exact
+    // fp32-MFMA kernel takes d == 8 and misaligned V
     const bool valign = ((reinterpret_cast<uintptr_t>(v) | (uintptr_t)(v_bs * 4)) & 15) == 0 && (Nk & 7) == 0;
-    if (!f32_only && d >= 16 && valign) {
+    if (d >= 16 && valign) {
         if (d == 16) hipLaunchKernelGGL((attention_cf_f16s_kernel<16>), grid, dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid);
         else if (d == 32) hipLaunchKernelGGL((attention_cf_f16s_kernel<32>), grid, dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid);
         else hipLaunchKernelGGL((attention_cf_f16s_kernel<64>), grid, dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid);

@@ -10,8 +10,6 @@
 // Operands are prefetched PF k-steps ahead in registers (no LDS, no barriers: every wave is independent and may exit
 // early).  Epilogue fuses alpha, bias, activation, residual, channel-offset (torch.cat elimination) and the
 // ConvTranspose2d(k=2,s=2) pixel scatter.
-#include <stdlib.h>
-
 #include "conv.h"
 #include "profile.h"
 
@@ -168,7 +166,7 @@ static int launch_t(const ConvParams& p, hipStream_t s) {
     dim3 grid((unsigned)ntiles, (unsigned)((p.Cout + 32 * MT - 1) / (32 * MT)));
     const double flops = 2.0 * (double)Ntot * p.Cout * (p.C1 + p.C2) * p.KH * p.KW;
     if (p.profile_kid >= 0) launch_profiled(p.profile_kid, p.profile_work, conv_igemm_f32_kernel<MT, NT>, grid, dim3(256), s, p);
-    else launch_profiled(MT == 1 ? PK_CONV_MT1 : (MT == 2 ? PK_CONV_MT2 : PK_CONV_MT4), flops, conv_igemm_f32_kernel<MT, NT>, grid, dim3(256), s, p);
+    else launch_profiled(MT == 1 ? PK_CONV_MT1 : PK_CONV_MT2, flops, conv_igemm_f32_kernel<MT, NT>, grid, dim3(256), s, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error(std::string("conv launch failed: ") + hipGetErrorString(e));
@@ -177,23 +175,10 @@ static int launch_t(const ConvParams& p, hipStream_t s) {
     return CF_OK;
 }
 
-// Tile choice.  MT=4 halves the input re-reads of wide layers but needs 276 registers (1 wave/SIMD); MT=2 runs at
-// 3 waves/SIMD, which hides the global-load latency of this LDS-free design better.  CF_CONV_MT overrides (A/B runs).
-static int conv_mt_override() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("CF_CONV_MT");
-        v = e ? atoi(e) : 0;
-    }
-    return v;
-}
-
+// Tile choice.  MT=2 runs at 3 waves/SIMD, which hides the global-load latency of this LDS-free design; an MT=4 tile halved the input
+// re-reads of wide layers but needed 276 registers (1 wave/SIMD) and was removed.
 int launch_conv(const ConvParams& p, hipStream_t s) {
-    int mt = conv_mt_override();
-    if (mt == 0) mt = p.Cout <= 32 ? 1 : 2;
-    if (p.Cout <= 32) mt = 1;
-    if (mt == 1) return launch_t<1, 2>(p, s);
-    if (mt == 4 && p.Cout > 64) return launch_t<4, 2>(p, s);
+    if (p.Cout <= 32) return launch_t<1, 2>(p, s);
     return launch_t<2, 2>(p, s);
 }
 

@@ -45,7 +45,7 @@ struct F16sGeom {
     int ostep;               // patch step between output pixels (stride, or 1 for 1x1 convs)
     int tiles_x, tiles_y, bgroups;
     int nchunk;
-    int ablate;              // timing experiments only (CF_F16S_ABLATE): 1 = every chunk reads chunk 0's weight fragments (L1-resident), 2 = no fragment loads, 3 = no output stores
+    int ablate;              // ablation build only (CF_F16S_ABLATE): 1 = every chunk reads chunk 0's weight fragments (L1-resident), 2 = no fragment loads, 3 = no output stores
     int c1_pad;              // C1 rounded up to a multiple of CK: chunks below it read x1, the others x2 (the packed weights follow the same split)
     int NQ;                  // vector staging: 16-byte column quads per patch row (0: scalar staging)
     // magic multipliers floor(2^32/d)+1 for the index decodes (exact for n < 2^32/d; d == 1 handled apart): the kernel's setup was
@@ -65,11 +65,10 @@ __device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
     lo = (_Float16)(x - (float)hi);
 }
 
-// NLW = number of dedicated loader waves.  NLW == 0: all four waves stage and compute (first design).  NLW > 0: waves
-// 0-3 only run MFMAs (their vmcnt queue holds nothing but weight fragments), waves 4.. only stage the input patch, two
-// chunks of loads in flight, always one LDS buffer ahead.  vmcnt retires in issue order, so in the mixed design every
-// wait for a weight fragment also waited for the staging loads issued before it (ablating those loads made the kernel
-// 19-33 % faster); with separate roles nothing in the MFMA waves ever waits for HBM.
+// Every wave both stages the input patch and runs MFMAs.  vmcnt retires in issue order, so every wait for a weight fragment also waits
+// for the staging loads issued before it (ablating those loads made the kernel 19-33 % faster); a design with dedicated loader waves
+// removed that coupling and won 10-24 % on stride-2 layers and small maps, but lost 15-25 % on the large 3x3 layers that dominate the
+// step, where the kernel is limited by bytes in flight; it was removed.
 // WL = 1: the weight fragments go through LDS instead of straight from L1/L2 into registers.  Ablations (profiles/r02_conv_weight_path.md)
 // showed that the per-wave fragment loads -- 2 KiB per k-step and wave, L1-resident or not -- cost 30-40 % of the kernel on every shape:
 // the vector-memory return path (64 B/clk/CU) is what the MFMAs wait for.  With WL the workgroup fetches each fragment ONCE by LDS-DMA
@@ -83,15 +82,15 @@ __device__ unsigned long long g_f16s_phase[9];   // [6..8]: epilogue split: scal
 // TERMS = 3: the hi/lo split (al*bh + ah*bl + ah*bh); TERMS = 1: ah*bh only -- operands rounded to fp16, fp32 accumulation: what the reference's
 // fp16 autocast computes on the segmentation path (mixed_precision=True, nnunet/network_architecture/neural_network.py:140-146), selected per
 // thread by cf_conv_terms(1).  Same staging, same packed weights (the lo planes are simply not multiplied).
-template <int KH, int KW, int CK, int WM, int NTW, int MAXT, int NLW, int NW, int VEC, int PRE, int WL, int TERMS>
-__global__ void __launch_bounds__(64 * NW + 64 * NLW, NLW ? 5 : (NW == 8 ? 4 : ((NTW <= 2 && MAXT <= 3) ? 4 : 2)))
+template <int KH, int KW, int CK, int WM, int NTW, int MAXT, int NW, int VEC, int PRE, int WL, int TERMS>
+__global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : ((NTW <= 2 && MAXT <= 3) ? 4 : 2))
 conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restrict__ wpk) {
     constexpr int KHW = KH * KW;           // taps: 3x3, 1x1, and the separable 1x5 / 5x1 of RAFT's SepConvGRU
     constexpr int KS = CK / 16;            // MFMA k-steps per tap per chunk
     constexpr int REC = CK * 4 + 16;       // bytes per pixel record
     constexpr int NT_WG = NTW * (NW / WM);  // n-tiles per workgroup (NW MFMA waves = WM m-tiles x NW/WM n-tile groups)
     constexpr int NG = CK / 8;             // 8-channel groups per record
-    constexpr int NSTAGE = NLW ? 64 * NLW : 64 * NW;   // threads that stage
+    constexpr int NSTAGE = 64 * NW;        // threads that stage
     (void)NT_WG;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     CF_CLOCK_BEGIN();
@@ -103,8 +102,7 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
     unsigned long long ph_t1 = 0, ph_stage = 0, ph_bar = 0, ph_t2 = 0;
 #endif
     const int half = lane >> 5, l31 = lane & 31;
-    const bool loader = NLW > 0 && wave >= NW;     // wave-uniform
-    const int cw = wave % NW;                       // index among the MFMA waves
+    const int cw = wave % NW;                       // wave inside the workgroup
     const int mt = blockIdx.y * WM + (cw % WM);     // 32-channel m-tile of this wave
     const int ngrp = cw / WM;                       // n-tile group of this wave
 
@@ -128,7 +126,7 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
     const bool do_stats = p.gn_ws != nullptr;
 
     // =================================================================================================================
-    // staging role (all waves when NLW == 0, waves 4.. otherwise)
+    // staging
     // =================================================================================================================
     // Inputs are read with raw buffer loads: the per-lane 32-bit byte offset of (sample, channel 0, iy, ix) is computed
     // once per task, the channel term is added per load, and the descriptor's range check returns 0 for (a) pixels
@@ -140,16 +138,13 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
     unsigned t_o1[MAXT], t_o2[MAXT];  // byte offsets into x1 / x2 (OOB when invalid)
     int t_lds[MAXT];                  // byte offset of the 16-byte hi slot inside a buffer, -1: no task
     unsigned t_g8[MAXT];              // (8-channel group inside the chunk) * 8
-    const int stid = NLW ? tid - 64 * NW : tid;
-    const bool stages = NLW ? loader : true;
 #pragma unroll
     for (int t = 0; t < MAXT; ++t) {
         t_o1[t] = OOB;
         t_o2[t] = OOB;
         t_lds[t] = -1;
         t_g8[t] = 0;
-        if (!stages) continue;
-        int task = stid + t * NSTAGE;
+        int task = tid + t * NSTAGE;
         int grp = fdiv(task, nrec, g.m_nrec);
         int pr = task - grp * nrec;
         if (grp < NG) {
@@ -305,39 +300,14 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
         }
     };
 
-    if (NLW > 0 && loader) {
-        // ---- loader waves: two register sets keep TWO chunks of loads in flight (loop unrolled by two so the sets are
-        // statically indexed); the wait in front of each LDS write is for loads issued a whole chunk period earlier.
-        // Barrier count must equal the MFMA branch: 1 + nchunk (+ 3 when statistics are fused).
-        float sa[MAXT][8], sb[MAXT][8];
-        const int n = g.nchunk;
-        issue_loads(0, sa);
-        if (n > 1) issue_loads(1, sb);
-        write_stage(0, sa);
-        __syncthreads();
-        int c = 0;
-        while (true) {
-            if (c + 2 < n) issue_loads(c + 2, sa);
-            if (c + 1 < n) write_stage(c + 1, sb);
-            __syncthreads();
-            if (++c >= n) break;
-            if (c + 2 < n) issue_loads(c + 2, sb);
-            if (c + 1 < n) write_stage(c + 1, sa);
-            __syncthreads();
-            if (++c >= n) break;
-        }
-        if (do_stats) { __syncthreads(); __syncthreads(); __syncthreads(); }
-        return;
-    }
-
     // =================================================================================================================
-    // MFMA role
+    // MFMAs
     // =================================================================================================================
     // the first chunk's loads leave before the (division-heavy) output-coordinate setup below, which then overlaps their latency
     float stg0[MAXT][8];   // dead (eliminated) in the VEC instantiations
     f32x4v stgv[VT][4];
     if (VEC) issue_loads_v(0, stgv);
-    else if (NLW == 0) issue_loads(0, stg0);
+    else issue_loads(0, stg0);
     // ---- per-lane B-fragment record offsets and output coordinates of this wave's n-tiles
     int b_rec[NTW];
 #pragma unroll
@@ -470,7 +440,7 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
         __syncthreads();
     }
     if (VEC) write_stage_v(0, stgv);
-    else if (NLW == 0) write_stage(0, stg0);
+    else write_stage(0, stg0);
     __syncthreads();
 #ifdef CF_F16S_ABLATION_BUILD
     ph_t1 = F16S_CLK();
@@ -491,7 +461,7 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
             const int cn = more ? c + 1 : c;
             if (step + D < NSTEP) load_a(c, step + D, (step + D) % R);
             else load_a(cn, step + D - NSTEP, (step + D) % R);
-            if (NLW == 0 && step == 0) {
+            if (step == 0) {
                 if (VEC) issue_loads_v(cn, stgv);
                 else issue_loads(cn, stg0);
             }
@@ -517,7 +487,7 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
 #ifdef CF_F16S_ABLATION_BUILD
         const unsigned long long ph_a = F16S_CLK();
 #endif
-        if (NLW == 0 && more) {
+        if (more) {
             if (VEC) write_stage_v(c + 1, stgv);
             else write_stage(c + 1, stg0);
         }
@@ -724,33 +694,17 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
 static thread_local int t_conv_terms = 3;
 int conv_terms() { return t_conv_terms; }
 
-static int f16s_deint() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("CF_F16S_DEINT"); v = e ? atoi(e) : 1; }
-    return v;
-}
-
-// CF_F16S_VEC=0 keeps the scalar (one dword per lane and channel) staging everywhere
-static int f16s_vec() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("CF_F16S_VEC");
-        v = e ? atoi(e) : 1;
-    }
-    return v;
-}
-
-template <int KH, int KW, int CK, int WM, int NTW, int MAXT, int NLW, int NW, int VEC, int PRE = 0, int WL = 0>
+template <int KH, int KW, int CK, int WM, int NTW, int MAXT, int NW, int VEC, int PRE = 0, int WL = 0>
 static int launch_f16s_v(const ConvParams& p, F16sGeom g, const _Float16* wpk, hipStream_t s);
 
 // picks the vector-staging instantiation when the layer qualifies (stride 1, W % 4 == 0, 16-byte aligned inputs, VT 4x4 tasks per
 // staging thread), else the scalar one.  VT = 1 for the 3x3 shapes; the 1x5 / 5x1 shapes (CK = 32, wider patches) take VT = 2.
-template <int KH, int KW, int CK, int WM, int NTW, int MAXT, int NLW = 0, int NW = 4>
+template <int KH, int KW, int CK, int WM, int NTW, int MAXT, int NW = 4>
 static int launch_f16s(const ConvParams& p, F16sGeom g, const _Float16* wpk, hipStream_t s) {
     constexpr int KHW = KH * KW;
     g.NQ = 0;
     // (1x1 layers measured 6-17 % slower with it -- their scalar loads are already whole rows -- so spatial kernels only)
-    if (NLW == 0 && KHW > 1 && f16s_vec() && p.stride == 1 && (p.W & 3) == 0 && (g.TW & 3) == 0 &&
+    if (KHW > 1 && p.stride == 1 && (p.W & 3) == 0 && (g.TW & 3) == 0 &&
         ((reinterpret_cast<uintptr_t>(p.x1) | reinterpret_cast<uintptr_t>(p.x2)) & 15) == 0) {
         const int a = (-p.pad_w) & 3;                       // ix_org mod 4 (tile origins are multiples of 4)
         const int nq = ((a + g.PW - 1) >> 2) + 1;
@@ -761,30 +715,34 @@ static int launch_f16s(const ConvParams& p, F16sGeom g, const _Float16* wpk, hip
                 // the stride-1 3x3 four-wave shapes are also built with the deferred input normalisation; not the 8-wave shape of the small
                 // maps (< 1024 workgroups): its short workgroups lose more to the table fill + barrier than the apply pass costs
                 // (256 channels at 32x32, B = 32: 192 us vs 120 + 15 us, tools/prenorm_ab.py)
-                if constexpr (MAXT == 2 && NLW == 0 && NW == 4) {
+                if constexpr (MAXT == 2 && NW == 4) {
                     if (p.in_norm && g.NIMG == 1 && p.C2 == 0 && (reinterpret_cast<uintptr_t>(p.in_norm) & 3) == 0)
-                        return launch_f16s_v<KH, KW, CK, WM, NTW, MAXT, NLW, NW, 1, 1>(p, g, wpk, s);
+                        return launch_f16s_v<KH, KW, CK, WM, NTW, MAXT, NW, 1, 1>(p, g, wpk, s);
                 }
                 if (p.in_norm) { set_error("conv_f16s: deferred input normalisation is not built for this layer shape"); return CF_ERR_ARG; }
-                return launch_f16s_v<KH, KW, CK, WM, NTW, MAXT, NLW, NW, 1>(p, g, wpk, s);
+                return launch_f16s_v<KH, KW, CK, WM, NTW, MAXT, NW, 1>(p, g, wpk, s);
             }
             // (two tasks per thread for the (2 TH + 1) x (2 TW + 1) patches of the stride-2 shapes: measured equal or 2 % slower, not built)
         } else if constexpr (KHW > 1) {
-            if (!p.in_norm && tasks <= 2 * 64 * NW) return launch_f16s_v<KH, KW, CK, WM, NTW, MAXT, NLW, NW, 2>(p, g, wpk, s);
+            if (!p.in_norm && tasks <= 2 * 64 * NW) return launch_f16s_v<KH, KW, CK, WM, NTW, MAXT, NW, 2>(p, g, wpk, s);
         }
         g.NQ = 0;
     }
     if (p.in_norm) { set_error("conv_f16s: deferred input normalisation needs the vector staging path (3x3, stride 1, W % 4 == 0)"); return CF_ERR_ARG; }
-    return launch_f16s_v<KH, KW, CK, WM, NTW, MAXT, NLW, NW, 0>(p, g, wpk, s);
+    return launch_f16s_v<KH, KW, CK, WM, NTW, MAXT, NW, 0>(p, g, wpk, s);
 }
 
-template <int KH, int KW, int CK, int WM, int NTW, int MAXT, int NLW, int NW, int VEC, int PRE, int WL>
+template <int KH, int KW, int CK, int WM, int NTW, int MAXT, int NW, int VEC, int PRE, int WL>
 static int launch_f16s_v(const ConvParams& p, F16sGeom g, const _Float16* wpk, hipStream_t s) {
     constexpr int REC = CK * 4 + 16;
     constexpr int WGRP = (KH * KW == 9) ? 3 : ((KH * KW == 1) ? CK / 16 : 5);      // k-steps per LDS weight slot (kernel: G)
-    constexpr int NSTAGE = NLW ? 64 * NLW : 64 * NW;
+    constexpr int NSTAGE = 64 * NW;
     const int nrec = g.NIMG * g.PH * g.PW;
+#ifdef CF_F16S_ABLATION_BUILD
     { static int ab = -1; if (ab < 0) { const char* e = getenv("CF_F16S_ABLATE"); ab = e ? atoi(e) : 0; } g.ablate = ab; }
+#else
+    g.ablate = 0;
+#endif
     g.m_tx = f16s_magic(g.tiles_x);
     g.m_ty = f16s_magic(g.tiles_y);
     g.m_percg = f16s_magic(g.NIMG * g.PH * g.NQ);
@@ -818,7 +776,7 @@ static int launch_f16s_v(const ConvParams& p, F16sGeom g, const _Float16* wpk, h
         return CF_ERR_ARG;
     }
     if (p.probe) return CF_OK;
-    auto kern = p.terms == 1 ? conv_f16s_kernel<KH, KW, CK, WM, NTW, MAXT, NLW, NW, VEC, PRE, WL, 1> : conv_f16s_kernel<KH, KW, CK, WM, NTW, MAXT, NLW, NW, VEC, PRE, WL, 3>;
+    auto kern = p.terms == 1 ? conv_f16s_kernel<KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL, 1> : conv_f16s_kernel<KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL, 3>;
     static bool attr_set[64][2] = {};       // per device and variant
     const int dev = current_device_slot();
     if (!attr_set[dev][p.terms == 1]) {
@@ -826,7 +784,7 @@ static int launch_f16s_v(const ConvParams& p, F16sGeom g, const _Float16* wpk, h
         attr_set[dev][p.terms == 1] = true;
     }
     dim3 grid((unsigned)(g.tiles_x * g.tiles_y * g.bgroups), (unsigned)((p.Cout + 32 * WM - 1) / (32 * WM)));
-    dim3 block(64 * NW + 64 * NLW);
+    dim3 block(64 * NW);
     const double flops = 2.0 * (double)p.B * p.Ho * p.Wo * p.Cout * (p.C1 + p.C2) * p.KH * p.KW;
     hipEvent_t e0, e1;
     if (profile_on() && profile_events(PK_CONV_F16S, flops, &e0, &e1))
@@ -846,7 +804,7 @@ static int launch_f16s_v(const ConvParams& p, F16sGeom g, const _Float16* wpk, h
 template <int WM, int NTW>
 static int launch_f16s_wl(const ConvParams& p, F16sGeom g, const _Float16* wpk, hipStream_t s, bool* probe_single) {
     constexpr int CK = 16, NW = 8;
-    if (!(f16s_vec() && p.stride == 1 && (p.W & 3) == 0 && (g.TW & 3) == 0 && g.NIMG == 1 &&
+    if (!(p.stride == 1 && (p.W & 3) == 0 && (g.TW & 3) == 0 && g.NIMG == 1 &&
           ((reinterpret_cast<uintptr_t>(p.x1) | reinterpret_cast<uintptr_t>(p.x2)) & 15) == 0))
         return -1;
     const int a = (-p.pad_w) & 3;
@@ -856,16 +814,9 @@ static int launch_f16s_wl(const ConvParams& p, F16sGeom g, const _Float16* wpk, 
     if (probe_single) { *probe_single = true; return CF_OK; }      // geometry probe: the layer takes this shape, one sample per workgroup
     if (p.in_norm) {
         if (p.C2 != 0 || (reinterpret_cast<uintptr_t>(p.in_norm) & 3) != 0) return -1;
-        return launch_f16s_v<3, 3, CK, WM, NTW, 2, 0, NW, 1, 1, 1>(p, g, wpk, s);
+        return launch_f16s_v<3, 3, CK, WM, NTW, 2, NW, 1, 1, 1>(p, g, wpk, s);
     }
-    return launch_f16s_v<3, 3, CK, WM, NTW, 2, 0, NW, 1, 0, 1>(p, g, wpk, s);
-}
-
-// CF_F16S_WL=0 keeps the weight fragments on the L1/L2 -> register path everywhere (A/B knob)
-static int f16s_wl() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("CF_F16S_WL"); v = e ? atoi(e) : 1; }
-    return v;
+    return launch_f16s_v<3, 3, CK, WM, NTW, 2, NW, 1, 0, 1>(p, g, wpk, s);
 }
 
 // kernel shapes of the f16-split kernel: 3x3 pad 1 and 1x1 pad 0 at stride 1 / 2, and the separable 1x5 (pad 0,2) / 5x1 (pad 2,0)
@@ -891,47 +842,11 @@ bool conv_f16s_supported(const ConvParams& p) {
     return true;
 }
 
-// CF_F16S_LOADERS=1 selects the wave-specialised variants (4 MFMA waves + 2-3 loader waves).  Measured (profiles/,
-// DESIGN.md 5.1): they win on stride-2 and on small maps (+10-24 %) but lose 15-25 % on the large 3x3 layers that dominate
-// the step, where the kernel is limited by bytes in flight rather than by the vmcnt coupling; default off.
-static int f16s_loader_waves() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("CF_F16S_LOADERS");
-        v = e ? atoi(e) : 0;
-    }
-    return v;
-}
-
-// CF_F16S_WIDE=0 disables the 128-channel workgroups used for Cout % 128 == 0 (the input patch is staged once per 128 output
-// channels instead of once per 64); 1 = automatic choice between the two 128-channel shapes, 2 / 3 force the 4-wave / 8-wave one.
-static int f16s_wide() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("CF_F16S_WIDE");
-        v = e ? atoi(e) : 1;
-    }
-    return v;
-}
-
-// CF_F16S_WIDE_PAD=0: only Cout % 128 == 0 takes the 128-channel workgroup shapes.  Default: also a Cout whose last 128-channel block is at
-// least three quarters full (the U-Net's 480 = 3 x 128 + 96): the packed weights are padded to whole 128-channel blocks anyway
-// (pack_conv_weight_f16s: an even number of 64-channel pairs), the rows past Cout are zero weights whose stores the epilogue drops.
-static int f16s_wide_pad() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("CF_F16S_WIDE_PAD"); v = e ? atoi(e) : 1; }
-    return v;
-}
-static bool f16s_cout_wide(int cout) { return cout % 128 == 0 || (f16s_wide_pad() && cout > 128 && cout % 128 >= 96); }
-
-static int f16s_small_tile() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("CF_F16S_SMALL_TILE");
-        v = e ? atoi(e) : 1;  // default: 128-pixel workgroup tiles (4 waves/SIMD hide the staging latency; A/B in DESIGN.md)
-    }
-    return v;
-}
+// Cout % 128 == 0 takes the 128-channel workgroup shapes (the input patch is staged once per 128 output channels instead of once per 64),
+// and so does a Cout whose last 128-channel block is at least three quarters full (the U-Net's 480 = 3 x 128 + 96): the packed weights
+// are padded to whole 128-channel blocks anyway (pack_conv_weight_f16s: an even number of 64-channel pairs), the rows past Cout are zero
+// weights whose stores the epilogue drops.
+static bool f16s_cout_wide(int cout) { return cout % 128 == 0 || (cout > 128 && cout % 128 >= 96); }
 
 static int launch_conv_f16s_impl(const ConvParams& p, const _Float16* wpk, hipStream_t s, bool* one_sample_per_wg);
 
@@ -1016,7 +931,6 @@ static int launch_conv_f16s_impl(const ConvParams& p, const _Float16* wpk, hipSt
     const bool spatial = k3 || sep;
     const int CK = k3 ? 16 : 32;
     const bool narrow = p.Cout <= 32;
-    const bool small = f16s_small_tile() != 0;
     const bool s2 = k3 && p.stride == 2;
     // Cout = 3 x 128 + 96 and the like ride on the 128-channel shapes with a partly empty last m-tile -- where the four-wave shape runs
     // (>= 1024 workgroups); a small launch keeps the 64-channel shapes (and with them the deferred input normalisation)
@@ -1028,9 +942,10 @@ static int launch_conv_f16s_impl(const ConvParams& p, const _Float16* wpk, hipSt
         const long nwg = (long)((p.Wo + tw - 1) / tw) * ((p.Ho + th - 1) / th) * p.B * ((p.Cout + 127) / 128);
         if (nwg < 1024) cout_wide = false;
     }
-    const bool wide = small && !s2 && f16s_wide() && cout_wide && f16s_loader_waves() == 0;
-    // n-tiles (of 32 output pixels) per workgroup
-    const int NT_WG = s2 ? ((small && !narrow) ? 2 : 4) : ((small || sep) ? 4 : 8);
+    const bool wide = !s2 && cout_wide;
+    // n-tiles (of 32 output pixels) per workgroup: 128-pixel tiles (64 for the stride-2 shapes of more than 32 channels) keep 4 waves
+    // per SIMD to hide the staging latency; 256-pixel tiles at 2 waves/SIMD were 15-60 % slower and were removed
+    const int NT_WG = (s2 && !narrow) ? 2 : 4;
     F16sGeom g;
     auto geometry = [&](int npx) {
     g.TW = p.Wo < 32 ? p.Wo : 32;
@@ -1056,16 +971,15 @@ static int launch_conv_f16s_impl(const ConvParams& p, const _Float16* wpk, hipSt
     }
     // keep the staging work within the per-thread task budget of the variant (MAXT x 256 eight-channel tasks)
     {
-        const bool ws = small && f16s_loader_waves() > 0 && !sep;   // 128 staging threads instead of 256
-        const int maxt = sep ? 4 : (ws ? 4 : (s2 ? ((small && !narrow) ? 3 : 5) : (small ? 2 : 4)));
-        const int nstage = ws ? ((s2 && !narrow) ? 192 : 128) : ((wide && !sep) ? 512 : 256);
+        const int maxt = sep ? 4 : (s2 ? (narrow ? 5 : 3) : 2);
+        const int nstage = (wide && !sep) ? 512 : 256;
         while (g.NIMG > 1 && (g.NIMG * g.PH * g.PW * (CK / 8) + nstage - 1) / nstage > maxt) --g.NIMG;
     }
     // Stride 2: output-pixel lanes read every second input column; with plain row-major records (80 B apart) their 160-byte lane
     // stride lands 16 lanes on 8 of the 16 LDS slots (2-way conflicts on every B-fragment read).  The patch rows are therefore stored
     // de-interleaved -- even columns, then odd columns -- so a tap's 32 lanes read consecutive records again.
     g.PWR = g.PW; g.pwh = 0; g.kx1 = 1; g.kx2 = 2;
-    if (s2 && f16s_deint()) { g.pwh = (g.PW + 1) / 2; g.PWR = 2 * g.pwh; g.kx1 = g.pwh; g.kx2 = 1; }
+    if (s2) { g.pwh = (g.PW + 1) / 2; g.PWR = 2 * g.pwh; g.kx1 = g.pwh; g.kx2 = 1; }
     g.tiles_x = (p.Wo + g.TW - 1) / g.TW;
     g.tiles_y = (p.Ho + g.TH - 1) / g.TH;
     g.bgroups = (p.B + g.NIMG - 1) / g.NIMG;
@@ -1073,18 +987,16 @@ static int launch_conv_f16s_impl(const ConvParams& p, const _Float16* wpk, hipSt
     g.c1_pad = p.C2 > 0 ? ((p.C1 + CK - 1) / CK) * CK : (1 << 30);
     g.nchunk = p.C2 > 0 ? g.c1_pad / CK + (p.C2 + CK - 1) / CK : (p.C1 + CK - 1) / CK;
     };
-    // The weights-through-LDS shapes come first (3x3, stride 1, Cout not a multiple of 128): 8 waves, 256 output pixels x 64 (or 32)
+    // The weights-through-LDS shapes come first (3x3, stride 1, not a 128-channel layer): 8 waves, 256 output pixels x 64 (or 32)
     // channels; they need one sample per workgroup and the vector staging path, else the register-fragment shapes below take the layer.
     // Measured (profiles/r02_conv_weight_path.md, B = 16): 64 -> 64 at 256x256 234 -> 263 TF, 32 -> 32 195 -> 205, 81 -> 64 208 -> 222; the
-    // 128-channel form of it (4 m-tiles x 2 pixel tiles per wave, 8 waves) LOSES to the four-wave shape whose fragments feed 12 MFMAs
-    // (128 -> 128 at 128x128: 294 vs 343 TF) and is not dispatched (CF_F16S_WL=2 forces it for A/B runs).
-    if (k3 && p.stride == 1 && f16s_wl() && small && f16s_loader_waves() == 0 && (!cout_wide || f16s_wl() == 2)) {
-        const bool w128 = cout_wide;
-        geometry(w128 ? 128 : 256);
+    // 128-channel form of it (4 m-tiles x 2 pixel tiles per wave, 8 waves) lost to the four-wave shape whose fragments feed 12 MFMAs
+    // (128 -> 128 at 128x128: 294 vs 343 TF) and was removed.
+    if (k3 && p.stride == 1 && !cout_wide) {
+        geometry(256);
         if (g.NIMG == 1) {
-            const int rc = w128 ? launch_f16s_wl<4, 2>(p, g, one_sample_per_wg ? nullptr : wpk, s, one_sample_per_wg)
-                                : (narrow ? launch_f16s_wl<1, 1>(p, g, one_sample_per_wg ? nullptr : wpk, s, one_sample_per_wg)
-                                          : launch_f16s_wl<2, 2>(p, g, one_sample_per_wg ? nullptr : wpk, s, one_sample_per_wg));
+            const int rc = narrow ? launch_f16s_wl<1, 1>(p, g, one_sample_per_wg ? nullptr : wpk, s, one_sample_per_wg)
+                                  : launch_f16s_wl<2, 2>(p, g, one_sample_per_wg ? nullptr : wpk, s, one_sample_per_wg);
             if (rc != -1) return rc;
         }
     }
@@ -1096,43 +1008,25 @@ static int launch_conv_f16s_impl(const ConvParams& p, const _Float16* wpk, hipSt
     if (sep) {
         // RAFT's SepConvGRU (384 -> 128 / 256 at 1/8 resolution): CK = 32 (10 k-steps per chunk keep the 2-slot fragment ring static);
         // 128-pixel tiles; 128-channel workgroups when Cout allows (8 waves: 4 m-tiles x 2 pixel groups), else 64-channel ones
-        if (kind == 15) return (p.Cout % 128 == 0) ? launch_f16s<1, 5, 32, 4, 2, 4, 0, 8>(p, g, wpk, s) : launch_f16s<1, 5, 32, 2, 2, 4>(p, g, wpk, s);
-        return (p.Cout % 128 == 0) ? launch_f16s<5, 1, 32, 4, 2, 4, 0, 8>(p, g, wpk, s) : launch_f16s<5, 1, 32, 2, 2, 4>(p, g, wpk, s);
+        if (kind == 15) return (p.Cout % 128 == 0) ? launch_f16s<1, 5, 32, 4, 2, 4, 8>(p, g, wpk, s) : launch_f16s<1, 5, 32, 2, 2, 4>(p, g, wpk, s);
+        return (p.Cout % 128 == 0) ? launch_f16s<5, 1, 32, 4, 2, 4, 8>(p, g, wpk, s) : launch_f16s<5, 1, 32, 2, 2, 4>(p, g, wpk, s);
     }
-    if (wide && k3) {
+    if (wide) {
         // Two 128-channel shapes.  Four waves, each ONE m-tile x FOUR pixel tiles: a weight fragment feeds 12 MFMAs instead of 6, which
         // halves the per-wave weight re-reads from L1/L2 -- the resource the time stamps and the persistent-kernel experiment pointed at
         // (+9-15 % on the 128- and 256-channel layers at 64x64 and above); 148 VGPRs (no scratch under a 2-workgroup launch bound; a bound of 3 made the allocator spill 168 B/lane for the same speed), 3 waves/SIMD.  With few workgroups (32x32 maps)
-        // the 8-wave shape (4 m-tiles x 2 pixel groups, 4 waves/SIMD) keeps more of the chip busy.  CF_F16S_WIDE=2 / 3 force one.
+        // the 8-wave shape (4 m-tiles x 2 pixel groups, 4 waves/SIMD) keeps more of the chip busy.  1x1 layers make the same choice.
         const long nwg = (long)g.tiles_x * g.tiles_y * g.bgroups * ((p.Cout + 127) / 128);
-        const int mode = f16s_wide();
-        const bool four = mode == 2 || (mode == 1 && nwg >= 1024 && g.NIMG == 1);
-        if (four && (g.NIMG * g.PH * g.PW * (CK / 8) + 255) / 256 <= 2) return launch_f16s<3, 3, 16, 4, 4, 2, 0, 4>(p, g, wpk, s);
-        return launch_f16s<3, 3, 16, 4, 2, 2, 0, 8>(p, g, wpk, s);
+        const bool four = nwg >= 1024 && g.NIMG == 1 && (g.NIMG * g.PH * g.PW * (CK / 8) + 255) / 256 <= 2;
+        if (k3) return four ? launch_f16s<3, 3, 16, 4, 4, 2>(p, g, wpk, s) : launch_f16s<3, 3, 16, 4, 2, 2, 8>(p, g, wpk, s);
+        return four ? launch_f16s<1, 1, 32, 4, 4, 2>(p, g, wpk, s) : launch_f16s<1, 1, 32, 4, 2, 2, 8>(p, g, wpk, s);
     }
-    if (wide) {   // 1x1: same choice between the two 128-channel shapes
-        const long nwg = (long)g.tiles_x * g.tiles_y * g.bgroups * ((p.Cout + 127) / 128);
-        static int k1four = -1;
-        if (k1four < 0) { const char* e = getenv("CF_F16S_K1FOUR"); k1four = e ? atoi(e) : 1; }
-        if (k1four && nwg >= 1024 && g.NIMG == 1 && (g.NIMG * g.PH * g.PW * (CK / 8) + 255) / 256 <= 2) return launch_f16s<1, 1, 32, 4, 4, 2, 0, 4>(p, g, wpk, s);
-        return launch_f16s<1, 1, 32, 4, 2, 2, 0, 8>(p, g, wpk, s);
-    }
-    if (small && f16s_loader_waves() > 0) {
-        if (narrow && !s2) return k3 ? launch_f16s<3, 3, 16, 1, 1, 4, 2>(p, g, wpk, s) : launch_f16s<1, 1, 32, 1, 1, 4, 2>(p, g, wpk, s);
-        if (s2 && !narrow) return launch_f16s<3, 3, 16, 2, 1, 4, 3>(p, g, wpk, s);
-        if (!narrow) return k3 ? launch_f16s<3, 3, 16, 2, 2, 4, 2>(p, g, wpk, s) : launch_f16s<1, 1, 32, 2, 2, 4, 2>(p, g, wpk, s);
-    }
-    if (small && narrow && !s2) return k3 ? launch_f16s<3, 3, 16, 1, 1, 2>(p, g, wpk, s) : launch_f16s<1, 1, 32, 1, 1, 2>(p, g, wpk, s);
+    if (narrow && !s2) return k3 ? launch_f16s<3, 3, 16, 1, 1, 2>(p, g, wpk, s) : launch_f16s<1, 1, 32, 1, 1, 2>(p, g, wpk, s);
+    if (narrow) return launch_f16s<3, 3, 16, 1, 1, 5>(p, g, wpk, s);      // stride-2 3x3 to <= 32 channels
     // stride 2 with Cout % 128 == 0: four m-tiles x two pixel tiles per wave -- every weight fragment is loaded once per workgroup and
     // feeds 6 MFMAs (the 64-channel shape below: loaded twice, 3 MFMAs each)
-    if (small && s2 && !narrow && f16s_cout_wide(p.Cout) && f16s_wide()) return launch_f16s<3, 3, 16, 4, 2, 3>(p, g, wpk, s);
-    if (small && s2 && !narrow) return launch_f16s<3, 3, 16, 2, 1, 3>(p, g, wpk, s);
-    if (small && !narrow) return k3 ? launch_f16s<3, 3, 16, 2, 2, 2>(p, g, wpk, s) : launch_f16s<1, 1, 32, 2, 2, 2>(p, g, wpk, s);
-    if (k3) {
-        if (p.stride == 1) return narrow ? launch_f16s<3, 3, 16, 1, 2, 4>(p, g, wpk, s) : launch_f16s<3, 3, 16, 2, 4, 4>(p, g, wpk, s);
-        return narrow ? launch_f16s<3, 3, 16, 1, 1, 5>(p, g, wpk, s) : launch_f16s<3, 3, 16, 2, 2, 5>(p, g, wpk, s);
-    }
-    return narrow ? launch_f16s<1, 1, 32, 1, 2, 4>(p, g, wpk, s) : launch_f16s<1, 1, 32, 2, 4, 4>(p, g, wpk, s);
+    if (s2) return f16s_cout_wide(p.Cout) ? launch_f16s<3, 3, 16, 4, 2, 3>(p, g, wpk, s) : launch_f16s<3, 3, 16, 2, 1, 3>(p, g, wpk, s);
+    return k3 ? launch_f16s<3, 3, 16, 2, 2, 2>(p, g, wpk, s) : launch_f16s<1, 1, 32, 2, 2, 2>(p, g, wpk, s);
 }
 
 }  // namespace cf

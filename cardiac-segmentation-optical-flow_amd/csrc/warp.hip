@@ -357,10 +357,9 @@ __global__ void __launch_bounds__(256) jacobian_det_3d_kernel(const float* __res
 
 using namespace cf;
 
-// CF_WARP_SCALAR=1: one-pixel-per-thread kernels also for W % 4 == 0 (A/B knob)
+// the four-pixel kernels need W % 4 == 0 and tensors below 2 GiB (32-bit indices and buffer offsets); the one-pixel kernels take the rest
 static bool warp_v4(int W, double max_tensor_bytes) {
-    static const bool scalar = [] { const char* e = getenv("CF_WARP_SCALAR"); return e && e[0] == '1'; }();
-    return W % 4 == 0 && !scalar && max_tensor_bytes < 2147483648.0;   // 32-bit indices and buffer offsets inside the four-pixel kernels
+    return W % 4 == 0 && max_tensor_bytes < 2147483648.0;
 }
 
 extern "C" int cf_warp_bilinear_2d(const float* flow, const float* src, float* out, int B, int C, int H, int W, void* stream) {

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""A/B of conv_f16s dispatch knobs on a few layer shapes: run once per environment setting (the knobs are read once per process).
-  CF_F16S_WL=0 python tools/shape_ab.py            # prints one line per case: plain conv (+ fused statistics) and the prenorm variant
+"""A/B of conv_f16s routing switches on a few layer shapes: run once per environment setting (the switches are read once per process).
+  CF_CONV_STREAM=0 python tools/shape_ab.py        # prints one line per case: plain conv (+ fused statistics) and the prenorm variant
 Cases: (B, C1, C2, H, Cout, act) -- the U-Net's 32 / 64-channel layers at B = 240 frames, the flow net's 64-channel layers at B = 128."""
 import math
 import os
