@@ -703,8 +703,10 @@ template <int KH, int KW, int CK, int WM, int NTW, int MAXT, int NW = 4>
 static int launch_f16s(const ConvParams& p, F16sGeom g, const _Float16* wpk, hipStream_t s) {
     constexpr int KHW = KH * KW;
     g.NQ = 0;
-    // (1x1 layers measured 6-17 % slower with it -- their scalar loads are already whole rows -- so spatial kernels only)
-    if (KHW > 1 && p.stride == 1 && (p.W & 3) == 0 && (g.TW & 3) == 0 &&
+    // (1x1 layers measured 6-17 % slower with it -- their scalar loads are already whole rows -- so spatial kernels only; the stride-2
+    // 3x3 shapes, MAXT 3 and 5, never qualify at run time and are not built with it)
+    if constexpr (KHW > 1 && !(KHW == 9 && MAXT > 2)) {
+    if (p.stride == 1 && (p.W & 3) == 0 && (g.TW & 3) == 0 &&
         ((reinterpret_cast<uintptr_t>(p.x1) | reinterpret_cast<uintptr_t>(p.x2)) & 15) == 0) {
         const int a = (-p.pad_w) & 3;                       // ix_org mod 4 (tile origins are multiples of 4)
         const int nq = ((a + g.PW - 1) >> 2) + 1;
@@ -727,6 +729,7 @@ static int launch_f16s(const ConvParams& p, F16sGeom g, const _Float16* wpk, hip
             if (!p.in_norm && tasks <= 2 * 64 * NW) return launch_f16s_v<KH, KW, CK, WM, NTW, MAXT, NW, 2>(p, g, wpk, s);
         }
         g.NQ = 0;
+    }
     }
     if (p.in_norm) { set_error("conv_f16s: deferred input normalisation needs the vector staging path (3x3, stride 1, W % 4 == 0)"); return CF_ERR_ARG; }
     return launch_f16s_v<KH, KW, CK, WM, NTW, MAXT, NW, 0>(p, g, wpk, s);

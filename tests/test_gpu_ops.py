@@ -763,6 +763,59 @@ def test_attention_slices_and_extremes(dev):
     check(ops.attention_cf(q, k, vc, heads), vc.cpu(), 1e-5)
 
 
+def _attention_ref(q, k, v, heads, nk=None):
+    """fp64 softmax attention of channel-first q [B,C,Nq], k / v [B,C,Nk] (CPU), over the first nk keys"""
+    B, C, Nq = q.shape
+    d = C // heads
+    nk = k.shape[2] if nk is None else nk
+    qh = q.double().view(B, heads, d, Nq).permute(0, 1, 3, 2)
+    kh = k[:, :, :nk].double().reshape(B, heads, d, nk).permute(0, 1, 3, 2)
+    vh = v[:, :, :nk].double().reshape(B, heads, d, nk).permute(0, 1, 3, 2)
+    return (torch.softmax((qh / math.sqrt(d)) @ kh.transpose(-1, -2), -1) @ vh).permute(0, 1, 3, 2).reshape(B, C, Nq)
+
+
+@pytest.mark.parametrize("d", [16, 32, 64])
+def test_attention_fp32_kernel_on_misaligned_v(dev, d):
+    """V not 16-byte aligned: the C ABI runs the exact fp32-MFMA kernel at d = 16 / 32 / 64 (the f16-split kernel reads V with 16-byte
+    loads); the product never passes such a V, so only this reaches those instantiations"""
+    from cineflow._lib import lib, check as lib_check
+    B, heads, Nq, Nk = 2, 2, 64, 96
+    C = heads * d
+    q, k, v = randn(B, C, Nq, seed=110), randn(B, C, Nk, seed=111), randn(B, C, Nk, seed=112)
+    buf = torch.full((B * C * Nk + 4,), float("nan"), device=dev)
+    vd = buf[1:1 + B * C * Nk].view(B, C, Nk)
+    vd.copy_(v.to(dev))
+    assert vd.data_ptr() % 16 == 4
+    qd, kd = q.to(dev), k.to(dev)
+    out = torch.empty(B, C, Nq, device=dev)
+    lib_check(lib().cf_attention_cf(qd.data_ptr(), C * Nq, kd.data_ptr(), C * Nk, vd.data_ptr(), C * Nk, out.data_ptr(), B, heads, d, Nq, Nk,
+                                    torch.cuda.current_stream().cuda_stream), "cf_attention_cf")
+    check(out, _attention_ref(q, k, v, heads), 2e-5, "fp32 attention, misaligned V")
+
+
+@pytest.mark.parametrize("d", [32, 64])
+def test_attention_f16s_slices_masks_and_extremes(dev, d):
+    """the f16-split kernel (d >= 16, aligned V) on what test_attention_slices_and_extremes checks at d = 8: batch-strided channel slices of
+    one fused qkv buffer, x30 logits (online-softmax rescale), and the masked path of token counts that are not multiples of 32"""
+    from cineflow import ops
+    B, heads, N = 2, 2, 64
+    C = heads * d
+    qkv = randn(B, 3 * C, N, seed=113).to(dev)
+    q, k, v = qkv.narrow(1, 0, C), qkv.narrow(1, C, C), qkv.narrow(1, 2 * C, C)
+    a = ops.attention_cf(q, k, v, heads)
+    check(a, ops.attention_cf(q.contiguous(), k.contiguous(), v.contiguous(), heads).cpu(), 0)
+    check(a, _attention_ref(q.cpu(), k.cpu(), v.cpu(), heads), 2e-5, "f16s attention on slices")
+    big = qkv.clone()
+    big[:, :2 * C] *= 30.0
+    out = ops.attention_cf(big.narrow(1, 0, C), big.narrow(1, C, C), big.narrow(1, 2 * C, C), heads)
+    bc = big.cpu()
+    check(out, _attention_ref(bc[:, :C], bc[:, C:2 * C], bc[:, 2 * C:], heads), 5e-4, "f16s attention, x30 logits")
+    assert torch.isfinite(out).all()
+    for Nq, Nk in ((45, 70), (33, 97), (64, 40)):
+        qm, km, vm = randn(B, C, Nq, seed=114), randn(B, C, Nk, seed=115), randn(B, C, Nk, seed=116)
+        check(ops.attention_cf(qm.to(dev), km.to(dev), vm.to(dev), heads), _attention_ref(qm, km, vm, heads), 2e-5, "masked f16s attention %d/%d" % (Nq, Nk))
+
+
 # ------------------------------------------------------------------------------------------------ plumbing kernels
 def test_gru_and_elementwise(dev):
     from cineflow import ops
