@@ -247,6 +247,14 @@ def wino_ok(B, C1, C2, H, W, cout, prenorm=False):
     return bool(WINO and CONV_MODE == "f16s" and lib().cf_conv2d_wino_ok(B, C1, C2, H, W, cout, 1 if prenorm else 0) == 1)
 
 
+def wino_form(B, C1, C2, H, W, cout, prenorm=False):
+    """the kernel form cf_conv2d_wino runs this layer on at the current route level: 0 (not taken), 2 / 4 (one tile per workgroup, NTW unit
+    tiles per wave; 4 only under the forced level 4) or 8 (persistent)"""
+    if not (WINO and CONV_MODE == "f16s"):
+        return 0
+    return int(lib().cf_conv2d_wino_form(B, C1, C2, H, W, cout, 1 if prenorm else 0))
+
+
 def pack_conv_weight_wino(w, c1=None):
     """torch conv weight [Cout,Cin,3,3] -> (packed fp16 tensor, scale exponent s) for cf_conv2d_wino.
 

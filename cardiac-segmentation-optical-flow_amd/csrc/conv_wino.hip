@@ -857,8 +857,8 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
 }
 
 // route level: 0 = off (every layer stays on the direct kernels), 1 = automatic (the persistent wave-specialised kernel where a layer has at
-// least two items per CU, else the one-tile-per-workgroup kernel with 2 or 4 unit tiles per wave), 2 / 4 = force the one-tile kernel with
-// NTW = 2 / 4, 8 = force the persistent kernel -- each where the geometry allows.  Initial value from CF_CONV_WINO (0 | 1 | 2 | 4 | 8);
+// least two items per CU, else the one-tile-per-workgroup kernel with 2 unit tiles per wave), 2 / 4 = force the one-tile kernel with
+// NTW = 2 / 4 (NTW 4 runs only when forced), 8 = force the persistent kernel -- each where the geometry allows.  Initial value from CF_CONV_WINO (0 | 1 | 2 | 4 | 8);
 // cf_conv_wino_enable changes it at run time (tests, A/B runs).
 int g_wino_level = -1;
 int wino_level() {
@@ -956,35 +956,32 @@ int wino_pick_ntw(const ConvParams& p, WinoGeom& g) {
         if (lvl == 8 || nitems >= 2L * wino_num_cus()) return 8;
     }
     if (lvl == 8) return 0;
-    const int force = wino_force_ntw();
-    if (force != 2 && wino_geometry(p, 4, g)) {
-        // one wave per SIMD wants the whole chip covered a few times over: >= 512 workgroups (two rounds of 256 CUs)
-        const long nwg = (long)g.tiles_x * g.tiles_y * p.B * cblocks;
-        if (force == 4) return 4;
-        (void)nwg;
-    }
-    if (force != 4 && wino_geometry(p, 2, g)) return 2;
-    return 0;
+    // the one-tile kernel: NTW 2 (two workgroups per CU) unless level 4 forces NTW 4 -- level 1 never picks NTW 4
+    const int ntw = wino_force_ntw() == 4 ? 4 : 2;
+    return wino_geometry(p, ntw, g) ? ntw : 0;
 }
 
 }  // namespace
 
 // Cout: whole 128-channel blocks, or a last block at least three quarters full (the U-Net's 480), as conv_f16s' 128-channel shapes
-bool conv_wino_applicable(const ConvParams& p) {
-    if (!wino_enabled()) return false;
-    if (conv_terms() != 3) return false;       // the one-term ("mixed precision") product mode is built in conv_f16s.hip only
-    if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad_h != 1 || p.pad_w != 1 || p.w_bstride || p.scatter2x2) return false;
-    if (!(p.Cout % 128 == 0 || (p.Cout > 128 && p.Cout % 128 >= 96))) return false;
-    if (p.W < 16 || (p.W & 15) != 0) return false;
-    if (((reinterpret_cast<uintptr_t>(p.x1) | reinterpret_cast<uintptr_t>(p.x2)) & 15) != 0) return false;
+// 0 = not a Winograd layer, else the kernel form wino_pick_ntw chooses (2 / 4 / 8)
+static int conv_wino_form(const ConvParams& p) {
+    if (!wino_enabled()) return 0;
+    if (conv_terms() != 3) return 0;       // the one-term ("mixed precision") product mode is built in conv_f16s.hip only
+    if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad_h != 1 || p.pad_w != 1 || p.w_bstride || p.scatter2x2) return 0;
+    if (!(p.Cout % 128 == 0 || (p.Cout > 128 && p.Cout % 128 >= 96))) return 0;
+    if (p.W < 16 || (p.W & 15) != 0) return 0;
+    if (((reinterpret_cast<uintptr_t>(p.x1) | reinterpret_cast<uintptr_t>(p.x2)) & 15) != 0) return 0;
     const long HW = (long)p.H * p.W;
-    if ((long)p.C1 * HW * 4 >= (1L << 31) || (long)p.C2 * HW * 4 >= (1L << 31)) return false;
-    if ((long)p.out_ctotal * HW * 4 >= (1L << 30)) return false;          // 32-bit store offsets, two parking values (kernel epilogue)
-    if (p.in_norm && (p.C2 != 0 || (reinterpret_cast<uintptr_t>(p.in_norm) & 3) != 0)) return false;
-    if (p.gn_ws && (p.gn_groups <= 0 || p.Cout % p.gn_groups != 0)) return false;
+    if ((long)p.C1 * HW * 4 >= (1L << 31) || (long)p.C2 * HW * 4 >= (1L << 31)) return 0;
+    if ((long)p.out_ctotal * HW * 4 >= (1L << 30)) return 0;          // 32-bit store offsets, two parking values (kernel epilogue)
+    if (p.in_norm && (p.C2 != 0 || (reinterpret_cast<uintptr_t>(p.in_norm) & 3) != 0)) return 0;
+    if (p.gn_ws && (p.gn_groups <= 0 || p.Cout % p.gn_groups != 0)) return 0;
     WinoGeom g;
-    return wino_pick_ntw(p, g) != 0;
+    return wino_pick_ntw(p, g);
 }
+
+bool conv_wino_applicable(const ConvParams& p) { return conv_wino_form(p) != 0; }
 
 int launch_conv_wino(const ConvParams& p, const _Float16* wpk, hipStream_t s) {
     WinoGeom g;
@@ -1027,13 +1024,17 @@ extern "C" int cf_conv_wino_enable(int level) {
     return prev;
 }
 
-extern "C" int cf_conv2d_wino_ok(int B, int C1, int C2, int H, int W, int Cout, int prenorm) {
+extern "C" int cf_conv2d_wino_form(int B, int C1, int C2, int H, int W, int Cout, int prenorm) {
     if (B <= 0 || C1 <= 0 || C2 < 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
     ConvParams p;
     float* dummy = reinterpret_cast<float*>(uintptr_t(256));      // never dereferenced
     wino_params(p, dummy, C1, C2 ? dummy : nullptr, C2, nullptr, nullptr, dummy, Cout, 0, B, H, W, Cout, CF_ACT_NONE, 1.f, nullptr, 0);
     if (prenorm) { p.in_norm = dummy; p.in_slope = 0.01f; }
-    return conv_wino_applicable(p) ? 1 : 0;
+    return conv_wino_form(p);
+}
+
+extern "C" int cf_conv2d_wino_ok(int B, int C1, int C2, int H, int W, int Cout, int prenorm) {
+    return cf_conv2d_wino_form(B, C1, C2, H, W, Cout, prenorm) != 0 ? 1 : 0;
 }
 
 extern "C" int cf_conv2d_wino(const float* x1, int C1, const float* x2, int C2, const void* wpk, const float* bias, const float* res, float* out,

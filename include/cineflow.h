@@ -206,8 +206,11 @@ int cf_conv2d_f16s_prenorm(const float* x, int C, const float* in_norm, float in
  * a shape qualifies (no launch); the calls fail with CF_ERR_ARG otherwise (the caller stays on cf_conv2d_f16s).  CF_CONV_WINO=0 in the
  * environment makes cf_conv2d_wino_ok answer 0 for every shape (A/B knob). */
 int cf_conv2d_wino_ok(int B, int C1, int C2, int H, int W, int Cout, int prenorm);
+/* which kernel form the current route level sends the shape to (no launch): 0 = none, 2 / 4 = one tile per workgroup with 2 / 4 unit tiles
+ * per wave, 8 = the persistent kernel.  Level 1 chooses between 8 and 2; the NTW 4 form runs only under the forced level 4. */
+int cf_conv2d_wino_form(int B, int C1, int C2, int H, int W, int Cout, int prenorm);
 /* route level (tests, A/B runs): 0 = off, 1 = automatic (default: the persistent wave-specialised kernel where a layer has at least two items per
- * CU, else one tile per workgroup), 2 / 4 = force the one-tile kernel with 2 / 4 unit tiles per wave, 8 = force the persistent kernel -- each
+ * CU, else one tile per workgroup with 2 unit tiles per wave), 2 / 4 = force the one-tile kernel with 2 / 4 unit tiles per wave, 8 = force the persistent kernel -- each
  * where the geometry allows (initial value from CF_CONV_WINO).  Returns the previous level. */
 int cf_conv_wino_enable(int level);
 int cf_conv2d_wino(const float* x1, int C1, const float* x2, int C2, const void* wpk, const float* bias, const float* res, float* out,

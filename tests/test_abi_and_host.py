@@ -234,3 +234,19 @@ def test_conv_f16s_output_sample_limit_falls_back_to_fp32_kernel():
     assert ops.f16s_dynamic_ok(x, None, 3, out_sample_elems=8 * 4096 * 4096, out_hw=4096 * 4096)
     assert not ops.f16s_dynamic_ok(x, None, 3, out_sample_elems=16 * 4096 * 4096, out_hw=4096 * 4096)      # 1 GiB output sample
     assert not ops.f16s_dynamic_ok(Fake((1, 8, 16, 16)), None, 3, out_sample_elems=2 ** 25, out_hw=256)      # 8 images per workgroup
+
+
+def test_wino_form_query_follows_the_route_level():
+    """cf_conv2d_wino_form names the kernel form the dispatch picks (host code, no launch); cf_conv2d_wino_ok is `form != 0`.  A layer with
+    few items: level 1 takes NTW 2 -- never NTW 4, which only the forced level 4 selects."""
+    from cineflow import _lib, ops
+    h = _lib.lib()
+    prev = h.cf_conv_wino_enable(1)
+    try:
+        for level, form in ((0, 0), (1, 2), (2, 2), (4, 4), (8, 8)):
+            h.cf_conv_wino_enable(level)
+            assert ops.wino_form(2, 128, 0, 16, 32, 128) == form and ops.wino_ok(2, 128, 0, 16, 32, 128) == (form != 0), level
+            assert ops.wino_form(2, 128, 0, 16, 48, 128) == 0 and not ops.wino_ok(2, 128, 0, 16, 48, 128)       # W = 48: no form
+            assert ops.wino_form(2, 128, 0, 12, 32, 128) == (0 if level in (0, 4) else level if level > 1 else 2)   # H % 8 != 0: no NTW 4
+    finally:
+        h.cf_conv_wino_enable(prev)

@@ -50,13 +50,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _split_exact import (ACTS, SPLIT_BAR, TORCH_ACT, check_stats, device_input, randn, ratio, samples_of, split_reference, split_w,
+                          split_x)
+
 pytestmark = pytest.mark.gpu
 
-SPLIT_BAR = 2.0 ** -18
 ONE_TERM_BAR = 3 * 2.0 ** -11
 PRE_ONE_TERM_BAR = 2.0 ** -13
-ACTS = ("gelu", "relu", "lrelu", "tanh", "sigmoid")
-TORCH_ACT = {"gelu": F.gelu, "relu": F.relu, "lrelu": lambda t: F.leaky_relu(t, 0.01), "tanh": torch.tanh, "sigmoid": torch.sigmoid}
 PAD = {(3, 3): (1, 1), (1, 1): (0, 0), (1, 5): (0, 2), (5, 1): (2, 0)}
 
 # tup: the instantiation <KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL> the layer lands on.  view: the input is a view one float into a
@@ -120,73 +120,8 @@ CONVT_ROWS = [
 ]
 
 
-def randn(*shape, seed):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
 def row_id(r):
     return "<%s>" % ",".join(map(str, r.tup)) + ("_view" if getattr(r, "view", False) else "")
-
-
-def samples_of(B, nimg):
-    s = {0, B - 1}
-    if 1 < nimg < B:
-        s |= {nimg - 1, nimg}
-    return sorted(s)
-
-
-def device_input(x, dev, view):
-    """x on the device; view=True: a contiguous view one float into a buffer fenced by NaNs (a read outside x poisons the output)"""
-    if not view:
-        return x.to(dev)
-    buf = torch.full((x.numel() + 8,), float("nan"), device=dev)
-    buf[1:1 + x.numel()] = x.reshape(-1).to(dev)
-    xd = buf[1:1 + x.numel()].view(x.shape)
-    assert xd.is_contiguous() and xd.data_ptr() % 16 == 4
-    return xd
-
-
-def split_x(x):
-    xh = x.half()
-    return xh.double(), (x - xh.float()).half().double()
-
-
-def split_w(w, s):
-    ws = w.float() * (2.0 ** s)
-    wh = ws.half()
-    return wh.double(), (ws - wh.float()).half().double()
-
-
-def split_reference(x, w, b, s, conv):
-    """fp64 {y3, y1, true, A, and the split-exact contribution of the last input channel (d3, d1)} of conv over the given operands"""
-    xh, xl = split_x(x)
-    wh, wl = split_w(w, s)
-    sc = 2.0 ** -s
-    hh = conv(xh, wh)
-    lo = conv(xh, wl) + conv(xl, wh)
-    bb = b.double().view(1, -1, 1, 1)
-    r = dict(y3=sc * (lo + hh) + bb, y1=sc * hh + bb, true=conv(x.double(), w.double()) + bb,
-             A=sc * conv(xh.abs() + xl.abs(), wh.abs() + wl.abs()) + bb.abs())
-    c = x.shape[1] - 1                                  # the last channel of the last chunk
-
-    one = lambda a, m: conv(a[:, c:c + 1], m[:, c:c + 1])   # weights: input channels on dim 1 (conv2d layout and the GEMM layout of convT)
-    r["d1"] = sc * one(xh, wh)
-    r["d3"] = sc * (one(xh, wh) + one(xh, wl) + one(xl, wh))
-    return r
-
-
-def ratio(got, want, bar):
-    return float(((got - want).abs() / bar).max())
-
-
-def check_stats(out_s, st, B, groups, samples):
-    yo = out_s.double()
-    n = yo.shape[0]
-    want = torch.stack([yo.reshape(n, groups, -1).sum(-1), (yo ** 2).reshape(n, groups, -1).sum(-1)], -1)
-    scale = yo.abs().reshape(n, groups, -1).sum(-1)[..., None] + 1.0
-    got = st.cpu().view(B, groups, 2)[samples]
-    rel = float(((got - want).abs() / scale).max())
-    assert rel <= 2e-6, rel
 
 
 @pytest.mark.parametrize("row", ROWS, ids=row_id)

@@ -687,7 +687,8 @@ def test_conv_full_size_linearity(dev):
 
 # ------------------------------------------------------------------------------------------------ norms
 @pytest.mark.parametrize("B,C,H,W,groups", [(2, 16, 32, 32, 8), (1, 64, 64, 64, 8), (3, 8, 5, 7, 8), (2, 24, 16, 16, 24), (2, 480, 4, 4, 480),
-                                            (1, 64, 256, 256, 8)])
+                                            (1, 64, 256, 256, 8),
+                                            (2, 8, 45, 47, 4)])       # H W = 2115 >= 2048 and not a multiple of 4: the scalar form of the large-map apply kernel
 def test_group_norm(dev, B, C, H, W, groups):
     from cineflow import ops
     x = 3 * randn(B, C, H, W, seed=50) + 1.5
@@ -1117,3 +1118,71 @@ def test_conv_stream_prenorm_matches(dev, B, C, H, W, Cout, act):
     xn = F.gelu(xn) if act == "gelu" else F.leaky_relu(xn, 0.01)
     check(out[i:i + 1], F.conv2d(xn, w.cpu().double(), b.cpu().double(), padding=1), 2e-5, "conv_stream prenorm vs fp64")
 
+
+
+# ------------------------------------------------------------------------------------------------ forms the bench's shapes never reach
+def test_group_norm_misaligned_large_map(dev):
+    """gn_apply_kernel<false>: maps of >= 2048 pixels whose tensors are not 16-byte aligned take the scalar form; the input is a view one
+    float into a NaN-fenced buffer, so a vector load that straddled the fence would poison a plane"""
+    from cineflow import ops
+    B, C, H, W, groups = 2, 16, 48, 64, 8
+    x = 3 * randn(B, C, H, W, seed=150) + 1.5
+    g, b = 1 + 0.1 * randn(C, seed=151), 0.1 * randn(C, seed=152)
+    res = randn(B, C, H, W, seed=153)
+    buf = torch.full((x.numel() + 8,), float("nan"), device=dev)
+    buf[1:1 + x.numel()] = x.reshape(-1).to(dev)
+    xd = buf[1:1 + x.numel()].view(x.shape)
+    assert xd.data_ptr() % 16 == 4
+    ref = F.group_norm(x.double(), groups, g.double(), b.double(), 1e-5)
+    check(ops.group_norm(xd, g.to(dev), b.to(dev), groups), ref, 2e-5, "gn, misaligned")
+    check(ops.group_norm(xd, g.to(dev), b.to(dev), groups, act="gelu", res=res.to(dev), res_mode="after_act"), F.gelu(ref) + res.double(), 2e-5)
+    aligned = ops.group_norm(x.to(dev), g.to(dev), b.to(dev), groups)
+    check(ops.group_norm(xd, g.to(dev), b.to(dev), groups), aligned.cpu(), 2e-6, "scalar against vector form")
+
+
+@pytest.mark.parametrize("B,H,W,levels,radius", [(2, 16, 16, 3, 3),      # radius != 4
+                                                 (2, 12, 20, 2, 4),      # H W = 240 is no multiple of 64
+                                                 (1, 32, 32, 5, 4)])     # five levels (the tiled kernel holds four)
+def test_corr_lookup_flat_kernel(dev, B, H, W, levels, radius):
+    """corr_lookup_kernel: every lookup outside the tiled kernel's radius 4 / <= 4 levels / H W % 64 == 0, against the oracle on the oracle's
+    own pyramid (uploaded level by level), at the tolerance of the tiled kernel's tests; coordinates reach past every border"""
+    from cineflow import ops
+    from oracle import ops as OO
+    C = 32
+    f1, f2 = randn(B, C, H, W, seed=160 + levels), randn(B, C, H, W, seed=161 + levels)
+    ref = OO.corr_pyramid(OO.corr_allpairs(f1, f2), levels)
+    pyr = torch.cat([r.reshape(-1) for r in ref]).float().to(dev)
+    assert pyr.numel() == ops.pyramid_numel(B, H, W, levels)
+    coords = OO.coords_grid(B, H, W) + 3.0 * randn(B, 2, H, W, seed=162)
+    out = ops.corr_lookup(pyr, coords.to(dev), levels, radius)
+    assert out.shape == (B, levels * (2 * radius + 1) ** 2, H, W)
+    check(out, OO.corr_lookup(ref, coords, radius), 2e-5, "flat lookup")
+
+
+@pytest.mark.parametrize("B,h,w", [(2, 8, 12), (3, 32, 32), (2, 6, 40)])
+def test_convex_upsample_single_channel(dev, B, h, w):
+    """convex_upsample_rows_kernel<1>: a one-channel field through the row kernel (C = 2 is the flow), a 40-wide map with a second, partly
+    filled 32-column block per row"""
+    from cineflow import ops
+    from oracle import ops as OO
+    f, mask = randn(B, 1, h, w, seed=170 + h), 2 * randn(B, 576, h, w, seed=171 + h)
+    out = ops.convex_upsample(f.to(dev), mask.to(dev))
+    assert out.shape == (B, 1, 8 * h, 8 * w)
+    check(out, OO.convex_upsample(f, mask), 1e-5, "convex upsample C = 1, %dx%d" % (h, w))
+
+
+@pytest.mark.parametrize("K", [2, 3, 8])
+def test_warp_labels_four_pixel_kernel_other_class_counts(dev, K):
+    """warp_labels_2d_v4_kernel<0>: the four-pixel label warp at a class count other than the networks' 4 (run-time class loop), against
+    the oracle's one-hot warp + argmax.  Two class weights that agree to fp32 rounding may resolve differently (the bound test_warp_labels
+    uses for such ties: <= 2 pixels); everything else is a wrong tap or a wrong class."""
+    from cineflow import ops
+    from oracle import ops as OO
+    for (B, H, W, amp) in [(3, 256, 256, 3.0), (2, 40, 24, 5.0)]:
+        flow = amp * randn(B, 2, H, W, seed=180 + H)
+        lab = (torch.rand(B, H, W, generator=torch.Generator().manual_seed(5 + K)) * K).to(torch.uint8)
+        assert int(lab.max()) == K - 1
+        wl = ops.warp_labels(flow[None].to(dev), lab.to(dev), num_classes=K).cpu()
+        wr = OO.warp_labels(flow[None], lab[:, None].float(), num_classes=K)[:, :, 0]
+        mism = int((wl.long() != wr).sum())
+        assert mism <= 2, "label warp K = %d, %dx%d: %d mismatches" % (K, H, W, mism)
