@@ -73,6 +73,8 @@ SIGNATURES = {
     "cf_flip2d": [P, P, I, I, I, I, I, P],
     "cf_tile_accumulate": [P, P, P, P, I, I, I, I, I, I, I, P],
     "cf_tile_finalize": [P, P, P, P, I, I, I, P],
+    "cf_tile_gather": [P, P, P, I, I, I, I, I, I, I, P],
+    "cf_tile_merge": [P, P, P, P, I, I, I, I, I, I, P, I, P, I, P],
     "cf_tta_accumulate_3d": [P, P, I, I, I, I, I, I, I, I, F, P],
     "cf_flip3d": [P, P, I, I, I, I, I, I, I, P],
     "cf_tile_accumulate_3d": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],

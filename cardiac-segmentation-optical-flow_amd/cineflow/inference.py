@@ -68,12 +68,17 @@ def _gaussian_on(device, patch_size):
 
 
 # ------------------------------------------------------------------------------------------------ TTA + tiles
-def mirror_and_predict_2d(net, x, mirror_axes=(0, 1), do_mirroring=True, mult=None):
+def mirror_and_predict_2d(net, x, mirror_axes=(0, 1), do_mirroring=True, mult=None, acc=None, weight=None):
     """SegmentationNetwork._internal_maybe_mirror_and_pred_2D, neural_network.py:573-621 (upstream 4-argument
-    semantics).  x [B,C,X,Y] on the GPU; returns the TTA-averaged softmax [B,K,X,Y] (times `mult` [X,Y])."""
+    semantics).  x [B,C,X,Y] on the GPU; returns the TTA-averaged softmax [B,K,X,Y] (times `mult` [X,Y]).
+    acc / weight: accumulate `weight` times every flip's softmax into the caller's buffer [B,K,X,Y] instead of 1 / flips into a fresh one --
+    the folds of an ensemble share one buffer with weight 1 / (flips * folds); `mult` is then applied by the caller, once."""
     B, _, X, Y = x.shape
-    acc = torch.zeros((B, net.num_classes, X, Y), dtype=torch.float32, device=x.device)
+    shared = acc is not None
+    if not shared:
+        acc = torch.zeros((B, net.num_classes, X, Y), dtype=torch.float32, device=x.device)
     n = 2 ** len(mirror_axes) if do_mirroring else 1
+    w = 1.0 / n if weight is None else weight
     variants = [(0, 0)]
     if do_mirroring:
         if 1 in mirror_axes:
@@ -84,10 +89,93 @@ def mirror_and_predict_2d(net, x, mirror_axes=(0, 1), do_mirroring=True, mult=No
             variants.append((1, 1))
     for fh, fw in variants:
         xin = x if (fh, fw) == (0, 0) else ops.flip2d(x, fh, fw)
-        ops.tta_accumulate(net(xin), acc, fh, fw, 1.0 / n)
+        ops.tta_accumulate(net(xin), acc, fh, fw, w)
+    if mult is not None:
+        assert not shared, "a shared accumulator is weighted by its owner"
+        ops.mul(acc, mult, out=acc)
+    return acc
+
+
+def ensemble_predict_2d(nets, x, mirror_axes=(0, 1), do_mirroring=True, mult=None, acc=None):
+    """The mean over `nets` (the folds; one network or a list) of each network's flip-TTA softmax on the same x [B,C,X,Y] (what
+    predict.py:952-960 / :1074-1082 intend), accumulated in one buffer (`acc` [B,K,X,Y], zero-filled, or a fresh one) through
+    cf_tta_accumulate with weight 1 / (flips * folds), then times `mult`.  One network: mirror_and_predict_2d, operation for operation."""
+    nets = list(nets) if isinstance(nets, (list, tuple)) else [nets]
+    if len(nets) == 1 and acc is None:
+        return mirror_and_predict_2d(nets[0], x, mirror_axes, do_mirroring, mult)
+    B, _, X, Y = x.shape
+    if acc is None:
+        acc = torch.zeros((B, nets[0].num_classes, X, Y), dtype=torch.float32, device=x.device)
+    flips = 2 ** len(mirror_axes) if do_mirroring else 1
+    for net in nets:
+        mirror_and_predict_2d(net, x, mirror_axes, do_mirroring, None, acc=acc, weight=1.0 / (flips * len(nets)))
     if mult is not None:
         ops.mul(acc, mult, out=acc)
     return acc
+
+
+# CF_TILE_JOBS: tiles per network batch of predict_cine_2Dconv_tiled.  64 is predict_3D_2Dconv_tiled's batch bound; the sweep that is to
+# confirm or replace it is `tools/cine_tiled_bench.py --step sweep` (profiles/r05_cine_tiled.md, DESIGN.md section 6)
+TILE_JOBS_PER_LAUNCH = int(os.environ.get("CF_TILE_JOBS", "64"))
+
+
+def _predict_cine_tiled_device(nets, volumes, patch_size, step_size, do_mirroring, mirror_axes, use_gaussian, pad_border_mode, pad_kwargs,
+                               max_batch):
+    """predict_cine_2Dconv_tiled up to the host copies: per volume (seg uint8 [Z,X,Y], softmax [K,Z,X,Y]) as device tensors."""
+    nets = list(nets) if isinstance(nets, (list, tuple)) else [nets]
+    patch_size = tuple(int(v) for v in patch_size)
+    max_batch = int(max_batch or TILE_JOBS_PER_LAUNCH)
+    assert max_batch > 0 and len(nets) > 0
+    dev = torch.device("cuda", torch.cuda.current_device())
+    K = nets[0].num_classes
+    padded, groups = [], {}
+    for i, x in enumerate(volumes):
+        assert x.ndim == 4, "every volume must be (c, z, x, y)"
+        data, slicer = pad_nd_image(x, patch_size, pad_border_mode, pad_kwargs, True)
+        padded.append((data, slicer))
+        groups.setdefault((data.shape[0],) + tuple(data.shape[2:]), []).append(i)
+    results = [None] * len(volumes)
+    for (C, Xp, Yp), idx in groups.items():
+        steps = compute_steps_for_sliding_window(patch_size, (Xp, Yp), step_size)
+        ntile = len(steps[0]) * len(steps[1])
+        stack = np.concatenate([padded[i][0].transpose(1, 0, 2, 3) for i in idx], axis=0)                      # [N,C,Xp,Yp], slice-major
+        vol = torch.from_numpy(np.ascontiguousarray(stack)).to(dev, dtype=torch.float32)
+        N = vol.shape[0]
+        gauss = _gaussian_on(dev, patch_size) if (use_gaussian and ntile > 1) else None
+        # the job table: slice-major, then tile order (lx outer, ly inner) -- the order cf_tile_merge reads the predictions in
+        table = np.empty((N, len(steps[0]), len(steps[1]), 3), dtype=np.int32)
+        table[..., 0] = np.arange(N, dtype=np.int32)[:, None, None]
+        table[..., 1] = np.asarray(steps[0], dtype=np.int32)[None, :, None]
+        table[..., 2] = np.asarray(steps[1], dtype=np.int32)[None, None, :]
+        jobs = torch.from_numpy(table.reshape(N * ntile, 3)).to(dev)
+        pred = torch.zeros((N * ntile, K) + patch_size, dtype=torch.float32, device=dev)
+        for j0 in range(0, N * ntile, max_batch):
+            j1 = min(N * ntile, j0 + max_batch)
+            batch = ops.tile_gather(vol, jobs[j0:j1], patch_size[0], patch_size[1])
+            ensemble_predict_2d(nets, batch, mirror_axes, do_mirroring, gauss, acc=pred[j0:j1])
+        seg, prob = ops.tile_merge(pred, gauss, Xp, Yp, steps[0], steps[1])                                 # [N,Xp,Yp], [N,K,Xp,Yp]
+        del pred
+        n0 = 0
+        for i in idx:
+            Z, slicer = padded[i][0].shape[1], padded[i][1]
+            results[i] = (seg[n0:n0 + Z, slicer[2], slicer[3]], prob[n0:n0 + Z].permute(1, 0, 2, 3)[:, :, slicer[2], slicer[3]])
+            n0 += Z
+    return results
+
+
+def predict_cine_2Dconv_tiled(nets, volumes, patch_size, step_size=0.5, do_mirroring=True, mirror_axes=(0, 1), use_gaussian=True,
+                              pad_border_mode="constant", pad_kwargs=None, max_batch=None):
+    """SegmentationNetwork._internal_predict_3D_2Dconv_tiled (neural_network.py:814-857) for MANY volumes and an ensemble of networks.
+    volumes: list of numpy [C,Z_i,X_i,Y_i] (all frames of a patient, or of several patients); nets: one network or a list (the folds).
+    Returns per volume (seg [Z,X,Y] uint8, softmax [K,Z,X,Y] fp32): the mean over the networks of predict_3D_2Dconv_tiled's softmax.
+
+    Every volume is padded as predict_3D_2Dconv_tiled pads it (pad_nd_image, the same step lists); volumes with one padded in-plane shape
+    are stacked on the slice axis and share one job table.  Per chunk of `max_batch` jobs (default TILE_JOBS_PER_LAUNCH): cf_tile_gather
+    cuts the tiles, every network's flips accumulate into the chunk's rows of the prediction buffer; one cf_tile_merge per group weights,
+    normalises and arg-maxes all slices (bit-identical to the per-tile cf_tile_accumulate + per-slice cf_tile_finalize sequence)."""
+    res = _predict_cine_tiled_device(nets, volumes, patch_size, step_size, do_mirroring, mirror_axes, use_gaussian, pad_border_mode,
+                                     pad_kwargs, max_batch)
+    return [(s.cpu().numpy(), p.cpu().numpy()) for s, p in res]
 
 
 def predict_3D_2Dconv_tiled(net, x, patch_size, step_size=0.5, do_mirroring=True, mirror_axes=(0, 1), use_gaussian=True,
@@ -316,6 +404,8 @@ def predict_cine_slices(flow_net, seg_net, frames, ed_labels=None, do_mirroring=
 
     frames [T,B,1,H,W] float32 on the GPU (B = slices x patients), z-scored;  ed_labels uint8 [B,H,W] or None
     (None -> argmax of the ED frame's segmentation is propagated).
+    seg_net: one network or a list (the selected folds): the softmax is the mean over the folds of each fold's flip-TTA softmax, and the
+    propagated labels are the arg-max of that ensembled ED softmax.  The flow always comes from the one `flow_net`.
     seg_mixed_precision: the segmentation U-Net's convolutions run in the one-term product mode (ops.conv_terms(1): operands rounded to fp16,
     fp32 accumulation and norms) -- the reference's `mixed_precision=True` on the segmentation path (neural_network.py:140-146); the flow
     network always stays f32-class (SegFlowGaussian.py:2905-2909).
@@ -332,11 +422,11 @@ def predict_cine_slices(flow_net, seg_net, frames, ed_labels=None, do_mirroring=
         side = _side_stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side), ops.conv_terms(seg_terms):
-            probs = mirror_and_predict_2d(seg_net, frames.reshape(T * B, 1, H, W), mirror_axes, do_mirroring)
+            probs = ensemble_predict_2d(seg_net, frames.reshape(T * B, 1, H, W), mirror_axes, do_mirroring)
             seg = ops.argmax_channels(probs).view(T, B, H, W)
     else:
         with ops.conv_terms(seg_terms):
-            probs = mirror_and_predict_2d(seg_net, frames.reshape(T * B, 1, H, W), mirror_axes, do_mirroring)
+            probs = ensemble_predict_2d(seg_net, frames.reshape(T * B, 1, H, W), mirror_axes, do_mirroring)
         seg = ops.argmax_channels(probs).view(T, B, H, W)
     # flow: two half sequences that both start at ED, the second one backwards in time (:3120-3127); flow is not
     # TTA-averaged (:3162).  Both chunks run as one batch of 2B sequences when they have equal length.

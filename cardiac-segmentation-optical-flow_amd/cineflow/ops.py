@@ -702,6 +702,34 @@ def tile_finalize(agg, cnt):
     return seg, probs
 
 
+def tile_gather(src, jobs, ph, pw):
+    """src [N,C,X,Y]; jobs: device int32 [J,3] = (n, lx, ly) -> [J,C,ph,pw], dst[j] = src[n_j][:, lx_j:lx_j+ph, ly_j:ly_j+pw]."""
+    N, C, X, Y = src.shape
+    if not isinstance(jobs, torch.Tensor) or not jobs.is_cuda or jobs.dtype != torch.int32 or not jobs.is_contiguous() or jobs.dim() != 2 \
+            or jobs.shape[1] != 3:
+        raise TypeError("jobs must be a contiguous CUDA int32 tensor [J,3]")
+    J = jobs.shape[0]
+    dst = torch.empty((J, C, ph, pw), dtype=torch.float32, device=src.device)
+    check(lib().cf_tile_gather(_f32(src), jobs.data_ptr(), _f32(dst), J, N, C, X, Y, ph, pw, _stream()), "cf_tile_gather")
+    return dst
+
+
+def tile_merge(pred, gauss, X, Y, lx, ly):
+    """pred [N*len(lx)*len(ly),K,ph,pw] (slice-major, then tile order lx outer / ly inner), gauss [ph,pw] or None, lx / ly: the host step
+    lists -> (seg uint8 [N,X,Y], probs [N,K,X,Y]); bit-identical to tile_accumulate per tile + tile_finalize per slice."""
+    import ctypes
+    J, K, ph, pw = pred.shape
+    nx, ny = len(lx), len(ly)
+    assert J % (nx * ny) == 0, (J, nx, ny)
+    N = J // (nx * ny)
+    probs = torch.empty((N, K, X, Y), dtype=torch.float32, device=pred.device)
+    seg = torch.empty((N, X, Y), dtype=torch.uint8, device=pred.device)
+    clx, cly = (ctypes.c_int * nx)(*[int(v) for v in lx]), (ctypes.c_int * ny)(*[int(v) for v in ly])
+    check(lib().cf_tile_merge(_f32(pred), _opt(gauss), _f32(probs), _u8(seg), N, K, X, Y, ph, pw, ctypes.cast(clx, ctypes.c_void_p), nx,
+                              ctypes.cast(cly, ctypes.c_void_p), ny, _stream()), "cf_tile_merge")
+    return seg, probs
+
+
 def tta_accumulate_3d(logits, acc, flip_d, flip_h, flip_w, weight):
     B, K, D, H, W = logits.shape
     assert acc.shape == logits.shape

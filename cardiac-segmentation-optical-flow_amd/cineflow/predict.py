@@ -16,6 +16,15 @@ Differences that are deliberate and documented in DESIGN.md:
     exporter resamples back; the heart centroid of `Processor` comes from the cropping network of plans['cropping_net']
     when the folder has one (the reference's MTLmodel cropper), else from the patch centre;
   * when no ED label map is supplied the ED segmentation predicted by the U-Net is the one propagated;
+  * every selected fold is used (`folds=None`: every `fold_X`): `CineTrainer.load_ensemble` keeps one packed segmentation U-Net per fold
+    resident and the segmentation softmax is the mean over the folds of each fold's flip-TTA softmax (what predict.py:952-960 / :1074-1082
+    intend; as written those lines cannot run with more than one fold).  The flow comes from the first selected fold's flow network only
+    (in the reference only params[0] ever produces one, :318 / :1028), flow fields are never averaged, and the propagated labels are the
+    arg-max of the ensembled ED softmax warped with that flow;
+  * a `plans.json` without 'flow_net' is a segmentation-only model (a plain 2-D nnU-Net folder): the dispatch of predict.py:320-353 then
+    takes the predict_non_flow side -- every frame is written to `<out>/<patient>/<case>.nii.gz` (+ `<case>.npz` / `.pkl` with save_npz,
+    :993-997), nothing under Flow/ or Registered/, postprocessing.json applied to those files; all frames of all patients of a device batch
+    go through the cine-batched sliding window (cineflow.inference.predict_cine_2Dconv_tiled) in one call;
   * `predict_from_folder` loads the model once and fills the device batch ACROSS patients: the cropped slices of as many patients as fit
     `MAX_SLICES_PER_LAUNCH` (64) go through the networks as one batch (`CineTrainer.predict_patients_flow`), the next group's files are
     read and preprocessed by the `num_threads_preprocessing` pool meanwhile, and the NIfTI / NPZ export of finished patients runs in the
@@ -36,7 +45,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .inference import Processor, chunk_orders, normalize_intensity_, pad_nd_image, predict_3D_2Dconv_tiled, predict_cine_slices
+from .inference import (Processor, _predict_cine_tiled_device, chunk_orders, normalize_intensity_, pad_nd_image, predict_3D_2Dconv_tiled,  # noqa: F401
+                        predict_cine_2Dconv_tiled, predict_cine_slices)
 from .models import Generic_UNet, SegFlowGaussian
 from .nifti import read_nifti, write_nifti
 
@@ -69,21 +79,28 @@ LAST_TIMING = {}                                                     # wall-time
 # ------------------------------------------------------------------------------------------------ model folder
 def save_model_folder(folder, seg_net, flow_net, plans, fold=0, checkpoint_name="model_final_checkpoint", seg_sd=None, flow_sd=None, crop_sd=None):
     """Write `<folder>/plans.json` and `<folder>/fold_<fold>/<checkpoint_name>.model` (state dicts keyed by the
-    reference's parameter names).  `seg_sd` / `flow_sd` / `crop_sd` (the Processor's cropping network, plans['cropping_net']): {name: tensor}."""
+    reference's parameter names).  `seg_sd` / `flow_sd` / `crop_sd` (the Processor's cropping network, plans['cropping_net']): {name: tensor}.
+    A segmentation-only folder (plans without 'flow_net') is written with flow_net = flow_sd = None: the checkpoint then has no
+    'flow_state_dict'."""
     os.makedirs(join(folder, "fold_%d" % fold), exist_ok=True)
     with open(join(folder, "plans.json"), "w") as f:
         json.dump(plans, f, indent=1)
-    ck = {"seg_state_dict": {k: v.cpu() for k, v in seg_sd.items()}, "flow_state_dict": {k: v.cpu() for k, v in flow_sd.items()}}
+    ck = {"seg_state_dict": {k: v.cpu() for k, v in seg_sd.items()}}
+    if flow_sd is not None:
+        ck["flow_state_dict"] = {k: v.cpu() for k, v in flow_sd.items()}
     if crop_sd is not None:
         ck["crop_state_dict"] = {k: v.cpu() for k, v in crop_sd.items()}
     torch.save(ck, join(folder, "fold_%d" % fold, checkpoint_name + ".model"))
 
 
 def default_plans(image_size=256, crop_size=None, flow_variant="video", seg_base=32, seg_pool=6, reduced=None):
+    """flow_variant=None: the plans of a segmentation-only model (no 'flow_net', no 'crop_size')."""
     p = {"num_modalities": 1, "num_classes": 4, "patch_size": [image_size, image_size], "transpose_forward": [0, 1, 2],
          "transpose_backward": [0, 1, 2], "mirror_axes": [0, 1], "crop_size": crop_size or image_size, "image_size": image_size,
          "seg_net": {"base_num_features": seg_base, "num_pool": seg_pool},
          "flow_net": {"variant": flow_variant, "kwargs": reduced or {}}}
+    if flow_variant is None:
+        del p["flow_net"], p["crop_size"]
     return p
 
 
@@ -131,7 +148,10 @@ class CineTrainer:
     `<weights>/config.yaml`.  `prediction: false` is supplied when the file lacks it (raft_config.yaml).
     plans['cropping_net'] = {'type': 'mtl', 'config': <adversarial_acdc.yaml values or file name>, 'window_size': 7} puts the reference's own
     cropping network -- MTLmodel(num_classes=2), voxelmorph_saver_Lib.py:340-348 -- into the Processor; {'base_num_features', 'num_pool'}
-    keeps the 2-class Generic_UNet stand-in of round 2."""
+    keeps the 2-class Generic_UNet stand-in of round 2.
+    Plans without 'flow_net' (or with null) describe a segmentation-only model -- a plain 2-D nnU-Net folder: `flow_net` is None, neither
+    'crop_size' nor a cropping network is needed, and the file-level API takes the reference's predict_non_flow route (predict.py:320-353).
+    `seg_nets` holds one packed Generic_UNet per selected fold (`load_ensemble`); `seg_net` is seg_nets[0]."""
 
     def __init__(self, plans, device, model_folder=None):
         self.plans = plans
@@ -139,13 +159,15 @@ class CineTrainer:
         self.num_classes = plans["num_classes"]
         self.data_aug_params = {"mirror_axes": tuple(plans["mirror_axes"])}
         self.patch_size = tuple(plans["patch_size"])
-        self.processor = Processor(crop_size=plans["crop_size"], image_size=plans["patch_size"][0])
+        fk = plans.get("flow_net")
+        # (a segmentation-only model has no heart-centred crop: no Processor)
+        self.processor = Processor(crop_size=plans["crop_size"], image_size=plans["patch_size"][0]) if (fk or "crop_size" in plans) else None
         # mixed_precision of load_model_and_checkpoint_files / predict_from_folder (the reference's default True): with CF_SEG_MIXED_PRECISION=1
         # the segmentation U-Net runs its convolutions in the one-term fp16 product mode (ops.conv_terms(1)), like the reference's autocast on
         # that path (neural_network.py:140-146); the flow network never does (SegFlowGaussian.py:2905-2909).  Default: flag accepted, f32-class.
         self.mixed_precision = False
         self.crop_net = None
-        ck = plans.get("cropping_net")
+        ck = plans.get("cropping_net") if self.processor is not None else None
         if ck:
             from .inference import CroppingNet
             if ck.get("type") == "mtl":
@@ -157,11 +179,11 @@ class CineTrainer:
             else:
                 self.crop_net = Generic_UNet(1, ck["base_num_features"], 2, ck["num_pool"])
                 self.processor.cropping_network = CroppingNet(self.crop_net)
-        sk = plans["seg_net"]
-        self.seg_net = Generic_UNet(plans["num_modalities"], sk["base_num_features"], self.num_classes, sk["num_pool"],
-                                    pool_op_kernel_sizes=sk.get("pool_op_kernel_sizes"))     # the plans' per-stage pooling (plans_per_stage[...]['pool_op_kernel_sizes'])
-        fk = plans["flow_net"]
-        if fk.get("config") is not None:
+        self.seg_net = self._new_seg_net()
+        self.seg_nets = [self.seg_net]                                           # one network per selected fold (load_ensemble)
+        if not fk:
+            self.flow_net = None
+        elif fk.get("config") is not None:
             from . import config as C
             cfg = C.with_defaults(_config_values(fk["config"], model_folder, C.read_config_video), prediction=False)
             net = C.build_flow_net(cfg, image_size=plans["crop_size"])
@@ -172,14 +194,38 @@ class CineTrainer:
             kw.update(fk.get("kwargs", {}))
             self.flow_net = SegFlowGaussian(**kw)
 
+    def _new_seg_net(self):
+        sk = self.plans["seg_net"]
+        return Generic_UNet(self.plans["num_modalities"], sk["base_num_features"], self.num_classes, sk["num_pool"],
+                            pool_op_kernel_sizes=sk.get("pool_op_kernel_sizes"))     # the plans' per-stage pooling (plans_per_stage[...]['pool_op_kernel_sizes'])
+
     # -- network_trainer.py:418 load_checkpoint_ram(params, train)
     def load_checkpoint_ram(self, params, train=False):
+        """one fold: its weights go into seg_net / flow_net / crop_net, and the ensemble is that fold alone"""
         self.seg_net.load_state_dict(params["seg_state_dict"], self.device)
-        self.flow_net.load_state_dict(params["flow_state_dict"], self.device)
+        self.seg_nets = [self.seg_net]
+        if self.flow_net is not None:
+            if "flow_state_dict" not in params:
+                raise KeyError("plans['flow_net'] is set but the checkpoint has no 'flow_state_dict' (a segmentation-only checkpoint)")
+            self.flow_net.load_state_dict(params["flow_state_dict"], self.device)
         if self.crop_net is not None:
             if "crop_state_dict" not in params:
                 raise KeyError("plans['cropping_net'] is set but the checkpoint has no 'crop_state_dict' (save_model_folder(..., crop_sd=...))")
             self.crop_net.load_state_dict(params["crop_state_dict"], self.device)
+
+    def load_ensemble(self, params_list):
+        """Every selected fold resident at once: fold 0 loads exactly as load_checkpoint_ram loads it (segmentation, flow and cropping
+        networks); every further fold gets a Generic_UNet of its own, built and packed here, once -- its f16 / Winograd weight forms are
+        derived on first use and then kept, never re-packed per batch.  The flow and the cropping network are fold 0's alone: in the
+        reference only params[0] ever produces a flow (predict.py:318, :1028)."""
+        assert len(params_list) >= 1
+        self.load_checkpoint_ram(params_list[0], False)
+        nets = [self.seg_net]
+        for p_ in params_list[1:]:
+            net = self._new_seg_net()
+            net.load_state_dict(p_["seg_state_dict"], self.device)
+            nets.append(net)
+        self.seg_nets = nets
 
     # -- nnUNetTrainer.py:571-597 preprocess_patient(list_of_files) -> (data[C,Z,Y,X], seg, properties)
     def preprocess_patient(self, input_files):
@@ -210,10 +256,35 @@ class CineTrainer:
                                                          step_size=0.5, use_gaussian=True, pad_border_mode="constant", pad_kwargs=None,
                                                          all_in_gpu=False, verbose=True, mixed_precision=True):
         mirror_axes = self.data_aug_params["mirror_axes"] if mirror_axes is None else mirror_axes
+        """(seg [Z,X,Y], softmax [K,Z,X,Y]) of one preprocessed volume; with several folds resident (load_ensemble) the softmax is the
+        mean over the folds of each fold's flip-TTA sliding-window softmax."""
         with ops.conv_terms(1 if (mixed_precision and SEG_MIXED_PRECISION) else 3):
-            return predict_3D_2Dconv_tiled(self.seg_net, data, self.patch_size, step_size=step_size, do_mirroring=do_mirroring,
-                                           mirror_axes=mirror_axes, use_gaussian=use_gaussian, pad_border_mode=pad_border_mode,
-                                           pad_kwargs=pad_kwargs)
+            if len(self.seg_nets) == 1:
+                return predict_3D_2Dconv_tiled(self.seg_net, data, self.patch_size, step_size=step_size, do_mirroring=do_mirroring,
+                                               mirror_axes=mirror_axes, use_gaussian=use_gaussian, pad_border_mode=pad_border_mode,
+                                               pad_kwargs=pad_kwargs)
+            return predict_cine_2Dconv_tiled(self.seg_nets, [data], self.patch_size, step_size=step_size, do_mirroring=do_mirroring,
+                                             mirror_axes=mirror_axes, use_gaussian=use_gaussian, pad_border_mode=pad_border_mode,
+                                             pad_kwargs=pad_kwargs)[0]
+
+    def predict_volumes_seg(self, volumes, do_mirroring=True, mirror_axes=None, step_size=0.5, use_gaussian=True, pad_border_mode="constant",
+                            pad_kwargs=None, mixed_precision=True, want_softmax=True):
+        """The segmentation-only device stage of the file-level API: every volume [C,Z,Y,X] of a patient group (all frames of all its
+        patients) through predict_cine_2Dconv_tiled's device path in ONE call, all resident folds ensembled.  Returns per volume
+        (seg uint8 [Z,Y,X], softmax [K,Z,Y,X] or None) as host arrays (pinned staging, one synchronisation)."""
+        mirror_axes = self.data_aug_params["mirror_axes"] if mirror_axes is None else mirror_axes
+        with ops.conv_terms(1 if (mixed_precision and SEG_MIXED_PRECISION) else 3):
+            res = _predict_cine_tiled_device(self.seg_nets, volumes, self.patch_size, step_size, do_mirroring, mirror_axes, use_gaussian,
+                                             pad_border_mode, pad_kwargs, None)
+        dev_out = []
+        for s_, p_ in res:
+            dev_out.append(s_.contiguous())
+            if want_softmax:
+                dev_out.append(p_.contiguous())
+        host = self._to_host(dev_out)
+        if want_softmax:
+            return [(host[2 * i], host[2 * i + 1]) for i in range(len(res))]
+        return [(h, None) for h in host]
 
     # -- SegFlowGaussian.py:3294-3533 up to the network call: pad, centre crop to the patch, heart-centred crop, z-score
     def _flow_prepare(self, unlabeled, target, processor, pad_border_mode, pad_kwargs, centroid):
@@ -316,6 +387,9 @@ class CineTrainer:
         on the slice axis, predict_cine_slices runs once per such group, and each patient's slices go back through its own un-crop
         (`_flow_finish`).  No kernel mixes batch entries; results are those of the one-patient calls up to the launch shapes the batch
         size selects.  Returns one result tuple per patient, in order."""
+        if self.flow_net is None:
+            raise RuntimeError("this is a segmentation-only model (plans.json has no 'flow_net'): there is no flow route; "
+                               "use predict_preprocessed_data_return_seg_and_softmax / predict_volumes_seg")
         processor = processor or self.processor
         mirror_axes = self.data_aug_params["mirror_axes"] if mirror_axes is None else mirror_axes
         n = len(unlabeled_list)
@@ -336,7 +410,7 @@ class CineTrainer:
         for (_T, has_ed), idx in by_T.items():
             frames = preps[idx[0]]["frames"] if len(idx) == 1 else torch.cat([preps[i]["frames"] for i in idx], dim=1)
             ed = None if not has_ed else (preps[idx[0]]["ed"] if len(idx) == 1 else torch.cat([preps[i]["ed"] for i in idx], dim=0))
-            out = predict_cine_slices(self.flow_net, self.seg_net, frames.contiguous(), ed, do_mirroring, mirror_axes,
+            out = predict_cine_slices(self.flow_net, self.seg_nets if len(self.seg_nets) > 1 else self.seg_net, frames.contiguous(), ed, do_mirroring, mirror_axes,
                                       seg_mixed_precision=bool(self.mixed_precision and SEG_MIXED_PRECISION))
             z0 = 0
             for i in idx:
@@ -442,10 +516,12 @@ def get_lowres_axis(new_spacing):
 def save_segmentation_nifti_from_softmax(segmentation_softmax, out_fname, properties_dict, order=1, region_class_order=None,
                                          seg_postprogess_fn=None, seg_postprocess_args=None, resampled_npz_fname=None,
                                          non_postprocessed_fname=None, force_separate_z=None, interpolation_order_z=0, verbose=True,
-                                         flow=None, flow_path=None, registered=None, registered_path=None, seg_precomputed=None):
+                                         flow=None, flow_path=None, registered=None, registered_path=None, seg_precomputed=None,
+                                         properties_pkl=False):
     """segmentation_export.py:29-223: resample softmax / flow / registered labels back to the size before resampling (device
     kernels, cineflow.ops.resample_data_or_seg), rescale the flow to the new pixel grid, argmax, place into the crop bounding
-    box, write uint8 NIfTI with the case's geometry; flow [2,Z,Y,X] -> npz `flow` [Y,X,Z,2] float32 + `spacing`."""
+    box, write uint8 NIfTI with the case's geometry; flow [2,Z,Y,X] -> npz `flow` [Y,X,Z,2] float32 + `spacing`.
+    properties_pkl: also write the properties next to the npz as `<npz name>.pkl` (segmentation_export.py:143; the segmentation-only route)."""
     if isinstance(segmentation_softmax, str):
         assert os.path.isfile(segmentation_softmax), "If isinstance(segmentation_softmax, str) then isfile(segmentation_softmax) must be True"
         del_file = segmentation_softmax
@@ -494,6 +570,10 @@ def save_segmentation_nifti_from_softmax(segmentation_softmax, out_fname, proper
         seg_old_spacing = segmentation_softmax
     if resampled_npz_fname is not None:
         np.savez_compressed(resampled_npz_fname, softmax=seg_old_spacing.astype(np.float16))
+        if properties_pkl:
+            import pickle
+            with open(resampled_npz_fname[:-4] + ".pkl", "wb") as f:
+                pickle.dump(properties_dict, f)
     if seg_precomputed is not None:
         seg = np.asarray(seg_precomputed)
     elif region_class_order is None:
@@ -701,28 +781,53 @@ def predict_flow(d, trainer, output_filenames, property_list, do_tta, mixed_prec
     return seg_paths, flow_paths, reg_paths
 
 
+def _export_seg_patient(results, trainer, output_filenames, property_list, interpolation_order, force_separate_z, interpolation_order_z,
+                        save_npz, pool):
+    """predict.py:962-997 for one patient's (seg, softmax or None) per frame: transpose back, one export job per frame writing
+    `output_filenames[t]` (+ <case>.npz / .pkl with save_npz).  Returns (paths, jobs)."""
+    tb_ = trainer.plans.get("transpose_backward") if trainer.plans.get("transpose_forward") is not None else None
+    jobs = []
+    for t, (seg, softmax) in enumerate(results):
+        if tb_ is not None:
+            if softmax is not None:
+                softmax = np.ascontiguousarray(softmax.transpose([0] + [i + 1 for i in tb_]))
+            else:
+                seg = np.ascontiguousarray(seg.transpose(tb_))
+        npz = output_filenames[t][:-7] + ".npz" if save_npz else None
+        jobs.append(pool.apply_async(_timed_export, (trainer.device, softmax, output_filenames[t], property_list[t], interpolation_order, None, None,
+                                                     None, npz, None, force_separate_z, interpolation_order_z, False, None, None, None, None,
+                                                     None if softmax is not None else seg, bool(save_npz))))
+    return list(output_filenames), jobs
+
+
+def _finish_seg_patient(paths, jobs, disable_postprocessing, model):
+    """wait for a patient's export jobs, then predict.py:1139-1156 on the files of the segmentation-only route"""
+    work = sum(j.get() for j in jobs)
+    if not disable_postprocessing:
+        pp_file = join(model, "postprocessing.json")
+        if os.path.isfile(pp_file):
+            print("postprocessing...")
+            shutil.copy(pp_file, os.path.abspath(os.path.dirname(paths[0])))
+            for_which_classes, min_valid_obj_size = load_postprocessing(pp_file)
+            for pth in paths:
+                load_remove_save(pth, pth, for_which_classes, min_valid_obj_size)
+        else:
+            print("WARNING! Cannot run postprocessing because the postprocessing file is missing (%s)" % model)
+    return work
+
+
 def predict_non_flow(d, trainer, output_filenames, property_list, do_tta, mixed_precision, params, interpolation_order, force_separate_z,
                      interpolation_order_z, all_in_gpu, step_size, save_npz, disable_postprocessing, model, pool):
-    """predict.py:926-1005: segmentation only, frame by frame, sliding window + TTA, fold ensembling."""
-    jobs = []
-    for t, input_img in enumerate(d):
-        print("predicting", output_filenames[t])
-        trainer.load_checkpoint_ram(params[0], False)
-        softmax = trainer.predict_preprocessed_data_return_seg_and_softmax(
-            input_img, do_mirroring=do_tta, mirror_axes=trainer.data_aug_params["mirror_axes"], use_sliding_window=True,
-            step_size=step_size, use_gaussian=True, all_in_gpu=all_in_gpu, mixed_precision=mixed_precision)[1]
-        for p_ in params[1:]:
-            trainer.load_checkpoint_ram(p_, False)
-            softmax += trainer.predict_preprocessed_data_return_seg_and_softmax(
-                input_img, do_mirroring=do_tta, mirror_axes=trainer.data_aug_params["mirror_axes"], use_sliding_window=True,
-                step_size=step_size, use_gaussian=True, all_in_gpu=all_in_gpu, mixed_precision=mixed_precision)[1]
-        if len(params) > 1:
-            softmax /= len(params)
-        npz = output_filenames[t][:-7] + ".npz" if save_npz else None
-        jobs.append(pool.apply_async(save_segmentation_nifti_from_softmax,
-                                     (softmax, output_filenames[t], property_list[t], interpolation_order, None, None, None, npz, None,
-                                      force_separate_z, interpolation_order_z)))
-    return jobs
+    """predict.py:926-1005: segmentation only, sliding window + TTA; the softmax of every frame is the mean over the folds in `params`
+    (what :952-960 intend; as written :955 passes the frame list and only the first frame is reached).  All folds are made resident once
+    (`load_ensemble`), all frames go through predict_cine_2Dconv_tiled in one call.  Returns the export jobs."""
+    if getattr(trainer, "_ensemble_of", None) is not params:
+        trainer.load_ensemble(params)
+        trainer._ensemble_of = params
+    print("predicting", output_filenames)
+    results = trainer.predict_volumes_seg(list(d), do_mirroring=do_tta, step_size=step_size, mixed_precision=mixed_precision)
+    return _export_seg_patient(results, trainer, output_filenames, property_list, interpolation_order, force_separate_z, interpolation_order_z,
+                               save_npz, pool)[1]
 
 
 _MODEL_CACHE = {}
@@ -757,7 +862,7 @@ def _model_stamp(model, folds, checkpoint_name):
 
 
 def _cached_model(model, folds, mixed_precision, checkpoint_name):
-    """load_model_and_checkpoint_files + load_checkpoint_ram once per (folder, folds, checkpoint, mixed_precision, device, the CF_* knobs in
+    """load_model_and_checkpoint_files + load_ensemble (every selected fold) once per (folder, folds, checkpoint, mixed_precision, device, the CF_* knobs in
     force) and per state of the files on disk (`_model_stamp`): predict_from_folder used to rebuild both networks and re-read the checkpoint
     for every patient.  The reference re-reads the checkpoint on every predict_cases call; `clear_model_cache()` forces that here."""
     knobs = tuple(sorted((k, v) for k, v in os.environ.items() if k.startswith("CF_")))
@@ -767,7 +872,8 @@ def _cached_model(model, folds, mixed_precision, checkpoint_name):
     if hit is None or hit[0] != stamp:
         _MODEL_CACHE.clear()                                                     # one model resident at a time
         trainer, params = load_model_and_checkpoint_files(model, folds, mixed_precision=mixed_precision, checkpoint_name=checkpoint_name)
-        trainer.load_checkpoint_ram(params[0], False)
+        trainer.load_ensemble(params)                                            # every selected fold resident, packed once
+        trainer._ensemble_of = params
         hit = (stamp, trainer, params)
         _MODEL_CACHE[key] = hit
     return hit[1], hit[2]
@@ -777,7 +883,10 @@ def _predict_patients(model, cases, folds, save_npz, num_threads_preprocessing, 
                       step_size, checkpoint_name, segmentation_export_kwargs, disable_postprocessing, max_slices=None):
     """predict.py:228-354 + :1008-1110 for a LIST of patients (`cases[i]` = (list_of_lists, output_filenames, ed_index)): the model is loaded
     once, frames are read and preprocessed by a thread pool one group of patients ahead, every group's cropped slices (up to `max_slices`)
-    share one device batch, and finished patients are exported by the NIfTI pool while the next group is on the device."""
+    share one device batch, and finished patients are exported by the NIfTI pool while the next group is on the device.
+    A segmentation-only model (trainer.flow_net is None) takes the reference's other branch (predict.py:320-353 -> predict_non_flow) inside the
+    same pipeline: all frames of all patients of a group go through predict_cine_2Dconv_tiled's device path in one call, every frame is
+    written to `output_filenames[t]` itself, nothing under Flow/ or Registered/; ED index, voxelmorph_raw and Processor are not used."""
     import sys
     import time
     from collections import deque
@@ -799,14 +908,18 @@ def _predict_patients(model, cases, folds, save_npz, num_threads_preprocessing, 
         force_separate_z = segmentation_export_kwargs["force_separate_z"]
         interpolation_order = segmentation_export_kwargs["interpolation_order"]
         interpolation_order_z = segmentation_export_kwargs["interpolation_order_z"]
+    seg_only = trainer.flow_net is None
     orders = []
     for list_of_lists, output_filenames, ed_index in cases:
         assert len(list_of_lists) == len(output_filenames)
         for o in output_filenames:
-            for sub in ("Segmentation", "Flow", "Registered"):
-                os.makedirs(join(os.path.dirname(o), sub), exist_ok=True)
+            for sub in ((None,) if seg_only else ("Segmentation", "Flow", "Registered")):
+                os.makedirs(join(os.path.dirname(o), sub) if sub else os.path.dirname(os.path.abspath(o)), exist_ok=True)
         T = len(list_of_lists)
-        orders.append(list(range(ed_index, T)) + list(range(0, ed_index)))      # ED first (put_ed_first, predict.py:1165-1193)
+        if seg_only:
+            orders.append(list(range(T)))                                        # frames are independent: no ED rotation
+        else:
+            orders.append(list(range(ed_index, T)) + list(range(0, ed_index)))  # ED first (put_ed_first, predict.py:1165-1193)
 
     import itertools
     import threading
@@ -840,6 +953,13 @@ def _predict_patients(model, cases, folds, save_npz, num_threads_preprocessing, 
             nxt += 1
 
     finishing = deque()                                                          # exports in flight: (seg_paths, reg_paths, jobs, output files)
+
+    def finish(item):
+        sp, rp, jobs, outs = item
+        if rp is None:                                                           # segmentation-only route
+            return _finish_seg_patient(sp, jobs, disable_postprocessing, model)
+        return _finish_flow_patient(sp, rp, jobs, outs, disable_postprocessing, model)
+
     sys.setswitchinterval(GIL_SWITCH_INTERVAL)                                   # restored in the finally below
     try:
         # slices of a patient are only known after preprocessing; groups are filled greedily in patient order.  The pool runs `ahead` patients
@@ -872,11 +992,33 @@ def _predict_patients(model, cases, folds, save_npz, num_threads_preprocessing, 
                 nslices += z
                 carry = None
             t0 = time.perf_counter()
-            unl = [np.stack([p_[0] for p_ in pre]) + 1e-8 for _ci, pre in group]      # predict.py:1025
             print("predicting %d patient(s), %d slices in one device batch" % (len(group), nslices))
             cap = min(max_slices, 2 * cap)
             ahead = max(ahead, 2 * len(group) + 2)
             submit_more(ahead)
+            if seg_only:
+                tf_ = list(trainer.plans["transpose_forward"])
+                resampled = any(tuple(p_[0].shape[1:]) != tuple(np.array(p_[2]["size_after_cropping"])[tf_]) for _ci, pre in group for p_ in pre)
+                flat = trainer.predict_volumes_seg([p_[0] for _ci, pre in group for p_ in pre], do_mirroring=do_tta, step_size=step_size,
+                                                   mixed_precision=mixed_precision, want_softmax=bool(save_npz or resampled))
+                torch.cuda.synchronize()
+                timing["device_s"] += time.perf_counter() - t0
+                timing["device_batches"] += 1
+                timing["slices"] += nslices
+                f0 = 0
+                for ci, pre in group:
+                    outs = [cases[ci][1][i] for i in orders[ci]]
+                    timing["frames"] += len(outs)
+                    paths, jobs = _export_seg_patient(flat[f0:f0 + len(pre)], trainer, outs, [p_[2] for p_ in pre], interpolation_order,
+                                                      force_separate_z, interpolation_order_z, save_npz, pool)
+                    f0 += len(pre)
+                    finishing.append((paths, None, jobs, outs))
+                while len(finishing) > 2 * max(1, len(group)):
+                    t0 = time.perf_counter()
+                    timing["export_work_s"] += finish(finishing.popleft())
+                    timing["export_wait_s"] += time.perf_counter() - t0
+                continue
+            unl = [np.stack([p_[0] for p_ in pre]) + 1e-8 for _ci, pre in group]      # predict.py:1025
             # the crop-space copies only when the voxelmorph_saver tree is being written; the `raw` tensor (frames + crop-space flow) the
             # reference returns for its trainer's plots is not consumed by the exporter
             # the probabilities come to the host only if the exporter needs them: for the npz, or to resample them back to the size
@@ -897,13 +1039,11 @@ def _predict_patients(model, cases, folds, save_npz, num_threads_preprocessing, 
                 finishing.append((sp, rp, jobs, outs))
             while len(finishing) > 2 * max(1, len(group)):                       # bound the host memory held by queued exports
                 t0 = time.perf_counter()
-                sp, rp, jobs, outs = finishing.popleft()
-                timing["export_work_s"] += _finish_flow_patient(sp, rp, jobs, outs, disable_postprocessing, model)
+                timing["export_work_s"] += finish(finishing.popleft())
                 timing["export_wait_s"] += time.perf_counter() - t0
         t0 = time.perf_counter()
         while finishing:
-            sp, rp, jobs, outs = finishing.popleft()
-            timing["export_work_s"] += _finish_flow_patient(sp, rp, jobs, outs, disable_postprocessing, model)
+            timing["export_work_s"] += finish(finishing.popleft())
         timing["export_wait_s"] += time.perf_counter() - t0
     except BaseException:
         # a failed batch must not wait for every queued preprocessing / export job: drop them
@@ -922,6 +1062,8 @@ def _predict_patients(model, cases, folds, save_npz, num_threads_preprocessing, 
         DEVICE_SPLIT.clear()
     LAST_TIMING.clear()
     LAST_TIMING.update(timing)
+    if seg_only:
+        return [list(c[1]) for c in cases]                                       # the written label files, per patient
     return [[(_subfolder_path(o, "Segmentation"), _subfolder_path(o, "Flow")[:-7] + ".npz", _subfolder_path(o, "Registered")) for o in c[1]]
             for c in cases]
 
@@ -964,13 +1106,16 @@ def predict_from_folder(model, input_folder, output_folder, folds, save_npz, num
                         overwrite_all_in_gpu=None, step_size=0.5, checkpoint_name="model_final_checkpoint",
                         segmentation_export_kwargs=None, disable_postprocessing=False):
     """predict.py:665-780.  Patients are sharded `patients[part_id::num_parts]` (one process per GPU); every patient of
-    the shard is processed.  (set_voxelmorph_raw / the CLI's --voxelmorph_raw additionally produce the voxelmorph_saver input tree;
+    the shard is processed.  Returns {patient: per frame (Segmentation, Flow, Registered) paths}; for a segmentation-only model folder
+    (plans.json without 'flow_net') {patient: the written `<out>/<patient>/<case>.nii.gz` paths}.  (set_voxelmorph_raw / the CLI's --voxelmorph_raw additionally produce the voxelmorph_saver input tree;
     the argument list itself is the reference's, name for name.)"""
     os.makedirs(output_folder, exist_ok=True)
     assert os.path.isfile(join(model, "plans.json")), "Folder with saved model weights must contain a plans.json file"
     shutil.copy(join(model, "plans.json"), output_folder)
     with open(join(model, "plans.json")) as f:
-        expected_num_modalities = json.load(f)["num_modalities"]
+        model_plans = json.load(f)
+    expected_num_modalities = model_plans["num_modalities"]
+    seg_only = not model_plans.get("flow_net")                                   # a plain 2-D nnU-Net folder: predict.py:320-353's other branch
     if mode not in ("normal", "fast", "fastest"):
         raise ValueError("unrecognized mode. Must be normal, fast or fastest")
     patients = sorted(p for p in os.listdir(input_folder) if os.path.isdir(join(input_folder, p)))
@@ -983,8 +1128,9 @@ def predict_from_folder(model, input_folder, output_folder, folds, save_npz, num
     for patient in shard:
         current_input_folder = join(input_folder, patient)
         current_output_folder = join(output_folder, patient)
-        for sub in ("Flow", "Registered", "Segmentation"):
+        for sub in (() if seg_only else ("Flow", "Registered", "Segmentation")):
             os.makedirs(join(current_output_folder, sub), exist_ok=True)
+        os.makedirs(current_output_folder, exist_ok=True)
         case_ids = check_input_folder_and_return_caseIDs(current_input_folder, expected_num_modalities)
         output_files = [join(current_output_folder, i + ".nii.gz") for i in case_ids]
         all_files = subfiles(current_input_folder, suffix=".nii.gz", join_=False, sort=True)

@@ -16,7 +16,10 @@ and `python -m cineflow.predict -m ...` take unchanged (save_model_folder).  Not
 `np.mean(...)` results, which plain `weights_only=True` refuses).  Every tensor is checked against the networks the new plans build before
 anything is written.  Values the build cannot honour raise `NotImplementedError` naming the key, as cineflow.config does.
 
-Command line:  python -m cineflow.reference_models -s SEG -w FLOW -o OUT [--crop_weights F --crop_config Y] [-f FOLDS] [-chk NAME]
+Without a flow folder (`import_reference_model_folder(seg_folder, None, out)`, no `-w`) a 2-D nnU-Net folder is imported on its own: the
+plans get no 'flow_net', the checkpoints no 'flow_state_dict', and predict_from_folder takes the segmentation-only route.
+
+Command line:  python -m cineflow.reference_models -s SEG [-w FLOW] -o OUT [--crop_weights F --crop_config Y] [-f FOLDS] [-chk NAME]
 """
 import argparse
 import os
@@ -234,11 +237,16 @@ def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, cr
     image_size / window_size override the task-number rule (crop_and_image_size) applied to the flow trainer's dataset directory
     (`.model.pkl` init[3]; the task folder's name when that file is absent).  The flow trainer predicts on [image_size, image_size]
     patches (SegFlowGaussian.py:366), which become plans['patch_size']; the segmentation stage's own patch stays in plans_per_stage.
+    flow_weight_folder=None imports the segmentation folder on its own (a segmentation-only model folder: the stage's patch size stays
+    plans['patch_size'], no 'flow_net' / 'crop_size'; a cropper or crop_size / image_size / window_size make no sense then and are refused).
     Returns the plans written."""
     from . import config as C
     from .predict import CineTrainer, save_model_folder
     if not os.path.isfile(join(seg_folder, "plans.pkl")):
         raise FileNotFoundError("%s has no plans.pkl (not the output folder of an nnU-Net trainer)" % seg_folder)
+    if flow_weight_folder is None:
+        return _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size,
+                                         window_size)
     config_path, task_dir = resolve_flow_folder(flow_weight_folder)
     seg_folds, flow_folds = _checkpoint_folds(seg_folder, checkpoint_name), _checkpoint_folds(task_dir, checkpoint_name)
     if folds is None or folds == "None":
@@ -301,11 +309,49 @@ def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, cr
     return plans
 
 
+def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size, window_size):
+    """import_reference_model_folder without a flow folder: every check of the segmentation side, nothing of the flow side"""
+    from .predict import CineTrainer, save_model_folder
+    given = {k: v for k, v in dict(crop_weights=crop_weights, crop_config=crop_config, crop_size=crop_size, image_size=image_size,
+                                   window_size=window_size).items() if v is not None}
+    if given:
+        raise ValueError("%s belong to the flow trainer's heart-centred crop; a segmentation-only import takes none of them" % ", ".join(sorted(given)))
+    seg_folds = _checkpoint_folds(seg_folder, checkpoint_name)
+    if folds is None or folds == "None":
+        if not seg_folds:
+            raise ValueError("the segmentation folder %s holds no fold_X/%s.model" % (seg_folder, checkpoint_name))
+        folds = sorted(seg_folds)
+    folds = [int(f) for f in ([folds] if isinstance(folds, (int, str)) else folds)]
+    for f in folds:
+        if f not in seg_folds:
+            raise FileNotFoundError("fold_%d/%s.model is missing from the segmentation folder %s" % (f, checkpoint_name, seg_folder))
+    seg_info = _trainer_info(seg_folds[folds[0]], checkpoint_name)
+    stage = seg_info["init"][5] if seg_info and len(seg_info.get("init") or ()) > 5 else None
+    plans = plans_from_reference(load_reference_pickle(join(seg_folder, "plans.pkl")), stage)
+    plans["image_size"] = int(plans["patch_size"][0])
+    trainer = CineTrainer(plans, torch.device("cpu"))                           # the network's key / shape list, no device work
+    params = {}
+    for f in folds:                                                             # every tensor of every fold is checked before anything is written
+        path = join(seg_folds[f], checkpoint_name + ".model")
+        shapes = trainer.seg_net.state_shapes()
+        sd = load_reference_checkpoint(path, shapes)["state_dict"]
+        check_state_dict(sd, shapes, "segmentation network %s" % path)
+        params[f] = {k: v for k, v in sd.items() if not k.endswith(_DERIVED_BUFFERS)}
+    os.makedirs(out_folder, exist_ok=True)
+    for f in folds:
+        save_model_folder(out_folder, trainer.seg_net, None, plans, fold=f, checkpoint_name=checkpoint_name, seg_sd=params[f], flow_sd=None)
+    if os.path.isfile(join(seg_folder, "postprocessing.json")):
+        shutil.copy(join(seg_folder, "postprocessing.json"), join(out_folder, "postprocessing.json"))
+    return plans
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description="Write a cineflow model folder (plans.json + fold_X/<chk>.model) from the folders the "
                                                  "reference's trainers wrote; predict_from_folder / cineflow.predict -m take it unchanged.")
     parser.add_argument("-s", "--seg_folder", required=True, help="output folder of the 2-D nnU-Net trainer (plans.pkl, fold_X/)")
-    parser.add_argument("-w", "--flow_weight_folder", required=True, help="the -w folder of run_training.py (config.yaml, <task>/fold_X/) or its <task> folder")
+    parser.add_argument("-w", "--flow_weight_folder", required=False, default=None,
+                        help="the -w folder of run_training.py (config.yaml, <task>/fold_X/) or its <task> folder; without it the segmentation folder "
+                             "is imported on its own (a segmentation-only model folder)")
     parser.add_argument("-o", "--output_folder", required=True)
     parser.add_argument("--crop_weights", default=None, help="the MTLmodel cropper's model_final_checkpoint.model")
     parser.add_argument("--crop_config", default=None, help="the cropper's YAML (adversarial_acdc.yaml)")
@@ -317,7 +363,10 @@ def main(argv=None):
     a = parser.parse_args(argv)
     plans = import_reference_model_folder(a.seg_folder, a.flow_weight_folder, a.output_folder, a.crop_weights, a.crop_config,
                                           None if a.folds == "None" else a.folds, a.chk, a.crop_size, a.image_size, a.window_size)
-    print("wrote %s (crop %d, image %d, %d classes)" % (a.output_folder, plans["crop_size"], plans["image_size"], plans["num_classes"]))
+    if "flow_net" not in plans:
+        print("wrote %s (segmentation only, patch %s, %d classes)" % (a.output_folder, plans["patch_size"], plans["num_classes"]))
+    else:
+        print("wrote %s (crop %d, image %d, %d classes)" % (a.output_folder, plans["crop_size"], plans["image_size"], plans["num_classes"]))
 
 
 if __name__ == "__main__":

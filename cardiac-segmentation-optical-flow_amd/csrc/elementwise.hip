@@ -195,6 +195,112 @@ __global__ void __launch_bounds__(256) tile_finalize_kernel(const float* __restr
     }
 }
 
+// ---- the cine-batched sliding window (neural_network.py:623-769 for many slices at once): cf_tile_gather / cf_tile_merge
+// dst[j] = src[n_j][:, lx_j:lx_j+ph, ly_j:ly_j+pw].  V = 4: one thread moves 4 floats of a row (pw % 4 == 0, Y % 4 == 0, both pointers 16-byte
+// aligned; the load is one 16-byte access when ly_j % 4 == 0, four 4-byte ones otherwise), V = 1: one float.  A job whose window leaves
+// the source (the table is device data the host never sees) reads nothing and gives zeros.
+template <int V>
+__global__ void __launch_bounds__(256) tile_gather_kernel(const float* __restrict__ src, const int* __restrict__ jobs, float* __restrict__ dst,
+                                                         int N, int C, int X, int Y, int ph, int pw, long total) {
+    const int pwv = pw / V;
+    GRID_STRIDE(i, total) {  // i over (j, c, px, py / V)
+        int py = (int)(i % pwv) * V;
+        long r = i / pwv;
+        int px = (int)(r % ph);
+        r /= ph;
+        int c = (int)(r % C);
+        long j = r / C;
+        const int n = jobs[j * 3], lx = jobs[j * 3 + 1], ly = jobs[j * 3 + 2];
+        const bool ok = (unsigned)n < (unsigned)N && lx >= 0 && ly >= 0 && lx <= X - ph && ly <= Y - pw;
+        const float* s = src + (((long)n * C + c) * X + lx + px) * Y + ly + py;
+        float* d = dst + ((j * C + c) * ph + px) * pw + py;
+        if constexpr (V == 4) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (ok) {
+                if ((ly & 3) == 0) v = *reinterpret_cast<const float4*>(s);
+                else v = make_float4(s[0], s[1], s[2], s[3]);
+            }
+            *reinterpret_cast<float4*>(d) = v;
+        } else {
+            d[0] = ok ? s[0] : 0.f;
+        }
+    }
+}
+
+struct TileSteps {   // the step lists of compute_steps_for_sliding_window, by value in the kernel arguments
+    int lx[16], ly[16];
+    int nx, ny;
+};
+
+// One thread per output pixel (V = 1) or per 4 pixels of a row (V = 4: Y % 4 == 0, pw % 4 == 0 and every ly % 4 == 0, so the 4 pixels are
+// covered by the same tiles and every access is 16-byte aligned).  Per pixel and class the covering tiles are added IN TILE ORDER (lx outer,
+// ly inner) to a zero start -- the fp32 sequence of the serial tile_accumulate launches -- then divided as tile_finalize divides.
+template <int V>
+__global__ void __launch_bounds__(256) tile_merge_kernel(const float* __restrict__ pred, const float* __restrict__ gauss, float* __restrict__ probs,
+                                                        uint8_t* __restrict__ seg, int K, int X, int Y, int ph, int pw, TileSteps st, long total) {
+    const int Yv = Y / V, ntile = st.nx * st.ny;
+    const long pp = (long)ph * pw, XY = (long)X * Y;
+    GRID_STRIDE(i, total) {  // i over (n, x, y / V)
+        const int y = (int)(i % Yv) * V;
+        long r = i / Yv;
+        const int x = (int)(r % X);
+        const long n = r / X;
+        float cnt[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) cnt[v] = 0.f;
+        for (int ix = 0; ix < st.nx; ++ix) {
+            const int tx = x - st.lx[ix];
+            if ((unsigned)tx >= (unsigned)ph) continue;
+            for (int iy = 0; iy < st.ny; ++iy) {
+                const int ty = y - st.ly[iy];
+                if ((unsigned)ty >= (unsigned)pw) continue;
+                if constexpr (V == 4) {
+                    float4 g = gauss ? *reinterpret_cast<const float4*>(gauss + (long)tx * pw + ty) : make_float4(1.f, 1.f, 1.f, 1.f);
+                    cnt[0] += g.x; cnt[1] += g.y; cnt[2] += g.z; cnt[3] += g.w;
+                } else {
+                    cnt[0] += gauss ? gauss[(long)tx * pw + ty] : 1.f;
+                }
+            }
+        }
+        float best[V];
+        int arg[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) { best[v] = -INFINITY; arg[v] = 0; }
+        for (int k = 0; k < K; ++k) {
+            float agg[V];
+#pragma unroll
+            for (int v = 0; v < V; ++v) agg[v] = 0.f;
+            for (int ix = 0; ix < st.nx; ++ix) {
+                const int tx = x - st.lx[ix];
+                if ((unsigned)tx >= (unsigned)ph) continue;
+                for (int iy = 0; iy < st.ny; ++iy) {
+                    const int ty = y - st.ly[iy];
+                    if ((unsigned)ty >= (unsigned)pw) continue;
+                    const float* p = pred + ((n * ntile + ix * st.ny + iy) * K + k) * pp + (long)tx * pw + ty;
+                    if constexpr (V == 4) {
+                        const float4 q = *reinterpret_cast<const float4*>(p);
+                        agg[0] += q.x; agg[1] += q.y; agg[2] += q.z; agg[3] += q.w;
+                    } else {
+                        agg[0] += p[0];
+                    }
+                }
+            }
+            float out[V];
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                out[v] = agg[v] / cnt[v];
+                if (out[v] > best[v]) { best[v] = out[v]; arg[v] = k; }
+            }
+            float* o = probs + (n * K + k) * XY + (long)x * Y + y;
+            if constexpr (V == 4) *reinterpret_cast<float4*>(o) = make_float4(out[0], out[1], out[2], out[3]);
+            else o[0] = out[0];
+        }
+        uint8_t* so = seg + n * XY + (long)x * Y + y;
+        if constexpr (V == 4) *reinterpret_cast<uchar4*>(so) = make_uchar4((uint8_t)arg[0], (uint8_t)arg[1], (uint8_t)arg[2], (uint8_t)arg[3]);
+        else so[0] = (uint8_t)arg[0];
+    }
+}
+
 __global__ void __launch_bounds__(256) argmax_channels_kernel(const float* __restrict__ x, uint8_t* __restrict__ out, int K, long HW,
                                                              long total) {
     GRID_STRIDE(i, total) {
@@ -304,6 +410,50 @@ extern "C" int cf_tile_finalize(const float* agg, const float* cnt, float* probs
     CF_REQUIRE(K > 0 && K <= 255 && X > 0 && Y > 0, "bad shape");
     long xy = (long)X * Y;
     LAUNCH_FLAT(tile_finalize_kernel, xy, agg, cnt, probs, seg, K, xy);
+}
+
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+extern "C" int cf_tile_gather(const float* src, const int* jobs, float* dst, int J, int N, int C, int X, int Y, int ph, int pw, void* stream) {
+    CF_REQUIRE(src && jobs && dst, "null pointer");
+    CF_REQUIRE(J > 0 && N > 0 && C > 0 && ph > 0 && pw > 0 && ph <= X && pw <= Y, "bad shape J=%d N=%d C=%d X=%d Y=%d patch %dx%d", J, N, C, X, Y, ph, pw);
+    if (pw % 4 == 0 && Y % 4 == 0 && aligned16(src) && aligned16(dst)) {
+        long total = (long)J * C * ph * (pw / 4);
+        LAUNCH_FLAT(tile_gather_kernel<4>, total, src, jobs, dst, N, C, X, Y, ph, pw, total);
+    }
+    long total = (long)J * C * ph * pw;
+    LAUNCH_FLAT(tile_gather_kernel<1>, total, src, jobs, dst, N, C, X, Y, ph, pw, total);
+}
+
+// a step list of compute_steps_for_sliding_window: ascending from 0, the last window ends at the image's end, no gap between windows
+static bool steps_cover(const int* l, int n, int p, int size) {
+    if (l[0] != 0 || l[n - 1] + p != size) return false;
+    for (int i = 1; i < n; ++i)
+        if (l[i] <= l[i - 1] || l[i] - l[i - 1] > p) return false;
+    return true;
+}
+
+extern "C" int cf_tile_merge(const float* pred, const float* gauss, float* probs, uint8_t* seg, int N, int K, int X, int Y, int ph, int pw,
+                             const int* lx, int nx, const int* ly, int ny, void* stream) {
+    CF_REQUIRE(pred && probs && seg && lx && ly, "null pointer");
+    CF_REQUIRE(N > 0 && K > 0 && K <= 255 && ph > 0 && pw > 0 && ph <= X && pw <= Y, "bad shape N=%d K=%d X=%d Y=%d patch %dx%d", N, K, X, Y, ph, pw);
+    CF_REQUIRE(nx > 0 && nx <= 16 && ny > 0 && ny <= 16, "1..16 steps per axis, got %d x %d", nx, ny);
+    CF_REQUIRE(steps_cover(lx, nx, ph, X) && steps_cover(ly, ny, pw, Y), "the step lists must rise from 0, leave no gap and end at X - ph / Y - pw");
+    TileSteps st;
+    bool vec = pw % 4 == 0 && Y % 4 == 0 && aligned16(pred) && aligned16(probs) && aligned16(gauss) && (reinterpret_cast<uintptr_t>(seg) & 3) == 0;
+    for (int i = 0; i < 16; ++i) {
+        st.lx[i] = i < nx ? lx[i] : 0;
+        st.ly[i] = i < ny ? ly[i] : 0;
+        vec = vec && st.ly[i] % 4 == 0;
+    }
+    st.nx = nx;
+    st.ny = ny;
+    if (vec) {
+        long total = (long)N * X * (Y / 4);
+        LAUNCH_FLAT(tile_merge_kernel<4>, total, pred, gauss, probs, seg, K, X, Y, ph, pw, st, total);
+    }
+    long total = (long)N * X * Y;
+    LAUNCH_FLAT(tile_merge_kernel<1>, total, pred, gauss, probs, seg, K, X, Y, ph, pw, st, total);
 }
 
 extern "C" int cf_argmax_channels(const float* x, uint8_t* out, int B, int K, int HW, void* stream) {

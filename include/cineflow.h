@@ -272,6 +272,21 @@ int cf_tile_accumulate(const float* pred, const float* gauss, float* agg, float*
                        int ly, int ph, int pw, void* stream);
 /* :741-744: probs = agg/cnt ; seg = argmax_K probs (first maximum).  seg uint8 [X,Y]. */
 int cf_tile_finalize(const float* agg, const float* cnt, float* probs, uint8_t* seg, int K, int X, int Y, void* stream);
+/* The cine-batched sliding window: _internal_predict_2D_2Dconv_tiled (neural_network.py:623-769) for every slice of every frame at once.
+ * cf_tile_gather cuts the tiles (:705-710): dst[j] = src[n_j][:, lx_j:lx_j+ph, ly_j:ly_j+pw];  jobs: DEVICE int32 [J,3] = (n, lx, ly);
+ * src [N,C,X,Y] -> dst [J,C,ph,pw].  A job whose window leaves the source reads nothing and gives zeros.  16-byte stores when pw % 4 == 0,
+ * Y % 4 == 0 and both pointers are 16-byte aligned (16-byte loads for the jobs with ly % 4 == 0), a scalar path otherwise. */
+int cf_tile_gather(const float* src, const int* jobs, float* dst, int J, int N, int C, int X, int Y, int ph, int pw, void* stream);
+/* The aggregation of :711-744 for N slices at once, in gather form.
+ * pred [N*nx*ny, K, ph, pw]: tile predictions that already carry the Gaussian weight, slice-major, then tile order (lx outer, ly inner);
+ * lx[nx], ly[ny]: HOST arrays (the step lists of :267-290: rising from 0, no gap, last window ending at X / Y; nx, ny <= 16), passed to the
+ * kernel by value;  gauss [ph,pw] nullable (= ones);
+ * per output pixel, over the covering tiles IN TILE ORDER: agg = 0 + pred_1 + pred_2 + ..., cnt = 0 + g_1 + g_2 + ...;
+ * probs [N,K,X,Y] = agg / cnt;  seg uint8 [N,X,Y] = first maximum over K.  No agg / cnt buffers, no atomics: for the same pred the result is
+ * bit-identical to cf_tile_accumulate per tile + cf_tile_finalize per slice.  16-byte accesses when pw % 4 == 0, Y % 4 == 0, every
+ * ly % 4 == 0 and the pointers are aligned, a scalar path otherwise. */
+int cf_tile_merge(const float* pred, const float* gauss, float* probs, uint8_t* seg, int N, int K, int X, int Y, int ph, int pw,
+                  const int* lx, int nx, const int* ly, int ny, void* stream);
 /* 3-D twins: _internal_maybe_mirror_and_pred_3D (neural_network.py:506-571; logits/acc [B,K,D,H,W], the three flags undo
  * the mirroring of axes 2,3,4) and the tile aggregation of _internal_predict_3D_3Dconv_tiled (:381-398; pred [K,px,py,pz],
  * gauss [px,py,pz] nullable, agg/cnt [K,X,Y,Z]).  cf_tile_finalize serves 3-D volumes as (K, X, Y*Z). */
