@@ -563,7 +563,8 @@ class ConvDropoutNormNonlin3D(Module):
         self.instnorm = InstanceNorm3d(cout)
 
     def forward(self, x, x2=None):
-        return self.instnorm(self.conv(x, x2=x2), act="lrelu")
+        y, ws = self.conv(x, x2=x2, stats_groups=self.instnorm.channels)
+        return self.instnorm(y, act="lrelu", ws=ws)
 
 
 class StackedConvLayers3D(Module):

@@ -266,13 +266,16 @@ class LayerNormCF(Module):
 
 
 
-# --------------------------------------------------------------------------------------------- 3-D layers (composition)
+# --------------------------------------------------------------------------------------------- 3-D layers
 class Conv3d(Module):
-    """nn.Conv3d for the 3-D U-Net behind _internal_predict_3D_3Dconv_tiled (generic_UNet.py with conv_op = nn.Conv3d).
-    A (kd, k, k) convolution is the sum over the kd depth taps of 2-D (k, k) convolutions of depth-shifted planes, so it
+    """nn.Conv3d for the 3-D U-Net behind _internal_predict_3D_3Dconv_tiled (generic_UNet.py with conv_op = nn.Conv3d).  Input/output NCDHW.
+    (1|3, 3, 3) kernels run on the native kernel cf_conv3d_f16s (conv3d_f16s.hip) where ops.conv3d_f16s_ok takes the shape: one call on the
+    NCDHW tensors, the InstanceNorm statistics of the output from its epilogue (stats_groups).  The (1, 1, 1) / stride-1 heads are a 1x1
+    Conv2d on the [B, C, D*H, W] view.  Everything else -- set_conv_mode("f32"), one-term mode, declined shapes -- runs the composition:
+    a (kd, k, k) convolution is the sum over the kd depth taps of 2-D (k, k) convolutions of depth-shifted planes, so it
     runs on the same MFMA implicit-GEMM kernels: the volume is re-laid as [B, D, C, H, W] planes, the centre tap writes
     every output plane (with the bias), the other taps accumulate through the kernel's residual input.  Kernel sizes 1 or 3
-    per axis (padding 1 for 3, as generic_UNet.py:252-254), strides 1 or 2, equal in H and W.  Input/output NCDHW."""
+    per axis (padding 1 for 3, as generic_UNet.py:252-254), strides 1 or 2, equal in H and W."""
 
     def __init__(self, cin, cout, kernel_size=(3, 3, 3), stride=(1, 1, 1), bias=True):
         super().__init__()
@@ -287,6 +290,17 @@ class Conv3d(Module):
         if "weight" not in self._p:
             return
         k, pad = self.ks[1], (self.ks[1] // 2, self.ks[1] // 2)
+        if self.ks == (1, 1, 1) and self.stride == (1, 1, 1):
+            # the segmentation heads: a 1x1 convolution on the [B, C, D*H, W] view of the NCDHW tensor, no re-layout
+            self._head = Conv2d(self.cin, self.cout, 1, bias="bias" in self._p)        # (leading underscore: not a state-dict child)
+            self._head._p["weight"] = self._p["weight"].reshape(self.cout, self.cin, 1, 1).contiguous()
+            if "bias" in self._p:
+                self._head._p["bias"] = self._p["bias"]
+            self._head._prepare()
+            return
+        # the native kernel (conv3d_f16s.hip) takes (1|3, 3, 3) kernels; packed per channel split on first use
+        self._native = self.ks[1:] == (3, 3)
+        self._pk3 = {}
         self._f16s = ops.f16s_supported(k, k, self.stride[1], pad)
         self._taps = []
         for dz in range(self.ks[0]):
@@ -304,7 +318,27 @@ class Conv3d(Module):
             return ops.conv2d_f16s(x, pk[0], pk[1], bias, self.cout, k, k, st, pad, x2=x2, res=res, out=out)
         return ops.conv2d(x, wt, bias, self.cout, k, k, st, pad, x2=x2, res=res, out=out)
 
-    def forward(self, x, x2=None):
+    def _packed3(self, x, x2):
+        key = x.shape[1] if (x2 is not None and x.shape[1] % 16) else None
+        if key not in self._pk3:
+            self._pk3[key] = ops.pack_conv3d_weight_f16s(self._p["weight"], c1=key)
+        return self._pk3[key]
+
+    def forward(self, x, x2=None, stats_groups=None):
+        """stats_groups=G: returns (out, ws) with the GroupNorm / InstanceNorm statistics of `out` when the native kernel ran, else (out, None)."""
+        B, _, D, H, W = x.shape
+        if hasattr(self, "_head"):
+            assert x2 is None
+            y = self._head(x.view(B, self.cin, D * H, W)).view(B, self.cout, D, H, W)
+            return (y, None) if stats_groups else y
+        if (self._native and ops.CONV_MODE == "f16s"
+                and ops.conv3d_f16s_ok(B, x.shape[1], 0 if x2 is None else x2.shape[1], D, H, W, self.cout, self.ks, self.stride)):
+            wpk, wsc = self._packed3(x, x2)
+            return ops.conv3d_f16s(x, wpk, wsc, self._p.get("bias"), self.cout, self.ks, self.stride, x2=x2, stats_groups=stats_groups)
+        y = self._forward_composed(x, x2)          # set_conv_mode("f32"), one-term mode and declined shapes
+        return (y, None) if stats_groups else y
+
+    def _forward_composed(self, x, x2=None):
         B, _, D, H, W = x.shape
         kd, sd, pd = self.ks[0], self.stride[0], self.ks[0] // 2
         k, st = self.ks[1], self.stride[1]
@@ -374,8 +408,12 @@ class InstanceNorm3d(Module):
         self._param("weight", (channels,))
         self._param("bias", (channels,))
 
-    def forward(self, x, act=None):
+    def forward(self, x, act=None, ws=None):
+        """ws: statistics already accumulated by the producing convolution (Conv3d with stats_groups) -> apply pass only."""
         B, C, D, H, W = x.shape
+        if ws is not None:
+            y = ops.group_norm_apply(x.view(B, C, D * H, W), self._p["weight"], self._p["bias"], C, ws, self.eps, act=act, out=x.view(B, C, D * H, W))
+            return y.view(B, C, D, H, W)
         y = ops.group_norm(x.view(B, C, D * H, W), self._p["weight"], self._p["bias"], C, self.eps, act=act, out=x.view(B, C, D * H, W))
         return y.view(B, C, D, H, W)
 

@@ -385,6 +385,66 @@ def conv2d_f16s(x1, wpk, wscale, bias, cout, kh, kw, stride=1, pad=(0, 0), x2=No
     return (out, ws) if stats_groups else out
 
 
+# ---- 3-D convolution (conv3d_f16s.hip) -----------------------------------------------------------------------------------
+def pack_conv3d_weight_f16s(w, c1=None):
+    """torch Conv3d weight [Cout,Cin,KD,3,3] -> (packed fp16 tensor, scale exponent s) for cf_conv3d_f16s: pack_conv_weight_f16s' fragment
+    order with the KD * 9 taps in (dz, ky, kx) order, 16-channel chunks; c1 as there (cat[x1, x2] with x1 padded to whole chunks)."""
+    import math
+    cout, cin, kd, kh, kw = w.shape
+    assert (kh, kw) == (3, 3) and kd in (1, 3)
+    ntap, ck = kd * 9, 16
+    nmt = 1 if cout <= 32 else 2 * ((cout + 63) // 64)
+    wmax = float(w.abs().max())
+    s = int(math.floor(math.log2(1024.0 / wmax))) if wmax > 0 else 0
+    s = max(-24, min(24, s))
+    ws = w.reshape(cout, cin, ntap).to(torch.float32) * (2.0 ** s)
+    split = c1 is not None and 0 < c1 < cin and c1 % ck
+    c1p = (c1 + ck - 1) // ck * ck if split else 0
+    nchunk = c1p // ck + (cin - c1 + ck - 1) // ck if split else (cin + ck - 1) // ck
+    wp = torch.zeros((nmt * 32, nchunk * ck, ntap), dtype=torch.float32, device=w.device)
+    if split:
+        wp[:cout, :c1] = ws[:, :c1]
+        wp[:cout, c1p:c1p + cin - c1] = ws[:, c1:]
+    else:
+        wp[:cout, :cin] = ws
+    hi = wp.half()
+    lo = (wp - hi.float()).half()
+    x = torch.stack([hi, lo]).view(2, nmt, 32, nchunk, 2, 8, ntap)      # part, mt, r, chunk, h, j, tap
+    return x.permute(1, 3, 6, 0, 4, 2, 5).contiguous().view(-1), s     # mt, chunk, tap, part, h, r, j
+
+
+def conv3d_f16s_ok(B, C1, C2, D, H, W, cout, kernel, stride):
+    """does cf_conv3d_f16s take this layer?  kernel (1|3,3,3), stride (1|2, s, s) with s in {1,2}, every sample < 2 GiB, three-term mode."""
+    kernel, stride = tuple(kernel), tuple(stride)
+    if kernel[1] != kernel[2] or stride[1] != stride[2]:
+        return False
+    return lib().cf_conv3d_f16s_ok(B, C1, C2, D, H, W, cout, kernel[0], kernel[1], stride[0], stride[1]) == 1
+
+
+def conv3d_f16s(x1, wpk, wscale, bias, cout, kernel, stride=(1, 1, 1), x2=None, out=None, alpha=1.0, stats_groups=None):
+    """cf_conv3d_f16s on NCDHW tensors, padding (kd // 2, 1, 1).  With stats_groups=G the call returns (out, ws): ws holds the GroupNorm /
+    InstanceNorm statistics of `out` over (D, H, W) for group_norm_apply."""
+    B, C1, D, H, W = x1.shape
+    C2 = 0 if x2 is None else x2.shape[1]
+    kd, kh, kw = kernel
+    sd, st = stride[0], stride[1]
+    assert stride[1] == stride[2]
+    if x2 is not None:
+        assert x2.shape[0] == B and tuple(x2.shape[2:]) == (D, H, W)
+    shape = (B, cout, (D + 2 * (kd // 2) - kd) // sd + 1, (H - 1) // st + 1, (W - 1) // st + 1)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x1.device)
+    assert tuple(out.shape) == shape
+    assert wpk.dtype == torch.float16 and wpk.is_cuda
+    if F16S_RANGE_CHECK:
+        _range_check(x1, x2)
+    ws = _zeroed_stats_ws(2 * B * stats_groups, x1.device) if stats_groups else None
+    check(lib().cf_conv3d_f16s(_f32(x1), C1, _opt(x2), C2, wpk.data_ptr(), _opt(bias), _f32(out), B, D, H, W, cout, kd, kh, kw, sd, st,
+                               float(alpha) * (2.0 ** -wscale), None if ws is None else ws.data_ptr(), -stats_groups if stats_groups else 0,
+                               _stream()), "cf_conv3d_f16s")
+    return (out, ws) if stats_groups else out
+
+
 def small_cin_supported(cin, kh, kw, stride, pad, stats_groups=None):
     """layers routed to cf_conv2d_small_cin: 1 or 2 input channels (3x3 pad 1 or 1x1) and 6 input channels 1x1, stride 1, <= 64
     statistics groups.  Measured at 256x256 (tools/microbench.py --only stem): 1 -> 32 B120 209 us vs 641 us on the MFMA kernel,

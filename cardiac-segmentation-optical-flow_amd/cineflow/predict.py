@@ -46,8 +46,8 @@ import torch
 
 from . import ops
 from .inference import (Processor, _predict_cine_tiled_device, chunk_orders, normalize_intensity_, pad_nd_image, predict_3D_2Dconv_tiled,  # noqa: F401
-                        predict_cine_2Dconv_tiled, predict_cine_slices)
-from .models import Generic_UNet, SegFlowGaussian
+                        predict_3D_3Dconv_tiled, predict_cine_2Dconv_tiled, predict_cine_slices)
+from .models import Generic_UNet, Generic_UNet3D, SegFlowGaussian
 from .nifti import read_nifti, write_nifti
 
 join = os.path.join
@@ -160,6 +160,12 @@ class CineTrainer:
         self.data_aug_params = {"mirror_axes": tuple(plans["mirror_axes"])}
         self.patch_size = tuple(plans["patch_size"])
         fk = plans.get("flow_net")
+        self.seg_dim = int((plans.get("seg_net") or {}).get("dim", 2))
+        if self.seg_dim == 3:
+            if fk:
+                raise ValueError("plans.json holds both seg_net.dim == 3 and flow_net: the flow path is 2-D (a 3-D segmentation folder is segmentation-only)")
+            if len(plans["patch_size"]) != 3:
+                raise ValueError("seg_net.dim == 3 needs a 3-entry patch_size, got %r" % (plans["patch_size"],))
         # (a segmentation-only model has no heart-centred crop: no Processor)
         self.processor = Processor(crop_size=plans["crop_size"], image_size=plans["patch_size"][0]) if (fk or "crop_size" in plans) else None
         # mixed_precision of load_model_and_checkpoint_files / predict_from_folder (the reference's default True): with CF_SEG_MIXED_PRECISION=1
@@ -196,6 +202,9 @@ class CineTrainer:
 
     def _new_seg_net(self):
         sk = self.plans["seg_net"]
+        if self.seg_dim == 3:           # a `3d_fullres` stage: Generic_UNet with conv_op = nn.Conv3d, at most MAX_NUM_FILTERS_3D = 320 filters
+            return Generic_UNet3D(self.plans["num_modalities"], sk["base_num_features"], self.num_classes, sk["num_pool"],
+                                  pool_op_kernel_sizes=sk.get("pool_op_kernel_sizes"), conv_kernel_sizes=sk.get("conv_kernel_sizes"))
         return Generic_UNet(self.plans["num_modalities"], sk["base_num_features"], self.num_classes, sk["num_pool"],
                             pool_op_kernel_sizes=sk.get("pool_op_kernel_sizes"))     # the plans' per-stage pooling (plans_per_stage[...]['pool_op_kernel_sizes'])
 
@@ -259,6 +268,9 @@ class CineTrainer:
         """(seg [Z,X,Y], softmax [K,Z,X,Y]) of one preprocessed volume; with several folds resident (load_ensemble) the softmax is the
         mean over the folds of each fold's flip-TTA sliding-window softmax."""
         with ops.conv_terms(1 if (mixed_precision and SEG_MIXED_PRECISION) else 3):
+            if self.seg_dim == 3:
+                seg, prob = self._predict_volume_3d(data, step_size, do_mirroring, mirror_axes, use_gaussian, pad_border_mode, pad_kwargs)
+                return seg.cpu().numpy(), prob.cpu().numpy()
             if len(self.seg_nets) == 1:
                 return predict_3D_2Dconv_tiled(self.seg_net, data, self.patch_size, step_size=step_size, do_mirroring=do_mirroring,
                                                mirror_axes=mirror_axes, use_gaussian=use_gaussian, pad_border_mode=pad_border_mode,
@@ -267,6 +279,22 @@ class CineTrainer:
                                              mirror_axes=mirror_axes, use_gaussian=use_gaussian, pad_border_mode=pad_border_mode,
                                              pad_kwargs=pad_kwargs)[0]
 
+    def _predict_volume_3d(self, data, step_size, do_mirroring, mirror_axes, use_gaussian, pad_border_mode, pad_kwargs):
+        """One volume [C,Z,Y,X] through predict_3D_3Dconv_tiled, one fold at a time, everything on the device: (seg uint8, softmax).  Several
+        folds: the softmax is the fold mean -- each fold's sliding-window softmax added in fold order, each with weight 1 / folds as in the
+        2-D ensemble -- and the labels are its arg-max; one fold: predict_3D_3Dconv_tiled's own labels."""
+        acc = seg = None
+        n = len(self.seg_nets)
+        for net in self.seg_nets:
+            seg, prob = predict_3D_3Dconv_tiled(net, data, self.patch_size, step_size, do_mirroring, mirror_axes, use_gaussian, pad_border_mode,
+                                                pad_kwargs, return_device=True)
+            if n == 1:
+                return seg, prob
+            prob = prob.contiguous().mul_(1.0 / n)
+            acc = prob if acc is None else ops.add(acc, prob, out=acc)
+        K, Z, Y, X = acc.shape
+        return ops.argmax_channels(acc.view(1, K, Z * Y, X)).view(Z, Y, X), acc
+
     def predict_volumes_seg(self, volumes, do_mirroring=True, mirror_axes=None, step_size=0.5, use_gaussian=True, pad_border_mode="constant",
                             pad_kwargs=None, mixed_precision=True, want_softmax=True):
         """The segmentation-only device stage of the file-level API: every volume [C,Z,Y,X] of a patient group (all frames of all its
@@ -274,8 +302,11 @@ class CineTrainer:
         (seg uint8 [Z,Y,X], softmax [K,Z,Y,X] or None) as host arrays (pinned staging, one synchronisation)."""
         mirror_axes = self.data_aug_params["mirror_axes"] if mirror_axes is None else mirror_axes
         with ops.conv_terms(1 if (mixed_precision and SEG_MIXED_PRECISION) else 3):
-            res = _predict_cine_tiled_device(self.seg_nets, volumes, self.patch_size, step_size, do_mirroring, mirror_axes, use_gaussian,
-                                             pad_border_mode, pad_kwargs, None)
+            if self.seg_dim == 3:
+                res = [self._predict_volume_3d(v, step_size, do_mirroring, mirror_axes, use_gaussian, pad_border_mode, pad_kwargs) for v in volumes]
+            else:
+                res = _predict_cine_tiled_device(self.seg_nets, volumes, self.patch_size, step_size, do_mirroring, mirror_axes, use_gaussian,
+                                                 pad_border_mode, pad_kwargs, None)
         dev_out = []
         for s_, p_ in res:
             dev_out.append(s_.contiguous())

@@ -16,8 +16,10 @@ and `python -m cineflow.predict -m ...` take unchanged (save_model_folder).  Not
 `np.mean(...)` results, which plain `weights_only=True` refuses).  Every tensor is checked against the networks the new plans build before
 anything is written.  Values the build cannot honour raise `NotImplementedError` naming the key, as cineflow.config does.
 
-Without a flow folder (`import_reference_model_folder(seg_folder, None, out)`, no `-w`) a 2-D nnU-Net folder is imported on its own: the
-plans get no 'flow_net', the checkpoints no 'flow_state_dict', and predict_from_folder takes the segmentation-only route.
+Without a flow folder (`import_reference_model_folder(seg_folder, None, out)`, no `-w`) an nnU-Net folder is imported on its own: the
+plans get no 'flow_net', the checkpoints no 'flow_state_dict', and predict_from_folder takes the segmentation-only route.  The stage's
+patch length picks the translation: 2 entries -> plans_from_reference (Generic_UNet), 3 entries -> plans_from_reference_3d (a `3d_fullres`
+folder, Generic_UNet3D on the native 3-D convolution).  A 3-D folder paired with a flow folder is refused: the flow path is 2-D.
 
 Command line:  python -m cineflow.reference_models -s SEG [-w FLOW] -o OUT [--crop_weights F --crop_config Y] [-f FOLDS] [-chk NAME]
 """
@@ -160,6 +162,69 @@ def plans_from_reference(plans, stage=None):
     })
 
 
+def plans_from_reference_3d(plans, stage=None):
+    """The reference's 3-D nnU-Net plans (experiment_planner_baseline_3DUNet.py:225-252, :343-357) -> the plans dict CineTrainer reads for a
+    `3d_fullres` folder: a 3-entry patch_size, mirror_axes [0, 1, 2] and seg_net {dim: 3, base_num_features, num_pool, pool_op_kernel_sizes,
+    conv_kernel_sizes} -- the Generic_UNet with conv_op = nn.Conv3d that nnUNetTrainerV2.py:147-169 builds (num_classes + 1 outputs,
+    conv_per_stage 2, at most 320 filters).  The preprocessing entries are those of the 2-D translation; preprocessor_name stays as the
+    plans give it (GenericPreprocessor).
+
+    stage=None: the only stage (nnUNetTrainer.py:478-482); with several stages, the last one -- the full-resolution stage of the
+    planner's cascade order, which is the stage run_training.py hands a full-resolution trainer."""
+    stages = plans["plans_per_stage"]
+    if stage is None:
+        stage = list(stages.keys())[0] if len(stages) == 1 else sorted(stages.keys())[-1]
+    if stage not in stages:
+        raise KeyError("plans_from_reference_3d: stage %r is not in plans_per_stage %s" % (stage, sorted(stages)))
+    sp = stages[stage]
+    patch = [int(v) for v in np.asarray(sp["patch_size"]).ravel()]
+    if len(patch) != 3:
+        _refuse("plans_per_stage[%r]['patch_size']" % stage, patch, "3-D stages (plans_from_reference translates 2-D ones)")
+    if "pool_op_kernel_sizes" in sp:
+        pool = [[int(v) for v in p_] for p_ in sp["pool_op_kernel_sizes"]]
+    else:                                                                      # nnUNetTrainer.py:489-501: old plans
+        per_axis = [int(v) for v in sp["num_pool_per_axis"]]
+        pool = [[2 if max(per_axis) - j <= i else 1 for j in per_axis] for i in range(max(per_axis))]
+    if any(len(p_) != 3 or any(v not in (1, 2) for v in p_) for p_ in pool):
+        _refuse("plans_per_stage[%r]['pool_op_kernel_sizes']" % stage, pool, "entries of {1, 2}^3")
+    if any(p_[1] != p_[2] for p_ in pool):
+        _refuse("plans_per_stage[%r]['pool_op_kernel_sizes']" % stage, pool, "equal in-plane pooling")
+    conv = sp.get("conv_kernel_sizes")
+    conv = [[int(v) for v in k] for k in ([[3, 3, 3]] * (len(pool) + 1) if conv is None else conv)]
+    if len(conv) != len(pool) + 1 or any(k not in ([1, 3, 3], [3, 3, 3]) for k in conv):
+        _refuse("plans_per_stage[%r]['conv_kernel_sizes']" % stage, conv, "(1, 3, 3) or (3, 3, 3), one per stage")
+    conv_per_stage = plans.get("conv_per_stage", 2)
+    if conv_per_stage != 2:
+        _refuse("conv_per_stage", conv_per_stage, "2")
+    dp = plans.get("dataset_properties") or {}
+    tf, tb = plans.get("transpose_forward"), plans.get("transpose_backward")
+    if tf is None or tb is None:                                               # nnUNetTrainer.py:526-531
+        tf, tb = [0, 1, 2], [0, 1, 2]
+    return _plain({
+        "num_modalities": int(plans["num_modalities"]),
+        "num_classes": int(plans["num_classes"]) + 1,                            # nnUNetTrainer.py:520: background is not in num_classes
+        "patch_size": patch,
+        "mirror_axes": [0, 1, 2],
+        "seg_net": {"dim": 3, "base_num_features": int(plans["base_num_features"]), "num_pool": len(pool), "pool_op_kernel_sizes": pool,
+                    "conv_kernel_sizes": conv},
+        "transpose_forward": [int(v) for v in tf], "transpose_backward": [int(v) for v in tb],
+        "normalization_schemes": plans.get("normalization_schemes"),
+        "use_mask_for_norm": plans.get("use_mask_for_norm"),
+        "dataset_properties": {"intensityproperties": dp.get("intensityproperties")},
+        "preprocessor_name": plans.get("preprocessor_name"),
+        "plans_per_stage": stages,
+        "stage": stage,
+    })
+
+
+def _stage_is_3d(plans, stage):
+    """does the stage a trainer would take (stage, else the only / the last one) have a 3-entry patch?"""
+    stages = plans["plans_per_stage"]
+    if stage is None or stage not in stages:
+        stage = sorted(stages.keys())[-1]
+    return len(np.asarray(stages[stage]["patch_size"]).ravel()) == 3
+
+
 def crop_and_image_size(task, successive=False):
     """(crop_size, image_size, window_size) of the flow trainers from the task folder name, substring rule for substring rule:
     SegFlowGaussian.py:117-135 (31 / 35 -> 128, 224, 7; 39 -> 192, 224, 7; else 192, 384, 8) and nnMTLTrainerV2FlowSuccessive.py:117-126
@@ -247,6 +312,11 @@ def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, cr
     if flow_weight_folder is None:
         return _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size,
                                          window_size)
+    first = _checkpoint_folds(seg_folder, checkpoint_name)
+    info = _trainer_info(first[sorted(first)[0]], checkpoint_name) if first else None
+    if _stage_is_3d(load_reference_pickle(join(seg_folder, "plans.pkl")), info["init"][5] if info and len(info.get("init") or ()) > 5 else None):
+        raise ValueError("%s is a 3-D segmentation folder (3-entry patch_size) and cannot be paired with a flow folder (-w %s): the flow path "
+                         "is 2-D.  Import it on its own (no -w)." % (seg_folder, flow_weight_folder))
     config_path, task_dir = resolve_flow_folder(flow_weight_folder)
     seg_folds, flow_folds = _checkpoint_folds(seg_folder, checkpoint_name), _checkpoint_folds(task_dir, checkpoint_name)
     if folds is None or folds == "None":
@@ -327,8 +397,12 @@ def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config,
             raise FileNotFoundError("fold_%d/%s.model is missing from the segmentation folder %s" % (f, checkpoint_name, seg_folder))
     seg_info = _trainer_info(seg_folds[folds[0]], checkpoint_name)
     stage = seg_info["init"][5] if seg_info and len(seg_info.get("init") or ()) > 5 else None
-    plans = plans_from_reference(load_reference_pickle(join(seg_folder, "plans.pkl")), stage)
-    plans["image_size"] = int(plans["patch_size"][0])
+    ref_plans = load_reference_pickle(join(seg_folder, "plans.pkl"))
+    if _stage_is_3d(ref_plans, stage):                                          # a `3d_fullres` folder: checked against Generic_UNet3D below
+        plans = plans_from_reference_3d(ref_plans, stage)
+    else:
+        plans = plans_from_reference(ref_plans, stage)
+        plans["image_size"] = int(plans["patch_size"][0])
     trainer = CineTrainer(plans, torch.device("cpu"))                           # the network's key / shape list, no device work
     params = {}
     for f in folds:                                                             # every tensor of every fold is checked before anything is written

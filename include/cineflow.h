@@ -143,6 +143,25 @@ int cf_conv2d_f16s(const float* x1, int C1, const float* x2, int C2, const void*
  * cf_conv2d_f16s* / cf_conv_transpose2d_k2s2_f16s call takes the one-tile kernel's hi x hi instantiation (a third of the MFMAs) and
  * cf_conv2d_wino_ok answers 0. */
 int cf_conv_terms(int terms);
+/* nn.Conv3d forward on the same f16 MFMA with the same 3-term split (csrc/conv3d_f16s.hip; generic_UNet.py with conv_op = nn.Conv3d): kernel
+ * (KD, 3, 3) with KD in {1, 3}, padding (KD/2, 1, 1), stride (stride_d, stride_hw, stride_hw) with each in {1, 2}.  x1 [B,C1,D,H,W], the optional
+ * x2 [B,C2,D,H,W] (cat[x1, x2] never materialised) and out [B,Cout,Do,Ho,Wo] are dense NCDHW, read and written in place; all KD * 9 taps of a
+ * channel chunk accumulate in one kernel and the output is written once with alpha * acc + bias.  wpk from
+ * cineflow.ops.pack_conv3d_weight_f16s (fragment order [m-tile][chunk of 16][dz][ky*3+kx][hi/lo][lane][8], scaled by 2^s: pass alpha * 2^-s;
+ * split-aware when C2 > 0 and C1 % 16 != 0).  gn_ws / gn_groups as in cf_conv2d_f16s: fp64 {sum, sum of squares} per (sample, group) of the
+ * output over (Do, Ho, Wo), from the epilogue or -- where a workgroup holds planes of several samples -- from a statistics pass; a negative
+ * gn_groups declares gn_ws already zeroed.
+ * Sizes: 32-bit offsets -- ONE SAMPLE of x1, x2 and out must each stay below 2 GiB; larger batches are cut into sub-batches inside the
+ * library.  Activation range as cf_conv2d_f16s.  Only the three-term product is built.
+ * cf_conv3d_f16s_ok (host code, no launch) returns 1 when the kernel takes the shape and 0 otherwise: a kernel other than (1|3, 3, 3), a
+ * stride outside {1, 2}, a sample of some tensor at or above 2 GiB, a one-column map taller than the staging budget, cf_conv_terms(1), or
+ * a shape class on which the caller's composition of 2-D convolutions was measured faster (no depth taps or in-plane-only stride 2 at
+ * >= 65536 output voxels per sample; fewer than 512 workgroups with more than 24 (chunk, depth tap) steps: csrc/conv3d_f16s.hip);
+ * cf_conv3d_f16s then fails with CF_ERR_ARG and the caller keeps its own route. */
+int cf_conv3d_f16s(const float* x1, int C1, const float* x2, int C2, const void* wpk, const float* bias, float* out, int B, int D, int H,
+                   int W, int Cout, int KD, int KH, int KW, int stride_d, int stride_hw, float alpha, double* gn_ws, int gn_groups,
+                   void* stream);
+int cf_conv3d_f16s_ok(int B, int C1, int C2, int D, int H, int W, int Cout, int KD, int KH, int stride_d, int stride_hw);
 int cf_conv_transpose2d_k2s2_f16s(const float* x, const void* wpk, const float* bias, float* out, int out_ctotal,
                                   int out_coff, int B, int Cin, int H, int W, int Cout, float alpha, double* gn_ws, int gn_groups,
                                   void* stream);
