@@ -862,6 +862,27 @@ def resize3d(src, new_shape, linear=(1, 1, 1)):
     return dst
 
 
+def prev_stage_onehot(seg, classes, out):
+    """Previous-stage labels -> one-hot network-input planes (nnunet/inference/predict.py:82-85) in one kernel: batchgenerators'
+    resize_segmentation(seg, out.shape[1:], order=1) then to_one_hot(., classes).  seg: uint8 [X,Y,Z]; out: float32
+    [len(classes), X2, Y2, Z2], contiguous -- typically the view `net_input[num_modalities:]`, written in place.  Returns `out`."""
+    import ctypes
+    classes = [int(c) for c in classes]
+    if seg.dim() != 3 or out.dim() != 4 or out.shape[0] != len(classes):
+        raise ValueError("prev_stage_onehot: seg must be [X,Y,Z] and out [len(classes),X2,Y2,Z2], got %s and %s for %d classes"
+                         % (tuple(seg.shape), tuple(out.shape), len(classes)))
+    if not classes or any(c < 0 or c > 255 for c in classes):
+        raise ValueError("prev_stage_onehot: classes must be 1..255 label values in 0..255, got %r" % (classes,))
+    if seg.device != out.device:
+        raise ValueError("prev_stage_onehot: seg and out live on different devices")
+    cls = (ctypes.c_uint8 * len(classes))(*classes)
+    X, Y, Z = seg.shape
+    _, X2, Y2, Z2 = out.shape
+    check(lib().cf_prev_stage_onehot(_u8(seg, "seg"), X, Y, Z, _f32(out, "out"), X2, Y2, Z2, ctypes.cast(cls, ctypes.c_void_p), len(classes),
+                                     _stream()), "cf_prev_stage_onehot")
+    return out
+
+
 def resample_data_or_seg(data, new_shape, is_seg, axis=None, order=3, do_separate_z=False, order_z=0):
     """nnunet/preprocessing/preprocessing.py:111-200 on the device for the orders the export uses (0 and 1).  data: numpy or
     device tensor (c, x, y, z); returns the same kind.  Segmentations of order 0 are nearest-neighbour in every axis; data is

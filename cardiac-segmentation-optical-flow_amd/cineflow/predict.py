@@ -151,7 +151,10 @@ class CineTrainer:
     keeps the 2-class Generic_UNet stand-in of round 2.
     Plans without 'flow_net' (or with null) describe a segmentation-only model -- a plain 2-D nnU-Net folder: `flow_net` is None, neither
     'crop_size' nor a cropping network is needed, and the file-level API takes the reference's predict_non_flow route (predict.py:320-353).
-    `seg_nets` holds one packed Generic_UNet per selected fold (`load_ensemble`); `seg_net` is seg_nets[0]."""
+    `seg_nets` holds one packed Generic_UNet per selected fold (`load_ensemble`); `seg_net` is seg_nets[0].
+    plans['seg_net']['prev_stage_classes'] (a list of label values, e.g. [1, 2, 3]) makes the model the full-resolution stage of a cascade
+    (`3d_cascade_fullres`, nnUNetTrainerCascadeFullRes.py:87-88): the network takes num_modalities + len(classes) input channels, and
+    preprocess_patient appends the previous stage's labels as one-hot channels.  3-D segmentation-only models alone."""
 
     def __init__(self, plans, device, model_folder=None):
         self.plans = plans
@@ -166,6 +169,17 @@ class CineTrainer:
                 raise ValueError("plans.json holds both seg_net.dim == 3 and flow_net: the flow path is 2-D (a 3-D segmentation folder is segmentation-only)")
             if len(plans["patch_size"]) != 3:
                 raise ValueError("seg_net.dim == 3 needs a 3-entry patch_size, got %r" % (plans["patch_size"],))
+        psc = (plans.get("seg_net") or {}).get("prev_stage_classes")
+        if psc is not None:
+            if self.seg_dim != 3:
+                raise ValueError("plans.json holds seg_net.prev_stage_classes with seg_net.dim == %d: only a 3-D model can be the full-resolution "
+                                 "stage of a cascade (nnU-Net has no 2-D cascade)" % self.seg_dim)
+            if fk:
+                raise ValueError("plans.json holds both seg_net.prev_stage_classes and flow_net: a cascade stage is segmentation-only")
+            if not isinstance(psc, (list, tuple)) or not psc or any(not isinstance(c, int) or isinstance(c, bool) or not 0 <= c <= 255 for c in psc):
+                raise ValueError("seg_net.prev_stage_classes must be a non-empty list of label values in 0..255, got %r" % (psc,))
+        self.prev_stage_classes = None if psc is None else [int(c) for c in psc]
+        self.model_folder = model_folder
         # (a segmentation-only model has no heart-centred crop: no Processor)
         self.processor = Processor(crop_size=plans["crop_size"], image_size=plans["patch_size"][0]) if (fk or "crop_size" in plans) else None
         # mixed_precision of load_model_and_checkpoint_files / predict_from_folder (the reference's default True): with CF_SEG_MIXED_PRECISION=1
@@ -203,7 +217,7 @@ class CineTrainer:
     def _new_seg_net(self):
         sk = self.plans["seg_net"]
         if self.seg_dim == 3:           # a `3d_fullres` stage: Generic_UNet with conv_op = nn.Conv3d, at most MAX_NUM_FILTERS_3D = 320 filters
-            return Generic_UNet3D(self.plans["num_modalities"], sk["base_num_features"], self.num_classes, sk["num_pool"],
+            return Generic_UNet3D(self.plans["num_modalities"] + len(self.prev_stage_classes or ()), sk["base_num_features"], self.num_classes, sk["num_pool"],
                                   pool_op_kernel_sizes=sk.get("pool_op_kernel_sizes"), conv_kernel_sizes=sk.get("conv_kernel_sizes"))
         return Generic_UNet(self.plans["num_modalities"], sk["base_num_features"], self.num_classes, sk["num_pool"],
                             pool_op_kernel_sizes=sk.get("pool_op_kernel_sizes"))     # the plans' per-stage pooling (plans_per_stage[...]['pool_op_kernel_sizes'])
@@ -237,12 +251,21 @@ class CineTrainer:
         self.seg_nets = nets
 
     # -- nnUNetTrainer.py:571-597 preprocess_patient(list_of_files) -> (data[C,Z,Y,X], seg, properties)
-    def preprocess_patient(self, input_files):
+    def check_prev_stage(self, given):
+        """a cascade stage needs the previous stage's labels and no other model takes them (the reference ends both cases in a
+        channel-count crash inside the first convolution)"""
+        _check_prev_stage(self.prev_stage_classes, given, self.model_folder)
+
+    def preprocess_patient(self, input_files, seg_from_prev_stage=None):
         """Crop to non-zero, resample to the stage's spacing and normalise on the device (cineflow.preprocessing), driven by the
         same plan entries as the reference: preprocessor_name (default PreprocessorFor2D -- the fork's networks are 2-D),
         normalization_schemes, use_mask_for_norm, transpose_forward, dataset_properties.intensityproperties and
-        plans_per_stage[stage].current_spacing (absent: the case keeps its own spacing)."""
+        plans_per_stage[stage].current_spacing (absent: the case keeps its own spacing).
+        seg_from_prev_stage: the previous stage's label file of this case (predict.py:68-85), for a model with seg_net.prev_stage_classes: data
+        then has num_modalities + len(classes) channels."""
         from . import preprocessing as P
+        self.check_prev_stage(seg_from_prev_stage is not None)
+        prev = {} if seg_from_prev_stage is None else {"seg_from_prev_stage": seg_from_prev_stage, "prev_stage_classes": self.prev_stage_classes}
         plans = self.plans
         nmod = plans["num_modalities"]
         as_int_keys = lambda d, default: {int(k): v for k, v in (d or {c: default for c in range(nmod)}).items()}   # noqa: E731  (JSON keys are strings)
@@ -257,8 +280,8 @@ class CineTrainer:
         stages = plans.get("plans_per_stage")
         if stages:
             st = stages[str(plans.get("stage", 0))] if isinstance(stages, dict) and str(plans.get("stage", 0)) in stages else stages[plans.get("stage", 0)]
-            return pre.preprocess_test_case(list(input_files), np.array(st["current_spacing"], dtype=float))
-        return pre.preprocess_test_case(list(input_files), None)      # (no stages in the plans: the case keeps its own spacing)
+            return pre.preprocess_test_case(list(input_files), np.array(st["current_spacing"], dtype=float), **prev)
+        return pre.preprocess_test_case(list(input_files), None, **prev)      # (no stages in the plans: the case keeps its own spacing)
 
     # -- nnUNetTrainer.py:637-679
     def predict_preprocessed_data_return_seg_and_softmax(self, data, do_mirroring=True, mirror_axes=None, use_sliding_window=True,
@@ -457,6 +480,16 @@ class CineTrainer:
             torch.cuda.synchronize()
             DEVICE_SPLIT["finish_s"] = DEVICE_SPLIT.get("finish_s", 0.0) + time.perf_counter() - t2
         return res
+
+
+def _check_prev_stage(prev_stage_classes, given, model_folder):
+    if prev_stage_classes and not given:
+        raise ValueError("the model%s is the full-resolution stage of a cascade (seg_net.prev_stage_classes = %r): it needs the previous stage's "
+                         "segmentations (-l / lowres_segmentations / segs_from_prev_stage, or --lowres_model)"
+                         % (" in %s" % model_folder if model_folder else "", list(prev_stage_classes)))
+    if given and not prev_stage_classes:
+        raise ValueError("segmentations from a previous stage were given (-l), but the model%s has no seg_net.prev_stage_classes in its plans.json: "
+                         "it is not a cascade stage and would ignore them" % (" in %s" % model_folder if model_folder else ""))
 
 
 def _fold_dirs(folder, folds):
@@ -917,7 +950,9 @@ def _predict_patients(model, cases, folds, save_npz, num_threads_preprocessing, 
     share one device batch, and finished patients are exported by the NIfTI pool while the next group is on the device.
     A segmentation-only model (trainer.flow_net is None) takes the reference's other branch (predict.py:320-353 -> predict_non_flow) inside the
     same pipeline: all frames of all patients of a group go through predict_cine_2Dconv_tiled's device path in one call, every frame is
-    written to `output_filenames[t]` itself, nothing under Flow/ or Registered/; ED index, voxelmorph_raw and Processor are not used."""
+    written to `output_filenames[t]` itself, nothing under Flow/ or Registered/; ED index, voxelmorph_raw and Processor are not used.
+    A case may carry a fourth entry, `segs_from_prev_stage` (one label file per frame, or None): it goes to preprocess_patient with its frame, so
+    the labels are resized and encoded on the preprocessing thread's stream (predict.py:302 -> :61-85)."""
     import sys
     import time
     from collections import deque
@@ -941,8 +976,12 @@ def _predict_patients(model, cases, folds, save_npz, num_threads_preprocessing, 
         interpolation_order_z = segmentation_export_kwargs["interpolation_order_z"]
     seg_only = trainer.flow_net is None
     orders = []
-    for list_of_lists, output_filenames, ed_index in cases:
+    for list_of_lists, output_filenames, ed_index, *prev in cases:
         assert len(list_of_lists) == len(output_filenames)
+        if prev and prev[0] is not None:
+            assert len(prev[0]) == len(output_filenames)
+        if hasattr(trainer, "check_prev_stage"):
+            trainer.check_prev_stage(bool(prev) and prev[0] is not None)
         for o in output_filenames:
             for sub in ((None,) if seg_only else ("Segmentation", "Flow", "Registered")):
                 os.makedirs(join(os.path.dirname(o), sub) if sub else os.path.dirname(os.path.abspath(o)), exist_ok=True)
@@ -957,7 +996,7 @@ def _predict_patients(model, cases, folds, save_npz, num_threads_preprocessing, 
     tls = threading.local()
     stream_ids = itertools.count()
 
-    def pre_one(files):
+    def pre_one(files, seg_prev=None):
         # every preprocessing thread issues its (small) device kernels on a HIP stream of its own: on the default stream they -- and the
         # host read-backs between them -- queued behind the seconds-long network batch of the main thread.  The streams are taken from a
         # process-wide pool (thread k of every call gets stream k): torch's caching allocator keeps one pool of blocks per stream, so fresh
@@ -967,7 +1006,7 @@ def _predict_patients(model, cases, folds, save_npz, num_threads_preprocessing, 
             torch.cuda.set_device(trainer.device)                                # the current device is per thread (a new thread starts on GPU 0)
             tls.stream = _pooled_stream(trainer.device, next(stream_ids))
         with torch.cuda.stream(tls.stream):
-            r = trainer.preprocess_patient(files)                                # predict.py:302
+            r = trainer.preprocess_patient(files) if seg_prev is None else trainer.preprocess_patient(files, seg_prev)   # predict.py:302
             tls.stream.synchronize()
         return r, time.perf_counter() - t0
 
@@ -980,7 +1019,8 @@ def _predict_patients(model, cases, folds, save_npz, num_threads_preprocessing, 
         nonlocal nxt
         while nxt < len(cases) and len(submitted) < lookahead:
             lol = cases[nxt][0]
-            submitted.append((nxt, [pre_pool.apply_async(pre_one, (lol[i],)) for i in orders[nxt]]))
+            prev = cases[nxt][3] if len(cases[nxt]) > 3 and cases[nxt][3] is not None else [None] * len(lol)
+            submitted.append((nxt, [pre_pool.apply_async(pre_one, (lol[i], prev[i])) for i in orders[nxt]]))
             nxt += 1
 
     finishing = deque()                                                          # exports in flight: (seg_paths, reg_paths, jobs, output files)
@@ -1108,7 +1148,7 @@ def predict_cases(model, list_of_lists, output_filenames, folds, save_npz, num_t
     assert len(list_of_lists) == len(output_filenames)
     if segs_from_prev_stage is not None:
         assert len(segs_from_prev_stage) == len(output_filenames)
-    return _predict_patients(model, [(list_of_lists, output_filenames, ed_index)], folds, save_npz, num_threads_preprocessing, num_threads_nifti_save,
+    return _predict_patients(model, [(list_of_lists, output_filenames, ed_index, segs_from_prev_stage)], folds, save_npz, num_threads_preprocessing, num_threads_nifti_save,
                              do_tta, mixed_precision, all_in_gpu, step_size, checkpoint_name, segmentation_export_kwargs, disable_postprocessing)[0]
 
 
@@ -1132,6 +1172,13 @@ def predict_cases_fastest(model, list_of_lists, output_filenames, folds, num_thr
                          {"force_separate_z": None, "interpolation_order": 0, "interpolation_order_z": 0}, disable_postprocessing)
 
 
+def lowres_segmentation_file(lowres_segmentations, patient, case_id):
+    """the previous stage's label file of one case: `<l>/<patient>/<case>.nii.gz` (what a segmentation-only predict_from_folder run writes)
+    when it exists, else `<l>/<case>.nii.gz` (predict.py:730)"""
+    own = join(lowres_segmentations, patient, case_id + ".nii.gz")
+    return own if os.path.isfile(own) else join(lowres_segmentations, case_id + ".nii.gz")
+
+
 def predict_from_folder(model, input_folder, output_folder, folds, save_npz, num_threads_preprocessing, num_threads_nifti_save,
                         lowres_segmentations, part_id, num_parts, tta, mixed_precision=True, overwrite_existing=True, mode="normal",
                         overwrite_all_in_gpu=None, step_size=0.5, checkpoint_name="model_final_checkpoint",
@@ -1139,7 +1186,11 @@ def predict_from_folder(model, input_folder, output_folder, folds, save_npz, num
     """predict.py:665-780.  Patients are sharded `patients[part_id::num_parts]` (one process per GPU); every patient of
     the shard is processed.  Returns {patient: per frame (Segmentation, Flow, Registered) paths}; for a segmentation-only model folder
     (plans.json without 'flow_net') {patient: the written `<out>/<patient>/<case>.nii.gz` paths}.  (set_voxelmorph_raw / the CLI's --voxelmorph_raw additionally produce the voxelmorph_saver input tree;
-    the argument list itself is the reference's, name for name.)"""
+    the argument list itself is the reference's, name for name.)
+    lowres_segmentations (predict.py:728-733): the folder with the previous stage's label files, for a cascade model.  Per case
+    `<l>/<patient>/<case>.nii.gz` is taken when it exists -- the layout a segmentation-only run of this function writes, so the output folder
+    of the lowres run is passed as it is -- else `<l>/<case>.nii.gz`, the reference's literal join.  Missing files, a non-directory, a cascade
+    model without the folder and a folder given to another model all raise before the checkpoint is read."""
     os.makedirs(output_folder, exist_ok=True)
     assert os.path.isfile(join(model, "plans.json")), "Folder with saved model weights must contain a plans.json file"
     shutil.copy(join(model, "plans.json"), output_folder)
@@ -1147,6 +1198,9 @@ def predict_from_folder(model, input_folder, output_folder, folds, save_npz, num
         model_plans = json.load(f)
     expected_num_modalities = model_plans["num_modalities"]
     seg_only = not model_plans.get("flow_net")                                   # a plain 2-D nnU-Net folder: predict.py:320-353's other branch
+    if lowres_segmentations is not None:
+        assert os.path.isdir(lowres_segmentations), "if lowres_segmentations is not None then it must point to a directory"
+    _check_prev_stage((model_plans.get("seg_net") or {}).get("prev_stage_classes"), lowres_segmentations is not None, model)
     if mode not in ("normal", "fast", "fastest"):
         raise ValueError("unrecognized mode. Must be normal, fast or fastest")
     patients = sorted(p for p in os.listdir(input_folder) if os.path.isdir(join(input_folder, p)))
@@ -1171,7 +1225,12 @@ def predict_from_folder(model, input_folder, output_folder, folds, save_npz, num
         csv_path = join(current_input_folder, patient + ".csv")                  # predict.py:700, :1196-1198
         if os.path.isfile(csv_path):
             ed_index = get_ed_es_indices(csv_path)[0]
-        cases.append((list_of_lists, output_files, ed_index))
+        prev = None
+        if lowres_segmentations is not None:
+            prev = [lowres_segmentation_file(lowres_segmentations, patient, i) for i in case_ids]
+            assert all([os.path.isfile(i) for i in prev]), "not all lowres_segmentations files are present. " \
+                                                           "(I was searching for case_id.nii.gz in that folder)"
+        cases.append((list_of_lists, output_files, ed_index, prev))
     seg_exp = segmentation_export_kwargs
     if mode != "normal":
         assert save_npz is False                                                 # predict.py:755, :771
@@ -1193,6 +1252,8 @@ def main(argv=None):
     parser.add_argument("-f", "--folds", nargs="+", default="None")
     parser.add_argument("-z", "--save_npz", required=False, action="store_true")
     parser.add_argument("-l", "--lowres_segmentations", required=False, default="None")
+    parser.add_argument("--lowres_model", required=False, default=None, help="model folder of the cascade's 3d_lowres stage: without -l it is "
+                        "predicted first into <output_folder>/3d_lowres_predictions, which then serves as -l (predict_simple.py:196-215)")
     parser.add_argument("--part_id", type=int, required=False, default=0)
     parser.add_argument("--num_parts", type=int, required=False, default=1)
     parser.add_argument("--num_threads_preprocessing", required=False, default=6, type=int)
@@ -1216,8 +1277,22 @@ def main(argv=None):
     tta = bool(a.tta) and not a.disable_tta
     if a.voxelmorph_raw is not None:
         set_voxelmorph_raw(a.voxelmorph_raw, a.voxelmorph_pkl)
+    lowres = None if a.lowres_segmentations == "None" else a.lowres_segmentations
+    if a.lowres_model is not None and lowres is None:
+        print("lowres_segmentations is None. Attempting to predict 3d_lowres first...")
+        assert a.part_id == 0 and a.num_parts == 1, "if you don't specify a --lowres_segmentations folder for the " \
+                                                    "inference of the cascade, custom values for part_id and num_parts " \
+                                                    "are not supported. If you wish to have multiple parts, please " \
+                                                    "run the 3d_lowres inference first (separately)"
+        assert os.path.isdir(a.lowres_model), "model output folder not found. Expected: %s" % a.lowres_model
+        lowres = join(a.output_folder, "3d_lowres_predictions")
+        predict_from_folder(a.lowres_model, a.input_folder, lowres, folds, False, a.num_threads_preprocessing, a.num_threads_nifti_save, None,
+                            a.part_id, a.num_parts, tta, mixed_precision=not a.disable_mixed_precision,
+                            overwrite_existing=bool(a.overwrite_existing), mode=a.mode, overwrite_all_in_gpu=all_in_gpu, step_size=a.step_size,
+                            checkpoint_name=a.chk)
+        print("3d_lowres done")
     return predict_from_folder(a.model_output_folder, a.input_folder, a.output_folder, folds, a.save_npz, a.num_threads_preprocessing,
-                               a.num_threads_nifti_save, None, a.part_id, a.num_parts, tta, mixed_precision=not a.disable_mixed_precision,
+                               a.num_threads_nifti_save, lowres, a.part_id, a.num_parts, tta, mixed_precision=not a.disable_mixed_precision,
                                overwrite_existing=bool(a.overwrite_existing), mode=a.mode, overwrite_all_in_gpu=all_in_gpu,
                                step_size=a.step_size, checkpoint_name=a.chk)
 

@@ -6,6 +6,7 @@ class names, argument meaning and return values; numpy in, numpy out like the re
 libcineflow_hip.so (csrc/preprocess.hip, csrc/postprocess.hip); torch only holds memory, slices and moves it.
 """
 import ctypes
+import os
 from collections import OrderedDict
 
 import numpy as np
@@ -197,6 +198,61 @@ def _resize_labels(t, new_shape, lin):
     return out
 
 
+def resize_segmentation(segmentation, new_shape, order=1):
+    """batchgenerators.augmentations.utils.resize_segmentation on the device route of `resample_data_or_seg`: order 0 resizes the label
+    map itself (nearest), order 1 resizes every label's indicator and assigns the label where it reaches 0.5, labels ascending.
+    segmentation: 2-D or 3-D, numpy or device tensor; the same kind and dtype come back.  Other orders are not built."""
+    was_numpy = not torch.is_tensor(segmentation)
+    assert len(segmentation.shape) == len(new_shape), "new shape must have same dimensionality as segmentation"
+    if order not in (0, 1):
+        raise NotImplementedError("resize_segmentation is built for orders 0 and 1 (got %s)" % (order,))
+    t = torch.from_numpy(np.ascontiguousarray(segmentation)) if was_numpy else segmentation
+    if t.dim() not in (2, 3):
+        raise ValueError("resize_segmentation takes a 2-D or 3-D label map, got shape %s" % (tuple(t.shape),))
+    dtype_in = t.dtype
+    lead = (1,) * (3 - t.dim())
+    new3 = lead + tuple(int(v) for v in new_shape)                          # (a 2-D map is a one-slice volume: that axis keeps its sample)
+    t = t.to(_dev(), dtype=torch.float32).reshape((1,) + lead + tuple(t.shape)).contiguous()
+    out = ops.resize3d(t, new3, [0, 0, 0]).round() if order == 0 else _resize_labels(t, new3, [1, 1, 1])
+    out = out.reshape(new3[len(lead):]).to(dtype_in)
+    return out.cpu().numpy() if was_numpy else out
+
+
+def to_one_hot(seg, all_seg_labels=None):
+    """nnunet/utilities/one_hot_encoding.py: [len(labels), *seg.shape] of seg's dtype, plane i is 1 where seg == all_seg_labels[i]
+    (default: the labels present).  numpy or tensor in, the same kind out."""
+    if torch.is_tensor(seg):
+        labels = torch.unique(seg).tolist() if all_seg_labels is None else list(all_seg_labels)
+        return torch.stack([(seg == l_) for l_ in labels]).to(seg.dtype) if labels else seg.new_zeros((0,) + tuple(seg.shape))
+    labels = np.unique(seg) if all_seg_labels is None else all_seg_labels
+    result = np.zeros((len(labels),) + tuple(seg.shape), dtype=seg.dtype)
+    for i, l_ in enumerate(labels):
+        result[i][seg == l_] = 1
+    return result
+
+
+def prev_stage_to_input(data, seg_prev, classes):
+    """nnunet/inference/predict.py:82-85 -- the network input of a cascade's full-resolution stage: `data` [C, X2, Y2, Z2] (preprocessed,
+    float32) with the previous stage's label map `seg_prev` [X, Y, Z] (already transposed, labels 0..255) appended as len(classes)
+    one-hot channels on data's grid.  One kernel (ops.prev_stage_onehot) resizes and encodes the labels straight into channels C.. of
+    the result: no intermediate label volume, no per-label pass, no vstack.  numpy or device tensor in (data decides), same kind out."""
+    was_numpy = not torch.is_tensor(data)
+    d = _to_dev(data)
+    assert d.dim() == 4 and len(seg_prev.shape) == 3, "data must be (c, x, y, z) and seg_prev (x, y, z)"
+    classes = [int(c) for c in classes]
+    s = seg_prev if torch.is_tensor(seg_prev) else torch.from_numpy(np.ascontiguousarray(seg_prev))
+    if s.dtype != torch.uint8:
+        lo, hi = (int(v) for v in torch.aminmax(s))
+        if lo < 0 or hi > 255:
+            raise ValueError("prev_stage_to_input: previous-stage labels must lie in 0..255, got %d..%d" % (lo, hi))
+    s = s.to(d.device, dtype=torch.uint8).contiguous()
+    C = d.shape[0]
+    out = torch.empty((C + len(classes),) + tuple(d.shape[1:]), dtype=torch.float32, device=d.device)
+    out[:C].copy_(d)
+    ops.prev_stage_onehot(s, classes, out[C:])
+    return out.cpu().numpy() if was_numpy else out
+
+
 def resample_data_or_seg(data, new_shape, is_seg, axis=None, order=3, do_separate_z=False, order_z=0):
     """preprocessing.py:111-200.  data (c, x, y, z), numpy or device tensor (the same kind is returned).  Built: data of order
     0, 1 or 3 and segmentations of order 0 or 1, with order_z 0 or 1 (data) / 0 (segmentations) along the separate axis."""
@@ -346,18 +402,33 @@ class GenericPreprocessor(object):
 
     _remove_nans = True
 
-    def preprocess_test_case(self, data_files, target_spacing=None, seg_file=None, force_separate_z=None, need_seg=True):
+    def preprocess_test_case(self, data_files, target_spacing=None, seg_file=None, force_separate_z=None, need_seg=True, seg_from_prev_stage=None,
+                             prev_stage_classes=None):
         """preprocessing.py:323-331 -> (data float32 [C, ...], seg, properties), numpy like the reference.  The case goes to the device once
         and comes back once: crop, transpose, resampling and normalisation hand device tensors to each other (the numpy-in / numpy-out
         functions above cost two more 2 MB copies and a 4 MB int64 label map per frame, with a stream synchronisation each, which the
-        file-level API paid under a running network batch -- profiles/r03_api_split.md).  need_seg=False skips the label map's read-back."""
+        file-level API paid under a running network batch -- profiles/r03_api_split.md).  need_seg=False skips the label map's read-back.
+        seg_from_prev_stage (a .nii.gz label file of the cascade's previous stage) + prev_stage_classes: nnunet/inference/predict.py:68-85 --
+        the UNCROPPED label map, transposed, is resized onto the cropped and resampled grid and appended as one-hot channels
+        (prev_stage_to_input), before the case leaves the device."""
         data, seg, properties = load_case_from_list_of_files(data_files, seg_file)
+        seg_prev = None
+        if seg_from_prev_stage is not None:
+            assert os.path.isfile(seg_from_prev_stage) and seg_from_prev_stage.endswith(".nii.gz"), \
+                "segs_from_prev_stage must point to a segmentation file"
+            seg_prev = read_nifti(seg_from_prev_stage)[0]
+            assert all([i == j for i, j in zip(seg_prev.shape, data.shape[1:])]) and seg_prev.ndim == data.ndim - 1, \
+                "image and segmentation from previous stage don't have the same pixel array shape! image: %s, seg_prev: %s" % \
+                (data_files[0], seg_from_prev_stage)
+            seg_prev = seg_prev.transpose(self.transpose_forward)
         data, seg, properties = ImageCropper.crop(_to_dev(data), properties, None if seg is None else _to_dev(seg))
         tf = (0, *[i + 1 for i in self.transpose_forward])
         if target_spacing is None:        # (plans without stages: the case keeps its own spacing)
             target_spacing = np.array(properties["original_spacing"], dtype=float)[list(self.transpose_forward)]
         d, s, properties = self.resample_and_normalize(data.permute(tf).contiguous(), target_spacing, properties, seg.permute(tf).contiguous(),
                                                        force_separate_z=force_separate_z)
+        if seg_prev is not None:
+            d = prev_stage_to_input(d, seg_prev, prev_stage_classes)
         return d.cpu().numpy().astype(np.float32, copy=False), (s.cpu().numpy() if need_seg else None), properties
 
     def preprocess_arrays(self, data, seg, properties, target_spacing, force_separate_z=None):

@@ -20,6 +20,9 @@ Without a flow folder (`import_reference_model_folder(seg_folder, None, out)`, n
 plans get no 'flow_net', the checkpoints no 'flow_state_dict', and predict_from_folder takes the segmentation-only route.  The stage's
 patch length picks the translation: 2 entries -> plans_from_reference (Generic_UNet), 3 entries -> plans_from_reference_3d (a `3d_fullres`
 folder, Generic_UNet3D on the native 3-D convolution).  A 3-D folder paired with a flow folder is refused: the flow path is 2-D.
+A `3d_cascade_fullres` folder -- recognised by its trainer's name or by a first convolution that is num_classes input channels wider than
+the modalities -- gets seg_net.prev_stage_classes = [1 .. num_classes]: the previous stage's labels become input channels
+(predict_from_folder's lowres_segmentations / -l).  Its `3d_lowres` sibling is an ordinary 3-D folder of stage 0 of the same plans.
 
 Command line:  python -m cineflow.reference_models -s SEG [-w FLOW] -o OUT [--crop_weights F --crop_config Y] [-f FOLDS] [-chk NAME]
 """
@@ -379,6 +382,20 @@ def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, cr
     return plans
 
 
+_FIRST_CONV = "conv_blocks_context.0.blocks.0.conv.weight"
+
+
+def _is_cascade_stage(trainer_info, checkpoint_path, plans):
+    """Is the 3-D folder the full-resolution stage of a cascade?  Either the trainer's `.model.pkl` name says so (nnUNetTrainerV2CascadeFullRes
+    and its variants) or the first convolution takes num_modalities + (num_classes - 1) input channels -- `plans` is the translated dict,
+    whose num_classes counts the background.  Any other width is left to check_state_dict's shape report."""
+    if trainer_info and "Cascade" in str(trainer_info.get("name") or ""):
+        return True
+    sd = load_reference_checkpoint(checkpoint_path)["state_dict"]
+    w = sd.get(_FIRST_CONV)
+    return w is not None and w.dim() == 5 and int(w.shape[1]) == plans["num_modalities"] + plans["num_classes"] - 1
+
+
 def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size, window_size):
     """import_reference_model_folder without a flow folder: every check of the segmentation side, nothing of the flow side"""
     from .predict import CineTrainer, save_model_folder
@@ -403,6 +420,10 @@ def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config,
     else:
         plans = plans_from_reference(ref_plans, stage)
         plans["image_size"] = int(plans["patch_size"][0])
+    if plans["seg_net"].get("dim") == 3 and _is_cascade_stage(seg_info, join(seg_folds[folds[0]], checkpoint_name + ".model"), plans):
+        # a `3d_cascade_fullres` folder (nnUNetTrainerCascadeFullRes.py:87-88: num_input_channels += num_classes - 1, background excluded):
+        # the previous stage's foreground labels come in as one-hot channels (predict.py:176, classes = range(1, num_classes))
+        plans["seg_net"]["prev_stage_classes"] = list(range(1, plans["num_classes"]))
     trainer = CineTrainer(plans, torch.device("cpu"))                           # the network's key / shape list, no device work
     params = {}
     for f in folds:                                                             # every tensor of every fold is checked before anything is written

@@ -378,6 +378,15 @@ int cf_nan_to_zero(float* x, long n, void* stream);
 int cf_assign_where_ge(float* dst, const float* src, long n, float thr, float value, void* stream);
 /* cropping.py:128-135: seg [C][V] gets `label` where seg == 0 and mask [V] == 0 (a zero-filled seg yields the created one) */
 int cf_seg_outside_mask(float* seg, const uint8_t* mask, int C, long V, float label, void* stream);
+/* Previous-stage labels of a `3d_cascade_fullres` model as network input (nnunet/inference/predict.py:82-85): batchgenerators'
+ * resize_segmentation(seg, (X2, Y2, Z2), order=1) and to_one_hot(., classes) in one pass.  seg: device uint8 [X][Y][Z], the previous
+ * stage's label map, already transposed.  dst: device fp32, n_classes planes of X2*Y2*Z2 -- a pointer INTO the network-input tensor
+ * [num_modalities + n_classes][X2][Y2][Z2] at channel num_modalities.  classes: HOST array, the label value of plane j
+ * (n_classes <= 255).  Sampling as cf_resize3d (linear on every axis); a voxel gets the largest label whose resized indicator is
+ * >= 0.5, else 0; plane j is 1.0f where that label is classes[j], else 0.0f.  Labels outside `classes` compete and get no plane.
+ * Indicators that are exactly 0.5 with weights that are not exact in fp32 are implementation-defined ties (csrc/prev_stage.hip). */
+int cf_prev_stage_onehot(const uint8_t* seg, int X, int Y, int Z, float* dst, int X2, int Y2, int Z2, const uint8_t* classes,
+                         int n_classes, void* stream);
 
 /* ---------------------------------------------------------------- downstream metrics (consumers of the output layout)
  * ConfusionMatrix.compute, nnunet/evaluation/metrics.py:65-82: counts3 (device u64 [3]) = {TP, FP, FN} of test != 0 vs

@@ -1,0 +1,109 @@
+"""Building the network input of a cascade's full-resolution stage from device-resident data and previous-stage labels, two routes:
+
+    unfused   preprocessing._resize_labels (per label: a compare, one cf_resize3d, one cf_assign_where_ge; a torch.unique().tolist()
+              host round trip first), then a compare per class and torch.cat with the data
+    fused     preprocessing.prev_stage_to_input: the data copied into the result and ONE cf_prev_stage_onehot writing the planes in place
+
+Workloads: a cine-sized volume (10, 256, 216) -> (13, 320, 270) and an isotropic one (80, 160, 160) -> (128, 256, 256), one modality,
+4 labels (smoothed seeded noise), classes [1, 2, 3].  Both routes run in one process, alternating, after warm-up; each sample is a host
+clock around `--calls` back-to-back calls that end in a device synchronise; the fused kernel alone is also timed by device events.  Per route: the median time per call and the bytes of the
+label planes written (3 x voxels x 4 B, the least any route must store) per second against the measured HBM copy rate of the chip.
+The planes of both routes are compared once (indicators of exactly 0.5 whose weights round in fp32 may fall on either side).
+
+    python tools/prev_stage_bench.py [--calls 20] [--runs 7]        one JSON line per workload, then the clocks rocm-smi reports"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "cardiac-segmentation-optical-flow_amd"))
+
+WORKLOADS = {"cine_10x256x216_to_13x320x270": ((10, 256, 216), (13, 320, 270)), "iso_80x160x160_to_128x256x256": ((80, 160, 160), (128, 256, 256))}
+CLASSES = [1, 2, 3]
+HBM_COPY_TBS = 6.29          # measured float4 copy rate of an MI355X (8.0 TB/s specified)
+
+
+def smoothed_labels(shape, seed, nlabels=4):
+    import numpy as np
+    from scipy.ndimage import gaussian_filter
+    g = gaussian_filter(np.random.RandomState(seed).randn(*shape), 3.0)
+    return np.digitize(g, np.quantile(g, np.linspace(0, 1, nlabels + 1)[1:-1])).astype(np.uint8)
+
+
+def smi():
+    try:
+        o = subprocess.run(["rocm-smi", "--showpower", "--showclocks", "--showperflevel"], capture_output=True, text=True, timeout=20).stdout
+    except (OSError, subprocess.TimeoutExpired) as e:
+        return ["rocm-smi unavailable: %s" % e]
+    return [ln.strip() for ln in o.splitlines() if "GPU[0]" in ln and any(k in ln.lower() for k in ("sclk", "mclk", "power", "performance"))]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--runs", type=int, default=7)
+    a = ap.parse_args()
+    import torch
+    assert torch.cuda.is_available(), "prev_stage_bench needs a GPU"
+    from cineflow import preprocessing as P
+    dev = torch.device("cuda:0")
+    print(json.dumps({"clocks_before": smi()}), flush=True)
+    for name, (src, dst) in WORKLOADS.items():
+        seg = torch.from_numpy(smoothed_labels(src, 5)).to(dev)
+        seg_f = seg.float()[None].contiguous()
+        data = torch.randn((1,) + dst, generator=torch.Generator().manual_seed(6)).to(dev)
+
+        def unfused():
+            lab = P._resize_labels(seg_f, dst, [1, 1, 1])[0]
+            return torch.cat([data] + [(lab == c).float()[None] for c in CLASSES])
+
+        def fused():
+            return P.prev_stage_to_input(data, seg, CLASSES)
+
+        def sample(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.calls):
+                fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / a.calls
+
+        xu, xf = unfused(), fused()
+        differ = int((xu != xf).sum())
+        del xu, xf
+        for fn in (unfused, fused):
+            sample(fn)                                                       # warm-up: code objects, allocator blocks
+        tu, tf = [], []
+        for _ in range(a.runs):                                              # the routes alternate: drift hits both
+            tu.append(sample(unfused))
+            tf.append(sample(fused))
+        mu, mf = statistics.median(tu), statistics.median(tf)
+        plane_bytes = len(CLASSES) * dst[0] * dst[1] * dst[2] * 4
+        # the kernel alone, by device events, into a resident buffer
+        from cineflow import ops
+        buf = torch.empty((1 + len(CLASSES),) + dst, dtype=torch.float32, device=dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        tk = []
+        for _ in range(a.runs + 1):
+            e0.record()
+            for _ in range(a.calls):
+                ops.prev_stage_onehot(seg, CLASSES, buf[1:])
+            e1.record()
+            e1.synchronize()
+            tk.append(e0.elapsed_time(e1) * 1e-3 / a.calls)
+        mk = statistics.median(tk[1:])
+        print(json.dumps({"workload": name, "calls_per_sample": a.calls, "plane_bytes": plane_bytes, "values_that_differ": differ,
+                          "unfused_us": [round(t * 1e6, 1) for t in tu], "fused_us": [round(t * 1e6, 1) for t in tf],
+                          "unfused_median_us": round(mu * 1e6, 1), "fused_median_us": round(mf * 1e6, 1), "unfused_over_fused": round(mu / mf, 2),
+                          "unfused_plane_GBs": round(plane_bytes / mu / 1e9, 1), "fused_plane_GBs": round(plane_bytes / mf / 1e9, 1),
+                          "kernel_median_us": round(mk * 1e6, 1), "kernel_plane_GBs": round(plane_bytes / mk / 1e9, 1),
+                          "kernel_share_of_hbm_copy_rate": round(plane_bytes / mk / (HBM_COPY_TBS * 1e12), 4)}), flush=True)
+    print(json.dumps({"clocks_after": smi()}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
