@@ -883,6 +883,61 @@ def prev_stage_onehot(seg, classes, out):
     return out
 
 
+ENSEMBLE_MAX_MEMBERS = 16
+
+
+def _ensemble_merge_into(members, seg, bbox_lo, mean, regions_class_order):
+    """cf_ensemble_merge on checked arguments: members [K,Z,Y,X] float16 / float32 -> labels into `seg` (uint8 [Zf,Yf,Xf], contiguous, every
+    voxel written) and, when `mean` is a tensor like a member, the mean into it."""
+    import ctypes
+    K, Z, Y, X = members[0].shape
+    Zf, Yf, Xf = seg.shape
+    ptrs = (ctypes.c_void_p * len(members))(*[m.data_ptr() for m in members])
+    order = None
+    if regions_class_order is not None:
+        order = ctypes.cast((ctypes.c_uint8 * K)(*regions_class_order), ctypes.c_void_p)
+    check(lib().cf_ensemble_merge(ctypes.cast(ptrs, ctypes.c_void_p), len(members), int(members[0].dtype == torch.float32), K, Z, Y, X,
+                                  _u8(seg, "seg"), Zf, Yf, Xf, int(bbox_lo[0]), int(bbox_lo[1]), int(bbox_lo[2]),
+                                  None if mean is None else mean.data_ptr(), order, _stream()), "cf_ensemble_merge")
+
+
+def ensemble_merge(members, full_shape=None, bbox_lo=(0, 0, 0), want_mean=False, regions_class_order=None):
+    """nnunet/inference/ensemble_predictions.py merge_files on the device, one kernel: members, a list of 1..16 softmax volumes [K,Z,Y,X]
+    of one shape, all float16 or all float32 -> (seg uint8 [Zf,Yf,Xf], mean [K,Z,Y,X] in the members' dtype or None).  The mean is numpy's
+    np.mean(np.vstack([m[None] for m in members]), 0) bit for bit; seg is its argmax(0) -- or, with a regions_class_order, 0 overwritten by
+    regions_class_order[i] where mean[i] > 0.5, in that order -- placed at bbox_lo inside zeros of full_shape (default: the members' own)."""
+    members = list(members)
+    if not 1 <= len(members) <= ENSEMBLE_MAX_MEMBERS:
+        raise ValueError("ensemble_merge: %d members (1..%d are supported)" % (len(members), ENSEMBLE_MAX_MEMBERS))
+    for i, m in enumerate(members):
+        if not isinstance(m, torch.Tensor) or not m.is_cuda:
+            raise TypeError("ensemble_merge: member %d must be a CUDA/HIP tensor (cineflow has no CPU path)" % i)
+    first = members[0]
+    if first.dtype not in (torch.float16, torch.float32) or first.dim() != 4:
+        raise ValueError("ensemble_merge: members must be [K,Z,Y,X] float16 or float32, member 0 is %s %s" % (tuple(first.shape), first.dtype))
+    for i, m in enumerate(members):
+        if m.dtype != first.dtype or m.shape != first.shape or m.device != first.device:
+            raise ValueError("ensemble_merge: member %d is %s %s on %s, member 0 is %s %s on %s"
+                             % (i, tuple(m.shape), m.dtype, m.device, tuple(first.shape), first.dtype, first.device))
+        if not m.is_contiguous():
+            raise ValueError("ensemble_merge: member %d must be contiguous" % i)
+    K = first.shape[0]
+    if not 1 <= K <= 255:
+        raise ValueError("ensemble_merge: %d classes (1..255 are supported)" % K)
+    full_shape = tuple(int(v) for v in (first.shape[1:] if full_shape is None else full_shape))
+    bbox_lo = tuple(int(v) for v in bbox_lo)
+    if len(full_shape) != 3 or len(bbox_lo) != 3 or any(lo < 0 or lo + n > f for lo, n, f in zip(bbox_lo, first.shape[1:], full_shape)):
+        raise ValueError("ensemble_merge: members of size %s at %s do not fit into %s" % (tuple(first.shape[1:]), bbox_lo, full_shape))
+    if regions_class_order is not None:
+        regions_class_order = [int(c) for c in regions_class_order]
+        if len(regions_class_order) != K or any(c < 0 or c > 255 for c in regions_class_order):
+            raise ValueError("ensemble_merge: regions_class_order must hold one label in 0..255 per class (%d), got %r" % (K, regions_class_order))
+    seg = torch.empty(full_shape, dtype=torch.uint8, device=first.device)
+    mean = torch.empty_like(first) if want_mean else None
+    _ensemble_merge_into(members, seg, bbox_lo, mean, regions_class_order)
+    return seg, mean
+
+
 def resample_data_or_seg(data, new_shape, is_seg, axis=None, order=3, do_separate_z=False, order_z=0):
     """nnunet/preprocessing/preprocessing.py:111-200 on the device for the orders the export uses (0 and 1).  data: numpy or
     device tensor (c, x, y, z); returns the same kind.  Segmentations of order 0 are nearest-neighbour in every axis; data is

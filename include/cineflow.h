@@ -387,6 +387,15 @@ int cf_seg_outside_mask(float* seg, const uint8_t* mask, int C, long V, float la
  * Indicators that are exactly 0.5 with weights that are not exact in fp32 are implementation-defined ties (csrc/prev_stage.hip). */
 int cf_prev_stage_onehot(const uint8_t* seg, int X, int Y, int Z, float* dst, int X2, int Y2, int Z2, const uint8_t* classes,
                          int n_classes, void* stream);
+/* Ensemble of saved softmax volumes (nnunet/inference/ensemble_predictions.py merge_files + the label step and bounding-box placement of
+ * segmentation_export.py) in one launch.  members: HOST array of n_members (1..16) device pointers, each [K][Z][Y][X] of __half (dtype 0)
+ * or float (dtype 1).  seg: device uint8 [Zf][Yf][Xf], written everywhere: the labels of the crop at (z0, y0, x0), 0 outside (a crop that
+ * overhangs the volume is refused).  mean: device [K][Z][Y][X] in the members' dtype, or NULL.  order: HOST array of K label values
+ * (regions_class_order), or NULL.  Bit for bit numpy's np.mean(np.vstack(...), 0): fp32 sum in member order, one true fp32 division by
+ * n_members, rounded to fp16 for __half members; label = first maximum over K of the rounded mean, or with `order` the last i with
+ * mean[i] > 0.5 mapped through order[i], else 0 (csrc/ensemble.hip). */
+int cf_ensemble_merge(const void* const* members, int n_members, int dtype, int K, int Z, int Y, int X, uint8_t* seg, int Zf, int Yf, int Xf,
+                      int z0, int y0, int x0, void* mean, const uint8_t* order, void* stream);
 
 /* ---------------------------------------------------------------- downstream metrics (consumers of the output layout)
  * ConfusionMatrix.compute, nnunet/evaluation/metrics.py:65-82: counts3 (device u64 [3]) = {TP, FP, FN} of test != 0 vs
