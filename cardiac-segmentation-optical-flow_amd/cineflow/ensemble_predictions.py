@@ -177,7 +177,7 @@ def merge(folders, output_folder, threads, override=True, postprocessing_file=No
             w.result()
 
     if postprocessing_file is not None:
-        from .predict import load_postprocessing, load_remove_save
+        from .export import load_postprocessing, load_remove_save
         for_which_classes, min_valid_obj_size = load_postprocessing(postprocessing_file)
         print("Postprocessing...")
         for p in patient_ids:                                             # apply_postprocessing_to_folder, connected_components.py:402-425

@@ -35,11 +35,12 @@ import numpy as np
 import torch
 
 from .safe_pickle import PlainUnpickler, load_plain_pickle
+from .trainer import CineTrainer, save_model_folder
 
 join = os.path.join
 
 _DROPPED_CHECKPOINT_KEYS = ("optimizer_state_dict", "lr_scheduler_state_dict", "amp_grad_scaler")
-# buffers the networks rebuild from their constructor arguments and never load: SpatialTransformer grids (predict._broadcast_params),
+# buffers the networks rebuild from their constructor arguments and never load: SpatialTransformer grids (trainer._broadcast_params),
 # BatchNorm step counters, Swin relative-position indices and shift masks (the MTLmodel cropper's state_dict holds all three)
 _DERIVED_BUFFERS = ("grid", "num_batches_tracked", "relative_position_index", "attn_mask")
 
@@ -309,7 +310,6 @@ def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, cr
     plans['patch_size'], no 'flow_net' / 'crop_size'; a cropper or crop_size / image_size / window_size make no sense then and are refused).
     Returns the plans written."""
     from . import config as C
-    from .predict import CineTrainer, save_model_folder
     if not os.path.isfile(join(seg_folder, "plans.pkl")):
         raise FileNotFoundError("%s has no plans.pkl (not the output folder of an nnU-Net trainer)" % seg_folder)
     if flow_weight_folder is None:
@@ -398,7 +398,6 @@ def _is_cascade_stage(trainer_info, checkpoint_path, plans):
 
 def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size, window_size):
     """import_reference_model_folder without a flow folder: every check of the segmentation side, nothing of the flow side"""
-    from .predict import CineTrainer, save_model_folder
     given = {k: v for k, v in dict(crop_weights=crop_weights, crop_config=crop_config, crop_size=crop_size, image_size=image_size,
                                    window_size=window_size).items() if v is not None}
     if given:

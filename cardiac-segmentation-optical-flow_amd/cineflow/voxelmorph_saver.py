@@ -36,9 +36,9 @@ import numpy as np
 import torch
 
 from . import ops
+from .export import load_remove_save, save_segmentation_nifti_from_softmax, subfiles
 from .inference import Processor
 from .nifti import read_nifti, write_nifti
-from .predict import load_remove_save, save_segmentation_nifti_from_softmax, subfiles
 from .safe_pickle import PlainUnpickler as _PlainUnpickler, load_plain_pickle  # noqa: F401  (shared with cineflow.reference_models)
 
 join = os.path.join
