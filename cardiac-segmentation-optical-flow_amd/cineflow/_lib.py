@@ -86,6 +86,10 @@ SIGNATURES = {
     "cf_cc_sweep": [P, I, I, I, P, P],
     "cf_cc_count": [P, P, L, P],
     "cf_cc_remove": [P, P, P, L, I, DBL, DBL, P],
+    "cf_cc_label": [P, P, I, I, I, P, P],
+    "cf_cc_sizes": [P, P, P, P, L, P, P, P, P],
+    "cf_pp_confusion": [P, P, I, I, I, I, P, P, P, P, P, P, P, DBL, P, P, P, P],
+    "cf_cc_apply": [P, P, L, I, I, I, P, P, P, P, P, P, DBL, P, P],
     "cf_conv2d_small_cin": [P, P, P, P, I, I, I, I, I, I, P, I, P],
     "cf_conv2d_small_cout": [P, P, P, P, P, I, I, I, I, I, P],
     "cf_nonzero_mask": [P, I, L, P, P],

@@ -1,0 +1,372 @@
+"""Folder evaluation on the device: the interface of nnunet/evaluation/evaluator.py:31-510 (Evaluator, NiftiEvaluator, run_evaluation,
+aggregate_scores, aggregate_scores_for_experiment, evaluate_folder; same names, argument lists, defaults and summary.json layout), restated.
+
+The numbers come from cineflow.metrics.  All confusion-type metrics of a case come from ONE cf_label_confusion launch whose 16 x 16 histogram
+is sliced per label; tuple labels (joint regions), `rv_rejection`'s label 1 and volumes holding a label value the histogram cannot place
+take one ConfusionMatrix per label instead.  Files go through cineflow.nifti; a thread pool reads and inflates the next cases while the
+device works on the current one, and only this process opens the GPU.
+
+    python -m cineflow.evaluation -ref GT_FOLDER -pred PRED_FOLDER -l 1 2 3
+"""
+import collections
+import hashlib
+import inspect
+import json
+from collections import OrderedDict
+from concurrent.futures import ThreadPoolExecutor
+from datetime import datetime
+from os.path import join
+
+import numpy as np
+import torch
+
+from . import metrics
+from ._lib import check, lib
+from .export import subfiles
+from .metrics import ALL_METRICS, ConfusionMatrix
+from .nifti import read_nifti
+from .ops import _stream, _u8
+
+HIST_K = 16
+
+# a volume that is already in memory: (file name it stands for, array [Z,Y,X], read_nifti's properties)
+Loaded = collections.namedtuple("Loaded", "path array props")
+
+
+def load_volume(path):
+    array, props = read_nifti(path)
+    return Loaded(path, array, props)
+
+
+def save_json(obj, file, indent=4, sort_keys=True):
+    with open(file, "w") as f:
+        json.dump(obj, f, sort_keys=sort_keys, indent=indent)
+
+
+def label_volume_u8(a, what="label volume"):
+    """numpy array or tensor holding the integers 0..255 (in any integer or float dtype) -> contiguous uint8 device tensor"""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if torch.is_tensor(a):
+        a = a.cpu().numpy() if a.dtype != torch.uint8 else a
+    if torch.is_tensor(a):
+        return a.to(dev).contiguous()
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        as_u8 = a.astype(np.uint8) if a.size and a.min() >= 0 and a.max() <= 255 else None
+        if as_u8 is None or not np.array_equal(as_u8, a):
+            raise ValueError("%s: the values must be the integers 0..255 (dtype %s, range %s..%s)"
+                             % (what, a.dtype, a.min() if a.size else "-", a.max() if a.size else "-"))
+        a = as_u8
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+class _SlicedMatrix(ConfusionMatrix):
+    """ConfusionMatrix of `test == label` vs `reference == label` whose counts are one row and one column of the label histogram.  The two
+    masks are only built when a surface metric asks for them."""
+
+    def __init__(self, hist, label, n, test_t, ref_t):
+        tp = int(hist[label, label])
+        fp, fn = int(hist[label, :].sum()) - tp, int(hist[:, label].sum()) - tp
+        self.tp, self.fp, self.fn, self.tn, self.size = tp, fp, fn, n - tp - fp - fn, n
+        self.test_empty, self.test_full = tp + fp == 0, tp + fp == n
+        self.reference_empty, self.reference_full = tp + fn == 0, tp + fn == n
+        self._label, self._test_t, self._ref_t = label, test_t, ref_t
+
+    test = property(lambda self: self._test_t == self._label)
+    reference = property(lambda self: self._ref_t == self._label)
+
+
+class Evaluator:
+    """Scores a test segmentation against a reference one, label by label.  `labels`: a list / tuple / set / array of label values, or a
+    dict {label value or tuple of values (a joint region): name}; without it the labels are the values found in the two volumes."""
+
+    default_metrics = ["False Positive Rate", "Dice", "Jaccard", "Precision", "Recall", "Accuracy", "False Omission Rate",
+                       "Negative Predictive Value", "False Negative Rate", "True Negative Rate", "False Discovery Rate", "Total Positives Test",
+                       "Total Positives Reference"]
+    default_advanced_metrics = ["Hausdorff Distance", "Hausdorff Distance 95", "Avg. Symmetric Surface Distance"]
+
+    def __init__(self, test=None, reference=None, labels=None, metrics=None, advanced_metrics=None, nan_for_nonexisting=True,
+                 rv_rejection=False):
+        self.test = self.reference = self.labels = self.result = None
+        self.confusion_matrix = ConfusionMatrix()
+        self.nan_for_nonexisting = nan_for_nonexisting
+        self.rv_rejection = rv_rejection
+        self.metrics = list(self.default_metrics if metrics is None else metrics)
+        self.advanced_metrics = list(self.default_advanced_metrics if advanced_metrics is None else advanced_metrics)
+        self.set_reference(reference)
+        self.set_test(test)
+        if labels is not None:
+            self.set_labels(labels)
+        elif test is not None and reference is not None:
+            self.construct_labels()
+
+    def set_test(self, test):
+        self.test = test
+
+    def set_reference(self, reference):
+        self.reference = reference
+
+    def set_labels(self, labels):
+        if isinstance(labels, dict):
+            self.labels = OrderedDict(labels)
+        elif isinstance(labels, (set, np.ndarray)):
+            self.labels = list(labels)
+        elif isinstance(labels, (list, tuple)):
+            self.labels = labels
+        else:
+            raise TypeError("Can only handle dict, list, tuple, set & numpy array, but input is of type {}".format(type(labels)))
+
+    def construct_labels(self):
+        """labels = the values present in the test and reference volumes (the reference volume alone when there is no test)"""
+        given = [v for v in (self.test, self.reference) if v is not None]
+        if not given:
+            raise ValueError("No test or reference segmentations.")
+        self.labels = [int(v) for v in np.unique(np.concatenate([np.unique(v) for v in given]))]
+
+    def set_metrics(self, metrics):
+        if isinstance(metrics, set):
+            metrics = list(metrics)
+        elif not isinstance(metrics, (list, tuple, np.ndarray)):
+            raise TypeError("Can only handle list, tuple, set & numpy array, but input is of type {}".format(type(metrics)))
+        self.metrics = metrics
+
+    def add_metric(self, metric):
+        if metric not in self.metrics:
+            self.metrics.append(metric)
+
+    def _metric_functions(self, names):
+        """ALL_METRICS, or -- evaluator.py:171-186 -- a function of that name in a local scope of one of the callers"""
+        funcs = {}
+        frames = None
+        for name in names:
+            if name in ALL_METRICS:
+                funcs[name] = ALL_METRICS[name]
+                continue
+            frames = inspect.getouterframes(inspect.currentframe()) if frames is None else frames
+            found = [f[0].f_locals[name] for f in frames if name in f[0].f_locals]
+            if not found:
+                raise NotImplementedError("Metric {} not implemented.".format(name))
+            funcs[name] = found[0]
+        return funcs
+
+    def _histogram(self):
+        """One cf_label_confusion launch for the case -> (hist [16,16] numpy, test_t, ref_t, n), or None when the volumes do not fit it:
+        values outside 0..255, or a voxel with a label >= 16 in either volume (the kernel counts those in one overflow bin, so no row or
+        column sum would be complete)."""
+        try:
+            test_t, ref_t = label_volume_u8(self.test, "test"), label_volume_u8(self.reference, "reference")
+        except ValueError:
+            return None
+        metrics.assert_shape(test_t, ref_t)
+        hist = torch.empty(HIST_K * HIST_K + 1, dtype=torch.int64, device=test_t.device)
+        check(lib().cf_label_confusion(_u8(test_t), _u8(ref_t), test_t.numel(), HIST_K, hist.data_ptr(), _stream()), "cf_label_confusion")
+        h = hist.cpu().numpy()
+        return None if h[-1] else (h[:-1].reshape(HIST_K, HIST_K), test_t, ref_t, test_t.numel())
+
+    def _per_label_matrix(self, label, joint, cut_rv):
+        """the per-label route: one ConfusionMatrix on masks (a joint region is the union of its labels, evaluator.py:204-210; rv_rejection
+        scores label 1 without the first two slices, evaluator.py:223-225)"""
+        values = list(label) if joint else [label]
+        test = np.isin(np.asarray(self.test), values)
+        reference = np.isin(np.asarray(self.reference), values)
+        if cut_rv:
+            test, reference = test[2:], reference[2:]
+        self.confusion_matrix.set_test(test)
+        self.confusion_matrix.set_reference(reference)
+        return self.confusion_matrix
+
+    def evaluate(self, test=None, reference=None, advanced=False, **metric_kwargs):
+        """-> OrderedDict {label name: {metric: value}}; with advanced=True the surface metrics are added"""
+        if test is not None:
+            self.set_test(test)
+        if reference is not None:
+            self.set_reference(reference)
+        if self.test is None or self.reference is None:
+            raise ValueError("Need both test and reference segmentations.")
+        if self.labels is None:
+            self.construct_labels()
+        self.metrics.sort()
+        wanted = list(self.metrics) + ([m for m in self.advanced_metrics if m not in self.metrics] if advanced else [])
+        funcs = self._metric_functions(wanted)
+        metric_kwargs.setdefault("reproducible", True)            # summary values must not depend on the order the border voxels were found in
+
+        named = isinstance(self.labels, dict)
+        items = list(self.labels.items()) if named else [(l, l) for l in self.labels]
+        routes = []
+        for label, name in items:
+            joint = hasattr(label, "__iter__")
+            if joint and not named:
+                raise TypeError("joint regions (tuple labels) need a dict of labels {tuple: name}")
+            cut_rv = bool(self.rv_rejection) and not named and label == 1
+            routes.append((label, name, joint, cut_rv, not joint and not cut_rv and 0 <= int(label) < HIST_K))
+        histogram = self._histogram() if any(r[4] for r in routes) else None
+
+        self.result = OrderedDict()
+        for label, name, joint, cut_rv, sliced in routes:
+            cm = _SlicedMatrix(histogram[0], int(label), histogram[3], histogram[1], histogram[2]) if sliced and histogram is not None \
+                else self._per_label_matrix(label, joint, cut_rv)
+            self.result[str(name)] = OrderedDict((m, funcs[m](confusion_matrix=cm, nan_for_nonexisting=self.nan_for_nonexisting, **metric_kwargs))
+                                                 for m in wanted)
+        return self.result
+
+    def to_dict(self):
+        if self.result is None:
+            self.evaluate()
+        return self.result
+
+    def _names_and_columns(self):
+        names = [str(v) for v in (self.labels.values() if isinstance(self.labels, dict) else self.labels)]
+        return names, sorted(self.to_dict()[names[0]])
+
+    def to_array(self):
+        """float32 [labels, metrics], metrics in sorted order"""
+        names, columns = self._names_and_columns()
+        return np.array([[self.result[n][m] for m in columns] for n in names], dtype=np.float32)
+
+    def to_pandas(self):
+        import pandas as pd
+        names, columns = self._names_and_columns()
+        return pd.DataFrame(self.to_array(), index=names, columns=columns)
+
+
+class NiftiEvaluator(Evaluator):
+    """Evaluator on files (cineflow.nifti); a `Loaded` volume is taken as it is, which is how aggregate_scores reads ahead."""
+
+    def __init__(self, *args, **kwargs):
+        self.test_nifti = self.reference_nifti = None
+        super().__init__(*args, **kwargs)
+
+    def set_test(self, test):
+        self.test_nifti = None if test is None else test if isinstance(test, Loaded) else load_volume(test)
+        super().set_test(None if test is None else self.test_nifti.array)
+
+    def set_reference(self, reference, binary=False):
+        self.reference_nifti = None if reference is None else reference if isinstance(reference, Loaded) else load_volume(reference)
+        mask = None if reference is None else self.reference_nifti.array
+        if binary and mask is not None:
+            mask = (mask > 0).astype(mask.dtype)
+        super().set_reference(mask)
+
+    def evaluate(self, test=None, reference=None, voxel_spacing=None, **metric_kwargs):
+        if voxel_spacing is None:                                  # array axes are (z, y, x), itk spacing is (x, y, z): evaluator.py:311
+            voxel_spacing = np.array(self.test_nifti.props["itk_spacing"])[::-1]
+        metric_kwargs["voxel_spacing"] = voxel_spacing
+        return super().evaluate(test, reference, **metric_kwargs)
+
+
+def _name(x):
+    return x.path if isinstance(x, Loaded) else x
+
+
+def run_evaluation(args):
+    """one case: (test, reference, evaluator, metric_kwargs, metadata, binary) -> its scores plus file names and metadata"""
+    test, ref, evaluator, metric_kwargs, metadata, binary = args
+    evaluator.set_test(test)
+    evaluator.set_reference(ref, binary)
+    if evaluator.labels is None:
+        evaluator.construct_labels()
+    scores = evaluator.evaluate(**metric_kwargs)
+    for key, source in (("test", test), ("reference", ref)):
+        if isinstance(_name(source), str):
+            scores[key] = _name(source)
+    scores.update(metadata)
+    return scores
+
+
+def _summary(name, description, task, author, results):
+    """the summary.json document; its id is the md5 of the document without the id (evaluator.py:414-424)"""
+    doc = OrderedDict([("name", name), ("description", description), ("timestamp", str(datetime.today())), ("task", task), ("author", author),
+                       ("results", results)])
+    doc["id"] = hashlib.md5(json.dumps(doc).encode("utf-8")).hexdigest()[:12]
+    return doc
+
+
+def aggregate_scores(test_ref_pairs, evaluator=NiftiEvaluator, labels=None, nanmean=True, json_output_file=None, json_name="",
+                     json_description="", json_author="Fabian", json_task="", num_threads=2, metadata_list=None, rv_rejection=False,
+                     nb_threads=1, binary=False, **metric_kwargs):
+    """Scores every (test, reference) pair -- file names or `Loaded` volumes -- and returns {"all": [scores of each case], "mean": {label:
+    {metric: mean over the cases}}} (nanmean: NaN cases do not count); with json_output_file the summary.json is written.  labels: a list of
+    ints or a dict int -> name.  num_threads / nb_threads: reader threads (the larger of the two); the device work stays in this process."""
+    if isinstance(evaluator, type):
+        evaluator = evaluator(rv_rejection=rv_rejection)
+    if labels is not None:
+        evaluator.set_labels(labels)
+    tests, refs = [p[0] for p in test_ref_pairs], [p[1] for p in test_ref_pairs]
+    metadata_list = [{}] * len(refs) if metadata_list is None else metadata_list
+    count = min(len(tests), len(metadata_list))                    # (the reference zips the lists: the shortest one ends the run)
+
+    readers = max(1, min(16, max(int(nb_threads or 1), int(num_threads or 1))))
+    prefetch = isinstance(evaluator, NiftiEvaluator)
+    per_case = []
+    with ThreadPoolExecutor(readers) as pool:
+        def start(i):
+            return [pool.submit(load_volume, f) if prefetch and isinstance(f, str) else f for f in (tests[i], refs[i])] if i < count else None
+
+        ahead = collections.deque(start(i) for i in range(min(readers, count)))
+        for i in range(count):
+            pair = [f.result() if hasattr(f, "result") else f for f in ahead.popleft()]
+            ahead.append(start(i + readers))
+            per_case.append(run_evaluation((pair[0], pair[1], evaluator, metric_kwargs, metadata_list[i], binary)))
+
+    mean_of = np.nanmean if nanmean else np.mean
+    collected = OrderedDict()
+    for scores, metadata in zip(per_case, metadata_list):
+        for label, by_metric in scores.items():
+            if label in ("test", "reference") or label in metadata:
+                continue
+            for metric, value in by_metric.items():
+                collected.setdefault(label, OrderedDict()).setdefault(metric, []).append(value)
+    results = OrderedDict([("all", per_case),
+                           ("mean", OrderedDict((label, OrderedDict((m, float(mean_of(v))) for m, v in by_metric.items()))
+                                                for label, by_metric in collected.items()))])
+    if json_output_file is not None:
+        save_json(_summary(json_name, json_description, json_task, json_author, results), json_output_file)
+    return results
+
+
+def aggregate_scores_for_experiment(score_file, labels=None, metrics=Evaluator.default_metrics, nanmean=True, json_output_file=None,
+                                    json_name="", json_description="", json_author="Fabian", json_task=""):
+    """score_file: .npy of shape [cases, labels, metrics] -> the summary document (plain mean over the cases, as in the reference)"""
+    scores = np.load(score_file)
+    labels = [str(i) for i in range(scores.shape[1])] if labels is None else labels
+
+    def table(block):
+        return OrderedDict((label, OrderedDict((m, float(block[l][k])) for k, m in enumerate(metrics))) for l, label in enumerate(labels))
+    doc = _summary(json_name, json_description, json_task, json_author, {"all": [table(case) for case in scores], "mean": table(scores.mean(0))})
+    if json_output_file is not None:
+        with open(json_output_file, "w") as f:
+            json.dump(doc, f, indent=4, separators=(",", ": "))
+    return doc
+
+
+def evaluate_folder(folder_with_gts, folder_with_predictions, labels, **metric_kwargs):
+    """Scores every .nii.gz of folder_with_predictions against the file of the same name in folder_with_gts (both folders must hold the same
+    names) and writes folder_with_predictions/summary.json; surface metrics included, rv_rejection on, as in the fork (evaluator.py:486-487)."""
+    files_gt = subfiles(folder_with_gts, suffix=".nii.gz", join_=False)
+    files_pred = subfiles(folder_with_predictions, suffix=".nii.gz", join_=False)
+    assert set(files_gt) <= set(files_pred), "files missing in folder_with_predictions"
+    assert set(files_pred) <= set(files_gt), "files missing in folder_with_gts"
+    pairs = [(join(folder_with_predictions, f), join(folder_with_gts, f)) for f in files_pred]
+    return aggregate_scores(pairs, json_output_file=join(folder_with_predictions, "summary.json"), num_threads=8, labels=labels, advanced=True,
+                            rv_rejection=True, **metric_kwargs)
+
+
+def build_parser():
+    import argparse
+    parser = argparse.ArgumentParser(description="Scores the label files of -pred against those of -ref and writes PRED/summary.json: the "
+                                                 "scores of every case under 'all', their means over the cases under 'mean'.")
+    parser.add_argument("-ref", required=True, type=str, help="folder of the reference label files (.nii.gz)")
+    parser.add_argument("-pred", required=True, type=str, help="folder of the predicted label files, named like the reference ones")
+    parser.add_argument("-l", nargs="+", type=int, required=True, help="label values to score, e.g. -l 1 2 3 (0 is the background)")
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    return evaluate_folder(args.ref, args.pred, args.l)
+
+
+nnunet_evaluate_folder = main
+
+if __name__ == "__main__":
+    main()

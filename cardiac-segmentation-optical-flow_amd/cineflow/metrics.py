@@ -249,7 +249,15 @@ def _max_sum(dist):
     return mx, sm
 
 
-def _surface_metric(kind, test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity):
+def _mean_distance(dist, reproducible):
+    """mean of a distance vector.  The vector's order follows the border compaction (one atomic per wave), so the device sum rounds
+    differently from call to call; reproducible=True sums the sorted vector on the host instead: one value for one pair of masks."""
+    if reproducible:
+        return float(np.sum(np.sort(dist.cpu().numpy())) / dist.numel())
+    return _max_sum(dist)[1] / dist.numel()
+
+
+def _surface_metric(kind, test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity, reproducible=False):
     cm = _cm(test, reference, confusion_matrix)
     test_empty, test_full, reference_empty, reference_full = cm.get_existence()
     if test_empty or test_full or reference_empty or reference_full:
@@ -257,12 +265,12 @@ def _surface_metric(kind, test, reference, confusion_matrix, nan_for_nonexisting
     test, reference = cm.test, cm.reference
     d1 = surface_distances(test, reference, voxel_spacing, connectivity)
     if kind == "asd":
-        return _max_sum(d1)[1] / d1.numel()
+        return _mean_distance(d1, reproducible)
     d2 = surface_distances(reference, test, voxel_spacing, connectivity)
     if kind == "hd":
         return max(_max_sum(d1)[0], _max_sum(d2)[0])
     if kind == "assd":
-        return float(np.mean((_max_sum(d1)[1] / d1.numel(), _max_sum(d2)[1] / d2.numel())))
+        return float(np.mean((_mean_distance(d1, reproducible), _mean_distance(d2, reproducible))))
     return float(np.percentile(np.hstack((d1.cpu().numpy(), d2.cpu().numpy())), 95))
 
 
@@ -276,15 +284,16 @@ def hausdorff_distance_95(test=None, reference=None, confusion_matrix=None, nan_
     return _surface_metric("hd95", test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity)
 
 
-def avg_surface_distance(test=None, reference=None, confusion_matrix=None, nan_for_nonexisting=True, voxel_spacing=None, connectivity=1, **kwargs):
+def avg_surface_distance(test=None, reference=None, confusion_matrix=None, nan_for_nonexisting=True, voxel_spacing=None, connectivity=1,
+                         reproducible=False, **kwargs):
     """metrics.py:359-374 (medpy.metric.asd)."""
-    return _surface_metric("asd", test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity)
+    return _surface_metric("asd", test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity, reproducible)
 
 
 def avg_surface_distance_symmetric(test=None, reference=None, confusion_matrix=None, nan_for_nonexisting=True, voxel_spacing=None, connectivity=1,
-                                   **kwargs):
+                                   reproducible=False, **kwargs):
     """metrics.py:377-392 (medpy.metric.assd)."""
-    return _surface_metric("assd", test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity)
+    return _surface_metric("assd", test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity, reproducible)
 
 
 ALL_METRICS = {

@@ -1008,3 +1008,95 @@ def remove_all_but_the_largest_connected_component(image, for_which_classes, vol
             check(lib().cf_cc_remove(_u8(image), labels.data_ptr(), counts.data_ptr(), n, max_count, float(volume_per_voxel), thr, _stream()),
                   "cf_cc_remove")
     return image, largest_removed, kept_size
+
+
+# ------------------------------------------------------------------------------------------------ determine_postprocessing (csrc/cc_label.hip)
+PP_KMAX = 16
+
+
+def _region_table(region_of):
+    """dict {label value: region id} or a sequence of 256 region ids -> ctypes uint8 [256] (a host table; region 0 = outside)"""
+    import ctypes
+    tab = [0] * 256
+    if isinstance(region_of, dict):
+        for k, v in region_of.items():
+            tab[int(k)] = int(v)
+    else:
+        tab = [int(v) for v in region_of]
+        assert len(tab) == 256, "region_of must name all 256 label values"
+    assert tab[0] == 0 and all(0 <= v < 256 for v in tab), "region ids are 0..255 and label 0 is outside"
+    return (ctypes.c_uint8 * 256)(*tab)
+
+
+def _dhw(t):
+    shape = tuple(t.shape)
+    assert 1 <= len(shape) <= 3, "2-D or 3-D label maps"
+    return (1,) * (3 - len(shape)) + shape
+
+
+def _host_array(ctype, values, K, fill):
+    """values: None, or a dict / sequence indexed by class -> ctypes array [K]"""
+    if values is None:
+        return None
+    vals = [fill] * K
+    for k, v in (values.items() if isinstance(values, dict) else enumerate(values)):
+        vals[int(k)] = v
+    return (ctype * K)(*vals)
+
+
+def connected_component_labels(image, region_of):
+    """Every connected component (face neighbours, scipy.ndimage.label's default) of every region of a uint8 label map in one call:
+    int32 tensor of image's shape, 0 outside, else 1 + the smallest flat voxel index of the component.  region_of: {label: region id};
+    neighbours are connected iff their region ids are equal and non-zero."""
+    import ctypes
+    D, H, W = _dhw(image)
+    labels = torch.empty(image.shape, dtype=torch.int32, device=image.device)
+    tab = _region_table(region_of)
+    check(lib().cf_cc_label(_u8(image, "image"), labels.data_ptr(), D, H, W, ctypes.cast(tab, ctypes.c_void_p), _stream()), "cf_cc_label")
+    return labels
+
+
+def connected_component_sizes(labels, image, region_of, alive=None):
+    """-> (counts int32 [n] indexed by label - 1, region_max int32 [256][, region_max_alive int32 [256] when `alive` is given])"""
+    import ctypes
+    n = image.numel()
+    assert labels.dtype == torch.int32 and labels.is_cuda and labels.is_contiguous() and labels.numel() == n
+    counts = torch.empty(n, dtype=torch.int32, device=image.device)
+    mx = torch.empty(256 * (2 if alive is not None else 1), dtype=torch.int32, device=image.device)
+    tab = _region_table(region_of)
+    check(lib().cf_cc_sizes(labels.data_ptr(), _u8(image, "image"), ctypes.cast(tab, ctypes.c_void_p), None if alive is None else _u8(alive, "alive"),
+                            n, counts.data_ptr(), mx.data_ptr(), None if alive is None else mx[256:].data_ptr(), _stream()), "cf_cc_sizes")
+    return (counts, mx) if alive is None else (counts, mx[:256], mx[256:])
+
+
+def pp_confusion(pred, gt, K, labels_fg, counts_fg, max_fg, labels_cls, counts_cls, max_cls, max_cls_alive, volume_per_voxel, min_valid=None,
+                 z_skip=None):
+    """{TP, FP, FN} of every class < K for the raw prediction and its three filtered variants -> int64 device tensor [4, K, 3].
+    min_valid: None or {0: foreground threshold, c: class threshold} (missing entries: always remove); z_skip: None or {class: first slice}."""
+    import ctypes
+    D, H, W = _dhw(pred)
+    assert tuple(pred.shape) == tuple(gt.shape), "Shape mismatch: {} and {}".format(pred.shape, gt.shape)
+    out = torch.empty((4, K, 3), dtype=torch.int64, device=pred.device)
+    mv = _host_array(ctypes.c_double, min_valid, K, -1.0)
+    zs = _host_array(ctypes.c_int, z_skip, K, 0)
+    check(lib().cf_pp_confusion(_u8(pred, "pred"), _u8(gt, "gt"), D, H, W, K, labels_fg.data_ptr(), counts_fg.data_ptr(), max_fg.data_ptr(),
+                                labels_cls.data_ptr(), counts_cls.data_ptr(), max_cls.data_ptr(), max_cls_alive.data_ptr(), float(volume_per_voxel),
+                                None if mv is None else ctypes.cast(mv, ctypes.c_void_p), None if zs is None else ctypes.cast(zs, ctypes.c_void_p),
+                                out.data_ptr(), _stream()), "cf_pp_confusion")
+    return out
+
+
+def cc_apply(src, K, do_fg, classes, labels_fg, counts_fg, max_fg, labels_cls, counts_cls, max_cls, volume_per_voxel, min_valid=None, out=None):
+    """The filtered image for "foreground step yes/no + the single classes in `classes`" from the label maps of one case."""
+    import ctypes
+    out = torch.empty_like(src) if out is None else out
+    bits = 0
+    for c in classes:
+        assert 1 <= int(c) < K, "class %r outside 1..%d" % (c, K - 1)
+        bits |= 1 << int(c)
+    mv = _host_array(ctypes.c_double, min_valid, K, -1.0)
+    ptr = lambda t: None if t is None else t.data_ptr()                                  # noqa: E731
+    check(lib().cf_cc_apply(_u8(src, "src"), _u8(out, "out"), src.numel(), K, int(bool(do_fg)), bits, ptr(labels_fg), ptr(counts_fg), ptr(max_fg),
+                            ptr(labels_cls), ptr(counts_cls), ptr(max_cls), float(volume_per_voxel), None if mv is None else ctypes.cast(mv, ctypes.c_void_p),
+                            _stream()), "cf_cc_apply")
+    return out

@@ -330,6 +330,33 @@ int cf_cc_count(const int* labels, int* counts, long n, void* stream);
 int cf_cc_remove(uint8_t* image, const int* labels, const int* counts, long n, int max_count, double volume_per_voxel,
                  double min_valid, void* stream);
 
+/* ---------------------------------------------------------------- determine_postprocessing (connected_components.py:123-447) on the device
+ * Union-find labelling of EVERY region of a label map in one call, without a host round trip.  region_of: HOST table [256], label value ->
+ * region id (0 = outside; region_of[0] must be 0).  Two face neighbours are connected iff their region ids are equal and non-zero:
+ * region_of[c] = 1 for every class labels "all foreground as one object", region_of[c] = c labels every class on its own.
+ * labels int32 [D*H*W]: 0 outside, else 1 + the smallest voxel index of the component (what converged cf_cc_sweep passes give). */
+int cf_cc_label(const uint8_t* image, int* labels, int D, int H, int W, const uint8_t* region_of, void* stream);
+/* counts int32 [n] (zeroed here): counts[l-1] = size of the component labelled l.  region_max int32 [256] (device): the largest size per
+ * region id.  alive (device uint8 [n], optional, together with region_max_alive int32 [256]): the largest size among the components whose
+ * voxels are alive (non-zero in `alive`); a component must be alive or dead as a whole. */
+int cf_cc_sizes(const int* labels, const uint8_t* image, const uint8_t* region_of, const uint8_t* alive, long n, int* counts,
+                int* region_max, int* region_max_alive, void* stream);
+/* The what-if pass: out (device u64 [4][K][3]) = {TP, FP, FN} of every class c < K (labels >= K are scored nowhere; K <= 16) for the raw
+ * prediction, the foreground-filtered one, the per-class-filtered raw one and the per-class-filtered one after the foreground filter;
+ * no filtered image is written.  labels_fg / counts_fg / max_fg: cf_cc_label with region id 1 for every class + cf_cc_sizes;
+ * labels_cls / counts_cls / max_cls / max_cls_alive: the same with region_of[c] = c (max_cls_alive restricted to what the foreground filter
+ * keeps).  min_valid: HOST double [K] or NULL, [0] for the foreground region and [c] for class c, in cf_cc_remove's convention (< 0:
+ * always remove; NULL: all -1).  z_skip: HOST int [K] or NULL: class c is scored on slices z >= z_skip[c] only. */
+int cf_pp_confusion(const uint8_t* pred, const uint8_t* gt, int D, int H, int W, int K, const int* labels_fg, const int* counts_fg,
+                    const int* max_fg, const int* labels_cls, const int* counts_cls, const int* max_cls, const int* max_cls_alive,
+                    double volume_per_voxel, const double* min_valid, const int* z_skip, unsigned long long* out, void* stream);
+/* dst = src with the foreground step applied (do_fg) and then the largest-component filter of every class whose bit is set in class_bits
+ * (bit c for class c, 1 <= c < K), from the same label maps; max_cls is the per-class maximum of the image the class step sees (the alive
+ * one after a foreground step).  src == dst is allowed. */
+int cf_cc_apply(const uint8_t* src, uint8_t* dst, long n, int K, int do_fg, int class_bits, const int* labels_fg, const int* counts_fg,
+                const int* max_fg, const int* labels_cls, const int* counts_cls, const int* max_cls, double volume_per_voxel,
+                const double* min_valid, void* stream);
+
 /* resample_data_or_seg, nnunet/preprocessing/preprocessing.py:111-200 (export path, orders 0 and 1): src [N,X,Y,Z] ->
  * dst [N,X2,Y2,Z2], sampling at src = (n/n2)*(dst+0.5)-0.5 with edge clamping (skimage resize mode='edge',
  * map_coordinates mode='nearest'); per axis linear (1) or nearest (0). */
