@@ -47,18 +47,16 @@ class Sequential(Module):
         for i, m in self._mods.items():
             yield str(i), m
 
+    def _prepare(self):
+        self._folded.clear()      # folded from the slots' weights on first use: a (re)load must not keep the previous checkpoint's
+
     def conv_bn(self, i, x, x2=None, act="gelu", stride_obj=None):
         """conv at slot i followed by the BatchNorm at slot i + 1 and `act`, as one convolution with folded weights"""
-        key = (i, ops.CONV_MODE)
         if i not in self._folded:
             conv, bn = self._mods[i], self._mods[i + 1]
             s, t = bn.scale_shift()
-            f = Conv2d(conv.cin, conv.cout, conv.ks, stride=conv.stride, padding=conv.pad)
-            f._p["weight"] = (conv._p["weight"] * s.view(-1, 1, 1, 1)).contiguous()
-            f._p["bias"] = (conv._p["bias"] * s + t).contiguous()
-            f._prepare()
-            self._folded[i] = f
-        del key
+            self._folded[i] = Conv2d.from_tensors(conv._p["weight"] * s.view(-1, 1, 1, 1), conv._p["bias"] * s + t,
+                                                  conv.cin, conv.cout, conv.ks, stride=conv.stride, padding=conv.pad)
         return self._folded[i](x, x2=x2, act=act)
 
     def convT_bn_gelu(self, x):
@@ -66,11 +64,7 @@ class Sequential(Module):
         if "T" not in self._folded:
             ct, bn = self._mods[0], self._mods[1]
             s, t = bn.scale_shift()
-            f = ConvTranspose2d(ct.cin, ct.cout)
-            f._p["weight"] = (ct._p["weight"] * s.view(1, -1, 1, 1)).contiguous()
-            f._p["bias"] = (ct._p["bias"] * s + t).contiguous()
-            f._prepare()
-            self._folded["T"] = f
+            self._folded["T"] = ConvTranspose2d.from_tensors(ct._p["weight"] * s.view(1, -1, 1, 1), ct._p["bias"] * s + t, ct.cin, ct.cout)
         y = self._folded["T"](x)
         return ops.copy_channels(y, 0, y.shape[1], dst=y, act="gelu")          # in place: GELU of the folded ConvT + BN
 
@@ -170,17 +164,18 @@ class SwinCrossAttention(Module):
         self.before_cross_attention_img1 = _BeforeCrossAttention(dim)
         self.before_cross_attention_img2 = _BeforeCrossAttention(dim)
         self.cross_attn = _CrossAttention(dim, self.window_size, num_heads)
+        self._rows = {}
+
+    def _prepare(self):
+        self._rows = {}      # cut from the Linears' weights on first use: a (re)load must not keep the previous checkpoint's
 
     def _proj(self, lin, rows, x):
         """rows [a, b) of a Linear as a 1x1 convolution on [B,C,H,W]"""
-        key = "_rows_%d_%d" % rows
-        if key not in lin.__dict__:
-            c = Conv2d(lin.cin, rows[1] - rows[0], 1)
-            c._p["weight"] = lin._p["weight"][rows[0]:rows[1]].reshape(rows[1] - rows[0], lin.cin, 1, 1).contiguous()
-            c._p["bias"] = lin._p["bias"][rows[0]:rows[1]].contiguous()
-            c._prepare()
-            lin.__dict__[key] = c
-        return lin.__dict__[key](x)
+        key = (id(lin),) + rows
+        if key not in self._rows:
+            self._rows[key] = Conv2d.from_tensors(lin._p["weight"][rows[0]:rows[1]].reshape(rows[1] - rows[0], lin.cin, 1, 1),
+                                                  lin._p["bias"][rows[0]:rows[1]], lin.cin, rows[1] - rows[0], 1)
+        return self._rows[key](x)
 
     def forward(self, rescaled, rescaler):
         B, C, H, W = rescaled.shape

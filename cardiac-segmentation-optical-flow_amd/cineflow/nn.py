@@ -8,11 +8,10 @@ channel-first ([B,C,N]) so the reference's permute/contiguous round trips never 
 """
 import math
 
-import os
-
 import torch
 
 from . import ops
+from .convroute import OWN, PackedConv, PackedConvT, split_key
 
 
 class Module:
@@ -67,7 +66,18 @@ class Module:
         return self
 
     def _prepare(self):
-        """Hook: derive device-side layouts (pre-transposed weights) after loading."""
+        """Hook: derive device-side layouts (packed weights) after loading."""
+
+    @classmethod
+    def from_tensors(cls, weight, bias, *args, **kwargs):
+        """a weight / bias layer (constructor arguments as given) holding these device tensors instead of a checkpoint's: the derived
+        layers (a folded BatchNorm, a 1x1 view of another layer's weights)"""
+        m = cls(*args, bias=bias is not None, **kwargs)
+        m._p["weight"] = weight.contiguous()
+        if bias is not None:
+            m._p["bias"] = bias.contiguous()
+        m._prepare()
+        return m
 
     def __call__(self, *a, **k):
         return self.forward(*a, **k)
@@ -75,7 +85,7 @@ class Module:
 
 # --------------------------------------------------------------------------------------------- basic layers
 class Conv2d(Module):
-    """nn.Conv2d.  Weights are transposed once to [Cin*KH*KW, Cout] for the implicit-GEMM kernel."""
+    """nn.Conv2d.  The device forms of the weight and the choice of kernel belong to its convroute.PackedConv (`_packed`)."""
 
     def __init__(self, cin, cout, kernel_size=3, stride=1, padding=0, bias=True):
         super().__init__()
@@ -98,87 +108,43 @@ class Conv2d(Module):
 
     def _prepare(self):
         if "weight" in self._p:
-            self._wt = ops.prep_conv_weight(self._p["weight"])
-            self._f16s = ops.f16s_supported(self.ks[0], self.ks[1], self.stride, self.pad)
-            if self._f16s:
-                self._wpk, self._ws = ops.pack_conv_weight_f16s(self._p["weight"])
-                self._wpk_split = {}
-            # 3x3 / stride 1 layers with whole 128-channel output blocks (or a last block >= 96) may take the row-Winograd kernel
-            # (ops.wino_ok decides per call shape); its weights are transformed and packed on first use
-            self._wino = (self._f16s and self.ks == (3, 3) and self.stride == 1 and self.pad == (1, 1) and self.sub is None
-                          and (self.cout % 128 == 0 or (self.cout > 128 and self.cout % 128 >= 96)))
-            self._wino_pk = {}
+            self._packed = PackedConv(self._p["weight"], self._p.get("bias"), self.stride, self.pad, wino=self.sub is None)
 
-    def _packed_wino(self, c1, split):
-        key = c1 if (split and c1 % 16) else None
-        if key not in self._wino_pk:
-            self._wino_pk[key] = ops.pack_conv_weight_wino(self._p["weight"], c1=key)
-        return self._wino_pk[key]
+    @property
+    def _ws(self):
+        """scale exponent s of the layer's f16-split packing (packed values are 2^s * w)"""
+        return self._packed.scale
 
     def prenorm_ok(self, x):
-        """can this convolution take the RAW convolution output x with its normalisation + activation deferred (applied while the tile is
-        staged)?  3x3 / stride 1 only; on the Winograd kernel where that takes the shape, else on conv_f16s' vector-staging shapes"""
-        if not (self.ks == (3, 3) and self.stride == 1 and self.sub is None and getattr(self, "_f16s", False) and x.data_ptr() % 16 == 0):
-            return False
-        B, C, H, W = x.shape
-        return (self._wino and ops.wino_ok(B, C, 0, H, W, self.cout, prenorm=True)) or ops.prenorm_ok(x, self.cout)
+        """PackedConv.prenorm_ok; never for a subsampled (per-axis stride) layer"""
+        return self.sub is None and self._packed.prenorm_ok(x)
 
     def prenorm(self, x, coef, slope, stats_groups=None):
-        """conv(act((x - mean) * scale + shift)) with coef from ops.group_norm_coef; slope < 0: GELU.  Caller checked prenorm_ok(x)."""
-        B, C, H, W = x.shape
-        if self._wino and ops.wino_ok(B, C, 0, H, W, self.cout, prenorm=True):
-            wpk, wsc = self._packed_wino(C, False)
-            return ops.conv2d_wino_prenorm(x, coef, slope, wpk, wsc, self._p.get("bias"), self.cout, stats_groups=stats_groups)
-        return ops.conv2d_f16s_prenorm(x, coef, slope, self._wpk, self._ws, self._p.get("bias"), self.cout, stats_groups=stats_groups)
+        return self._packed.prenorm(x, coef, slope, stats_groups)
 
-    def _packed(self, x, x2):
-        """packed weights for this call's channel split (cat[x, x2] with x.shape[1] not a chunk multiple: packed once per split)"""
-        c1 = x.shape[1]
-        if x2 is None or c1 % ops.f16s_chunk(*self.ks) == 0:
-            return self._wpk, self._ws
-        if c1 not in self._wpk_split:
-            self._wpk_split[c1] = ops.pack_conv_weight_f16s(self._p["weight"], c1=c1)
-        return self._wpk_split[c1]
-
-    def forward(self, x, x2=None, act=None, res=None, out=None, out_coff=0, stats_groups=None):
+    def forward(self, x, x2=None, act=None, res=None, out=None, out_coff=0, stats_groups=None, alpha=1.0, bias=OWN):
         """stats_groups=G: returns (out, ws) with the GroupNorm statistics of `out` when the f16 kernel can fuse them, else (out, None)."""
         if self.sub is not None:
             assert act is None and res is None and out is None, "per-axis strides: plain convolution only"
-            y = self.forward_plain(x, x2)
+            y = self.forward_plain(x, x2, alpha=alpha, bias=bias)
             y = y[:, :, ::self.sub[0], ::self.sub[1]].contiguous()
             return (y, None) if stats_groups else y
-        return self.forward_plain(x, x2, act, res, out, out_coff, stats_groups)
+        return self.forward_plain(x, x2, act, res, out, out_coff, stats_groups, alpha, bias)
 
-    def forward_plain(self, x, x2=None, act=None, res=None, out=None, out_coff=0, stats_groups=None):
-        if (x2 is None and act is None and out is None and not stats_groups and ops.CONV_MODE == "f16s"
-                and ops.small_cout_supported(self.cout, self.ks[0], self.ks[1], self.stride, self.pad)):
-            return ops.conv2d_small_cout(x, self._p["weight"], self._p.get("bias"), res)          # the flow heads: direct fp32, HBM-bound
-        if (x2 is None and act is None and res is None and out is None and ops.CONV_MODE == "f16s"
-                and ops.small_cin_supported(self.cin, self.ks[0], self.ks[1], self.stride, self.pad, stats_groups)):
-            return ops.conv2d_small_cin(x, self._p["weight"], self._p.get("bias"), stats_groups)      # the stems: direct fp32, HBM-bound
-        Ho = (x.shape[2] + 2 * self.pad[0] - self.ks[0]) // self.stride + 1
-        Wo = (x.shape[3] + 2 * self.pad[1] - self.ks[1]) // self.stride + 1
-        if self._f16s and ops.CONV_MODE == "f16s" and ops.f16s_dynamic_ok(x, x2, self.ks[0], out_sample_elems=(self.cout if out is None else out.shape[1]) * Ho * Wo,
-                                                                           out_hw=Ho * Wo):
-            if (self._wino and x.data_ptr() % 16 == 0 and (x2 is None or x2.data_ptr() % 16 == 0)
-                    and ops.wino_ok(x.shape[0], x.shape[1], 0 if x2 is None else x2.shape[1], x.shape[2], x.shape[3], self.cout)):
-                wpk, wsc = self._packed_wino(x.shape[1], x2 is not None)
-                return ops.conv2d_wino(x, wpk, wsc, self._p.get("bias"), self.cout, x2=x2, act=act, res=res, out=out, out_coff=out_coff,
-                                       stats_groups=stats_groups)
-            wpk, wsc = self._packed(x, x2)
-            return ops.conv2d_f16s(x, wpk, wsc, self._p.get("bias"), self.cout, self.ks[0], self.ks[1], self.stride, self.pad,
-                                   x2=x2, act=act, res=res, out=out, out_coff=out_coff, stats_groups=stats_groups)
-        if stats_groups:
-            return ops.conv2d(x, self._wt, self._p.get("bias"), self.cout, self.ks[0], self.ks[1], self.stride, self.pad, x2=x2, act=act,
-                              res=res, out=out, out_coff=out_coff), None
-        return ops.conv2d(x, self._wt, self._p.get("bias"), self.cout, self.ks[0], self.ks[1], self.stride, self.pad, x2=x2, act=act,
-                          res=res, out=out, out_coff=out_coff)
+    def forward_plain(self, x, x2=None, act=None, res=None, out=None, out_coff=0, stats_groups=None, alpha=1.0, bias=OWN):
+        # the direct fp32 kernels (HBM-bound layers) take a plain call of this layer class only; everything else is PackedConv's choice
+        if ops.CONV_MODE == "f16s" and x2 is None and act is None and out is None and alpha == 1.0 and bias is OWN:
+            if not stats_groups and ops.small_cout_supported(self.cout, self.ks[0], self.ks[1], self.stride, self.pad):
+                return ops.conv2d_small_cout(x, self._p["weight"], self._p.get("bias"), res)          # the flow heads
+            if res is None and ops.small_cin_supported(self.cin, self.ks[0], self.ks[1], self.stride, self.pad, stats_groups):
+                return ops.conv2d_small_cin(x, self._p["weight"], self._p.get("bias"), stats_groups)      # the stems
+        return self._packed(x, x2, act, res, out, out_coff, alpha, bias, stats_groups)
 
 
 class ConvTranspose2d(Module):
-    """nn.ConvTranspose2d(kernel_size = stride = (2, 2)); (2, 1) / (1, 2) for the plans' anisotropic stages (generic_UNet.py:343-344): a 1x1
-    convolution to Cout * k rows of the GEMM whose outputs are interleaved along the up-sampled axis by a strided copy (bottom-of-the-net
-    maps of a few pixels)."""
+    """nn.ConvTranspose2d(kernel_size = stride = (2, 2)) on its convroute.PackedConvT; (2, 1) / (1, 2) for the plans' anisotropic stages
+    (generic_UNet.py:343-344): a 1x1 convolution to Cout * k rows of the GEMM whose outputs are interleaved along the up-sampled axis by a
+    strided copy (bottom-of-the-net maps of a few pixels)."""
 
     def __init__(self, cin, cout, bias=True, kernel_size=(2, 2)):
         super().__init__()
@@ -190,16 +156,13 @@ class ConvTranspose2d(Module):
 
     def _prepare(self):
         if "weight" in self._p:
-            w = self._p["weight"]  # [Cin,Cout,kh,kw] -> GEMM rows m = co*kh*kw + dy*kw + dx
+            w, b = self._p["weight"], self._p.get("bias")  # [Cin,Cout,kh,kw] -> GEMM rows m = co*kh*kw + dy*kw + dx
             if self.ks == (2, 2):
-                self._wpk, self._ws = ops.pack_conv_weight_f16s(w.permute(1, 2, 3, 0).reshape(self.cout * 4, self.cin, 1, 1))
+                self._packed = PackedConvT(w, b)
             else:
                 k = self.ks[0] * self.ks[1]
-                self._w1 = Conv2d(self.cin, self.cout * k, 1, bias="bias" in self._p)     # (leading underscore: not a state-dict child)
-                self._w1._p["weight"] = w.permute(1, 2, 3, 0).reshape(self.cout * k, self.cin, 1, 1).contiguous()
-                if "bias" in self._p:
-                    self._w1._p["bias"] = self._p["bias"].repeat_interleave(k).contiguous()
-                self._w1._prepare()
+                self._w1 = Conv2d.from_tensors(w.permute(1, 2, 3, 0).reshape(self.cout * k, self.cin, 1, 1),
+                                               None if b is None else b.repeat_interleave(k), self.cin, self.cout * k, 1)
 
     def _forward_aniso(self, x):
         B, _, H, W = x.shape
@@ -211,12 +174,7 @@ class ConvTranspose2d(Module):
             assert out is None, "anisotropic transposed convolution writes its own tensor"
             y = self._forward_aniso(x)
             return (y, None) if stats_groups else y
-        if ops.CONV_MODE == "f16s" and ops.f16s_dynamic_ok(x, None, 1, out_sample_elems=(self.cout if out is None else out.shape[1]) * 4 * x.shape[2] * x.shape[3],
-                                                           out_hw=x.shape[2] * x.shape[3]):
-            return ops.conv_transpose2d_k2s2_f16s(x, self._wpk, self._ws, self._p.get("bias"), self.cout, out=out, out_coff=out_coff,
-                                                  stats_groups=stats_groups)
-        y = ops.conv_transpose2d_k2s2(x, self._p["weight"], self._p.get("bias"), out=out, out_coff=out_coff)
-        return (y, None) if stats_groups else y
+        return self._packed(x, out, out_coff, stats_groups)
 
 
 class GroupNorm(Module):
@@ -289,37 +247,19 @@ class Conv3d(Module):
     def _prepare(self):
         if "weight" not in self._p:
             return
-        k, pad = self.ks[1], (self.ks[1] // 2, self.ks[1] // 2)
+        pad = (self.ks[1] // 2, self.ks[1] // 2)
         if self.ks == (1, 1, 1) and self.stride == (1, 1, 1):
             # the segmentation heads: a 1x1 convolution on the [B, C, D*H, W] view of the NCDHW tensor, no re-layout
-            self._head = Conv2d(self.cin, self.cout, 1, bias="bias" in self._p)        # (leading underscore: not a state-dict child)
-            self._head._p["weight"] = self._p["weight"].reshape(self.cout, self.cin, 1, 1).contiguous()
-            if "bias" in self._p:
-                self._head._p["bias"] = self._p["bias"]
-            self._head._prepare()
+            self._head = Conv2d.from_tensors(self._p["weight"].reshape(self.cout, self.cin, 1, 1), self._p.get("bias"), self.cin, self.cout, 1)
             return
         # the native kernel (conv3d_f16s.hip) takes (1|3, 3, 3) kernels; packed per channel split on first use
         self._native = self.ks[1:] == (3, 3)
         self._pk3 = {}
-        self._f16s = ops.f16s_supported(k, k, self.stride[1], pad)
-        self._taps = []
-        for dz in range(self.ks[0]):
-            w2 = self._p["weight"][:, :, dz].contiguous()
-            self._taps.append((ops.prep_conv_weight(w2), {None: ops.pack_conv_weight_f16s(w2)} if self._f16s else None, w2))
-
-    def _conv2d(self, dz, x, x2, bias, res, out):
-        k, st, pad = self.ks[1], self.stride[1], (self.ks[1] // 2, self.ks[1] // 2)
-        wt, pks, w2 = self._taps[dz]
-        if self._f16s and ops.CONV_MODE == "f16s" and ops.f16s_dynamic_ok(x, x2, k):
-            key = x.shape[1] if (x2 is not None and x.shape[1] % ops.f16s_chunk(k, k)) else None
-            if key not in pks:
-                pks[key] = ops.pack_conv_weight_f16s(w2, c1=key)      # split-aware packing, once per channel split
-            pk = pks[key]
-            return ops.conv2d_f16s(x, pk[0], pk[1], bias, self.cout, k, k, st, pad, x2=x2, res=res, out=out)
-        return ops.conv2d(x, wt, bias, self.cout, k, k, st, pad, x2=x2, res=res, out=out)
+        # the composed route: one 2-D convolution per depth tap (the layer's bias rides on the centre tap's call; never Winograd)
+        self._taps = [PackedConv(self._p["weight"][:, :, dz].contiguous(), None, self.stride[1], pad) for dz in range(self.ks[0])]
 
     def _packed3(self, x, x2):
-        key = x.shape[1] if (x2 is not None and x.shape[1] % 16) else None
+        key = split_key(x, x2, 16)
         if key not in self._pk3:
             self._pk3[key] = ops.pack_conv3d_weight_f16s(self._p["weight"], c1=key)
         return self._pk3[key]
@@ -360,7 +300,7 @@ class Conv3d(Module):
                 xin = xp[b, sl] if sd == 1 else xp[b, sl].contiguous()
                 xin2 = None if x2p is None else (x2p[b, sl] if sd == 1 else x2p[b, sl].contiguous())
                 osl = outp[b, zo_lo:zo_hi + 1]
-                self._conv2d(dz, xin, xin2, bias if n == 0 else None, None if n == 0 else osl, osl)
+                self._taps[dz](xin, xin2, res=None if n == 0 else osl, out=osl, bias=bias if n == 0 else None)
         return outp.permute(0, 2, 1, 3, 4).contiguous()
 
 
@@ -378,10 +318,7 @@ class ConvTranspose3d(Module):
 
     def _prepare(self):
         if "weight" in self._p:
-            self._taps = []
-            for dz in range(self.ks[0]):
-                w2 = self._p["weight"][:, :, dz].contiguous()    # [Cin,Cout,2,2]
-                self._taps.append((w2, ops.pack_conv_weight_f16s(w2.permute(1, 2, 3, 0).reshape(self.cout * 4, self.cin, 1, 1))))
+            self._taps = [PackedConvT(self._p["weight"][:, :, dz].contiguous(), self._p.get("bias")) for dz in range(self.ks[0])]    # [Cin,Cout,2,2] each
 
     def forward(self, x):
         B, C, D, H, W = x.shape
@@ -389,12 +326,7 @@ class ConvTranspose3d(Module):
         xp = x.permute(0, 2, 1, 3, 4).contiguous().view(B * D, C, H, W)
         outp = torch.empty((B, D, kd, self.cout, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
         for dz in range(kd):
-            w2, pk = self._taps[dz]
-            if ops.CONV_MODE == "f16s" and ops.f16s_dynamic_ok(xp, None, 1):
-                y = ops.conv_transpose2d_k2s2_f16s(xp, pk[0], pk[1], self._p.get("bias"), self.cout)
-            else:
-                y = ops.conv_transpose2d_k2s2(xp, w2, self._p.get("bias"))
-            outp[:, :, dz] = y.view(B, D, self.cout, 2 * H, 2 * W)
+            outp[:, :, dz] = self._taps[dz](xp).view(B, D, self.cout, 2 * H, 2 * W)
         return outp.view(B, D * kd, self.cout, 2 * H, 2 * W).permute(0, 2, 1, 3, 4).contiguous()
 
 
@@ -616,30 +548,21 @@ class MultiheadAttention(Module):
     def _prepare(self):
         if "in_proj_weight" in self._p:
             C = self.C
-            w, b = self._p["in_proj_weight"], self._p["in_proj_bias"]
-            self._wq, self._wk, self._wv = (w[i * C:(i + 1) * C].t().contiguous() for i in range(3))
-            self._wqk = w[:2 * C].t().contiguous()
-            self._bq, self._bk, self._bv = (b[i * C:(i + 1) * C].contiguous() for i in range(3))
-            self._bqk = b[:2 * C].contiguous()
-            pk = lambda m: ops.pack_conv_weight_f16s(m[:, :, None, None])
-            self._pq, self._pk, self._pv, self._pqk = pk(w[:C]), pk(w[C:2 * C]), pk(w[2 * C:]), pk(w[:2 * C])
-
-    def _proj(self, x, wt, packed, bias, cout):
-        if ops.CONV_MODE == "f16s" and ops.f16s_dynamic_ok(x, None, 1):
-            return ops.conv2d_f16s(x, packed[0], packed[1], bias, cout, 1, 1)
-        return ops.conv2d(x, wt, bias, cout, 1, 1)
+            w, b = self._p["in_proj_weight"].view(3 * C, C, 1, 1), self._p["in_proj_bias"]
+            self._q, self._k, self._v = (PackedConv(w[i * C:(i + 1) * C], b[i * C:(i + 1) * C]) for i in range(3))
+            self._qk = PackedConv(w[:2 * C], b[:2 * C])          # q and k of one input in one launch (same_qk)
 
     def forward(self, q_in, k_in, v_in, residual, same_qk=False):
         """q_in [B,C,Nq,1], k_in/v_in [B,C,Nk,1]; returns residual + out_proj(attention)."""
         C = self.C
         B, _, Nq, _ = q_in.shape
         if same_qk:
-            qk = self._proj(q_in, self._wqk, self._pqk, self._bqk, 2 * C)
+            qk = self._qk(q_in)
             q, k = qk.view(B, 2 * C, Nq).narrow(1, 0, C), qk.view(B, 2 * C, Nq).narrow(1, C, C)
         else:
-            q = self._proj(q_in, self._wq, self._pq, self._bq, C).view(B, C, Nq)
-            k = self._proj(k_in, self._wk, self._pk, self._bk, C).view(B, C, -1)
-        v = self._proj(v_in, self._wv, self._pv, self._bv, C).view(B, C, -1)
+            q = self._q(q_in).view(B, C, Nq)
+            k = self._k(k_in).view(B, C, -1)
+        v = self._v(v_in).view(B, C, -1)
         att = ops.attention_cf(q, k, v, self.nhead).view(B, C, Nq, 1)
         return self.out_proj(att, res=residual)
 
@@ -655,13 +578,10 @@ class _Linear(Module):
 
     def _prepare(self):
         if "weight" in self._p:
-            self._wt = self._p["weight"].t().contiguous()
-            self._wpk, self._ws = ops.pack_conv_weight_f16s(self._p["weight"][:, :, None, None])
+            self._packed = PackedConv(self._p["weight"].view(self.cout, self.cin, 1, 1), self._p.get("bias"))
 
     def forward(self, x, act=None, res=None):
-        if ops.CONV_MODE == "f16s" and ops.f16s_dynamic_ok(x, None, 1):
-            return ops.conv2d_f16s(x, self._wpk, self._ws, self._p["bias"], self.cout, 1, 1, act=act, res=res)
-        return ops.conv2d(x, self._wt, self._p["bias"], self.cout, 1, 1, act=act, res=res)
+        return self._packed(x, act=act, res=res)
 
 
 class TransformerFlowLayer(Module):

@@ -4,6 +4,8 @@ PyTorch is used for device memory (torch.empty on the caching allocator) and the
 number is produced by a hand-written HIP kernel in libcineflow_hip.so.  Inputs must be CUDA(=HIP) tensors; nothing
 here runs on the CPU and nothing falls back to torch operators.
 """
+import contextlib
+import math
 import os
 
 import numpy as np
@@ -158,9 +160,6 @@ def set_conv_mode(mode):
     CONV_MODE = mode
 
 
-import contextlib
-
-
 @contextlib.contextmanager
 def conv_terms(terms):
     """Product mode of the f16-MFMA convolutions launched from this thread inside the block (cf_conv_terms): 3 = hi/lo split (f32-class,
@@ -200,6 +199,29 @@ def f16s_dynamic_ok(x1, x2, kh, kw=None, out_sample_elems=None, out_hw=None):
     return per(x1) < 2 ** 31 and per(x2) < 2 ** 31
 
 
+def _scaled_split(wmat, ck, nmt, c1=None):
+    """The part the weight packers share: wmat [Cout, Cin, nstep] -> (hi, lo, s, nchunk).  s = clamp(floor(log2(1024 / max|wmat|)), -24, 24)
+    (0 for an all-zero weight); 2^s * wmat is rounded to fp32, its rows zero-padded to nmt * 32 and its channels to whole chunks of ck --
+    with 0 < c1 < Cin and c1 % ck the first c1 channels are padded to whole chunks on their own and the others follow (cat[x1, x2]) --
+    and split into hi = fp16(v), lo = fp16(v - hi), each [nmt * 32, nchunk * ck, nstep]."""
+    cout, cin, nstep = wmat.shape
+    wmax = float(wmat.abs().max())
+    s = int(math.floor(math.log2(1024.0 / wmax))) if wmax > 0 else 0
+    s = max(-24, min(24, s))
+    ws = (wmat * (2.0 ** s)).to(torch.float32)
+    split = c1 is not None and 0 < c1 < cin and c1 % ck
+    c1p = (c1 + ck - 1) // ck * ck if split else 0
+    nchunk = c1p // ck + (cin - c1 + ck - 1) // ck if split else (cin + ck - 1) // ck
+    wp = torch.zeros((nmt * 32, nchunk * ck, nstep), dtype=torch.float32, device=wmat.device)
+    if split:
+        wp[:cout, :c1] = ws[:, :c1]
+        wp[:cout, c1p:c1p + cin - c1] = ws[:, c1:]
+    else:
+        wp[:cout, :cin] = ws
+    hi = wp.half()
+    return hi, (wp - hi.float()).half(), s, nchunk
+
+
 def pack_conv_weight_f16s(w, c1=None):
     """torch conv weight [Cout,Cin,KH,KW] (3x3, 1x1, 1x5, 5x1) -> (packed fp16 tensor, scale exponent s).
 
@@ -208,28 +230,12 @@ def pack_conv_weight_f16s(w, c1=None):
     2^s brings max|W| to ~2^10 so that the lo halves stay in fp16's normal range (exact scaling, undone through alpha).
     c1: the input is cat[x1 (c1 channels), x2]: x1's channels are padded to whole chunks (zero weights), x2's follow -- the kernel
     switches input pointers at a chunk boundary."""
-    import math
     cout, cin, kh, kw = w.shape
     ntap = kh * kw
     ck = f16s_chunk(kh, kw)
     ks = ck // 16
     nmt = 1 if cout <= 32 else 2 * ((cout + 63) // 64)
-    wmax = float(w.abs().max())
-    s = int(math.floor(math.log2(1024.0 / wmax))) if wmax > 0 else 0
-    s = max(-24, min(24, s))
-    ws = w.reshape(cout, cin, ntap).to(torch.float32) * (2.0 ** s)
-    if c1 is not None and 0 < c1 < cin and c1 % ck:
-        c1p = (c1 + ck - 1) // ck * ck
-        nchunk = c1p // ck + (cin - c1 + ck - 1) // ck
-        wp = torch.zeros((nmt * 32, nchunk * ck, ntap), dtype=torch.float32, device=w.device)
-        wp[:cout, :c1] = ws[:, :c1]
-        wp[:cout, c1p:c1p + cin - c1] = ws[:, c1:]
-    else:
-        nchunk = (cin + ck - 1) // ck
-        wp = torch.zeros((nmt * 32, nchunk * ck, ntap), dtype=torch.float32, device=w.device)
-        wp[:cout, :cin] = ws
-    hi = wp.half()
-    lo = (wp - hi.float()).half()
+    hi, lo, s, nchunk = _scaled_split(w.reshape(cout, cin, ntap), ck, nmt, c1)
     x = torch.stack([hi, lo])                                  # [part, co, ci, tap]
     x = x.view(2, nmt, 32, nchunk, ks, 2, 8, ntap)             # part, mt, r, chunk, ks, h, j, tap
     x = x.permute(1, 3, 7, 4, 0, 5, 2, 6).contiguous()        # mt, chunk, tap, ks, part, h, r, j
@@ -262,29 +268,12 @@ def pack_conv_weight_wino(w, c1=None):
     rounded to fp32 and split into fp16 hi / lo.  Fragment order [m-tile][chunk][step = ky * 4 + pos][part hi/lo][lane = h*32 + r][j]:
     value = 2^s * U[mt*32 + r][chunk*16 + 8h + j][ky][pos]; m-tiles padded to whole 128-channel blocks, channels to 16; c1 as in
     pack_conv_weight_f16s (cat[x1, x2] with x1's channels padded to whole chunks)."""
-    import math
     cout, cin, kh, kw = w.shape
     assert (kh, kw) == (3, 3)
     G = torch.tensor(_WINO_G, dtype=torch.float64, device=w.device)
     U = torch.einsum("pk,ocyk->ocyp", G, w.to(torch.float64)).reshape(cout, cin, 12)
-    umax = float(U.abs().max())
-    s = int(math.floor(math.log2(1024.0 / umax))) if umax > 0 else 0
-    s = max(-24, min(24, s))
-    us = (U * (2.0 ** s)).to(torch.float32)
-    ck = 16
     nmt = 4 * ((cout + 127) // 128)
-    if c1 is not None and 0 < c1 < cin and c1 % ck:
-        c1p = (c1 + ck - 1) // ck * ck
-        nchunk = c1p // ck + (cin - c1 + ck - 1) // ck
-        wp = torch.zeros((nmt * 32, nchunk * ck, 12), dtype=torch.float32, device=w.device)
-        wp[:cout, :c1] = us[:, :c1]
-        wp[:cout, c1p:c1p + cin - c1] = us[:, c1:]
-    else:
-        nchunk = (cin + ck - 1) // ck
-        wp = torch.zeros((nmt * 32, nchunk * ck, 12), dtype=torch.float32, device=w.device)
-        wp[:cout, :cin] = us
-    hi = wp.half()
-    lo = (wp - hi.float()).half()
+    hi, lo, s, nchunk = _scaled_split(U, 16, nmt, c1)
     x = torch.stack([hi, lo])                                  # [part, co, ci, step]
     x = x.view(2, nmt, 32, nchunk, 2, 8, 12)                   # part, mt, r, chunk, h, j, step
     x = x.permute(1, 3, 6, 0, 4, 2, 5).contiguous()           # mt, chunk, step, part, h, r, j
@@ -303,10 +292,9 @@ def conv2d_wino(x1, wpk, wscale, bias, cout, x2=None, act=None, res=None, out=No
     assert wpk.dtype == torch.float16 and wpk.is_cuda
     if F16S_RANGE_CHECK:
         _range_check(x1, x2)
-    ws = _zeroed_stats_ws(2 * B * stats_groups, x1.device) if stats_groups else None
+    ws, ws_ptr, ws_groups = _stats_args(stats_groups, B, x1.device)
     check(lib().cf_conv2d_wino(_f32(x1), C1, _opt(x2), C2, wpk.data_ptr(), _opt(bias), _opt(res), _f32(out), out.shape[1], out_coff, B, H, W,
-                               cout, ACT[act], float(alpha) * (2.0 ** -wscale), None if ws is None else ws.data_ptr(),
-                               -stats_groups if stats_groups else 0, _stream()), "cf_conv2d_wino")
+                               cout, ACT[act], float(alpha) * (2.0 ** -wscale), ws_ptr, ws_groups, _stream()), "cf_conv2d_wino")
     return (out, ws) if stats_groups else out
 
 
@@ -314,9 +302,9 @@ def conv2d_wino_prenorm(x, coef, slope, wpk, wscale, bias, cout, stats_groups=No
     """cf_conv2d_wino_prenorm: as conv2d_f16s_prenorm on the Winograd kernel."""
     B, C, H, W = x.shape
     out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
-    ws = _zeroed_stats_ws(2 * B * stats_groups, x.device) if stats_groups else None
+    ws, ws_ptr, ws_groups = _stats_args(stats_groups, B, x.device)
     check(lib().cf_conv2d_wino_prenorm(_f32(x), C, _f32(coef), float(slope), wpk.data_ptr(), _opt(bias), _f32(out), B, H, W, cout, 2.0 ** -wscale,
-                                       None if ws is None else ws.data_ptr(), -stats_groups if stats_groups else 0, _stream()), "cf_conv2d_wino_prenorm")
+                                       ws_ptr, ws_groups, _stream()), "cf_conv2d_wino_prenorm")
     return (out, ws) if stats_groups else out
 
 
@@ -363,6 +351,15 @@ def _zeroed_stats_ws(n, device):
     return ws
 
 
+def _stats_args(stats_groups, B, device):
+    """the statistics arguments of a convolution launch: (workspace or None, its pointer or None, the group count as the C ABI takes it --
+    negative: the workspace is already zero, no memset in the library)"""
+    if not stats_groups:
+        return None, None, 0
+    ws = _zeroed_stats_ws(2 * B * stats_groups, device)
+    return ws, ws.data_ptr(), -stats_groups
+
+
 def conv2d_f16s(x1, wpk, wscale, bias, cout, kh, kw, stride=1, pad=(0, 0), x2=None, act=None, res=None, out=None, out_coff=0, alpha=1.0,
                 stats_groups=None):
     """With stats_groups=G the call returns (out, ws): ws holds the GroupNorm statistics of `out` for group_norm_apply."""
@@ -378,10 +375,10 @@ def conv2d_f16s(x1, wpk, wscale, bias, cout, kh, kw, stride=1, pad=(0, 0), x2=No
     assert wpk.dtype == torch.float16 and wpk.is_cuda
     if F16S_RANGE_CHECK:
         _range_check(x1, x2)
-    ws = _zeroed_stats_ws(2 * B * stats_groups, x1.device) if stats_groups else None
+    ws, ws_ptr, ws_groups = _stats_args(stats_groups, B, x1.device)
     check(lib().cf_conv2d_f16s(_f32(x1), C1, _opt(x2), C2, wpk.data_ptr(), _opt(bias), _opt(res), _f32(out), out.shape[1], out_coff, B, H, W,
                                cout, kh, kw, stride, pad[0], pad[1], ACT[act], float(alpha) * (2.0 ** -wscale),
-                               None if ws is None else ws.data_ptr(), -stats_groups if stats_groups else 0, _stream()), "cf_conv2d_f16s")
+                               ws_ptr, ws_groups, _stream()), "cf_conv2d_f16s")
     return (out, ws) if stats_groups else out
 
 
@@ -389,26 +386,11 @@ def conv2d_f16s(x1, wpk, wscale, bias, cout, kh, kw, stride=1, pad=(0, 0), x2=No
 def pack_conv3d_weight_f16s(w, c1=None):
     """torch Conv3d weight [Cout,Cin,KD,3,3] -> (packed fp16 tensor, scale exponent s) for cf_conv3d_f16s: pack_conv_weight_f16s' fragment
     order with the KD * 9 taps in (dz, ky, kx) order, 16-channel chunks; c1 as there (cat[x1, x2] with x1 padded to whole chunks)."""
-    import math
     cout, cin, kd, kh, kw = w.shape
     assert (kh, kw) == (3, 3) and kd in (1, 3)
-    ntap, ck = kd * 9, 16
+    ntap = kd * 9
     nmt = 1 if cout <= 32 else 2 * ((cout + 63) // 64)
-    wmax = float(w.abs().max())
-    s = int(math.floor(math.log2(1024.0 / wmax))) if wmax > 0 else 0
-    s = max(-24, min(24, s))
-    ws = w.reshape(cout, cin, ntap).to(torch.float32) * (2.0 ** s)
-    split = c1 is not None and 0 < c1 < cin and c1 % ck
-    c1p = (c1 + ck - 1) // ck * ck if split else 0
-    nchunk = c1p // ck + (cin - c1 + ck - 1) // ck if split else (cin + ck - 1) // ck
-    wp = torch.zeros((nmt * 32, nchunk * ck, ntap), dtype=torch.float32, device=w.device)
-    if split:
-        wp[:cout, :c1] = ws[:, :c1]
-        wp[:cout, c1p:c1p + cin - c1] = ws[:, c1:]
-    else:
-        wp[:cout, :cin] = ws
-    hi = wp.half()
-    lo = (wp - hi.float()).half()
+    hi, lo, s, nchunk = _scaled_split(w.reshape(cout, cin, ntap), 16, nmt, c1)
     x = torch.stack([hi, lo]).view(2, nmt, 32, nchunk, 2, 8, ntap)      # part, mt, r, chunk, h, j, tap
     return x.permute(1, 3, 6, 0, 4, 2, 5).contiguous().view(-1), s     # mt, chunk, tap, part, h, r, j
 
@@ -438,9 +420,9 @@ def conv3d_f16s(x1, wpk, wscale, bias, cout, kernel, stride=(1, 1, 1), x2=None, 
     assert wpk.dtype == torch.float16 and wpk.is_cuda
     if F16S_RANGE_CHECK:
         _range_check(x1, x2)
-    ws = _zeroed_stats_ws(2 * B * stats_groups, x1.device) if stats_groups else None
+    ws, ws_ptr, ws_groups = _stats_args(stats_groups, B, x1.device)
     check(lib().cf_conv3d_f16s(_f32(x1), C1, _opt(x2), C2, wpk.data_ptr(), _opt(bias), _f32(out), B, D, H, W, cout, kd, kh, kw, sd, st,
-                               float(alpha) * (2.0 ** -wscale), None if ws is None else ws.data_ptr(), -stats_groups if stats_groups else 0,
+                               float(alpha) * (2.0 ** -wscale), ws_ptr, ws_groups,
                                _stream()), "cf_conv3d_f16s")
     return (out, ws) if stats_groups else out
 
@@ -521,9 +503,9 @@ def conv2d_f16s_prenorm(x, coef, slope, wpk, wscale, bias, cout, stats_groups=No
     group_norm_coef.  Returns (out, ws) with stats_groups like conv2d_f16s."""
     B, C, H, W = x.shape
     out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
-    ws = _zeroed_stats_ws(2 * B * stats_groups, x.device) if stats_groups else None
+    ws, ws_ptr, ws_groups = _stats_args(stats_groups, B, x.device)
     check(lib().cf_conv2d_f16s_prenorm(_f32(x), C, _f32(coef), float(slope), wpk.data_ptr(), _opt(bias), _f32(out), B, H, W, cout, 2.0 ** -wscale,
-                                       None if ws is None else ws.data_ptr(), -stats_groups if stats_groups else 0, _stream()), "cf_conv2d_f16s_prenorm")
+                                       ws_ptr, ws_groups, _stream()), "cf_conv2d_f16s_prenorm")
     return (out, ws) if stats_groups else out
 
 
@@ -533,9 +515,9 @@ def conv_transpose2d_k2s2_f16s(x, wpk, wscale, bias, cout, out=None, out_coff=0,
         _range_check(x)
     if out is None:
         out = torch.empty((B, cout, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
-    ws = _zeroed_stats_ws(2 * B * stats_groups, x.device) if stats_groups else None       # fused into the scatter epilogue (atomics: zero start)
+    ws, ws_ptr, ws_groups = _stats_args(stats_groups, B, x.device)       # fused into the scatter epilogue (atomics: zero start)
     check(lib().cf_conv_transpose2d_k2s2_f16s(_f32(x), wpk.data_ptr(), _opt(bias), _f32(out), out.shape[1], out_coff, B, Cin, H, W, cout,
-                                              2.0 ** -wscale, None if ws is None else ws.data_ptr(), -stats_groups if stats_groups else 0, _stream()),
+                                              2.0 ** -wscale, ws_ptr, ws_groups, _stream()),
           "cf_conv_transpose2d_k2s2_f16s")
     return (out, ws) if stats_groups else out
 

@@ -236,6 +236,45 @@ def test_conv_f16s_output_sample_limit_falls_back_to_fp32_kernel():
     assert not ops.f16s_dynamic_ok(Fake((1, 8, 16, 16)), None, 3, out_sample_elems=2 ** 25, out_hw=256)      # 8 images per workgroup
 
 
+def test_packed_conv_objects_take_the_fp32_call_at_the_output_sample_limit(monkeypatch):
+    """the same limit at every site: a convroute.PackedConv of a 1x1 layer and a PackedConvT (destination sample x4: the scatter) make the
+    fp32 call when one sample of the destination buffer reaches 1 GiB and the f16 call one channel below it.  Host logic only: fake
+    tensors, the ops launch functions replaced by recorders."""
+    from cineflow import ops
+    from cineflow.convroute import PackedConv, PackedConvT
+
+    class Fake:
+        def __init__(self, shape):
+            self.shape = shape
+
+        def numel(self):
+            n = 1
+            for v in self.shape:
+                n *= v
+            return n
+
+        def data_ptr(self):
+            return 0
+    calls = []
+    for name in ("conv2d_f16s", "conv2d", "conv2d_wino", "conv_transpose2d_k2s2_f16s", "conv_transpose2d_k2s2"):
+        monkeypatch.setattr(ops, name, lambda *a, _n=name, **k: calls.append(_n) or _n)
+    monkeypatch.setattr(ops, "CONV_MODE", "f16s")
+    g = torch.Generator().manual_seed(0)
+    conv = PackedConv(torch.randn(8, 16, 1, 1, generator=g), torch.randn(8, generator=g))
+    x = Fake((1, 16, 4096, 4096))
+    assert conv(x, out=Fake((1, 15, 4096, 4096)), out_coff=2) == "conv2d_f16s"           # 15 * 2^24 * 4 bytes < 1 GiB
+    assert conv(x, out=Fake((1, 16, 4096, 4096)), out_coff=2) == "conv2d"                # 16 * 2^24 * 4 bytes = 1 GiB
+    assert conv(x, out=Fake((1, 16, 4096, 4096)), stats_groups=8) == ("conv2d", None)
+    up = PackedConvT(torch.randn(16, 8, 2, 2, generator=g), torch.randn(8, generator=g))
+    x = Fake((1, 16, 2048, 2048))
+    assert up(x, out=Fake((1, 15, 4096, 4096))) == "conv_transpose2d_k2s2_f16s"          # 15 * 4 * 2^22 * 4 bytes < 1 GiB
+    assert up(x, out=Fake((1, 16, 4096, 4096))) == "conv_transpose2d_k2s2"
+    assert up(Fake((1, 16, 16, 16)), out=Fake((1, 2 ** 15, 32, 32))) == "conv_transpose2d_k2s2"      # <= 256 pixels: 8 images per workgroup
+    assert up(Fake((1, 16, 16, 16)), out=Fake((1, 2 ** 15 - 1, 32, 32))) == "conv_transpose2d_k2s2_f16s"
+    assert calls == ["conv2d_f16s", "conv2d", "conv2d", "conv_transpose2d_k2s2_f16s", "conv_transpose2d_k2s2", "conv_transpose2d_k2s2",
+                     "conv_transpose2d_k2s2_f16s"]
+
+
 def test_wino_form_query_follows_the_route_level():
     """cf_conv2d_wino_form names the kernel form the dispatch picks (host code, no launch); cf_conv2d_wino_ok is `form != 0`.  A layer with
     few items: level 1 takes NTW 2 -- never NTW 4, which only the forced level 4 selects."""
