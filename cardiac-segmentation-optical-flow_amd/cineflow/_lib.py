@@ -45,6 +45,8 @@ SIGNATURES = {
     "cf_conv2d_f16s": [P, I, P, I, P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, I, F, P, I, P],
     "cf_conv3d_f16s": [P, I, P, I, P, P, P, I, I, I, I, I, I, I, I, I, I, F, P, I, P],
     "cf_conv3d_f16s_ok": [I, I, I, I, I, I, I, I, I, I, I],
+    "cf_conv3d_pw_f16s": [P, P, P, P, I, I, I, I, I, I, I, I, F, P, I, P],
+    "cf_conv3d_pw_f16s_ok": [I, I, I, I, I, I, I, I],
     "cf_conv_transpose2d_k2s2_f16s": [P, P, P, P, I, I, I, I, I, I, I, F, P, I, P],
     "cf_group_norm_apply": [P, P, P, P, P, I, I, I, I, F, I, I, P, P],
     "cf_group_norm_coef": [P, P, P, I, I, I, I, F, P, P],

@@ -10,7 +10,7 @@ import torch
 
 from . import ops
 from .convroute import PackedConv
-from .nn import (Module, conv_norm, Conv2d, ConvTranspose2d, GroupNorm, Conv3d, ConvTranspose3d, InstanceNorm3d, ConvBlocks2DGroupLegacy, Encoder2D, Decoder2D, CrossAttentionLayer,
+from .nn import (Module, conv_norm, Conv2d, ConvTranspose2d, GroupNorm, Conv3d, ConvTranspose3d, InstanceNorm3d, ResidualLayer3D, ConvBlocks2DGroupLegacy, Encoder2D, Decoder2D, CrossAttentionLayer,
                  TransformerFlowEncoderSuccessiveNoEmb, ConvGRUCell, SpatialTransformer, VecInt)
 
 
@@ -611,3 +611,108 @@ class Generic_UNet3D(Generic_UNet):
         self.conv_blocks_context = ctx
         self.tu = tu
         self.seg_outputs = seg
+
+
+# ------------------------------------------------------------------------------------------------ FabiansUNet (3D residual encoder)
+class ConvDropoutNormReLU3D(Module):
+    """custom_modules/conv_blocks.py:21-55 with conv_op = nn.Conv3d: conv -> InstanceNorm3d(affine) -> LeakyReLU(0.01); keys `conv`, `norm`
+    (the reference registers the same tensors a second time under `all.0` / `all.2`: the importer drops those aliases)."""
+
+    def __init__(self, cin, cout, kernel=(3, 3, 3), stride=(1, 1, 1)):
+        super().__init__()
+        self.conv = Conv3d(cin, cout, kernel, stride, bias=True)
+        self.norm = InstanceNorm3d(cout)
+
+    def forward(self, x, x2=None):
+        y, ws = self.conv(x, x2=x2, stats_groups=self.norm.channels)
+        return self.norm(y, act="lrelu", ws=ws)
+
+
+class PlainStackedConvLayers3D(Module):
+    """custom_modules/conv_blocks.py:58-83 (StackedConvLayers of the modular U-Nets): keys `convs.N`; the StackedConvLayers3D pattern."""
+
+    def __init__(self, cin, cout, kernel, num_convs, first_stride=None):
+        super().__init__()
+        self.convs = [ConvDropoutNormReLU3D(cin, cout, kernel, first_stride if first_stride is not None else (1, 1, 1))] + \
+                     [ConvDropoutNormReLU3D(cout, cout, kernel) for _ in range(num_convs - 1)]
+
+    def forward(self, x, x2=None):
+        for i, b in enumerate(self.convs):
+            x = b(x, x2=x2) if i == 0 else b(x)
+        return x
+
+
+class ResidualUNetEncoder3D(Module):
+    """generic_modular_residual_UNet.py:28-110: a (3,3,3) stem, then one ResidualLayer3D per stage whose first block strides by the stage's
+    pool_op_kernel_sizes entry (the first entry, [1,1,1], is the first stage's stride).  forward returns every stage's output."""
+
+    def __init__(self, input_channels, base_num_features, num_blocks_per_stage, pool_op_kernel_sizes, conv_kernel_sizes, max_num_features):
+        super().__init__()
+        assert len(pool_op_kernel_sizes) == len(conv_kernel_sizes) == len(num_blocks_per_stage)
+        self.initial_conv = Conv3d(input_channels, base_num_features, (3, 3, 3), (1, 1, 1), bias=True)
+        self.initial_norm = InstanceNorm3d(base_num_features)
+        self.stages, self.stage_output_features = [], []
+        cin = base_num_features
+        for st in range(len(conv_kernel_sizes)):
+            cout = min(base_num_features * 2 ** st, max_num_features)
+            self.stages.append(ResidualLayer3D(cin, cout, conv_kernel_sizes[st], num_blocks_per_stage[st], pool_op_kernel_sizes[st]))
+            self.stage_output_features.append(cout)
+            cin = cout
+
+    def forward(self, x):
+        y, ws = self.initial_conv(x, stats_groups=self.initial_norm.channels)
+        x = self.initial_norm(y, act="lrelu", ws=ws)
+        skips = []
+        for s in self.stages:
+            x = s(x)
+            skips.append(x)
+        return skips
+
+
+class PlainConvUNetDecoder3D(Module):
+    """generic_modular_UNet.py:184-283 on a ResidualUNetEncoder3D: per stage a bias-free transposed convolution (kernel = stride = the
+    pooling kernel below), cat(up, skip) -- never materialised, the skip rides in as x2 -- and a plain conv stack; a bias-free (1,1,1)
+    head.  The deep-supervision heads are declared (the checkpoint holds them) and never evaluated."""
+
+    def __init__(self, encoder, num_classes, num_blocks_per_stage, pool_op_kernel_sizes, conv_kernel_sizes):
+        super().__init__()
+        feats = encoder.stage_output_features
+        n = len(feats) - 1
+        assert len(num_blocks_per_stage) == n
+        self.tus, self.stages, self.deep_supervision_outputs = [], [], []
+        for i, s in enumerate(range(n)[::-1]):
+            self.tus.append(ConvTranspose3d(feats[s + 1], feats[s], pool_op_kernel_sizes[s + 1], bias=False))
+            self.stages.append(PlainStackedConvLayers3D(2 * feats[s], feats[s], conv_kernel_sizes[s], num_blocks_per_stage[i]))
+            if s != 0:
+                self.deep_supervision_outputs.append(Conv3d(feats[s], num_classes, (1, 1, 1), bias=False))
+        self.segmentation_output = Conv3d(feats[0], num_classes, (1, 1, 1), bias=False)
+
+    def forward(self, skips):
+        skips = skips[::-1]
+        x = skips[0]
+        for i in range(len(self.tus)):
+            x = self.stages[i](self.tus[i](x), x2=skips[i + 1])
+        return self.segmentation_output(x)
+
+
+class FabiansUNet3D(Module):
+    """generic_modular_residual_UNet.py:305-337 as nnUNetTrainerV2_ResencUNet.py:25-45 builds it: residual encoder, plain conv decoder,
+    conv_op = nn.Conv3d, InstanceNorm3d(affine), LeakyReLU(0.01), features doubling per stage up to max_features = 320.  Same state_dict
+    keys as the reference.  forward: [B,C,D,H,W] -> full-resolution logits [B,K,D,H,W] (deep supervision off at inference)."""
+
+    def __init__(self, input_channels, base_num_features, num_blocks_per_stage_encoder, pool_op_kernel_sizes, conv_kernel_sizes, num_classes,
+                 num_blocks_per_stage_decoder, max_features=320):
+        super().__init__()
+        pool = [tuple(int(v) for v in p_) for p_ in pool_op_kernel_sizes]
+        kern = [tuple(int(v) for v in k) for k in conv_kernel_sizes]
+        nenc, ndec = [int(v) for v in num_blocks_per_stage_encoder], [int(v) for v in num_blocks_per_stage_decoder]
+        if len(pool) != len(kern) or len(nenc) != len(kern) or len(ndec) != len(kern) - 1:
+            raise ValueError("FabiansUNet3D: %d pooling entries, %d conv kernels, %d encoder and %d decoder block counts: one pooling entry, "
+                             "kernel and encoder count per stage, one decoder count less" % (len(pool), len(kern), len(nenc), len(ndec)))
+        self.num_classes, self.input_channels = num_classes, input_channels
+        self.pool_op_kernel_sizes, self.conv_kernel_sizes = pool, kern
+        self.encoder = ResidualUNetEncoder3D(input_channels, base_num_features, nenc, pool, kern, max_features)
+        self.decoder = PlainConvUNetDecoder3D(self.encoder, num_classes, ndec, pool, kern)
+
+    def forward(self, x):
+        return self.decoder(self.encoder(x))

@@ -229,7 +229,9 @@ class Conv3d(Module):
     """nn.Conv3d for the 3-D U-Net behind _internal_predict_3D_3Dconv_tiled (generic_UNet.py with conv_op = nn.Conv3d).  Input/output NCDHW.
     (1|3, 3, 3) kernels run on the native kernel cf_conv3d_f16s (conv3d_f16s.hip) where ops.conv3d_f16s_ok takes the shape: one call on the
     NCDHW tensors, the InstanceNorm statistics of the output from its epilogue (stats_groups).  The (1, 1, 1) / stride-1 heads are a 1x1
-    Conv2d on the [B, C, D*H, W] view.  Everything else -- set_conv_mode("f32"), one-term mode, declined shapes -- runs the composition:
+    Conv2d on the [B, C, D*H, W] view.  A (1, 1, 1) kernel with a stride above 1 -- the skip projection of BasicResidualBlock3D -- runs
+    on cf_conv3d_pw_f16s (conv3d_pw_f16s.hip) where ops.conv3d_pw_f16s_ok takes the shape, statistics likewise.
+    Everything else -- set_conv_mode("f32"), one-term mode, declined shapes -- runs the composition:
     a (kd, k, k) convolution is the sum over the kd depth taps of 2-D (k, k) convolutions of depth-shifted planes, so it
     runs on the same MFMA implicit-GEMM kernels: the volume is re-laid as [B, D, C, H, W] planes, the centre tap writes
     every output plane (with the bias), the other taps accumulate through the kernel's residual input.  Kernel sizes 1 or 3
@@ -255,6 +257,9 @@ class Conv3d(Module):
         # the native kernel (conv3d_f16s.hip) takes (1|3, 3, 3) kernels; packed per channel split on first use
         self._native = self.ks[1:] == (3, 3)
         self._pk3 = {}
+        # a strided (1, 1, 1) kernel: the gathered pointwise kernel (conv3d_pw_f16s.hip); packed on first use
+        self._pointwise = self.ks == (1, 1, 1)
+        self._pkpw = None
         # the composed route: one 2-D convolution per depth tap (the layer's bias rides on the centre tap's call; never Winograd)
         self._taps = [PackedConv(self._p["weight"][:, :, dz].contiguous(), None, self.stride[1], pad) for dz in range(self.ks[0])]
 
@@ -275,6 +280,12 @@ class Conv3d(Module):
                 and ops.conv3d_f16s_ok(B, x.shape[1], 0 if x2 is None else x2.shape[1], D, H, W, self.cout, self.ks, self.stride)):
             wpk, wsc = self._packed3(x, x2)
             return ops.conv3d_f16s(x, wpk, wsc, self._p.get("bias"), self.cout, self.ks, self.stride, x2=x2, stats_groups=stats_groups)
+        if (self._pointwise and x2 is None and ops.CONV_MODE == "f16s"
+                and ops.conv3d_pw_f16s_ok(B, x.shape[1], D, H, W, self.cout, self.stride)):
+            if self._pkpw is None:
+                self._pkpw = ops.pack_conv3d_pw_weight_f16s(self._p["weight"])
+            wpk, wsc = self._pkpw
+            return ops.conv3d_pw_f16s(x, wpk, wsc, self._p.get("bias"), self.cout, self.stride, stats_groups=stats_groups)
         y = self._forward_composed(x, x2)          # set_conv_mode("f32"), one-term mode and declined shapes
         return (y, None) if stats_groups else y
 
@@ -340,14 +351,68 @@ class InstanceNorm3d(Module):
         self._param("weight", (channels,))
         self._param("bias", (channels,))
 
-    def forward(self, x, act=None, ws=None):
-        """ws: statistics already accumulated by the producing convolution (Conv3d with stats_groups) -> apply pass only."""
+    def forward(self, x, act=None, ws=None, res=None, res_mode=None, res_norm=None):
+        """ws: statistics already accumulated by the producing convolution (Conv3d with stats_groups) -> apply pass only.
+        res / res_mode / res_norm as GroupNorm.forward: a residual added before or after the activation inside the pass;
+        res_norm=(raw residual's statistics, its InstanceNorm3d module): that norm is applied to `res` inside this pass."""
         B, C, D, H, W = x.shape
+        v = x.view(B, C, D * H, W)
+        if res is not None:
+            assert res.shape == x.shape
+            res = res.view(B, C, D * H, W)
+        if res_norm is not None:
+            ws_r, norm_r = res_norm
+            if ws is not None and ws_r is not None and norm_r.eps == self.eps:
+                y = ops.group_norm_apply(v, self._p["weight"], self._p["bias"], C, ws, self.eps, act=act, res=res, res_mode=res_mode, out=v,
+                                         res_norm=(ws_r, norm_r._p["weight"], norm_r._p["bias"]))
+                return y.view(B, C, D, H, W)
+            res = norm_r(res.view(B, C, D, H, W), ws=ws_r).view(B, C, D * H, W)          # the branch's own pass (statistics not fused)
         if ws is not None:
-            y = ops.group_norm_apply(x.view(B, C, D * H, W), self._p["weight"], self._p["bias"], C, ws, self.eps, act=act, out=x.view(B, C, D * H, W))
+            y = ops.group_norm_apply(v, self._p["weight"], self._p["bias"], C, ws, self.eps, act=act, res=res, res_mode=res_mode, out=v)
             return y.view(B, C, D, H, W)
-        y = ops.group_norm(x.view(B, C, D * H, W), self._p["weight"], self._p["bias"], C, self.eps, act=act, out=x.view(B, C, D * H, W))
+        y = ops.group_norm(v, self._p["weight"], self._p["bias"], C, self.eps, act=act, res=res, res_mode=res_mode, out=v)
         return y.view(B, C, D, H, W)
+
+
+class BasicResidualBlock3D(Module):
+    """custom_modules/conv_blocks.py:86-145 with conv_op = nn.Conv3d, InstanceNorm3d(affine), LeakyReLU(0.01), no dropout:
+    lrelu(IN2(conv2(lrelu(IN1(conv1 x)))) + skip(x)), skip = identity or IN(conv1x1x1 at conv1's stride, no bias) -- the projection exists
+    when any stride entry differs from 1 or cin != cout (:126).  The tail is ONE apply pass: IN2, the projection's own InstanceNorm (on
+    its raw map, statistics from the projection's epilogue), the add and the LeakyReLU."""
+
+    def __init__(self, cin, cout, kernel, stride=None):
+        super().__init__()
+        kernel = tuple(int(k) for k in kernel)
+        st = (1, 1, 1) if stride is None else tuple(int(v) for v in stride)
+        self.conv1 = Conv3d(cin, cout, kernel, st, bias=True)
+        self.norm1 = InstanceNorm3d(cout)
+        self.conv2 = Conv3d(cout, cout, kernel, (1, 1, 1), bias=True)
+        self.norm2 = InstanceNorm3d(cout)
+        self.has_skip = any(v != 1 for v in st) or cin != cout
+        if self.has_skip:
+            self.downsample_skip = {0: Conv3d(cin, cout, (1, 1, 1), st, bias=False), 1: InstanceNorm3d(cout)}
+
+    def forward(self, x):
+        t, ws1 = self.conv1(x, stats_groups=self.norm1.channels)
+        t = self.norm1(t, act="lrelu", ws=ws1)
+        y, ws2 = self.conv2(t, stats_groups=self.norm2.channels)
+        if not self.has_skip:
+            return self.norm2(y, act="lrelu", ws=ws2, res=x, res_mode="before_act")
+        r, ws_r = self.downsample_skip[0](x, stats_groups=self.downsample_skip[1].channels)
+        return self.norm2(y, act="lrelu", ws=ws2, res=r, res_mode="before_act", res_norm=(ws_r, self.downsample_skip[1]))
+
+
+class ResidualLayer3D(Module):
+    """custom_modules/conv_blocks.py:214-227: num_blocks BasicResidualBlock3D, the first one strided and widening."""
+
+    def __init__(self, cin, cout, kernel, num_blocks, first_stride=None):
+        super().__init__()
+        self.convs = [BasicResidualBlock3D(cin, cout, kernel, first_stride)] + [BasicResidualBlock3D(cout, cout, kernel) for _ in range(num_blocks - 1)]
+
+    def forward(self, x):
+        for b in self.convs:
+            x = b(x)
+        return x
 
 # --------------------------------------------------------------------------------------------- lib/utils.py blocks
 

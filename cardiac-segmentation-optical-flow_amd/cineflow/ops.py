@@ -427,6 +427,45 @@ def conv3d_f16s(x1, wpk, wscale, bias, cout, kernel, stride=(1, 1, 1), x2=None, 
     return (out, ws) if stats_groups else out
 
 
+# ---- strided (1,1,1) 3-D convolution (conv3d_pw_f16s.hip) -------------------------------------------------------------------
+def pack_conv3d_pw_weight_f16s(w):
+    """torch Conv3d weight [Cout,Cin,1,1,1] -> (packed fp16 tensor, scale exponent s) for cf_conv3d_pw_f16s: pack_conv_weight_f16s' 1x1
+    fragment order (32-channel chunks of two k-steps)."""
+    cout, cin = w.shape[:2]
+    assert tuple(w.shape[2:]) == (1, 1, 1)
+    return pack_conv_weight_f16s(w.reshape(cout, cin, 1, 1))
+
+
+def conv3d_pw_f16s_ok(B, Cin, D, H, W, cout, stride):
+    """does cf_conv3d_pw_f16s take this layer?  stride (1|2, s, s) with s in {1,2}, every sample < 2 GiB, three-term mode."""
+    stride = tuple(stride)
+    if stride[1] != stride[2]:
+        return False
+    return lib().cf_conv3d_pw_f16s_ok(B, Cin, D, H, W, cout, stride[0], stride[1]) == 1
+
+
+def conv3d_pw_f16s(x, wpk, wscale, bias, cout, stride, out=None, alpha=1.0, stats_groups=None):
+    """cf_conv3d_pw_f16s on NCDHW tensors: the (1,1,1) convolution at stride (sd, s, s), no padding.  With stats_groups=G the call returns
+    (out, ws): ws holds the GroupNorm / InstanceNorm statistics of `out` over (D, H, W) for group_norm_apply."""
+    B, Cin, D, H, W = x.shape
+    sd, st = stride[0], stride[1]
+    assert stride[1] == stride[2]
+    shape = (B, cout, (D - 1) // sd + 1, (H - 1) // st + 1, (W - 1) // st + 1)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    assert tuple(out.shape) == shape
+    assert wpk.dtype == torch.float16 and wpk.is_cuda
+    nmt = 1 if cout <= 32 else 2 * ((cout + 63) // 64)
+    assert wpk.numel() == nmt * 32 * ((Cin + 31) // 32) * 32 * 2, "wpk is not pack_conv3d_pw_weight_f16s of a [%d, %d, 1, 1, 1] weight" % (cout, Cin)
+    assert bias is None or tuple(bias.shape) == (cout,)
+    if F16S_RANGE_CHECK:
+        _range_check(x)
+    ws, ws_ptr, ws_groups = _stats_args(stats_groups, B, x.device)
+    check(lib().cf_conv3d_pw_f16s(_f32(x), wpk.data_ptr(), _opt(bias), _f32(out), B, Cin, D, H, W, cout, sd, st,
+                                  float(alpha) * (2.0 ** -wscale), ws_ptr, ws_groups, _stream()), "cf_conv3d_pw_f16s")
+    return (out, ws) if stats_groups else out
+
+
 def small_cin_supported(cin, kh, kw, stride, pad, stats_groups=None):
     """layers routed to cf_conv2d_small_cin: 1 or 2 input channels (3x3 pad 1 or 1x1) and 6 input channels 1x1, stride 1, <= 64
     statistics groups.  Measured at 256x256 (tools/microbench.py --only stem): 1 -> 32 B120 209 us vs 641 us on the MFMA kernel,

@@ -23,6 +23,9 @@ folder, Generic_UNet3D on the native 3-D convolution).  A 3-D folder paired with
 A `3d_cascade_fullres` folder -- recognised by its trainer's name or by a first convolution that is num_classes input channels wider than
 the modalities -- gets seg_net.prev_stage_classes = [1 .. num_classes]: the previous stage's labels become input channels
 (predict_from_folder's lowres_segmentations / -l).  Its `3d_lowres` sibling is an ordinary 3-D folder of stage 0 of the same plans.
+A folder of nnUNetTrainerV2_ResencUNet (or its _DA3 variant) -- recognised by num_blocks_encoder in the stage, cross-checked against the
+trainer's name -- gets seg_net.arch = 'resenc': the residual-encoder U-Net (FabiansUNet3D).  The decoder tensors the reference registers
+twice are checked for equality and kept once.  Its BatchNorm variants (_BN trainers, running statistics in the checkpoint) are refused.
 
 Command line:  python -m cineflow.reference_models -s SEG [-w FLOW] -o OUT [--crop_weights F --crop_config Y] [-f FOLDS] [-chk NAME]
 """
@@ -171,7 +174,8 @@ def plans_from_reference_3d(plans, stage=None):
     `3d_fullres` folder: a 3-entry patch_size, mirror_axes [0, 1, 2] and seg_net {dim: 3, base_num_features, num_pool, pool_op_kernel_sizes,
     conv_kernel_sizes} -- the Generic_UNet with conv_op = nn.Conv3d that nnUNetTrainerV2.py:147-169 builds (num_classes + 1 outputs,
     conv_per_stage 2, at most 320 filters).  The preprocessing entries are those of the 2-D translation; preprocessor_name stays as the
-    plans give it (GenericPreprocessor).
+    plans give it (GenericPreprocessor).  A stage that holds num_blocks_encoder is the residual planner's and is translated by
+    _plans_from_reference_resenc instead.
 
     stage=None: the only stage (nnUNetTrainer.py:478-482); with several stages, the last one -- the full-resolution stage of the
     planner's cascade order, which is the stage run_training.py hands a full-resolution trainer."""
@@ -184,6 +188,8 @@ def plans_from_reference_3d(plans, stage=None):
     patch = [int(v) for v in np.asarray(sp["patch_size"]).ravel()]
     if len(patch) != 3:
         _refuse("plans_per_stage[%r]['patch_size']" % stage, patch, "3-D stages (plans_from_reference translates 2-D ones)")
+    if "num_blocks_encoder" in sp:
+        return _plans_from_reference_resenc(plans, stages, stage, patch)
     if "pool_op_kernel_sizes" in sp:
         pool = [[int(v) for v in p_] for p_ in sp["pool_op_kernel_sizes"]]
     else:                                                                      # nnUNetTrainer.py:489-501: old plans
@@ -211,6 +217,56 @@ def plans_from_reference_3d(plans, stage=None):
         "mirror_axes": [0, 1, 2],
         "seg_net": {"dim": 3, "base_num_features": int(plans["base_num_features"]), "num_pool": len(pool), "pool_op_kernel_sizes": pool,
                     "conv_kernel_sizes": conv},
+        "transpose_forward": [int(v) for v in tf], "transpose_backward": [int(v) for v in tb],
+        "normalization_schemes": plans.get("normalization_schemes"),
+        "use_mask_for_norm": plans.get("use_mask_for_norm"),
+        "dataset_properties": {"intensityproperties": dp.get("intensityproperties")},
+        "preprocessor_name": plans.get("preprocessor_name"),
+        "plans_per_stage": stages,
+        "stage": stage,
+    })
+
+
+def _plans_from_reference_resenc(plans, stages, stage, patch):
+    """plans_from_reference_3d for a stage of the residual planner (experiment_planner_residual_3DUNet_v21.py:57-120): pool_op_kernel_sizes
+    starts with the first stage's stride [1, 1, 1] and has one entry per conv_kernel_sizes entry; num_blocks_encoder / num_blocks_decoder
+    give the residual blocks per encoder stage and the plain convolutions per decoder stage.  seg_net gets arch = 'resenc' -- the FabiansUNet
+    nnUNetTrainerV2_ResencUNet.py:25-45 builds (num_classes + 1 outputs, features doubling up to 320)."""
+    sp = stages[stage]
+    where = "plans_per_stage[%r]" % stage
+    pool = [[int(v) for v in p_] for p_ in sp["pool_op_kernel_sizes"]]
+    if any(len(p_) != 3 or any(v not in (1, 2) for v in p_) for p_ in pool):
+        _refuse("%s['pool_op_kernel_sizes']" % where, pool, "entries of {1, 2}^3")
+    if any(p_[1] != p_[2] for p_ in pool):
+        _refuse("%s['pool_op_kernel_sizes']" % where, pool, "equal in-plane pooling")
+    if not pool or pool[0] != [1, 1, 1]:
+        _refuse("%s['pool_op_kernel_sizes']" % where, pool, "a leading [1, 1, 1] (the residual planner's first-stage stride)")
+    if any(p_[0] == 2 and p_[1] == 1 for p_ in pool):
+        _refuse("%s['pool_op_kernel_sizes']" % where, pool, "(1, 2, 2) or (2, 2, 2) after the first entry (transposed kernels (1|2, 2, 2))")
+    if any(p_ == [1, 1, 1] for p_ in pool[1:]):
+        _refuse("%s['pool_op_kernel_sizes']" % where, pool, "(1, 2, 2) or (2, 2, 2) after the first entry")
+    conv = [[int(v) for v in k] for k in sp["conv_kernel_sizes"]]
+    if len(conv) != len(pool) or any(k not in ([1, 3, 3], [3, 3, 3]) for k in conv):
+        _refuse("%s['conv_kernel_sizes']" % where, conv, "(1, 3, 3) or (3, 3, 3), one per pool_op_kernel_sizes entry")
+    nenc = [int(v) for v in sp["num_blocks_encoder"]]
+    if "num_blocks_decoder" not in sp:                                          # nnUNetTrainerV2_ResencUNet.py:36 reads it unconditionally
+        _refuse("%s['num_blocks_decoder']" % where, None, "one positive count per stage but the bottleneck")
+    ndec = [int(v) for v in sp["num_blocks_decoder"]]
+    if len(nenc) != len(conv) or any(v < 1 for v in nenc):
+        _refuse("%s['num_blocks_encoder']" % where, nenc, "one positive count per stage")
+    if len(ndec) != len(conv) - 1 or any(v < 1 for v in ndec):
+        _refuse("%s['num_blocks_decoder']" % where, ndec, "one positive count per stage but the bottleneck")
+    dp = plans.get("dataset_properties") or {}
+    tf, tb = plans.get("transpose_forward"), plans.get("transpose_backward")
+    if tf is None or tb is None:                                               # nnUNetTrainer.py:526-531
+        tf, tb = [0, 1, 2], [0, 1, 2]
+    return _plain({
+        "num_modalities": int(plans["num_modalities"]),
+        "num_classes": int(plans["num_classes"]) + 1,                            # nnUNetTrainer.py:520: background is not in num_classes
+        "patch_size": patch,
+        "mirror_axes": [0, 1, 2],
+        "seg_net": {"dim": 3, "arch": "resenc", "base_num_features": int(plans["base_num_features"]), "num_pool": len(pool) - 1,
+                    "pool_op_kernel_sizes": pool, "conv_kernel_sizes": conv, "num_blocks_encoder": nenc, "num_blocks_decoder": ndec},
         "transpose_forward": [int(v) for v in tf], "transpose_backward": [int(v) for v in tb],
         "normalization_schemes": plans.get("normalization_schemes"),
         "use_mask_for_norm": plans.get("use_mask_for_norm"),
@@ -396,6 +452,41 @@ def _is_cascade_stage(trainer_info, checkpoint_path, plans):
     return w is not None and w.dim() == 5 and int(w.shape[1]) == plans["num_modalities"] + plans["num_classes"] - 1
 
 
+_ALIAS = re.compile(r"^(?P<head>.*\.convs\.\d+)\.all\.(?P<slot>\d+)\.(?P<leaf>[^.]+)$")
+_ALIAS_SLOT = {"0": "conv", "2": "norm"}                                       # ConvDropoutNormReLU.all = Sequential(conv, do, norm, nonlin)
+
+
+def _drop_resenc_aliases(sd, path):
+    """The reference's ConvDropoutNormReLU (custom_modules/conv_blocks.py:35-52) registers its convolution and its norm twice: as `conv` /
+    `norm` and as slots 0 / 2 of the nn.Sequential `all`, so a FabiansUNet checkpoint holds every decoder tensor under two names.  Each
+    pair must be present and bit-equal (ValueError naming the key otherwise); the `all.*` names are dropped.  A checkpoint with BatchNorm
+    running statistics is a norm_type='bn' network, which the build does not implement."""
+    bn = [k for k in sd if k.endswith(("running_mean", "running_var"))]
+    if bn:
+        raise NotImplementedError("%s holds BatchNorm running statistics (%s): a network built with norm_type='bn'; the build implements "
+                                  "norm_type='in'" % (path, _first(bn)))
+    out = {}
+    for k, v in sd.items():
+        m = _ALIAS.match(k)
+        if m is None:
+            out[k] = v
+            continue
+        if m.group("slot") not in _ALIAS_SLOT:
+            raise ValueError("%s: %s is no slot of ConvDropoutNormReLU.all that holds tensors (0 = conv, 2 = norm)" % (path, k))
+        twin = "%s.%s.%s" % (m.group("head"), _ALIAS_SLOT[m.group("slot")], m.group("leaf"))
+        if twin not in sd:
+            raise ValueError("%s: %s has no twin %s (ConvDropoutNormReLU registers both)" % (path, k, twin))
+        if sd[twin].shape != v.shape or sd[twin].dtype != v.dtype or not torch.equal(sd[twin], v):
+            raise ValueError("%s: %s and %s name one tensor of the reference's network but differ in the checkpoint" % (path, k, twin))
+    for k in out:                                                              # ... and every `conv` / `norm` of a decoder stage has its alias
+        m = re.match(r"^(.*\.convs\.\d+)\.(conv|norm)\.([^.]+)$", k)
+        if m and k.startswith("decoder."):
+            alias = "%s.all.%s.%s" % (m.group(1), "0" if m.group(2) == "conv" else "2", m.group(3))
+            if alias not in sd:
+                raise ValueError("%s: %s has no twin %s (ConvDropoutNormReLU registers both)" % (path, k, alias))
+    return out
+
+
 def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size, window_size):
     """import_reference_model_folder without a flow folder: every check of the segmentation side, nothing of the flow side"""
     given = {k: v for k, v in dict(crop_weights=crop_weights, crop_config=crop_config, crop_size=crop_size, image_size=image_size,
@@ -419,7 +510,15 @@ def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config,
     else:
         plans = plans_from_reference(ref_plans, stage)
         plans["image_size"] = int(plans["patch_size"][0])
-    if plans["seg_net"].get("dim") == 3 and _is_cascade_stage(seg_info, join(seg_folds[folds[0]], checkpoint_name + ".model"), plans):
+    resenc = plans["seg_net"].get("arch") == "resenc"
+    name = str((seg_info or {}).get("name") or "")
+    if seg_info is not None and name and (("ResencUNet" in name) != resenc):
+        raise ValueError("%s: the trainer's name %r and the plans disagree -- the stage %s num_blocks_encoder, which makes it %s "
+                         "residual-encoder folder" % (seg_folder, name, "holds" if resenc else "has no", "a" if resenc else "no"))
+    if resenc and ("_BN" in name or name.endswith("BN")):
+        raise NotImplementedError("%s: trainer %s builds its network with norm_type='bn' (BatchNorm); the build implements norm_type='in'"
+                                  % (seg_folder, name))
+    if not resenc and plans["seg_net"].get("dim") == 3 and _is_cascade_stage(seg_info, join(seg_folds[folds[0]], checkpoint_name + ".model"), plans):
         # a `3d_cascade_fullres` folder (nnUNetTrainerCascadeFullRes.py:87-88: num_input_channels += num_classes - 1, background excluded):
         # the previous stage's foreground labels come in as one-hot channels (predict.py:176, classes = range(1, num_classes))
         plans["seg_net"]["prev_stage_classes"] = list(range(1, plans["num_classes"]))
@@ -429,6 +528,8 @@ def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config,
         path = join(seg_folds[f], checkpoint_name + ".model")
         shapes = trainer.seg_net.state_shapes()
         sd = load_reference_checkpoint(path, shapes)["state_dict"]
+        if resenc:
+            sd = _drop_resenc_aliases(sd, path)
         check_state_dict(sd, shapes, "segmentation network %s" % path)
         params[f] = {k: v for k, v in sd.items() if not k.endswith(_DERIVED_BUFFERS)}
     os.makedirs(out_folder, exist_ok=True)

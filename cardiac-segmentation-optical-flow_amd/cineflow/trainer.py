@@ -23,7 +23,7 @@ import torch.distributed as dist
 from . import ops, parallel, preprocessing
 from .inference import (CroppingNet, Processor, _predict_cine_tiled_device, normalize_intensity_, pad_nd_image, predict_3D_2Dconv_tiled,
                         predict_3D_3Dconv_tiled, predict_cine_2Dconv_tiled, predict_cine_slices)
-from .models import Generic_UNet, Generic_UNet3D, SegFlowGaussian
+from .models import FabiansUNet3D, Generic_UNet, Generic_UNet3D, SegFlowGaussian
 
 join = os.path.join
 
@@ -109,7 +109,10 @@ class CineTrainer:
     `seg_nets` holds one packed Generic_UNet per selected fold (`load_ensemble`); `seg_net` is seg_nets[0].
     plans['seg_net']['prev_stage_classes'] (a list of label values, e.g. [1, 2, 3]) makes the model the full-resolution stage of a cascade
     (`3d_cascade_fullres`, nnUNetTrainerCascadeFullRes.py:87-88): the network takes num_modalities + len(classes) input channels, and
-    preprocess_patient appends the previous stage's labels as one-hot channels.  3-D segmentation-only models alone."""
+    preprocess_patient appends the previous stage's labels as one-hot channels.  3-D segmentation-only models alone.
+    plans['seg_net']['arch'] = 'resenc' (with num_blocks_encoder / num_blocks_decoder, and a pool_op_kernel_sizes list that starts with the
+    first stage's stride [1, 1, 1]) makes the network the residual-encoder U-Net of nnUNetTrainerV2_ResencUNet (FabiansUNet3D): 3-D
+    segmentation-only models alone, never a cascade stage."""
 
     def __init__(self, plans, device, model_folder=None):
         self.plans = plans
@@ -119,6 +122,19 @@ class CineTrainer:
         self.patch_size = tuple(plans["patch_size"])
         fk = plans.get("flow_net")
         self.seg_dim = int((plans.get("seg_net") or {}).get("dim", 2))
+        arch = (plans.get("seg_net") or {}).get("arch")
+        if arch is not None:
+            if arch != "resenc":
+                raise ValueError("seg_net.arch must be 'resenc' (the residual-encoder U-Net) or absent (Generic_UNet), got %r" % (arch,))
+            if self.seg_dim != 3:
+                raise ValueError("plans.json holds seg_net.arch == 'resenc' with seg_net.dim == %d: the residual-encoder U-Net is built in 3-D "
+                                 "only (the reference's 2-D branch cannot be built either)" % self.seg_dim)
+            if fk:
+                raise ValueError("plans.json holds both seg_net.arch == 'resenc' and flow_net: the flow path is 2-D (a residual-encoder folder is "
+                                 "segmentation-only)")
+            if (plans.get("seg_net") or {}).get("prev_stage_classes") is not None:
+                raise ValueError("plans.json holds both seg_net.arch == 'resenc' and seg_net.prev_stage_classes: the reference has no cascade "
+                                 "trainer for the residual-encoder U-Net")
         if self.seg_dim == 3:
             if fk:
                 raise ValueError("plans.json holds both seg_net.dim == 3 and flow_net: the flow path is 2-D (a 3-D segmentation folder is segmentation-only)")
@@ -134,6 +150,7 @@ class CineTrainer:
             if not isinstance(psc, (list, tuple)) or not psc or any(not isinstance(c, int) or isinstance(c, bool) or not 0 <= c <= 255 for c in psc):
                 raise ValueError("seg_net.prev_stage_classes must be a non-empty list of label values in 0..255, got %r" % (psc,))
         self.prev_stage_classes = None if psc is None else [int(c) for c in psc]
+        self.seg_arch = arch
         self.model_folder = model_folder
         # (a segmentation-only model has no heart-centred crop: no Processor)
         self.processor = Processor(crop_size=plans["crop_size"], image_size=plans["patch_size"][0]) if (fk or "crop_size" in plans) else None
@@ -170,6 +187,9 @@ class CineTrainer:
 
     def _new_seg_net(self):
         sk = self.plans["seg_net"]
+        if self.seg_arch == "resenc":   # nnUNetTrainerV2_ResencUNet: FabiansUNet with conv_op = nn.Conv3d, at most 320 filters
+            return FabiansUNet3D(self.plans["num_modalities"], sk["base_num_features"], sk["num_blocks_encoder"], sk["pool_op_kernel_sizes"],
+                                 sk["conv_kernel_sizes"], self.num_classes, sk["num_blocks_decoder"])
         if self.seg_dim == 3:           # a `3d_fullres` stage: Generic_UNet with conv_op = nn.Conv3d, at most MAX_NUM_FILTERS_3D = 320 filters
             return Generic_UNet3D(self.plans["num_modalities"] + len(self.prev_stage_classes or ()), sk["base_num_features"], self.num_classes, sk["num_pool"],
                                   pool_op_kernel_sizes=sk.get("pool_op_kernel_sizes"), conv_kernel_sizes=sk.get("conv_kernel_sizes"))

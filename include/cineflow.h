@@ -162,6 +162,23 @@ int cf_conv3d_f16s(const float* x1, int C1, const float* x2, int C2, const void*
                    int W, int Cout, int KD, int KH, int KW, int stride_d, int stride_hw, float alpha, double* gn_ws, int gn_groups,
                    void* stream);
 int cf_conv3d_f16s_ok(int B, int C1, int C2, int D, int H, int W, int Cout, int KD, int KH, int stride_d, int stride_hw);
+/* Strided (1, 1, 1) nn.Conv3d forward -- the skip projection of a residual block (conv_blocks.py:126-129) -- on the same f16 MFMA with the
+ * same 3-term split (csrc/conv3d_pw_f16s.hip): out[b, co, zo, yo, xo] = alpha * sum_ci W[co][ci] * x[b, ci, zo*stride_d, yo*stride_hw,
+ * xo*stride_hw] + bias[co], no padding, each stride in {1, 2}, Do = (D - 1) / stride_d + 1 and likewise Ho, Wo.  x [B,Cin,D,H,W] and out
+ * [B,Cout,Do,Ho,Wo] are dense NCDHW, read and written in place: only the planes, rows and columns the strides select are addressed.  wpk
+ * from cineflow.ops.pack_conv3d_pw_weight_f16s (the 1x1 fragment order of cf_conv2d_f16s: [m-tile][chunk of 32][k-step][hi/lo][lane][8],
+ * scaled by 2^s: pass alpha * 2^-s); bias nullable.  gn_ws / gn_groups as in cf_conv3d_f16s: fp64 {sum, sum of squares} per (sample, group)
+ * of the output, from the epilogue or -- where a workgroup holds several whole samples -- from a statistics pass; a negative gn_groups
+ * declares gn_ws already zeroed.
+ * Sizes: 32-bit offsets -- ONE SAMPLE of x and out must each stay below 2 GiB; larger batches are cut into sub-batches inside the library.
+ * Activation range as cf_conv2d_f16s.  Only the three-term product is built.
+ * cf_conv3d_pw_f16s_ok (host code, no launch) returns 1 when the kernel takes the shape and 0 otherwise: a stride outside {1, 2}, a sample of
+ * x or out at or above 2 GiB, or cf_conv_terms(1); cf_conv3d_pw_f16s then fails with CF_ERR_ARG and the caller keeps its own route.  No
+ * shape class is declined on measured time: the trainer-width projections (32 -> 64 at 128^3 down to 320 -> 320 at 8^3, strides (2,2,2)
+ * and (1,2,2)) all measure faster than the caller's composition (profiles/resenc_pw3d.txt). */
+int cf_conv3d_pw_f16s(const float* x, const void* wpk, const float* bias, float* out, int B, int Cin, int D, int H, int W, int Cout,
+                      int stride_d, int stride_hw, float alpha, double* gn_ws, int gn_groups, void* stream);
+int cf_conv3d_pw_f16s_ok(int B, int Cin, int D, int H, int W, int Cout, int stride_d, int stride_hw);
 int cf_conv_transpose2d_k2s2_f16s(const float* x, const void* wpk, const float* bias, float* out, int out_ctotal,
                                   int out_coff, int B, int Cin, int H, int W, int Cout, float alpha, double* gn_ws, int gn_groups,
                                   void* stream);
