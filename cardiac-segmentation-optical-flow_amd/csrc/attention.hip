@@ -125,10 +125,12 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void split_h(float x, _Float16& hi, _Float16& lo) {
-    x = __builtin_amdgcn_fmed3f(x, -60000.f, 60000.f);
-    hi = (_Float16)x;
-    lo = (_Float16)(x - (float)hi);
+// hi / lo split of eight values clamped to the f16 range first (scores and probabilities are bounded; Q, K, V need not be)
+__device__ __forceinline__ void split_h8(const float (&x)[8], h8& hi, h8& lo) {
+    float c[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) c[j] = __builtin_amdgcn_fmed3f(x[j], -60000.f, 60000.f);
+    split8_f16(c, hi, lo);
 }
 
 template <int D>
@@ -158,15 +160,12 @@ __global__ void __launch_bounds__(256, 2) attention_cf_f16s_kernel(const float* 
     // Q^T fragments (pre-scaled), hi / lo: lane (q, half) holds dd = 16 s + 8 half + j
     h8 qh[KS], ql[KS];
 #pragma unroll
-    for (int s = 0; s < KS; ++s)
+    for (int s = 0; s < KS; ++s) {
+        float x[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float x = active ? qp[(long)(16 * s + 8 * half + j) * Nq + q0 + l31] * scale : 0.f;
-            _Float16 a, c;
-            split_h(x, a, c);
-            qh[s][j] = a;
-            ql[s][j] = c;
-        }
+        for (int j = 0; j < 8; ++j) x[j] = active ? qp[(long)(16 * s + 8 * half + j) * Nq + q0 + l31] * scale : 0.f;
+        split_h8(x, qh[s], ql[s]);
+    }
 
     // staging tasks: K -- thread = (key, 8-dd group): 8 coalesced dword loads, one 16-B hi and one 16-B lo write;
     //                V -- thread = (dd, 8-key group): two dwordx4 loads, one 16-B hi and one 16-B lo write
@@ -191,25 +190,14 @@ __global__ void __launch_bounds__(256, 2) attention_cf_f16s_kernel(const float* 
         unsigned char* vb_ = kb_ + KBUF;
         if (k_task) {
             h8 a, c;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                _Float16 x, y;
-                split_h(kst[j], x, y);
-                a[j] = x;
-                c[j] = y;
-            }
+            split_h8(kst, a, c);
             *reinterpret_cast<h8*>(kb_ + k_key * KREC + k_g * 16) = a;
             *reinterpret_cast<h8*>(kb_ + k_key * KREC + 2 * D + k_g * 16) = c;
         }
         if (v_task) {
             h8 a, c;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                _Float16 x, y;
-                split_h(vst[j >> 2][j & 3], x, y);
-                a[j] = x;
-                c[j] = y;
-            }
+            const float vv[8] = {vst[0][0], vst[0][1], vst[0][2], vst[0][3], vst[1][0], vst[1][1], vst[1][2], vst[1][3]};
+            split_h8(vv, a, c);
             *reinterpret_cast<h8*>(vb_ + v_dd * VREC + v_g * 16) = a;
             *reinterpret_cast<h8*>(vb_ + v_dd * VREC + 64 + v_g * 16) = c;
         }
@@ -257,15 +245,14 @@ __global__ void __launch_bounds__(256, 2) attention_cf_f16s_kernel(const float* 
             m_run = m_new;
             float psum = 0.f;
             h8 ph[2], pl[2];
+            float pv[2][8];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float pv = expf(sT[r] - m_new);
-                psum += pv;
-                _Float16 a, c;
-                split_h(pv, a, c);
-                ph[r >> 3][r & 7] = a;
-                pl[r >> 3][r & 7] = c;
+                pv[r >> 3][r & 7] = expf(sT[r] - m_new);
+                psum += pv[r >> 3][r & 7];
             }
+            split_h8(pv[0], ph[0], pl[0]);
+            split_h8(pv[1], ph[1], pl[1]);
             l_run = l_run * alpha + psum;
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {

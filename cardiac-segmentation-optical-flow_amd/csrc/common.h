@@ -67,6 +67,40 @@ __device__ __forceinline__ float act_apply(float v, int act) {
     }
 }
 
+// ---- fp32 -> f16 hi + f16 lo operand split of the 3-term MFMA products: hi = f16(x), lo = f16(x - hi).  x - hi is exact in fp32, so lo is
+// x - hi rounded ONCE to f16, which is what v_fma_mix{lo,hi}_f16 (f16 and fp32 sources, fp32 arithmetic, f16 result) gives in one instruction
+// per value: a pair costs one v_cvt_pk_f16_f32 and two mixed FMAs reading the halves of the packed hi in place.  Written as
+// (f16)(x - (float)hi) the compiler spends 13 instructions on four values (it converts hi back to fp32, and computes hi a second time with the
+// scalar conversion to feed that), and it folds an fmaf((float)hi, -1.f, x) back into the same sequence: hence the inline assembly.  No hazard
+// applies (plain VALU results consumed by VALU), and the statements are not volatile: the scheduler moves them like any other arithmetic.
+// Bitwise equal to the plain form for every fp32 input (tests/test_gpu_split.py).
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void split2_f16(float x0, float x1, f16x2& hi, f16x2& lo) {
+    typedef float f32x2s __attribute__((ext_vector_type(2)));
+    hi = __builtin_convertvector((f32x2s){x0, x1}, f16x2);
+    const unsigned h = __builtin_bit_cast(unsigned, hi);
+    unsigned l;
+    asm("v_fma_mixlo_f16 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(h), "v"(x0));
+    asm("v_fma_mixhi_f16 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(h), "v"(x1));
+    lo = __builtin_bit_cast(f16x2, l);
+}
+__device__ __forceinline__ void split4_f16(float x0, float x1, float x2, float x3, f16x4& hi, f16x4& lo) {
+    f16x2 h0, l0, h1, l1;
+    split2_f16(x0, x1, h0, l0);
+    split2_f16(x2, x3, h1, l1);
+    hi = __builtin_shufflevector(h0, h1, 0, 1, 2, 3);
+    lo = __builtin_shufflevector(l0, l1, 0, 1, 2, 3);
+}
+__device__ __forceinline__ void split8_f16(const float (&v)[8], f16x8& hi, f16x8& lo) {
+    f16x4 h0, l0, h1, l1;
+    split4_f16(v[0], v[1], v[2], v[3], h0, l0);
+    split4_f16(v[4], v[5], v[6], v[7], h1, l1);
+    hi = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7);
+    lo = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
 // Sampling coordinate of SpatialTransformer.forward (integration.py:61-79) followed by
 // grid_sample's align_corners=True un-normalisation, with the reference's fp32 rounding path:
 //   g = 2 * ((i + f) / (S - 1) - 0.5);  pos = ((g + 1) / 2) * (S - 1)

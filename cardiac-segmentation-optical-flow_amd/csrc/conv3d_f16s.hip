@@ -51,11 +51,6 @@ struct C3Geom {
 inline unsigned magic(int d) { return d <= 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)d + 1ull); }
 __device__ __forceinline__ int fdiv(int n, int d, unsigned m) { return d <= 1 ? n : (int)__umulhi((unsigned)n, m); }
 
-__device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
-    hi = (_Float16)x;
-    lo = (_Float16)(x - (float)hi);
-}
-
 template <int WM, int NTW, int MAXT, int NW>
 __global__ void __launch_bounds__(64 * NW, (NTW <= 2 && MAXT <= 3) ? 4 : 2)
 conv3d_f16s_kernel(const C3Params p, const C3Geom g, const _Float16* __restrict__ wpk) {
@@ -155,13 +150,7 @@ conv3d_f16s_kernel(const C3Params p, const C3Geom g, const _Float16* __restrict_
         for (int t = 0; t < MAXT; ++t) {
             if (t_lds[t] < 0) continue;
             f16x8 hi, lo;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                _Float16 h, l;
-                split_f16(stg[t][j], h, l);
-                hi[j] = h;
-                lo[j] = l;
-            }
+            split8_f16(stg[t], hi, lo);
             *reinterpret_cast<f16x8*>(base + t_lds[t]) = hi;
             *reinterpret_cast<f16x8*>(base + t_lds[t] + CK * 2) = lo;
         }

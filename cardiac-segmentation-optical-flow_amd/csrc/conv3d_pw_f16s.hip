@@ -41,11 +41,6 @@ struct PwParams {
 
 constexpr int NPX = 128;  // output voxels per workgroup
 
-__device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
-    hi = (_Float16)x;
-    lo = (_Float16)(x - (float)hi);
-}
-
 // tile voxel -> (sample, voxel of the sample); false: the slot is past the tile's samples, the batch or the sample
 __device__ __forceinline__ bool decode(const PwParams& p, int b0, int q0, int P, int pidx, int& b, int& q) {
     const int img = p.nimg > 1 ? pidx / P : 0;
@@ -153,13 +148,7 @@ __global__ void __launch_bounds__(64 * NW, 2) conv3d_pw_f16s_kernel(const PwPara
 #pragma unroll
         for (int t = 0; t < MAXT; ++t) {
             f16x8 hi, lo;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                _Float16 h, l;
-                split_f16(stg[t][j], h, l);
-                hi[j] = h;
-                lo[j] = l;
-            }
+            split8_f16(stg[t], hi, lo);
             *reinterpret_cast<f16x8*>(base + t_lds[t]) = hi;
             *reinterpret_cast<f16x8*>(base + t_lds[t] + CK * 2) = lo;
         }

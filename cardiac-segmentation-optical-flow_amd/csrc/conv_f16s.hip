@@ -60,11 +60,6 @@ __device__ __forceinline__ int fdiv(int n, int d, unsigned m) { return d <= 1 ? 
 // No range clamp: an activation beyond fp16's range (|x| >= 65520) becomes hi = inf, lo = NaN and poisons the output loudly, NaN and
 // Inf inputs propagate as they do through an fp32 convolution (a clamp here saturated them silently and cost one VALU per element).
 // Supported activation range: |x| < 65504, stated in include/cineflow.h.
-__device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
-    hi = (_Float16)x;
-    lo = (_Float16)(x - (float)hi);
-}
-
 // Every wave both stages the input patch and runs MFMAs.  vmcnt retires in issue order, so every wait for a weight fragment also waits
 // for the staging loads issued before it (ablating those loads made the kernel 19-33 % faster); a design with dedicated loader waves
 // removed that coupling and won 10-24 % on stride-2 layers and small maps, but lost 15-25 % on the large 3x3 layers that dominate the
@@ -191,13 +186,7 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
         for (int t = 0; t < MAXT; ++t) {
             if (t_lds[t] < 0) continue;
             f16x8 hi, lo;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                _Float16 h, l;
-                split_f16(stg[t][j], h, l);
-                hi[j] = h;
-                lo[j] = l;
-            }
+            split8_f16(stg[t], hi, lo);
             *reinterpret_cast<f16x8*>(base + t_lds[t]) = hi;
             *reinterpret_cast<f16x8*>(base + t_lds[t] + CK * 2) = lo;
         }
@@ -281,19 +270,17 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
             for (int k = 0; k < 4; ++k) {
                 if (!((v_mask[t] >> k) & 1u)) continue;
                 f16x4 hi, lo;
+                float v[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    float v = stg[t][j][k];
+                    v[j] = stg[t][j][k];
                     if (PRE) {
-                        v = (v - cm[j]) * ca[j] + cs[j];
-                        v = p.in_slope < 0.f ? gelu_as(v) : (v > 0.f ? v : v * p.in_slope);
-                        v = valid ? v : 0.f;
+                        v[j] = (v[j] - cm[j]) * ca[j] + cs[j];
+                        v[j] = p.in_slope < 0.f ? gelu_as(v[j]) : (v[j] > 0.f ? v[j] : v[j] * p.in_slope);
+                        v[j] = valid ? v[j] : 0.f;
                     }
-                    _Float16 h, l;
-                    split_f16(v, h, l);
-                    hi[j] = h;
-                    lo[j] = l;
                 }
+                split4_f16(v[0], v[1], v[2], v[3], hi, lo);
                 *reinterpret_cast<f16x4*>(base + k * REC) = hi;
                 *reinterpret_cast<f16x4*>(base + k * REC + CK * 2) = lo;
             }
@@ -1141,3 +1128,38 @@ extern "C" int cf_debug_f16s_phases(unsigned long long* out9) {
     return 0;
 }
 #endif
+
+// Test hook (tests/test_gpu_split.py; not in the header): common.h's split against the plain form it replaced, both on the same n values in
+// one launch.  The plain form is kept HERE, as the statement of what the split has to equal bit for bit.
+namespace cf {
+namespace {
+__global__ void __launch_bounds__(256) debug_split_kernel(const float* __restrict__ x, unsigned short* __restrict__ hi_old, unsigned short* __restrict__ lo_old,
+                                                          unsigned short* __restrict__ hi_new, unsigned short* __restrict__ lo_new, long n) {
+    const long npair = n >> 1;      // host: n even
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < npair; i += (long)gridDim.x * blockDim.x) {
+        const float x0 = x[2 * i], x1 = x[2 * i + 1];
+        const _Float16 h0 = (_Float16)x0, h1 = (_Float16)x1;
+        const _Float16 l0 = (_Float16)(x0 - (float)h0), l1 = (_Float16)(x1 - (float)h1);
+        hi_old[2 * i] = __builtin_bit_cast(unsigned short, h0);
+        hi_old[2 * i + 1] = __builtin_bit_cast(unsigned short, h1);
+        lo_old[2 * i] = __builtin_bit_cast(unsigned short, l0);
+        lo_old[2 * i + 1] = __builtin_bit_cast(unsigned short, l1);
+        f16x2 hn, ln;
+        split2_f16(x0, x1, hn, ln);
+        reinterpret_cast<unsigned*>(hi_new)[i] = __builtin_bit_cast(unsigned, hn);
+        reinterpret_cast<unsigned*>(lo_new)[i] = __builtin_bit_cast(unsigned, ln);
+    }
+}
+}  // namespace
+}  // namespace cf
+
+extern "C" int cf_debug_split_f16(const float* x, void* hi_old, void* lo_old, void* hi_new, void* lo_new, long n, void* stream) {
+    CF_REQUIRE(x && hi_old && lo_old && hi_new && lo_new, "null pointer");
+    CF_REQUIRE(n > 0 && n % 2 == 0, "n must be positive and even");
+    CF_REQUIRE(((reinterpret_cast<uintptr_t>(hi_new) | reinterpret_cast<uintptr_t>(lo_new)) & 3) == 0, "outputs must be 4-byte aligned");
+    hipLaunchKernelGGL(cf::debug_split_kernel, dim3(cf::flat_grid(n / 2, 256)), dim3(256), 0, cf::as_stream(stream), x,
+                       static_cast<unsigned short*>(hi_old), static_cast<unsigned short*>(lo_old), static_cast<unsigned short*>(hi_new),
+                       static_cast<unsigned short*>(lo_new), n);
+    CF_CHECK_LAUNCH();
+    return CF_OK;
+}

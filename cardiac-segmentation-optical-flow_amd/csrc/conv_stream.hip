@@ -42,11 +42,6 @@ struct StreamGeom {
 #endif
 };
 
-__device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
-    hi = (_Float16)x;
-    lo = (_Float16)(x - (float)hi);
-}
-
 // Development build only (make trace -> libcineflow_hip_trace.so, read by tools/stream_trace.py): per-wave shader-clock totals of the phases of a
 // step.  s_memtime shares the LGKM counter with the LDS, so a stamp waits for the wave's outstanding LDS traffic -- the stamps sit where that
 // queue is empty or about to be drained anyway.
@@ -248,19 +243,17 @@ __global__ void __launch_bounds__(64 * ST_NW) conv_stream_kernel(const ConvParam
         // patch are masked: a load whose only uses sit behind a branch stays "maybe pending" for the compiler's wait insertion, which
         // then fences every later reuse of that register with a vmcnt wait that drains the chunks in flight
         f16x4 hi, lo;
+        float v[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float v = stg[t][j][k];
+            v[j] = stg[t][j][k];
             if (PRE) {
-                v = (v - cm[j]) * ca[j] + cs[j];
-                v = p.in_slope < 0.f ? gelu_as(v) : (v > 0.f ? v : v * p.in_slope);
-                v = ok[t] ? v : 0.f;
+                v[j] = (v[j] - cm[j]) * ca[j] + cs[j];
+                v[j] = p.in_slope < 0.f ? gelu_as(v[j]) : (v[j] > 0.f ? v[j] : v[j] * p.in_slope);
+                v[j] = ok[t] ? v[j] : 0.f;
             }
-            _Float16 h, l;
-            split_f16(v, h, l);
-            hi[j] = h;
-            lo[j] = l;
         }
+        split4_f16(v[0], v[1], v[2], v[3], hi, lo);
         asm volatile("" ::"v"(hi), "v"(lo));      // (pins the conversions here: the optimiser would sink them into the masked block)
         if (((v_mask[t] >> k) & 1u) && !ABL(5)) {
             *reinterpret_cast<f16x4*>(base + k * REC) = hi;

@@ -69,11 +69,6 @@ __device__ unsigned long long g_wino_phase[12];
 #define WINO_ADD(i, v) do { } while (0)
 #endif
 
-__device__ __forceinline__ void split_f16(float x, _Float16& hi, _Float16& lo) {
-    hi = (_Float16)x;
-    lo = (_Float16)(x - (float)hi);
-}
-
 // value of the lane one below / above inside its row of 16 lanes (DPP row_shr:1 / row_shl:1); the row's first / last lane keeps `own`
 __device__ __forceinline__ float from_lane_below(float v) {
     const int i = __builtin_bit_cast(int, v);
@@ -212,6 +207,7 @@ conv_wino_kernel(const ConvParams p, const WinoGeom g, const _Float16* __restric
             }
             const bool valid = v_off[t] != OOB, evalid = e_off[t] != OOB;
             f16x4 hi[2][4], lo[2][4];      // [unit 2q | 2q + 1][position] over the 4 channels
+            float va[4][4], vb[4][4];      // [position][channel]
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float c0 = stg[t][j][0], c1 = stg[t][j][1], c2 = stg[t][j][2], c3 = stg[t][j][3], e = edg[t][j];
@@ -226,18 +222,14 @@ conv_wino_kernel(const ConvParams p, const WinoGeom g, const _Float16* __restric
                 float left = from_lane_below(c3), right = from_lane_above(c0);
                 left = v_first[t] ? e : left;
                 right = v_last[t] ? e : right;
-                const float va[4] = {left - c1, c0 + c1, c1 - c0, c0 - c2};      // unit 2q:     d = (left, c0, c1, c2)
-                const float vb[4] = {c1 - c3, c2 + c3, c3 - c2, c2 - right};     // unit 2q + 1: d = (c1, c2, c3, right)
+                va[0][j] = left - c1, va[1][j] = c0 + c1, va[2][j] = c1 - c0, va[3][j] = c0 - c2;      // unit 2q:     d = (left, c0, c1, c2)
+                vb[0][j] = c1 - c3, vb[1][j] = c2 + c3, vb[2][j] = c3 - c2, vb[3][j] = c2 - right;     // unit 2q + 1: d = (c1, c2, c3, right)
+            }
+            // split after the channel loop: a packed pair is two adjacent channels of one position
 #pragma unroll
-                for (int pos = 0; pos < 4; ++pos) {
-                    _Float16 h, l;
-                    split_f16(va[pos], h, l);
-                    hi[0][pos][j] = h;
-                    lo[0][pos][j] = l;
-                    split_f16(vb[pos], h, l);
-                    hi[1][pos][j] = h;
-                    lo[1][pos][j] = l;
-                }
+            for (int pos = 0; pos < 4; ++pos) {
+                split4_f16(va[pos][0], va[pos][1], va[pos][2], va[pos][3], hi[0][pos], lo[0][pos]);
+                split4_f16(vb[pos][0], vb[pos][1], vb[pos][2], vb[pos][3], hi[1][pos], lo[1][pos]);
             }
             if (v_has[t]) {
 #pragma unroll
@@ -460,7 +452,7 @@ struct StageRegs {
     f32x4v stg[4];
     float edg[4];
     f32x4v cm, ca, cs;
-    bool valid, evalid;
+    bool evalid;
 };
 
 template <int PRE>
@@ -563,21 +555,21 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
                     const int c = c0 + (int)c4[t];                               // C1 % 4 == 0 (host): a quad is wholly inside or wholly the padded tail
                     const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in_norm + (long)ld_b * 3 * p.C1), 0,
                                                                                         3 * p.C1 * 4, 0x00020000);
-                    const unsigned o = c < p.C1 ? (unsigned)c * 4u : OOB;
+                    // rows outside the image take ZERO coefficients: their loads read 0, (0 - 0) * 0 + 0 = 0 and both activations map 0 to 0, so the
+                    // padding stays exactly zero without a select per value
+                    const unsigned o = (c < p.C1 && v_off[t] < OOB) ? (unsigned)c * 4u : OOB;
                     R[t].cm = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rn, o, 0, 0));
                     R[t].ca = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rn, o + (unsigned)p.C1 * 4u, 0, 0));
                     R[t].cs = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rn, o + (unsigned)p.C1 * 8u, 0, 0));
                 }
-                R[t].valid = v_off[t] < OOB;
                 R[t].evalid = e_off[t] < OOB;
             }
             if (ld_c + 1 < g.nchunk) ++ld_c;
             else if (ld_i + 1 < n_my) { ld_c = 0; ++ld_i; setup(ld_i); }
         };
-        auto pre_apply = [&](float v, float cm, float ca, float cs, bool valid) -> float {
+        auto pre_apply = [&](float v, float cm, float ca, float cs) -> float {
             v = (v - cm) * ca + cs;
-            v = p.in_slope < 0.f ? gelu_as(v) : (v > 0.f ? v : v * p.in_slope);
-            return valid ? v : 0.f;
+            return p.in_slope < 0.f ? gelu_as(v) : (v > 0.f ? v : v * p.in_slope);
         };
         auto write = [&](const StageRegs (&RR)[VT], int gc) __attribute__((always_inline)) {
 #if defined(CF_WINO_ABLATE) && CF_WINO_ABLATE == 1
@@ -588,31 +580,27 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
                 const StageRegs& R = RR[t];
                 unsigned char* base = lds + (gc & (PS_NBUF - 1)) * buf_bytes + v_lds[t];
                 f16x4 hi[2][4], lo[2][4];
+                float va[4][4], vb[4][4];      // [position][channel]
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     float c0 = R.stg[j][0], c1 = R.stg[j][1], c2 = R.stg[j][2], c3 = R.stg[j][3], e = R.edg[j];
                     if (PRE) {
-                        c0 = pre_apply(c0, R.cm[j], R.ca[j], R.cs[j], R.valid);
-                        c1 = pre_apply(c1, R.cm[j], R.ca[j], R.cs[j], R.valid);
-                        c2 = pre_apply(c2, R.cm[j], R.ca[j], R.cs[j], R.valid);
-                        c3 = pre_apply(c3, R.cm[j], R.ca[j], R.cs[j], R.valid);
-                        e = pre_apply(e, R.cm[j], R.ca[j], R.cs[j], R.evalid);
+                        c0 = pre_apply(c0, R.cm[j], R.ca[j], R.cs[j]);
+                        c1 = pre_apply(c1, R.cm[j], R.ca[j], R.cs[j]);
+                        c2 = pre_apply(c2, R.cm[j], R.ca[j], R.cs[j]);
+                        c3 = pre_apply(c3, R.cm[j], R.ca[j], R.cs[j]);
+                        e = R.evalid ? pre_apply(e, R.cm[j], R.ca[j], R.cs[j]) : 0.f;      // (a column outside an inside row: the coefficients are live)
                     }
                     float left = from_lane_below(c3), right = from_lane_above(c0);
                     left = first[t] ? e : left;
                     right = last[t] ? e : right;
-                    const float va[4] = {left - c1, c0 + c1, c1 - c0, c0 - c2};
-                    const float vb[4] = {c1 - c3, c2 + c3, c3 - c2, c2 - right};
+                    va[0][j] = left - c1, va[1][j] = c0 + c1, va[2][j] = c1 - c0, va[3][j] = c0 - c2;
+                    vb[0][j] = c1 - c3, vb[1][j] = c2 + c3, vb[2][j] = c3 - c2, vb[3][j] = c2 - right;
+                }
 #pragma unroll
-                    for (int pos = 0; pos < 4; ++pos) {
-                        _Float16 h, l;
-                        split_f16(va[pos], h, l);
-                        hi[0][pos][j] = h;
-                        lo[0][pos][j] = l;
-                        split_f16(vb[pos], h, l);
-                        hi[1][pos][j] = h;
-                        lo[1][pos][j] = l;
-                    }
+                for (int pos = 0; pos < 4; ++pos) {
+                    split4_f16(va[pos][0], va[pos][1], va[pos][2], va[pos][3], hi[0][pos], lo[0][pos]);
+                    split4_f16(vb[pos][0], vb[pos][1], vb[pos][2], vb[pos][3], hi[1][pos], lo[1][pos]);
                 }
                 if (has[t]) {
 #pragma unroll

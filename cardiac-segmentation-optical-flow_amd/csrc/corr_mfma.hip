@@ -74,15 +74,6 @@ struct CmGeom {
     static_assert(NPT <= 384 && (2 * NPT) % 64 == 0, "prev staging half-tasks fill whole waves (0..11)");
 };
 
-__device__ __forceinline__ void split8(const float (&v)[8], f16x8& hi, f16x8& lo) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const _Float16 h = (_Float16)v[j];
-        hi[j] = h;
-        lo[j] = (_Float16)(v[j] - (float)h);
-    }
-}
-
 template <int S>
 __global__ void __launch_bounds__(CM_THREADS, 4)
 corr_volume_mfma_kernel(const float* __restrict__ cur, const float* __restrict__ prev, float* __restrict__ out, int B, int C, int H, int W,
@@ -170,13 +161,7 @@ corr_volume_mfma_kernel(const float* __restrict__ cur, const float* __restrict__
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             f16x4 hi, lo;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float v = stg[c][k];
-                const _Float16 h = (_Float16)v;
-                hi[c] = h;
-                lo[c] = (_Float16)(v - (float)h);
-            }
+            split4_f16(stg[0][k], stg[1][k], stg[2][k], stg[3][k], hi, lo);
             const int wk = w_lds0 + (k % S) * (is_prev ? G::PCLS : G::CCLS) + (k / S) * 32;
             *reinterpret_cast<f16x4*>(base + wk + hi_off) = hi;
             *reinterpret_cast<f16x4*>(base + wk + 16 - hi_off) = lo;
