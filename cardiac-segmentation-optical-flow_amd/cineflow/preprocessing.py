@@ -79,7 +79,8 @@ def crop_to_bbox(image, bbox):
 
 
 def crop_to_nonzero(data, seg=None, nonzero_label=-1):
-    """cropping.py:104-137 -> (data, seg, bbox); seg is created (0 inside the mask, nonzero_label outside) when absent."""
+    """cropping.py:104-137 -> (data, seg, bbox); seg is created (0 inside the mask, nonzero_label outside; all 0 for a positive label,
+    as the reference leaves it) when absent."""
     was_numpy = not torch.is_tensor(data)
     t = _to_dev(data)
     nonzero_mask = create_nonzero_mask(t)
@@ -89,7 +90,9 @@ def crop_to_nonzero(data, seg=None, nonzero_label=-1):
     m = nonzero_mask[sl[1:]].to(torch.uint8).contiguous()
     # a created segmentation is the zero map with `nonzero_label` outside the mask (cropping.py:131-135)
     s = _to_dev(seg)[sl].contiguous() if seg is not None else torch.zeros((1,) + tuple(m.shape), dtype=torch.float32, device=t.device)
-    check(lib().cf_seg_outside_mask(_f32(s), _u8(m), s.shape[0], m.numel(), float(nonzero_label), _stream()), "cf_seg_outside_mask")
+    # (the reference builds a created segmentation as mask -> label outside -> `[> 0] = 0`: a positive label leaves it all zero)
+    if seg is not None or nonzero_label <= 0:
+        check(lib().cf_seg_outside_mask(_f32(s), _u8(m), s.shape[0], m.numel(), float(nonzero_label), _stream()), "cf_seg_outside_mask")
     seg_dtype = seg.dtype if seg is not None else (np.int64 if was_numpy else torch.int64)
     if was_numpy:
         return t.cpu().numpy(), s.cpu().numpy().astype(seg_dtype), bbox

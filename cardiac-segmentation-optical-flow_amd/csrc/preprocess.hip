@@ -208,12 +208,13 @@ __global__ void __launch_bounds__(256) masked_moments_kernel(const float* __rest
 }
 
 // x = ((clip ? clamp(x, lo, hi) : x) - sub) / div in fp32 like the reference's float32 arrays; voxels with seg < 0 become 0 when
-// zero_outside; with only_inside the voxels outside the mask are left for zero_outside to clear (preprocessing.py:311-315)
+// zero_outside; with only_inside the voxels outside the mask are left for zero_outside to clear (preprocessing.py:311-315).
+// np.clip keeps a NaN (PreprocessorFor2D does not remove them); fmaxf(NaN, lo) alone would return lo
 __global__ void __launch_bounds__(256) normalize_kernel(float* __restrict__ x, const float* __restrict__ seg, long n, int clip, float lo, float hi,
                                                         float sub, float div, int zero_outside) {
     GRID_STRIDE(i, n) {
         float v = x[i];
-        if (clip) v = fminf(fmaxf(v, lo), hi);
+        if (clip && v == v) v = fminf(fmaxf(v, lo), hi);
         v = __fdiv_rn(__fsub_rn(v, sub), div);
         if (zero_outside && seg[i] < 0.f) v = 0.f;
         x[i] = v;

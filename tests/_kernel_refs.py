@@ -1,0 +1,188 @@
+"""Plain numpy / scipy / torch-fp64 restatements of the operators around the convolutions (preprocessing, metrics, the 3-D sliding
+window and the Swin window attention), each a few lines.  The GPU tables test_gpu_preprocess_kernels.py, test_gpu_metrics_kernels.py,
+test_gpu_volume_ops.py and test_gpu_window_attention.py hold the HIP kernels to these; test_kernel_refs_cpu.py pins every restatement
+to the oracle (and through it to the reference's golden vectors) so that helper and kernel cannot be wrong together."""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+
+def ratio_line(tag, worst, bar):
+    """one printed line per row (pytest -s): the worst measured figure over its bar"""
+    r = worst / bar if bar else (0.0 if worst == 0 else float("inf"))
+    print("  %-58s worst %.3e  bar %.1e  ratio %.3f" % (tag, worst, bar, r))
+    return r
+
+
+# ------------------------------------------------------------------------------------------------ cropping
+def nonzero_fill_holes(data):
+    """cropping.py:25-32: OR over the channels of data != 0 (NaN != 0 holds, -0.0 != 0 does not), then scipy's binary_fill_holes on
+    the array as given: (C, X, Y, Z) fills 3-D cavities only, (C, X, Y) fills 2-D holes."""
+    from scipy.ndimage import binary_fill_holes
+    data = np.asarray(data)
+    return binary_fill_holes(np.any(data != 0, axis=0))
+
+
+def bbox(mask):
+    """cropping.py:47-55 -> [[min, max + 1]] per axis; an empty mask raises ValueError like np.min of an empty sequence"""
+    co = np.nonzero(np.asarray(mask))
+    return [[int(c.min()), int(c.max()) + 1] for c in co]
+
+
+def seg_outside_mask(seg, mask, label):
+    """cropping.py:128-135: seg[(seg == 0) & (mask == 0)] = label, the mask broadcast over seg's channels"""
+    seg = np.array(seg, copy=True)
+    seg[(seg == 0) & (np.asarray(mask)[None] == 0)] = label
+    return seg
+
+
+# ------------------------------------------------------------------------------------------------ normalisation
+def masked_moments(x, seg=None, lo=None, hi=None):
+    """(count, sum x, sum x^2, sum |x|) over the voxels with seg >= 0 and lo < x < hi (strict), fp64 sums of the fp32 values"""
+    x = np.asarray(x, np.float32).ravel()
+    sel = np.ones(x.shape, bool)
+    if seg is not None:
+        sel &= np.asarray(seg).ravel() >= 0
+    if lo is not None:
+        sel &= (x > np.float32(lo)) & (x < np.float32(hi))
+    v = x[sel].astype(np.float64)
+    return int(v.size), float(v.sum()), float((v * v).sum()), float(np.abs(v).sum())
+
+
+def normalize_f32(x, sub, div, clip=None, seg=None, zero_outside=False):
+    """((clip ? np.clip(x, lo, hi) : x) - float32(sub)) / float32(div) in float32; voxels with seg < 0 become 0 when zero_outside"""
+    x = np.asarray(x, np.float32)
+    with np.errstate(all="ignore"):
+        y = np.clip(x, np.float32(clip[0]), np.float32(clip[1])) if clip is not None else x
+        y = ((y - np.float32(sub)) / np.float32(div)).astype(np.float32)
+    if zero_outside:
+        y = np.where(np.asarray(seg) < 0, np.float32(0), y)
+    return y
+
+
+# ------------------------------------------------------------------------------------------------ metrics
+def confusion(test, reference, K):
+    """K x K int64 matrix M[t, r] = #voxels with test label t and reference label r"""
+    t, r = np.asarray(test).ravel().astype(np.int64), np.asarray(reference).ravel().astype(np.int64)
+    return np.bincount(t * K + r, minlength=K * K).reshape(K, K)
+
+
+def surface_border(mask):
+    """medpy's border: mask ^ binary_erosion(mask, face structure) -> sorted (z, y, x) rows (z = 0 for a 2-D mask)"""
+    from scipy.ndimage import binary_erosion, generate_binary_structure
+    m = np.asarray(mask).astype(bool)
+    co = np.argwhere(m ^ binary_erosion(m, structure=generate_binary_structure(m.ndim, 1), iterations=1))
+    co = np.concatenate([np.zeros((len(co), 3 - m.ndim), co.dtype), co], 1)
+    return co[np.lexsort(co.T[::-1])]
+
+
+def region_stats(x, lab, K):
+    """per label k < K: (sum x, count, #(x < 0), sum |x|) in fp64; labels >= K are ignored"""
+    x, lab = np.asarray(x, np.float64).ravel(), np.asarray(lab).ravel()
+    return np.array([[x[lab == k].sum(), (lab == k).sum(), (x[lab == k] < 0).sum(), np.abs(x[lab == k]).sum()] for k in range(K)])
+
+
+# ------------------------------------------------------------------------------------------------ resampling
+def cubic_axis(x, axis, m):
+    """skimage.transform.resize(order=3, mode='edge') along one axis = scipy.ndimage.zoom(order=3, mode='nearest', grid_mode=True), fp64"""
+    from scipy.ndimage import zoom
+    x = np.asarray(x, np.float64)
+    z = [1.0] * x.ndim
+    z[axis] = m / float(x.shape[axis])
+    out = zoom(x, z, order=3, mode="nearest", grid_mode=True)
+    assert out.shape[axis] == m
+    return out
+
+
+def slab_minmax(x):
+    """x [C, A, S, B] -> (min, max) of every slab (c, s), each [C, S]"""
+    x = np.asarray(x)
+    return x.min(axis=(1, 3)), x.max(axis=(1, 3))
+
+
+def slab_clip_f32(y, mn=None, mx=None):
+    """y [C, A, S, B] fp64 clipped to its slab's range (when given) and rounded to float32"""
+    y = np.asarray(y, np.float64)
+    if mn is not None:
+        y = np.clip(y, mn[:, None, :, None], mx[:, None, :, None])
+    return y.astype(np.float32)
+
+
+def resize_edge(x, new_shape, linear):
+    """x [N, X, Y, Z] -> [N, *new_shape], fp64: per axis src = (n / n2) (dst + 0.5) - 0.5; linear between the two edge-clamped
+    neighbours, or nearest = floor(src + 0.5) edge-clamped."""
+    x = np.asarray(x, np.float64)
+    for ax, (n2, lin) in enumerate(zip(new_shape, linear), 1):
+        n = x.shape[ax]
+        s = (float(n) / n2) * (np.arange(n2) + 0.5) - 0.5
+        if lin:
+            f = np.floor(s)
+            w = (s - f).reshape([-1 if a == ax else 1 for a in range(x.ndim)])
+            i0, i1 = np.clip(f.astype(int), 0, n - 1), np.clip(f.astype(int) + 1, 0, n - 1)
+            x = np.take(x, i0, ax) * (1.0 - w) + np.take(x, i1, ax) * w
+        else:
+            x = np.take(x, np.clip(np.floor(s + 0.5).astype(int), 0, n - 1), ax)
+    return x
+
+
+# ------------------------------------------------------------------------------------------------ sliding window
+def flip(x, flags):
+    """torch.flip over the trailing axes whose flag is set"""
+    nd = x.dim()
+    dims = [nd - len(flags) + a for a, f in enumerate(flags) if f]
+    return torch.flip(x, dims) if dims else x.clone()
+
+
+def tta_softmax(logits):
+    """what mirroring TTA converges to when every mirrored pass sees the mirrored logits: the fp64 softmax over the channels"""
+    return torch.softmax(logits.double(), 1)
+
+
+def tile_add(agg, cnt, pred, gauss, corner):
+    """agg[:, tile] += pred, cnt[:, tile] += gauss (1 when absent), in the tensors' own precision"""
+    sl = (slice(None),) + tuple(slice(c, c + p) for c, p in zip(corner, pred.shape[1:]))
+    agg[sl] += pred
+    cnt[sl] += gauss if gauss is not None else 1.0
+    return agg, cnt
+
+
+# ------------------------------------------------------------------------------------------------ Swin window attention
+def window_attention(q, k, v, bias_table, heads, ws, shift, mask=True):
+    """q, k, v [B, C, H, W], bias_table [(2 ws - 1)^2, heads] -> [B, C, H, W], all in fp64: roll by -shift, partition into ws x ws
+    windows, softmax(scale q k^T + bias_table[relative index] + (-100 between border regions of the rolled map)) v, reverse, roll back."""
+    q, k, v, bias_table = (t.double() for t in (q, k, v, bias_table))
+    B, C, H, W = v.shape
+    hd, N = C // heads, ws * ws
+
+    def part(t):
+        t = torch.roll(t, (-shift, -shift), (2, 3)) if shift else t
+        t = t.reshape(B, heads, hd, H // ws, ws, W // ws, ws).permute(0, 3, 5, 1, 4, 6, 2)     # B, wy, wx, head, ty, tx, d
+        return t.reshape(B, H // ws, W // ws, heads, N, hd)
+
+    ty, tx = np.divmod(np.arange(N), ws)
+    rel = (ty[:, None] - ty[None, :] + ws - 1) * (2 * ws - 1) + (tx[:, None] - tx[None, :] + ws - 1)
+    bias = bias_table[torch.from_numpy(rel).reshape(-1)].reshape(N, N, heads).permute(2, 0, 1)
+    attn = (hd ** -0.5) * part(q) @ part(k).transpose(-1, -2) + bias
+    if shift and mask:
+        def region(n):
+            r = np.zeros(n, np.int64)
+            r[n - ws:n - shift], r[n - shift:] = 1, 2
+            return r
+        reg = torch.from_numpy(3 * region(H)[:, None] + region(W)[None, :])
+        reg = reg.reshape(H // ws, ws, W // ws, ws).permute(0, 2, 1, 3).reshape(H // ws, W // ws, N)
+        attn = attn + torch.where(reg[..., :, None] != reg[..., None, :], -100.0, 0.0).double()[None, :, :, None]
+    o = torch.softmax(attn, -1) @ part(v)                                                     # B, wy, wx, head, N, hd
+    o = o.reshape(B, H // ws, W // ws, heads, ws, ws, hd).permute(0, 3, 6, 1, 4, 2, 5).reshape(B, C, H, W)
+    return torch.roll(o, (shift, shift), (2, 3)) if shift else o
+
+
+# ------------------------------------------------------------------------------------------------ point sampling
+def sample_points(field, pts):
+    """SpatialTransformerContour (integration.py:5-34): field [B, C, H, W], pts [B, 2, P] (channel 0 along W, 1 along H) -> [B, C, P]
+    through F.grid_sample(align_corners=True, padding_mode='zeros') in the dtype of `field`."""
+    B, C, H, W = field.shape
+    p = pts.to(field.dtype)
+    gx = 2 * (p[:, 0] / (W - 1) - 0.5)
+    gy = 2 * (p[:, 1] / (H - 1) - 0.5)
+    grid = torch.stack([gx, gy], -1)[:, :, None, :]                                           # B, P, 1, 2
+    return F.grid_sample(field, grid, mode="bilinear", padding_mode="zeros", align_corners=True)[..., 0]
