@@ -13,7 +13,7 @@
 //   * a wave owns 32 n1 rows x 8 n2 map rows (8 accumulator tiles): lanes run along x2, so level-0 stores are 128-byte row
 //     segments, and every pooled level comes out of the SAME registers -- x2 neighbours by __shfl_xor(1 / 2 / 4), y2 neighbours are
 //     accumulator tiles of the same wave -- in ATen's summation order on the rounded level-0 values, bit-compatible with pooling the
-//     stored level;
+//     stored level (the file is built with -ffp-contract=off: an FMA of acc * scale into the first sum would use the unrounded product);
 //   * workgroup = 8 waves = 128 n1 x 16 map rows (512 n2); grid = B x (N / 128) x (H / 16), n1 blocks fastest so that the
 //     workgroups sharing an f2 tile run together.
 // Built for W == 32, H % 16 == 0, C % 16 == 0 (RAFT at 1/8 resolution of 256 x 256: 32 x 32 x 256); other shapes keep the generic path.
@@ -21,6 +21,9 @@
 
 #include "common.h"
 #include "profile.h"
+
+// the pooled levels sum the ROUNDED level-0 values: no a * b + c -> FMA contraction in this file (the Makefile passes -ffp-contract=off too)
+#pragma clang fp contract(off)
 
 namespace cf {
 

@@ -357,9 +357,13 @@ __global__ void __launch_bounds__(256) jacobian_det_3d_kernel(const float* __res
 
 using namespace cf;
 
-// the four-pixel kernels need W % 4 == 0 and tensors below 2 GiB (32-bit indices and buffer offsets); the one-pixel kernels take the rest
-static bool warp_v4(int W, double max_tensor_bytes) {
-    return W % 4 == 0 && max_tensor_bytes < 2147483648.0;
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// the four-pixel kernels need W % 4 == 0, tensors below 2 GiB (32-bit indices and buffer offsets) and every tensor they touch with a 16-byte
+// access on a 16-byte boundary (`vec16`: what the caller found for flow, source / addend and output; the label output needs 4 bytes); the
+// one-pixel kernels take the rest
+static bool warp_v4(int W, double max_tensor_bytes, bool vec16) {
+    return W % 4 == 0 && max_tensor_bytes < 2147483648.0 && vec16;
 }
 
 extern "C" int cf_warp_bilinear_2d(const float* flow, const float* src, float* out, int B, int C, int H, int W, void* stream) {
@@ -368,7 +372,7 @@ extern "C" int cf_warp_bilinear_2d(const float* flow, const float* src, float* o
     CF_REQUIRE(out != src, "out must not alias src");
     long n = (long)B * H * W;
     const double bytes = 4.0 * n * (2.0 + 2.0 * C);   // flow + src read once, out written once
-    if (warp_v4(W, 4.0 * n * (C > 2 ? C : 2)))
+    if (warp_v4(W, 4.0 * n * (C > 2 ? C : 2), aligned16(flow) && aligned16(src) && aligned16(out)))
         launch_profiled(PK_WARP, bytes, warp_bilinear_2d_v4_kernel<false>, dim3(flat_grid(n / 4, 256)), dim3(256), as_stream(stream), flow,
                         src, out, B, C, H, W, (const float*)nullptr);
     else
@@ -391,7 +395,7 @@ extern "C" int cf_vecint_2d(const float* vec, float* out, float* tmp, int B, int
     CF_CHECK_LAUNCH();
     long np = (long)B * H * W;
     for (int it = 0; it < nsteps; ++it) {
-        if (warp_v4(W, 8.0 * np))
+        if (warp_v4(W, 8.0 * np, aligned16(out) && aligned16(tmp)))
             hipLaunchKernelGGL(warp_bilinear_2d_v4_kernel<true>, dim3(flat_grid(np / 4, 256)), dim3(256), 0, s, cur, cur, nxt, B, 2, H, W,
                                (const float*)cur);
         else
@@ -409,7 +413,7 @@ extern "C" int cf_warp_labels_2d(const float* flow, const uint8_t* labels, uint8
     CF_REQUIRE(T > 0 && B > 0 && K > 0 && K <= 8 && H > 1 && W > 1, "bad shape");
     long n = (long)T * B * H * W;
     const double bytes = 10.0 * n;   // flow read (8 B), one label gathered (1 B) and one written (1 B) per pixel
-    if (warp_v4(W, 8.0 * n))
+    if (warp_v4(W, 8.0 * n, aligned16(flow) && (reinterpret_cast<uintptr_t>(out) & 3) == 0))
         launch_profiled(PK_WARP_LABELS, bytes, K == 4 ? warp_labels_2d_v4_kernel<4> : warp_labels_2d_v4_kernel<0>, dim3(flat_grid(n / 4, 256)),
                         dim3(256), as_stream(stream), flow, labels, out, T, B, K, H, W);
     else
@@ -433,7 +437,7 @@ extern "C" int cf_jacobian_det_2d(const float* disp, double* det, int B, int H, 
     CF_REQUIRE(B > 0 && H >= 2 && W >= 2, "bad shape");
     long n = (long)B * H * W;
     const double bytes = 16.0 * n;   // displacement read (8 B), determinant written (8 B, float64 like numpy)
-    if (warp_v4(W, 8.0 * n))
+    if (warp_v4(W, 8.0 * n, aligned16(disp) && aligned16(det)))
         launch_profiled(PK_JACOBIAN, bytes, jacobian_det_2d_v4_kernel, dim3(flat_grid(n / 4, 256)), dim3(256), as_stream(stream), disp, det, B,
                         H, W);
     else

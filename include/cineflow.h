@@ -47,7 +47,10 @@ int cf_version(void);
 /* ---------------------------------------------------------------- VoxelMorph warp family
  * SpatialTransformer.forward, nnunet/network_architecture/integration.py:61-79 (2-D branch):
  * out[b,c,i,j] = bilinear(src[b,c], i + flow[b,0,i,j], j + flow[b,1,i,j]), align_corners=True, zero padding,
- * with the reference's normalise/un-normalise fp32 rounding path reproduced. */
+ * with the reference's normalise/un-normalise fp32 rounding path reproduced.
+ * No entry point of this family requires more than the natural alignment of its element type: the four-pixel kernels (W % 4 == 0) run
+ * only when every tensor they access 16 bytes at a time (4 for the label output) lies on such a boundary, the one-pixel kernels
+ * otherwise, with bit-identical results. */
 int cf_warp_bilinear_2d(const float* flow, const float* src, float* out, int B, int C, int H, int W, void* stream);
 
 /* VecInt.forward, integration.py:95-99: v = v/2^nsteps; nsteps x { v = v + warp(v, v) }.

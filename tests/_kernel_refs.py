@@ -1,6 +1,6 @@
 """Plain numpy / scipy / torch-fp64 restatements of the operators around the convolutions (preprocessing, metrics, the 3-D sliding
-window and the Swin window attention), each a few lines.  The GPU tables test_gpu_preprocess_kernels.py, test_gpu_metrics_kernels.py,
-test_gpu_volume_ops.py and test_gpu_window_attention.py hold the HIP kernels to these; test_kernel_refs_cpu.py pins every restatement
+window, the Swin window attention and the RAFT all-pairs pyramid), each a few lines.  The GPU tables test_gpu_preprocess_kernels.py,
+test_gpu_metrics_kernels.py, test_gpu_volume_ops.py, test_gpu_window_attention.py and test_gpu_flow_op_shapes.py hold the HIP kernels to these; test_kernel_refs_cpu.py pins every restatement
 to the oracle (and through it to the reference's golden vectors) so that helper and kernel cannot be wrong together."""
 import numpy as np
 import torch
@@ -186,3 +186,15 @@ def sample_points(field, pts):
     gy = 2 * (p[:, 1] / (H - 1) - 0.5)
     grid = torch.stack([gx, gy], -1)[:, :, None, :]                                           # B, P, 1, 2
     return F.grid_sample(field, grid, mode="bilinear", padding_mode="zeros", align_corners=True)[..., 0]
+
+
+# ------------------------------------------------------------------------------------------------ RAFT all-pairs pyramid
+def allpairs_pyramid(f1, f2, levels):
+    """CorrBlock.__init__ of the published RAFT in float64: corr[b, n1, (y2, x2)] = sum_c f1[b, c, n1] f2[b, c, n2] / sqrt(C), then
+    avg_pool2d(2, 2) per level (an odd size drops its last row / column) -> list of [B, H W, H >> l, W >> l]"""
+    B, C, H, W = f1.shape
+    corr = torch.einsum("bcn,bcm->bnm", f1.double().reshape(B, C, H * W), f2.double().reshape(B, C, H * W)) / float(C) ** 0.5
+    pyr = [corr.reshape(B, H * W, H, W)]
+    for _ in range(levels - 1):
+        pyr.append(F.avg_pool2d(pyr[-1], 2, stride=2))
+    return pyr

@@ -143,3 +143,20 @@ def test_sample_points_equals_oracle_strain(golden):
     B, P = pts.shape[0], pts.shape[-1] if pts.dim() == 3 else pts.numel() // (2 * pts.shape[0])
     out = R.sample_points(field, pts.reshape(B, 2, P))
     assert float((out - torch.from_numpy(g["stc_out"])[:, :, 0]).abs().max()) <= 2e-6
+
+
+@pytest.mark.parametrize("B,C,H,W,levels", [(2, 32, 16, 20, 4), (1, 24, 8, 24, 3), (2, 16, 16, 32, 4)])
+def test_allpairs_pyramid_equals_oracle(B, C, H, W, levels):
+    """the fp64 restatement against oracle.ops.corr_allpairs / corr_pyramid run in float64 (rounding only) and in their own float32 (the
+    fp32 matmul's error on unit-normal features: sqrt(C) x 2^-24 x a few), at a size whose levels pool 5 -> 2"""
+    from oracle import ops as OO
+    g = torch.Generator().manual_seed(H + W)
+    f1, f2 = torch.randn(B, C, H, W, generator=g), torch.randn(B, C, H, W, generator=g)
+    out = R.allpairs_pyramid(f1, f2, levels)
+    ref64 = OO.corr_pyramid(OO.corr_allpairs(f1.double(), f2.double()), levels)
+    ref32 = OO.corr_pyramid(OO.corr_allpairs(f1, f2), levels)
+    assert len(out) == len(ref64) == levels
+    for l in range(levels):
+        assert out[l].dtype == torch.float64 and out[l].shape == ref64[l].shape == (B, H * W, H >> l, W >> l)
+        assert float((out[l] - ref64[l]).abs().max()) <= 1e-13
+        assert float((out[l] - ref32[l].double()).abs().max()) <= 5e-6
