@@ -267,6 +267,13 @@ __device__ __forceinline__ float xor_sum(float s) {
     else { float a = s, b = s; swap_halves32(a, b); return a + b; }
 }
 
+// xor_sum on an fp64 value (the statistics epilogues past their fp32 per-wave totals): the partner lane's value by a plain shuffle
+template <int MASK>
+__device__ __forceinline__ double xor_sum(double s) {
+    static_assert(MASK == 2 || MASK == 4 || MASK == 8 || MASK == 16 || MASK == 32, "lane mask");
+    return s + __shfl_xor(s, MASK, 64);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

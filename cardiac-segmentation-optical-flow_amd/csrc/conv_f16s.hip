@@ -632,15 +632,18 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
         xreduce16(ssq, lane);
         // workgroup-level combine in LDS (the staging buffers are free now), then ONE fp64 atomic pair per (group, workgroup):
         // thousands of workgroups adding to the same 8 groups of a sample would otherwise serialise at the memory side.
-        float* red = reinterpret_cast<float*>(lds);  // [WM*32 channels][2]
+        // fp32 ends with the wave's per-channel totals: from here on the sums are fp64.  A map with |mean| / std of 6 .. 9 (a large bias)
+        // loses two digits in E[x^2] - E[x]^2, and a workgroup total rounded to fp32 (2^-24 of the sum of squares) then shows as
+        // 1e-5 .. 4e-5 on the normalised map (tests/test_gpu_deferred_norm_blocks.py, the offset rows).
+        double* red = reinterpret_cast<double*>(lds);  // [WM*32 channels][2]
         __syncthreads();                              // every wave is done reading the last LDS buffer
-        if (tid < WM * 64) red[tid] = 0.f;
+        if (tid < WM * 64) red[tid] = 0.0;
         __syncthreads();
         if ((lane & 1) == 0) {
             const int r = ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
             const int cl = (cw % WM) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;  // channel inside the workgroup's block
-            atomicAdd(&red[2 * cl], ssum[0]);
-            atomicAdd(&red[2 * cl + 1], ssq[0]);
+            atomicAdd(&red[2 * cl], (double)ssum[0]);
+            atomicAdd(&red[2 * cl + 1], (double)ssq[0]);
         }
         __syncthreads();
         if (tid < WM * 32 && b0 < p.B) {
@@ -651,11 +654,11 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
                 int n = cpg - co % cpg;               // channels of this group from co on
                 if (n > WM * 32 - tid) n = WM * 32 - tid;
                 if (n > p.Cout - co) n = p.Cout - co;
-                float s1 = 0.f, s2 = 0.f;
+                double s1 = 0.0, s2 = 0.0;
                 for (int j = 0; j < n; ++j) { s1 += red[2 * (tid + j)]; s2 += red[2 * (tid + j) + 1]; }
                 double* w = p.gn_ws + 2L * ((long)b0 * p.gn_groups + co / cpg);
-                atomicAdd(w, (double)s1);
-                atomicAdd(w + 1, (double)s2);
+                atomicAdd(w, s1);
+                atomicAdd(w + 1, s2);
             }
         }
     }
@@ -753,6 +756,7 @@ static int launch_f16s_v(const ConvParams& p, F16sGeom g, const _Float16* wpk, h
     }
     size_t lds_bytes = (size_t)2 * g.NIMG * g.PH * g.PWR * REC + (PRE ? (size_t)3 * g.nchunk * CK * sizeof(float) : 0) +
                              (WL ? (size_t)2 * WM * WGRP * 2 * 1024 : 0);
+    if (p.gn_ws && lds_bytes < (size_t)WM * 64 * sizeof(double)) lds_bytes = (size_t)WM * 64 * sizeof(double);   // the statistics epilogue's fp64 totals
 #ifdef CF_F16S_ABLATION_BUILD
     { static long pad = -1; if (pad < 0) { const char* e = getenv("CF_F16S_LDSPAD"); pad = e ? atol(e) : 0; }   // timing builds: fewer resident workgroups
       if (pad > (long)lds_bytes) lds_bytes = (size_t)pad; }

@@ -391,15 +391,16 @@ conv_wino_kernel(const ConvParams p, const WinoGeom g, const _Float16* __restric
         xreduce16(ssum, lane);      // common.h: DPP + v_permlane16_swap, no LDS traffic
         xreduce16(ssq, lane);
         // workgroup-level combine in LDS (the V buffers are free now), then ONE fp64 atomic pair per (group, workgroup)
-        float* red = reinterpret_cast<float*>(lds);  // [128 channels][2]
+        // (fp64 from the wave's per-channel totals on, as in conv_f16s.hip)
+        double* red = reinterpret_cast<double*>(lds);  // [128 channels][2]
         __syncthreads();
-        red[tid] = 0.f;
+        red[tid] = 0.0;
         __syncthreads();
         if ((lane & 1) == 0) {
             const int r = ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
             const int cl = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            atomicAdd(&red[2 * cl], ssum[0]);
-            atomicAdd(&red[2 * cl + 1], ssq[0]);
+            atomicAdd(&red[2 * cl], (double)ssum[0]);
+            atomicAdd(&red[2 * cl + 1], (double)ssq[0]);
         }
         __syncthreads();
         if (tid < 128) {
@@ -409,11 +410,11 @@ conv_wino_kernel(const ConvParams p, const WinoGeom g, const _Float16* __restric
                 int n = cpg - co % cpg;               // channels of this group from co on
                 if (n > 128 - tid) n = 128 - tid;
                 if (n > p.Cout - co) n = p.Cout - co;
-                float s1 = 0.f, s2 = 0.f;
+                double s1 = 0.0, s2 = 0.0;
                 for (int j = 0; j < n; ++j) { s1 += red[2 * (tid + j)]; s2 += red[2 * (tid + j) + 1]; }
                 double* w = p.gn_ws + 2L * ((long)b * p.gn_groups + co / cpg);
-                atomicAdd(w, (double)s1);
-                atomicAdd(w + 1, (double)s2);
+                atomicAdd(w, s1);
+                atomicAdd(w + 1, s2);
             }
         }
     }
@@ -817,7 +818,7 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
             // xor-shuffles over the lane bits of cl's low k bits, and one lane per group adds the pair to the fp64 workspace.
             xreduce16(ssum, lane);      // common.h: DPP + v_permlane16_swap, no LDS traffic
             xreduce16(ssq, lane);
-            float s1 = ssum[0], s2 = ssq[0];
+            double s1 = ssum[0], s2 = ssq[0];                                // fp64 from the wave's per-channel totals on (conv_f16s.hip)
             const int cpg = p.Cout / p.gn_groups;
             const int cl = ((lane >> 1) & 1) + 2 * ((lane >> 2) & 1) + 4 * half + 8 * ((lane >> 3) & 1) + 16 * ((lane >> 4) & 1);
             int k = 0;
@@ -832,8 +833,8 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
             const int co = mt * 32 + cl;
             if ((lane & 1) == 0 && (cl & (span - 1)) == 0 && co < p.Cout) {
                 double* w = p.gn_ws + 2L * ((long)b * p.gn_groups + co / cpg);
-                atomicAdd(w, (double)s1);
-                atomicAdd(w + 1, (double)s2);
+                atomicAdd(w, s1);
+                atomicAdd(w + 1, s2);
             }
         }
         tm_e3 += WINO_T() - te2;

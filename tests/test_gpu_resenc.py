@@ -66,6 +66,39 @@ def test_residual_block_matches_the_reference_block(dev, n, monkeypatch):
     assert d <= 2e-5, d
 
 
+@pytest.mark.parametrize("n", range(len(BLOCKS)))
+def test_residual_block_fp32_mode_composed_with_own_pass_norms(dev, n, monkeypatch):
+    """set_conv_mode("f32"): every convolution runs composed and fuses no statistics, so each InstanceNorm3d -- the projection's one
+    included, which InstanceNorm3d.forward then runs as the branch's own pass -- is a cf_group_norm call; same fp64 output, same bar"""
+    from cineflow import ops
+    from cineflow.nn import BasicResidualBlock3D
+    from cineflow.weights import seeded_state_dict
+    cin, cout, kernel, stride, shape, has_skip = BLOCKS[n]
+    g = np.load(os.path.join(HERE, "golden", "resenc_block_%d.npz" % n))
+    blk = BasicResidualBlock3D(cin, cout, kernel, stride)
+    blk.load_state_dict(seeded_state_dict(blk.state_shapes(), BLOCK_SEED + n), dev)
+    asked, composed = _count_routes(monkeypatch)
+    norms = {"group_norm": 0, "group_norm_apply": 0}
+    for name in norms:
+        monkeypatch.setattr(ops, name, lambda *a, _real=getattr(ops, name), _name=name, **k: norms.__setitem__(_name, norms[_name] + 1) or _real(*a, **k))
+    x = torch.from_numpy(g["x"]).to(dev)
+    x_before = x.clone()
+    ops.set_conv_mode("f32")
+    try:
+        y = blk(x)
+    finally:
+        ops.set_conv_mode("f16s")
+    torch.cuda.synchronize()
+    assert torch.equal(x, x_before), "the block wrote into its input (the encoder keeps it as a skip)"
+    assert not asked, asked
+    st = (1, 1, 1) if stride is None else stride
+    assert composed == [(kernel, st), (kernel, (1, 1, 1))] + ([((1, 1, 1), st)] if has_skip else []), composed
+    assert norms == {"group_norm": 3 if has_skip else 2, "group_norm_apply": 0}, norms
+    d = float((y.cpu().double() - torch.from_numpy(g["y64"])).abs().max())
+    print("\nblock %d in fp32 mode max|diff| vs the reference in fp64: %.3e" % (n, d))
+    assert d <= 2e-5, d
+
+
 @pytest.fixture(scope="module")
 def imported(tmp_path_factory):
     from cineflow import reference_models as R
