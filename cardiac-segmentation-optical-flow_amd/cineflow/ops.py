@@ -114,6 +114,13 @@ def corr_volume(cur, prev, radius=4, stride=1):
     return out
 
 
+def corr_volume_route(cur, prev, radius=4, stride=1):
+    """the kernel corr_volume launches for these tensors: 0 generic, 1 persistent fp32 (corr_volume_p7_kernel), 2 f16 MFMA; launches nothing"""
+    B, C, H, W = cur.shape
+    assert prev.shape == cur.shape
+    return lib().cf_corr_volume_route(_f32(cur), _f32(prev), C, H, W, radius, stride)
+
+
 def pyramid_numel(B, H, W, levels):
     N = H * W
     return sum(B * N * (H >> l) * (W >> l) for l in range(levels))

@@ -352,10 +352,14 @@ __global__ void __launch_bounds__(256) corr_volume_generic_kernel(const float* _
         int y = p / W, x = p - y * W;
         int yy = y + (ch / D - radius) * stride, xx = x + (ch % D - radius) * stride;
         float s = 0.f;
+        const float* cp = cur + (long)b * C * HW + p;
         if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
-            const float* cp = cur + (long)b * C * HW + p;
             const float* pp = prev + (long)b * C * HW + (long)yy * W + xx;
             for (int c = 0; c < C; ++c) s = fmaf(cp[(long)c * HW], pp[(long)c * HW], s);
+        } else {
+            // zero padding as the oracle and the two tiled kernels have it: cur * 0, so a NaN / Inf in cur shows at every displacement
+            // whichever kernel the pointers' alignment selects
+            for (int c = 0; c < C; ++c) s = fmaf(cp[(long)c * HW], 0.f, s);
         }
         out[idx] = s / (float)C;
     }
@@ -552,14 +556,26 @@ __global__ void __launch_bounds__(256) convex_upsample_rows_kernel(const float* 
 
 using namespace cf;
 
+// The kernel cf_corr_volume launches for these arguments: 0 = corr_volume_generic_kernel, 1 = corr_volume_p7_kernel<stride>, 2 =
+// corr_volume_mfma_kernel<stride> (corr_mfma.hip; honours cf_corr_mfma_enable / CF_CORR_MFMA).  Host code, launches nothing; cf_corr_volume
+// dispatches on this value and holds no condition of its own.
+extern "C" int cf_corr_volume_route(const float* cur, const float* prev, int C, int H, int W, int radius, int stride) {
+    if (radius != 4 || !(stride == 1 || stride == 2 || stride == 4)) return 0;
+    if (corr_mfma_applicable(C, H, W, stride, cur, prev)) return 2;
+    if ((W & 3) == 0 && (long)(C + P7_CC) * H * W * 4 < (1L << 31) &&
+        ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(prev)) & 15) == 0)
+        return 1;
+    return 0;
+}
+
 extern "C" int cf_corr_volume(const float* cur, const float* prev, float* out, int B, int C, int H, int W, int radius, int stride,
                               void* stream) {
     CF_REQUIRE(cur && prev && out, "null pointer");
     CF_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && radius >= 0 && radius <= 8 && stride >= 1, "bad shape");
     hipStream_t s = as_stream(stream);
-    if (radius == 4 && corr_mfma_applicable(C, H, W, stride, cur, prev)) return launch_corr_volume_mfma(cur, prev, out, B, C, H, W, stride, s);
-    if (radius == 4 && (stride == 1 || stride == 2 || stride == 4) && (W & 3) == 0 && (long)(C + P7_CC) * H * W * 4 < (1L << 31) &&
-        ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(prev)) & 15) == 0) {
+    const int route = cf_corr_volume_route(cur, prev, C, H, W, radius, stride);
+    if (route == 2) return launch_corr_volume_mfma(cur, prev, out, B, C, H, W, stride, s);
+    if (route == 1) {
         // algorithmic bytes: read cur + prev once, write the 81-channel volume once
         const double bytes = 4.0 * (double)B * H * W * (2.0 * C + 81.0);
         // persistent kernel: one workgroup per CU (256 on MI355X), each walking its XCD's band of 7-row x 64-column tiles

@@ -24,8 +24,18 @@
 //     What bounds it (profiles/r04_corr_mfma.txt): the bytes in flight.  A second staging set (two chunks in flight) needs 16 more registers than
 //     the 128 a 1024-thread workgroup has per lane; tried twice (with every fragment register given up: one A and one B fragment live) it still
 //     spills 40-60 B per lane INSIDE the chunk loop, the reloads collapse the counted waits to vmcnt(0), and the loop gets slower, not faster.
-// Shapes: C % 8 == 0, W % 64 == 0, H % (8 S) == 0 (the three levels of the flow network: (64, 256, 4), (128, 128, 2), (256, 64, 1)); anything else
-// stays on corr.hip.  Numerics: exact products of the split operands, fp32 accumulation: within 1e-5 of the fp32 / fp64 oracle on O(1) features.
+// Shapes: C % 16 == 0 (corr_mfma_applicable; the kernel itself walks 8-channel chunks, so through the ABI the chunk count is always even), W % 64 == 0,
+// H % (8 S) == 0 (the three levels of the flow network: (64, 256, 4), (128, 128, 2), (256, 64, 1)); anything else stays on corr.hip.
+// Numerics: exact products of the split operands, fp32 accumulation: within 1e-5 of the fp32 / fp64 oracle on O(1) features.
+// Measured (tests/test_gpu_corr_volume_routes.py): at most 0.07 x 2^-18 A from the four-term sum of the split operands at every shape there, A = (1/C) sum
+// (|ch| + |cl|)(|ph| + |pl|); against the true result max |out - true| / A = 1.7e-7 on unit normals x 30 (the fp32 kernel: 2.6e-7), i.e. fp32 class WHILE
+// THE lo HALVES ARE NORMAL f16 NUMBERS.  lo = fp16(x - hi) is an f16 subnormal (absolute resolution 2^-24) for |x| < 0.125, so the split keeps 22 bits relative
+// to O(1) operands only: unit normals x 1e-2 on both sides give 2.7e-6 A, cur x 300 with prev x 1e-3 gives 1.7e-5 A (the fp32 kernel 2.6e-7 A at both).
+// Feature maps far below O(1) belong on the fp32 kernel (cf_corr_mfma_enable(0)); a finite |x| >= 65520 becomes hi = Inf, lo = -Inf and every output that
+// reads it NaN (include/cineflow.h).  The row-parity swap of a record's halves, as long as the writer (hi_off) and both readers (the `py & 1`
+// of a_part and b_part) apply it consistently -- or hi_off alone drops it, which exchanges hi and lo in BOTH fragments of odd rows -- only permutes the four
+// terms of the K = 32 sum: it is a bank-conflict measure that no numerical test can observe.  The k-group part of a_part / b_part is not of that kind:
+// A = [ah ah al al] against B = [bh bh bl bl] is 2 ah bh + 2 al bl, wrong by O(1).
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 

@@ -84,9 +84,21 @@ int cf_jacobian_det_3d(const float* disp, double* det, int B, int D, int H, int 
  * out[b,(dy+r)(2r+1)+(dx+r),y,x] = mean_c cur[b,c,y,x] * prev[b,c,y+dy*stride,x+dx*stride], zero outside. */
 int cf_corr_volume(const float* cur, const float* prev, float* out, int B, int C, int H, int W, int radius, int stride,
                    void* stream);
+/* The kernel cf_corr_volume launches for these arguments (host code, launches nothing; cf_corr_volume dispatches on this very value):
+ * 0 = the one-thread-per-output kernel (any radius <= 8, any stride, any alignment), 1 = the persistent fp32 kernel (radius 4, stride 1 / 2 / 4,
+ * W % 4 == 0, both inputs 16-byte aligned), 2 = the f16-MFMA kernel (see cf_corr_mfma_enable).
+ * Non-finite inputs.  The zero padding is a factor like any other: on every route a NaN in cur makes all (2r+1)^2 outputs of its pixel NaN
+ * (cur * 0 at the displacements that leave the map), and a NaN in prev reaches exactly the outputs that read it, as in the oracle.  An Inf in
+ * cur makes all outputs of its pixel non-finite: NaN where the displacement leaves the map (Inf * 0), +-Inf or NaN elsewhere (Inf * prev) on
+ * routes 0 and 1, NaN on route 2.  Routes 0 and 1 are fp32 throughout.  Route 2 splits both operands into f16 halves: a finite |value| above
+ * the f16 range (65504, after rounding: >= 65520) has hi = Inf, lo = -Inf there, and every output that reads it is NaN; nothing else is
+ * affected and no range scan is made.  Features of that size belong on route 1 (cf_corr_mfma_enable(0)). */
+int cf_corr_volume_route(const float* cur, const float* prev, int C, int H, int W, int radius, int stride);
 /* A/B knob without a reference counterpart: CorrVolume calls with radius 4, dilation 1 / 2 / 4, C % 16 == 0, W % 64 == 0 and H % (8 x dilation) == 0
  * run on the f16-MFMA kernel (csrc/corr_mfma.hip: 2-D banded products of hi/lo-split operands, fp32 accumulation, within 1e-5 of the fp32 kernel);
- * 0 keeps them on the fp32 vector kernel (also CF_CORR_MFMA=0).  Returns the previous setting. */
+ * 0 keeps them on the fp32 vector kernel (also CF_CORR_MFMA=0).  Returns the previous setting.  The 1e-5 is for O(1) features: the split keeps
+ * 22 bits relative to O(1) only (measured |out - true| up to 1.7e-5 x the sum of |cur||prev| / C with cur x 300, prev x 1e-3) and has the f16
+ * range; see the comment of cf_corr_volume_route above and the header of csrc/corr_mfma.hip. */
 int cf_corr_mfma_enable(int on);
 
 /* CorrBlock (published RAFT; call site SegFlowGaussian.py:929): all-pairs volume

@@ -1,6 +1,7 @@
 """Plain numpy / scipy / torch-fp64 restatements of the operators around the convolutions (preprocessing, metrics, the 3-D sliding
-window, the Swin window attention and the RAFT all-pairs pyramid), each a few lines.  The GPU tables test_gpu_preprocess_kernels.py,
-test_gpu_metrics_kernels.py, test_gpu_volume_ops.py, test_gpu_window_attention.py and test_gpu_flow_op_shapes.py hold the HIP kernels to these; test_kernel_refs_cpu.py pins every restatement
+window, the Swin window attention, the RAFT all-pairs pyramid and CorrVolume), each a few lines.  The GPU tables test_gpu_preprocess_kernels.py,
+test_gpu_metrics_kernels.py, test_gpu_volume_ops.py, test_gpu_window_attention.py, test_gpu_flow_op_shapes.py and
+test_gpu_corr_volume_routes.py hold the HIP kernels to these; test_kernel_refs_cpu.py pins every restatement
 to the oracle (and through it to the reference's golden vectors) so that helper and kernel cannot be wrong together."""
 import numpy as np
 import torch
@@ -198,3 +199,42 @@ def allpairs_pyramid(f1, f2, levels):
     for _ in range(levels - 1):
         pyr.append(F.avg_pool2d(pyr[-1], 2, stride=2))
     return pyr
+
+
+# ------------------------------------------------------------------------------------------------ CorrVolume
+def _corr64(a, b, radius, stride):
+    """(1/C) sum_c a[b, c, y, x] * b[b, c, y + dy stride, x + dx stride] in float64, zeros outside -> [B, (2r+1)^2, H, W]"""
+    B, C, H, W = a.shape
+    pad, D = radius * stride, 2 * radius + 1
+    bp = F.pad(b, (pad, pad, pad, pad))
+    out = a.new_empty(B, D * D, H, W)
+    for i in range(D):
+        for j in range(D):
+            out[:, i * D + j] = (a * bp[:, :, i * stride:i * stride + H, j * stride:j * stride + W]).sum(1)
+    return out / float(C)
+
+
+def corr_volume_refs(cur, prev, radius, stride):
+    """CorrVolume (oracle.ops.corr_volume) of float32 cur / prev [B, C, H, W] in float64, with the f16 hi/lo split of _split_exact.split_x
+    (hi = fp16(x), lo = fp16(x - hi), subnormal lo halves kept) that corr_mfma.hip stages:
+      true     the operator on the true operands
+      y4       (1/C) sum (ch + cl)(ph + pl): all four split terms, what one K = 32 MFMA of corr_mfma.hip adds up
+      y1       hi x hi only
+      A        (1/C) sum (|ch| + |cl|)(|ph| + |pl|): the bound of every partial sum of the split kernel; 0 exactly where the displacement leaves the map
+      A1       (1/C) sum |c| |p|: the same for the fp32 kernels
+      d_last   the contribution of the last channel (true operands)
+      d_lohi8  the cl x ph terms of the last 8 channels
+    y4 - true is the split's own truncation, <= about 2^-21 A (each operand keeps 22 bits): an eighth of SPLIT_BAR = 2^-18.  The lo x lo
+    term is smaller still (measured 0.005 - 0.023 of the bar at the shapes of test_kernel_refs_cpu.py): no test can tell a kernel that
+    drops it from one that keeps it, and none asserts it."""
+    from _split_exact import split_x
+    assert cur.dtype == torch.float32 and prev.dtype == torch.float32 and cur.shape == prev.shape
+    C = cur.shape[1]
+    ch, cl = split_x(cur)
+    ph, pl = split_x(prev)
+    cd, pd = cur.double(), prev.double()
+    lo8 = slice(max(0, C - 8), C)
+    return dict(true=_corr64(cd, pd, radius, stride), y4=_corr64(ch + cl, ph + pl, radius, stride), y1=_corr64(ch, ph, radius, stride),
+                A=_corr64(ch.abs() + cl.abs(), ph.abs() + pl.abs(), radius, stride), A1=_corr64(cd.abs(), pd.abs(), radius, stride),
+                d_last=_corr64(cd[:, C - 1:], pd[:, C - 1:], radius, stride) / float(C),
+                d_lohi8=_corr64(cl[:, lo8], ph[:, lo8], radius, stride) * (float(lo8.stop - lo8.start) / float(C)))

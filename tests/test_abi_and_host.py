@@ -71,6 +71,28 @@ def test_argument_validation_needs_no_gpu():
     assert rc == -1
 
 
+def test_corr_volume_route_probe_needs_no_gpu():
+    """cf_corr_volume_route is host code: the dispatch of cf_corr_volume (0 generic, 1 persistent fp32, 2 f16 MFMA) on shape, alignment
+    and the cf_corr_mfma_enable knob, asked here with made-up addresses"""
+    from cineflow import _lib
+    h = _lib.lib()
+    a, m = 4096, 4096 + 4                                          # a 16-byte aligned and a misaligned address
+    route = lambda cur, prev, C, H, W, radius, stride: h.cf_corr_volume_route(cur, prev, C, H, W, radius, stride)
+    before = h.cf_corr_mfma_enable(1)
+    try:
+        for C, H, W, S in ((16, 8, 64, 1), (16, 16, 64, 2), (16, 32, 64, 4), (256, 64, 64, 1), (64, 256, 256, 4)):
+            assert route(a, a, C, H, W, 4, S) == 2, (C, H, W, S)
+            assert route(m, a, C, H, W, 4, S) == 0 and route(a, m, C, H, W, 4, S) == 0, (C, H, W, S)
+            assert route(a, a, C, H, W, 3, S) == 0 and route(a, a, C, H, W, 4, 3) == 0
+        for C, H, W, S in ((8, 8, 64, 1), (24, 8, 64, 1), (16, 8, 128 + 4, 1), (16, 7, 64, 1), (16, 8, 64, 2), (16, 16, 64, 4), (5, 9, 12, 2)):
+            assert route(a, a, C, H, W, 4, S) == 1, (C, H, W, S)      # C % 16, W % 64, H % (8 S): the MFMA kernel declines, p7 takes it
+        assert route(a, a, 16, 8, 66, 4, 1) == 0 and route(a, a, 5, 7, 9, 4, 2) == 0      # W % 4 != 0
+        assert h.cf_corr_mfma_enable(0) == 1
+        assert route(a, a, 16, 8, 64, 4, 1) == 1 and route(m, a, 16, 8, 64, 4, 1) == 0
+    finally:
+        h.cf_corr_mfma_enable(before)
+
+
 def test_product_fails_loudly_without_library(monkeypatch):
     from cineflow import _lib
     monkeypatch.setattr(_lib, "_lib", None)

@@ -35,8 +35,7 @@ entry point -> kernel -> test
   cf_convex_upsample      convex_upsample_kernel (C = 4)                                   test_second_trip_convex_upsample
                           convex_upsample_rows_kernel<1>, <2> (one workgroup per map row: no grid-stride loop) stay with
                           test_gpu_ops.py::test_convex_upsample and ::test_convex_upsample_single_channel
-  cf_corr_volume          corr_volume_generic_kernel: not a RAFT operator; its table is test_gpu_ops.py::test_corr_volume_radius4
-                          (widths that are no multiple of 4) and ::test_corr_volume_generic_and_symmetry (radius 2, stride 3)
+  cf_corr_volume          not a RAFT operator: all three of its kernels have their table in test_gpu_corr_volume_routes.py
   cf_gru_reset_mul, cf_gru_blend, cf_binary, cf_copy_channels, cf_crop2d, cf_pad2d, cf_flip2d, cf_tta_accumulate, cf_tile_accumulate,
   cf_tile_finalize, cf_argmax_channels, cf_coords_grid, cf_count_out_of_range -> the kernel of the same name -> test_second_trip_elementwise_*
 

@@ -160,3 +160,56 @@ def test_allpairs_pyramid_equals_oracle(B, C, H, W, levels):
         assert out[l].dtype == torch.float64 and out[l].shape == ref64[l].shape == (B, H * W, H >> l, W >> l)
         assert float((out[l] - ref64[l]).abs().max()) <= 1e-13
         assert float((out[l] - ref32[l].double()).abs().max()) <= 5e-6
+
+
+def _inside(H, W, radius, stride):
+    """[(2r+1)^2, H, W] bool: the displacement stays inside the map"""
+    D = 2 * radius + 1
+    y, x = torch.arange(H)[:, None], torch.arange(W)[None, :]
+    m = torch.zeros(D * D, H, W, dtype=torch.bool)
+    for i in range(D):
+        for j in range(D):
+            yy, xx = y + (i - radius) * stride, x + (j - radius) * stride
+            m[i * D + j] = (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W)
+    return m
+
+
+@pytest.mark.parametrize("B,C,H,W,radius,stride", [(1, 16, 8, 64, 4, 1), (2, 256, 8, 64, 4, 1), (2, 128, 16, 64, 4, 2), (3, 64, 32, 64, 4, 4),
+                                                  (2, 5, 7, 9, 4, 2), (1, 4, 6, 10, 8, 1), (1, 4, 6, 10, 0, 1), (1, 4, 6, 10, 4, 3)])
+def test_corr_volume_refs_equal_oracle_and_resolve(B, C, H, W, radius, stride):
+    """corr_volume_refs against oracle.ops.corr_volume, and what the two bars of test_gpu_corr_volume_routes.py resolve, as multiples of
+    SPLIT_BAR x A = 2^-18 A (maximum over the volume; unit-normal operands):
+        (B, C, H, W, S)       hi x hi only   lo x hi of 8 channels   last channel   lo x lo   y4 - true
+        (1, 16, 8, 64, 1)        124             68.4                 1.4e5          0.023     0.035
+        (2, 256, 8, 64, 1)        31.8            6.35                1.5e4          0.005     0.007
+        (2, 128, 16, 64, 2)       52.4           12.7                 3.6e4          0.008     0.010
+        (3, 64, 32, 64, 4)        72.9           28.7                 6.2e4          0.012     0.016
+    lo x lo is below the bar: it cannot be resolved and is not asserted.  The split's own truncation y4 - true is bounded by reasoning:
+    |x - xh - xl| <= 2^-22 |x| (two roundings to 11 bits), so |y4 - true| <= (2 x 2^-22 + 2^-44) A1 < 0.13 x 2^-18 A."""
+    from oracle import ops as OO
+    from _split_exact import SPLIT_BAR
+    cur, prev = (torch.randn(B, C, H, W, generator=torch.Generator().manual_seed(s)) for s in (C + H, C + W + 1))
+    r = R.corr_volume_refs(cur, prev, radius, stride)
+    D = 2 * radius + 1
+    for k, v in r.items():
+        assert v.dtype == torch.float64 and v.shape == (B, D * D, H, W), k
+    ref64 = OO.corr_volume(cur.double(), prev.double(), radius, stride)
+    assert float((r["true"] - ref64).abs().max()) <= 1e-14
+    inside = _inside(H, W, radius, stride)[None].expand(B, -1, -1, -1)
+    assert torch.equal(r["A"] == 0, ~inside) and torch.equal(r["A1"] == 0, ~inside)
+    for k in ("true", "y4", "y1", "d_last", "d_lohi8"):
+        assert bool((r[k][~inside] == 0).all()), k
+    bar = (SPLIT_BAR * r["A"])[inside]
+    of = lambda d: float((d[inside].abs() / bar).max())
+    assert float((r["A"] - r["A1"]).abs().max()) <= 2.0 ** -10 * float(r["A1"].max()) and bool((r["A"] >= r["A1"] * (1 - 2.0 ** -20)).all())
+    split_err = of(r["y4"] - r["true"])
+    hh, lohi8, last = of(r["y1"] - r["y4"]), of(r["d_lohi8"]), of(r["d_last"])
+    print("\n  %s: hi x hi only %.3g, lo x hi of 8 channels %.3g, last channel %.3g, y4 - true %.3g (x 2^-18 A)" % ((B, C, H, W, stride), hh, lohi8, last, split_err))
+    assert split_err <= 0.13, split_err
+    assert hh > 1 and lohi8 > 1 and last > 1, (hh, lohi8, last)                       # the split-exact bar resolves each of them
+    # the fp32 bar of the two fp32 kernels: any C-term fp32 sum, the rounding of 1 / C and of the final product -> (C + 3) 2^-24 A1;
+    # the oracle's own float32 run meets it, and taking one channel away does not
+    bar32 = ((C + 3) * 2.0 ** -24 * r["A1"])[inside]
+    own = float(((OO.corr_volume(cur, prev, radius, stride).double() - r["true"])[inside].abs() / bar32).max())
+    assert own <= 1.0, own
+    assert float((r["d_last"][inside].abs() / bar32).max()) > 1
