@@ -95,6 +95,10 @@ SIGNATURES = {
     "cf_cc_apply": [P, P, L, I, I, I, P, P, P, P, P, P, DBL, P, P],
     "cf_conv2d_small_cin": [P, P, P, P, I, I, I, I, I, I, P, I, P],
     "cf_conv2d_small_cout": [P, P, P, P, P, I, I, I, I, I, P],
+    "cf_conv2d_small_cout_norm2_ok": [I, I, I, I, I],
+    "cf_conv2d_small_cout_norm2": [P, P, P, P, P, P, P, I, I, I, I, I, P],
+    "cf_stem_block_ok": [I, I, I, I, I, I],
+    "cf_stem_block": [P, P, P, P, P, P, P, I, I, I, I, I, P, P, I, P],
     "cf_nonzero_mask": [P, I, L, P, P],
     "cf_fill_holes": [P, P, P, I, I, I, I, P],
     "cf_mask_bbox": [P, I, I, I, P, P],

@@ -432,10 +432,12 @@ def predict_cine_slices(flow_net, seg_net, frames, ed_labels=None, do_mirroring=
     # TTA-averaged (:3162).  Both chunks run as one batch of 2B sequences when they have equal length.
     flow = torch.zeros((T, B, 2, H, W), dtype=torch.float32, device=dev)
     o1, o2 = chunk_orders(T)
+    # both half sequences of a slice start from its ED frame: the recurrent dispatches encode it once (SegFlowGaussian.forward, shared_first)
+    shared = {"shared_first": B} if hasattr(flow_net, "_narrow") and not getattr(flow_net, "raft", False) else {}
     ragged = len(o1) == len(o2) + 1 and len(o2) > 1 and RAGGED_CHUNKS and hasattr(flow_net, "_narrow") and not getattr(flow_net, "raft", False)
     if len(o1) == len(o2) and len(o1) > 1:
         xin = torch.cat([frames[o1], frames[o2]], dim=1)  # [Tc, 2B, 1, H, W]  (copies only)
-        bf = flow_net(xin)["backward_flow"]
+        bf = flow_net(xin, **shared)["backward_flow"]
         for j, t in enumerate(o1[1:]):
             flow[t] = bf[j, :B]
         for j, t in enumerate(o2[1:]):
@@ -445,7 +447,7 @@ def predict_cine_slices(flow_net, seg_net, frames, ed_labels=None, do_mirroring=
         # longer group alone.  Twice the work per launch for 28 of 29 steps; per-sequence numbers are those of separate calls.
         o2p = o2 + [o2[-1]]                                 # padding frame of the shorter group: never consumed
         xin = torch.cat([frames[o1], frames[o2p]], dim=1)   # [Tc, 2B, 1, H, W]
-        bf = flow_net(xin, keep_from=len(o2), keep=B)["backward_flow"]
+        bf = flow_net(xin, keep_from=len(o2), keep=B, **shared)["backward_flow"]
         for j, t in enumerate(o1[1:]):
             flow[t] = bf[j, :B]
         for j, t in enumerate(o2[1:]):

@@ -189,18 +189,22 @@ class SegFlowGaussian(Module):
         if raft:
             self.update_block = BasicUpdateBlock(hidden_dim=d_model // 2)
 
-    def forward(self, x, keep_from=None, keep=None):
+    def forward(self, x, keep_from=None, keep=None, shared_first=None):
         """keep_from / keep (not in the reference, whose forward runs one sequence batch): from recurrence step `keep_from` on only the first
         `keep` sequences of the batch go on (their state is sliced out) -- lets two sequence groups of lengths T and T-1 share the launches of
         their common steps (cineflow.inference.predict_cine_slices).  The returned flow is [T-1, B, ...]; rows >= keep of the steps >= keep_from
         are zero.  No kernel mixes batch entries; per-sequence results differ from separate calls only through the launch shapes the batch size
-        selects (~5e-6 px measured)."""
+        selects (~5e-6 px measured).
+        shared_first=n (not in the reference either): the caller states that sequences i and i + n of the batch (B = 2n) start from the same
+        frame x[0] -- the two ED-anchored half sequences of one slice -- so the two encoder passes over x[0] run on the first n sequences and
+        their outputs are repeated along the batch."""
         if self.raft:
-            assert keep_from is None, "ragged batches are built for the two recurrent dispatches only"
+            assert keep_from is None and shared_first is None, "ragged / shared-ED batches are built for the two recurrent dispatches only"
             return self.forward_multi_task_flow_deformable_raft(x)
+        assert shared_first is None or x.shape[1] == 2 * shared_first, "shared_first=n describes a batch of 2n sequences"
         if self.motion_appearance:
-            return self.forward_motion_appearance(x, keep_from, keep)
-        return self.forward_multi_task_flow_deformable_cost_volume_transformer_cat(x, keep_from, keep)
+            return self.forward_motion_appearance(x, keep_from, keep, shared_first)
+        return self.forward_multi_task_flow_deformable_cost_volume_transformer_cat(x, keep_from, keep, shared_first)
 
     @staticmethod
     def _narrow(t, n):
@@ -218,27 +222,48 @@ class SegFlowGaussian(Module):
             out[i, :f.shape[0]] = f
         return out
 
-    def _step_tail(self, f1, f2, hidden, new_skips, cum, x0, xt):
-        """SegFlowGaussian.py:1410-1435 == :1878-1905."""
+    @staticmethod
+    def _twice(t):
+        """the encoder outputs of n sequences for the batch [0..n) + [n..2n) that shares them (shared_first)"""
+        if isinstance(t, (list, tuple)):
+            return [SegFlowGaussian._twice(u) for u in t]
+        return t.repeat(2, 1, 1, 1)
+
+    def _step_tail(self, f1, f2, hidden, new_skips, cum, x0, xt, last=False, go_on=None):
+        """SegFlowGaussian.py:1410-1435 == :1878-1905.  The memory encoder's output is consumed by the NEXT step only: none follows the last
+        one (`last`: the pass is left out), and behind step keep_from - 1 only the first `go_on` sequences go on (the pass runs on those)."""
         gru_in = self.reduce_transformer(f1, x2=f2)
         hidden = self.gru_cell(gru_in, hidden)
         flow = self.flow_decoder(hidden, new_skips)
         cum = ops.add(cum, flow)
-        past_motion, past_skips = self.memory_encoder(ops.memory_input(x0, xt, cum))
+        if last:
+            return hidden, cum, None, None
+        if go_on is not None and go_on < cum.shape[0]:
+            past_motion, past_skips = self.memory_encoder(ops.memory_input(*self._narrow((x0, xt, cum), go_on)))
+        else:
+            past_motion, past_skips = self.memory_encoder(ops.memory_input(x0, xt, cum))
         return hidden, cum, past_motion, past_skips
 
-    def forward_motion_appearance(self, x, keep_from=None, keep=None):
+    def _tail_flags(self, t, T, B, keep_from, keep):
+        """_step_tail's (last, go_on) at step t of T - 1 with B sequences in the batch"""
+        return dict(last=t == T - 1, go_on=keep if (keep_from is not None and t == keep_from - 1 and B != keep) else None)
+
+    def forward_motion_appearance(self, x, keep_from=None, keep=None, shared_first=None):
         """SegFlowGaussian.py:1813-1912."""
         T, B, C, H, W = x.shape
         B_all = B
         dev = x.device
         cum = torch.zeros((B, 2, H, W), dtype=torch.float32, device=dev)
         hidden = torch.zeros((B, self.d_model, self.H, self.W), dtype=torch.float32, device=dev)
-        past_motion, past_skips = self.memory_encoder(ops.memory_input(x[0], x[0], cum))
-        pair = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev)
-        ops.copy_channels(x[0], 0, 1, dst=pair, dst_coff=0)
-        ops.copy_channels(x[0], 0, 1, dst=pair, dst_coff=1)
+        n0 = shared_first or B           # the sequences whose first frame is encoded (the others share it)
+        e0, c0 = self._narrow((x[0], cum), n0)
+        past_motion, past_skips = self.memory_encoder(ops.memory_input(e0, e0, c0))
+        pair = torch.empty((n0, 2, H, W), dtype=torch.float32, device=dev)
+        ops.copy_channels(e0, 0, 1, dst=pair, dst_coff=0)
+        ops.copy_channels(e0, 0, 1, dst=pair, dst_coff=1)
         first_app, _, _ = self.query_encoder(pair)
+        if shared_first:
+            past_motion, past_skips, first_app = self._twice((past_motion, past_skips, first_app))
         prev_app = first_app
         flows = []
         x0 = x[0]
@@ -257,20 +282,24 @@ class SegFlowGaussian(Module):
             new_skips = [self.skip_co_reduction_list[s](skips[s], x2=past_skips[s]) for s in range(self.num_stages)]
             f1 = self.bottleneck1(query=cur_app, key=prev_app, value=prev_app)
             f2 = self.bottleneck2(query=cur_app, key=first_app, value=past_motion)
-            hidden, cum, past_motion, past_skips = self._step_tail(f1, f2, hidden, new_skips, cum, x0, xt)
+            hidden, cum, past_motion, past_skips = self._step_tail(f1, f2, hidden, new_skips, cum, x0, xt, **self._tail_flags(t, T, B, keep_from, keep))
             flows.append(cum)
             prev_app = cur_app
         return {"backward_flow": self._stack_flows(flows, B_all)}
 
-    def forward_multi_task_flow_deformable_cost_volume_transformer_cat(self, x, keep_from=None, keep=None):
+    def forward_multi_task_flow_deformable_cost_volume_transformer_cat(self, x, keep_from=None, keep=None, shared_first=None):
         """SegFlowGaussian.py:1330-1447 (skip_co_type 'both', correlation_value False, warp False)."""
         T, B, C, H, W = x.shape
         B_all = B
         dev = x.device
         cum = torch.zeros((B, 2, H, W), dtype=torch.float32, device=dev)
         hidden = torch.zeros((B, self.d_model, self.H, self.W), dtype=torch.float32, device=dev)
-        past_motion, past_skips = self.memory_encoder(ops.memory_input(x[0], x[0], cum))
-        first_feat, first_skips = self.query_encoder(x[0])
+        n0 = shared_first or B           # the sequences whose first frame is encoded (the others share it)
+        e0, c0 = self._narrow((x[0], cum), n0)
+        past_motion, past_skips = self.memory_encoder(ops.memory_input(e0, e0, c0))
+        first_feat, first_skips = self.query_encoder(e0)
+        if shared_first:
+            past_motion, past_skips, first_feat, first_skips = self._twice((past_motion, past_skips, first_feat, first_skips))
         prev_feat, prev_skips = first_feat, first_skips
         flows = []
         x0 = x[0]
@@ -290,7 +319,7 @@ class SegFlowGaussian(Module):
                 new_skips.append(self.skip_co_reduction_list[s](corr, x2=past_skips[s]))
             f1 = self.bottleneck1(query=cur_feat, key=prev_feat, value=prev_feat)
             f2 = self.bottleneck2(query=cur_feat, key=first_feat, value=past_motion)
-            hidden, cum, past_motion, past_skips = self._step_tail(f1, f2, hidden, new_skips, cum, x0, xt)
+            hidden, cum, past_motion, past_skips = self._step_tail(f1, f2, hidden, new_skips, cum, x0, xt, **self._tail_flags(t, T, B, keep_from, keep))
             flows.append(cum)
             prev_feat, prev_skips = cur_feat, cur_skips
         return {"backward_flow": self._stack_flows(flows, B_all)}

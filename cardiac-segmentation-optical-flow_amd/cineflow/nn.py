@@ -437,25 +437,46 @@ class DoubleConv(Module):
         coef = ops.group_norm_coef(ws1, self.norm1._p["weight"], self.norm1._p["bias"], self.norm1.groups, B, C, H * W, self.norm1.eps)
         return self.conv2.prenorm(t_raw, coef, -1.0, stats_groups=self.norm2.groups)
 
-    def forward(self, x, x2=None):
+    def _stem_ok(self, x, x2):
+        """conv1 and the 1x1 downsample convolution read the same few-channel input: one launch writes both raw maps (ops.stem_block)"""
+        c1 = self.conv1
+        return (x2 is None and self.has_ds and c1.sub is None and c1.stride == 1 and c1.cin <= 8 and c1.ks == (3, 3) and c1.pad == (1, 1)
+                and self.downsample[1].groups == self.norm1.groups and ops.stem_block_ok(x, c1.cout, self.norm1.groups))
+
+    def forward(self, x, x2=None, defer_last=None):
+        """defer_last = the 3x3 head convolution that will consume this block's output alone (Decoder2D.final_conv): when it can form
+        GELU(GN2(y2)) + GN_ds(r) itself while staging (ops.conv2d_small_cout_norm2), the final apply pass is left to it and the pending
+        norms are handed on as ((y2, ws2, norm2), (r, ws_r, norm_ds)).  Returns x, or (x, pending) when defer_last is given (one of the
+        two is None)."""
         kw1 = {} if x2 is None else {"x2": x2}
-        t, ws1 = self.conv1(x, stats_groups=self.norm1.groups, **kw1)
+        r = ws_r = None
+        if self._stem_ok(x, x2):
+            ds = self.downsample[0]
+            t, ws1, r, ws_r = ops.stem_block(x, self.conv1._p["weight"], self.conv1._p.get("bias"), ds._p["weight"], ds._p.get("bias"), self.norm1.groups)
+        else:
+            t, ws1 = self.conv1(x, stats_groups=self.norm1.groups, **kw1)
         pre = ws1 is not None and ops.CONV_MODE == "f16s" and self.conv2.prenorm_ok(t)
+        y2 = ws2 = None
         if pre:
             y2, ws2 = self._conv2(t, ws1)
             conv2 = lambda **k: self.norm2(y2, act="gelu", ws=ws2, **k)                       # noqa: E731
         else:
             t = self.norm1(t, act="gelu", ws=ws1)
             conv2 = lambda **k: conv_norm(self.conv2, self.norm2, t, act="gelu", **k)          # noqa: E731
+        done = (lambda out: out) if defer_last is None else (lambda out: (out, None))          # noqa: E731
         if not self.residual:
-            return conv2()
+            return done(conv2())
         if self.has_ds:
             # the branch's GroupNorm rides in the final apply pass: GELU(GN2(conv2(t))) + GN_ds(conv1x1(x)) in one kernel
-            kw = {} if x2 is None else {"x2": x2}
-            r, ws_r = self.downsample[0](x, stats_groups=self.downsample[1].groups, **kw)
-            return conv2(res=r, res_mode="after_act", res_norm=(ws_r, self.downsample[1]))
+            if r is None:
+                kw = {} if x2 is None else {"x2": x2}
+                r, ws_r = self.downsample[0](x, stats_groups=self.downsample[1].groups, **kw)
+            if (defer_last is not None and ws2 is not None and ws_r is not None and defer_last.sub is None
+                    and ops.small_cout_norm2_ok(y2, defer_last.cout, defer_last.ks[0], defer_last.ks[1], defer_last.stride, defer_last.pad)):
+                return None, ((y2, ws2, self.norm2), (r, ws_r, self.downsample[1]))
+            return done(conv2(res=r, res_mode="after_act", res_norm=(ws_r, self.downsample[1])))
         assert x2 is None
-        return conv2(res=x, res_mode="after_act")
+        return done(conv2(res=x, res_mode="after_act"))
 
 
 class SingleConv(Module):
@@ -487,10 +508,16 @@ class ConvBlocks2DGroupLegacy(Module):
         fn = DoubleConv if nb_conv == 2 else SingleConv
         self.blocks = [fn(in_dim=int(dims[i]), out_dim=int(dims[i + 1]), residual=residual, stride=stride) for i in range(nb_blocks)]
 
-    def forward(self, x, x2=None):
+    def forward(self, x, x2=None, defer_last=None):
+        """defer_last: DoubleConv.forward's, asked of the last block -> (x, pending)"""
+        pending = None
         for i, b in enumerate(self.blocks):
-            x = b(x, x2=x2) if i == 0 else b(x)
-        return x
+            kw = {"x2": x2} if i == 0 else {}
+            if defer_last is not None and i == len(self.blocks) - 1 and isinstance(b, DoubleConv):
+                x, pending = b(x, defer_last=defer_last, **kw)
+            else:
+                x = b(x, **kw)
+        return (x, pending) if defer_last is not None else x
 
 
 class PatchExpand2DGroup(Module):
@@ -568,9 +595,20 @@ class Decoder2D(Module):
         self.final_conv = Conv2d(out_encoder_dims[-1], num_classes, 3, padding=1)
 
     def forward(self, x, skips):
-        for layer, up, skip in zip(self.layers, self.upsample_layers, reversed(skips)):
-            x = layer(skip, x2=up(x))
-        return self.final_conv(x)
+        pending = None
+        for i, (layer, up, skip) in enumerate(zip(self.layers, self.upsample_layers, reversed(skips))):
+            if i == self.num_stages - 1:
+                x, pending = layer(skip, x2=up(x), defer_last=self.final_conv)      # the head is the last block's only consumer
+            else:
+                x = layer(skip, x2=up(x))
+        if pending is None:
+            return self.final_conv(x)
+        coefs = []
+        for raw, ws, norm in pending:
+            B, C, H, W = raw.shape
+            coefs.append(ops.group_norm_coef(ws, norm._p["weight"], norm._p["bias"], norm.groups, B, C, H * W, norm.eps))
+        (y2, _, _), (r, _, _) = pending
+        return ops.conv2d_small_cout_norm2(y2, coefs[0], r, coefs[1], self.final_conv._p["weight"], self.final_conv._p.get("bias"))
 
 
 # --------------------------------------------------------------------------------------------- transformers

@@ -515,6 +515,46 @@ def conv2d_small_cout(x, weight, bias, res=None):
     return out
 
 
+def small_cout_norm2_ok(y2, cout, kh, kw, stride, pad):
+    """can cf_conv2d_small_cout_norm2 take the raw block outputs y2 (and r, same shape) into a `cout`-channel 3x3 head?"""
+    B, C, H, W = y2.shape
+    return bool(CONV_MODE == "f16s" and small_cout_supported(cout, kh, kw, stride, pad) and lib().cf_conv2d_small_cout_norm2_ok(B, C, H, W, cout) == 1)
+
+
+def conv2d_small_cout_norm2(y2, coef2, r, coefr, weight, bias):
+    """conv2d_small_cout of GELU(GN2(y2)) + GN_ds(r) -- a DoubleConv's output -- from the block's raw maps y2, r [B,Cin,H,W] and their
+    group_norm_coef tables [B,3,Cin]: the block's final apply pass happens while the head stages its input."""
+    B, Cin, H, W = y2.shape
+    cout = weight.shape[0]
+    assert tuple(weight.shape) == (cout, Cin, 3, 3) and r.shape == y2.shape
+    assert tuple(coef2.shape) == (B, 3, Cin) and tuple(coefr.shape) == (B, 3, Cin)
+    out = torch.empty((B, cout, H, W), dtype=torch.float32, device=y2.device)
+    check(lib().cf_conv2d_small_cout_norm2(_f32(y2), _f32(coef2), _f32(r), _f32(coefr), _f32(weight), _opt(bias), _f32(out), B, Cin, H, W, cout,
+                                           _stream()), "cf_conv2d_small_cout_norm2")
+    return out
+
+
+def stem_block_ok(x, cout, groups):
+    """can cf_stem_block take x [B,Cin,H,W] (Cin 1 or 6) into the `cout`-channel 3x3 and 1x1 maps with `groups` statistics groups?"""
+    B, Cin, H, W = x.shape
+    return bool(CONV_MODE == "f16s" and lib().cf_stem_block_ok(B, Cin, H, W, cout, groups) == 1)
+
+
+def stem_block(x, w3, b3, w1, b1, groups):
+    """conv1 (3x3 pad 1) and the 1x1 downsample convolution of a stem DoubleConv in one launch over x: -> (y, ws_y, r, ws_r), the two raw
+    maps [B,Cout,H,W] with the GroupNorm statistics of each (as conv2d_small_cin returns them)."""
+    B, Cin, H, W = x.shape
+    cout = w3.shape[0]
+    assert tuple(w3.shape) == (cout, Cin, 3, 3) and tuple(w1.shape) == (cout, Cin, 1, 1)
+    y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+    r = torch.empty_like(y)
+    ws = _zeroed_stats_ws(4 * B * groups, x.device)
+    ws_y, ws_r = ws[:2 * B * groups], ws[2 * B * groups:]
+    check(lib().cf_stem_block(_f32(x), _f32(w3), _opt(b3), _f32(w1), _opt(b1), _f32(y), _f32(r), B, Cin, H, W, cout, ws_y.data_ptr(), ws_r.data_ptr(),
+                              -groups, _stream()), "cf_stem_block")
+    return y, ws_y, r, ws_r
+
+
 def prenorm_ok(x, cout):
     """can cf_conv2d_f16s_prenorm take this input (raw conv output [B,C,H,W]) for a 3x3 / stride 1 convolution to `cout` channels?"""
     B, C, H, W = x.shape

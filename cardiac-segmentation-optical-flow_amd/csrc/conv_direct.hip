@@ -155,6 +155,101 @@ __global__ void __launch_bounds__(256, 4) conv3x3_small_cout_kernel(const float*
         }
 }
 
+// The same head behind a DoubleConv whose final apply pass is left out (Decoder2D's last block, nnunet/lib/utils.py:1182-1215): the head's input
+//   v = GELU((y2 - m2) * s2 + b2) + ((r - mr) * sr + br)        {m, s, b} = cf_group_norm_coef rows of conv2's / the downsample branch's norm
+// is formed while the tile is staged, from the two raw maps, instead of being written by gn_apply_kernel and read back (16 -> 8 bytes per element
+// of the Cin-channel map).  A workgroup owns a 64 x (4 PY) output tile; per input channel its 256 threads form the tile with its one-pixel halo
+// ONCE (66 x (4 PY + 2) values: 1.1x the tile's elements, against the 3.75x a per-thread neighbourhood would cost in GELUs) into one of two LDS
+// planes, and every thread then reads its (PY + 2) x 3 neighbourhood from there: one barrier per channel.  A tap outside the image is the zero
+// padding of v, not v of a zero.  Expression order as gn_apply_kernel / gelu_as; the FMA order over (ci, co, ky, kx) is conv3x3_small_cout_kernel's.
+template <int COUT, int PY>
+__global__ void __launch_bounds__(256, 4) conv3x3_small_cout_norm2_kernel(const float* __restrict__ y2, const float* __restrict__ coef2,
+                                                                          const float* __restrict__ r, const float* __restrict__ coefr,
+                                                                          const float* __restrict__ w, const float* __restrict__ bias,
+                                                                          float* __restrict__ out, int Cin, int H, int W) {
+    constexpr int NR = PY + 2;
+    constexpr int TH = 4 * PY + 2, TW = 66, TN = TH * TW, NS = (TN + 255) / 256;
+    constexpr unsigned OOB = 0x80000000u;
+    __shared__ float tile[2][TN];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int bx0 = blockIdx.x * 64, by0 = blockIdx.y * 4 * PY, b = blockIdx.z;
+    const int x0 = bx0 + tx, y0 = by0 + ty * PY;
+    const long HW = (long)H * W;
+    const int bytes = (int)((long)Cin * HW * 4);
+    const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(y2 + (long)b * Cin * HW), 0, bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(r + (long)b * Cin * HW), 0, bytes, 0x00020000);
+    // the thread's share of the staged tile: element e = threadIdx.x + 256 k of the TH x TW plane (row-major: a wave loads contiguous row pieces)
+    unsigned off[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const int e = (int)threadIdx.x + 256 * k, tr = e / TW, tc = e - tr * TW;
+        const int yy = by0 + tr - 1, xx = bx0 + tc - 1;
+        off[k] = (e < TN && yy >= 0 && yy < H && xx >= 0 && xx < W) ? (unsigned)(yy * W + xx) * 4u : OOB;
+    }
+    float acc[COUT][PY];
+#pragma unroll
+    for (int co = 0; co < COUT; ++co)
+#pragma unroll
+        for (int rr = 0; rr < PY; ++rr) acc[co][rr] = bias ? bias[co] : 0.f;
+    const unsigned HW4 = (unsigned)HW * 4u;
+    const float* c2 = coef2 + (long)b * 3 * Cin;                 // wave-uniform: scalar loads
+    const float* cr = coefr + (long)b * 3 * Cin;
+    float a[NS], q[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        a[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs2, off[k], 0, 0));
+        q[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsr, off[k], 0, 0));
+    }
+#pragma unroll 1
+    for (int ci = 0; ci < Cin; ++ci) {
+        float* t = tile[ci & 1];
+        const float m2 = c2[ci], s2 = c2[Cin + ci], b2 = c2[2 * Cin + ci];
+        const float mr = cr[ci], sr = cr[Cin + ci], br = cr[2 * Cin + ci];
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const int e = (int)threadIdx.x + 256 * k;
+            float v = (a[k] - m2) * s2 + b2;
+            v = gelu_as(v);
+            v += (q[k] - mr) * sr + br;
+            if (e < TN) t[e] = off[k] != OOB ? v : 0.f;
+        }
+        if (ci + 1 < Cin) {                                      // the next channel's loads fly under this channel's FMAs
+            const unsigned cofs = (unsigned)(ci + 1) * HW4;
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                a[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs2, off[k] + cofs, 0, 0));
+                q[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsr, off[k] + cofs, 0, 0));
+            }
+        }
+        __syncthreads();                                         // plane ci & 1 is complete; plane (ci + 1) & 1 was last read before the previous barrier
+        float in[NR][3];
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) in[rr][c] = t[(ty * PY + rr) * TW + tx + c];
+#pragma unroll
+        for (int co = 0; co < COUT; ++co) {
+            const float* wc = w + ((long)co * Cin + ci) * 9;      // wave-uniform: scalar loads
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) {
+                    const float wv = wc[ky * 3 + kx];
+#pragma unroll
+                    for (int rr = 0; rr < PY; ++rr) acc[co][rr] = fmaf(wv, in[rr + ky][kx], acc[co][rr]);
+                }
+        }
+    }
+    if (x0 >= W) return;
+#pragma unroll
+    for (int co = 0; co < COUT; ++co)
+#pragma unroll
+        for (int rr = 0; rr < PY; ++rr) {
+            if (y0 + rr >= H) continue;
+            out[((long)b * COUT + co) * HW + (long)(y0 + rr) * W + x0] = acc[co][rr];
+        }
+}
+
 }  // namespace cf
 
 using namespace cf;
@@ -203,6 +298,29 @@ extern "C" int cf_conv2d_small_cout(const float* x, const float* weight, const f
         default: CF_LAUNCH_SC(4); break;
     }
 #undef CF_LAUNCH_SC
+    CF_CHECK_LAUNCH();
+    return CF_OK;
+}
+
+extern "C" int cf_conv2d_small_cout_norm2_ok(int B, int Cin, int H, int W, int Cout) {
+    return B > 0 && B < 65536 && Cin > 0 && H > 0 && W > 0 && Cout >= 1 && Cout <= 4 && (H + 31) / 32 < 65536 && (double)Cin * H * W * 4.0 < 2147483648.0 ? 1 : 0;
+}
+
+extern "C" int cf_conv2d_small_cout_norm2(const float* y2, const float* coef2, const float* r, const float* coefr, const float* weight, const float* bias,
+                                          float* out, int B, int Cin, int H, int W, int Cout, void* stream) {
+    CF_REQUIRE(y2 && coef2 && r && coefr && weight && out && y2 != out && r != out, "null or aliased pointer");
+    CF_REQUIRE(cf_conv2d_small_cout_norm2_ok(B, Cin, H, W, Cout) == 1,
+               "built for 1..4 output channels and input samples below 2 GiB (32-bit buffer offsets): B=%d Cin=%d H=%d W=%d Cout=%d", B, Cin, H, W, Cout);
+    hipStream_t s = as_stream(stream);
+    constexpr int PY = 8;
+    dim3 grid((unsigned)((W + 63) / 64), (unsigned)((H + 4 * PY - 1) / (4 * PY)), (unsigned)B);
+    const double bytes = 4.0 * B * H * W * (2.0 * Cin + Cout);
+    switch (Cout) {
+        case 1: launch_profiled(PK_CONV_SMALL_COUT, bytes, conv3x3_small_cout_norm2_kernel<1, PY>, grid, dim3(256), s, y2, coef2, r, coefr, weight, bias, out, Cin, H, W); break;
+        case 2: launch_profiled(PK_CONV_SMALL_COUT, bytes, conv3x3_small_cout_norm2_kernel<2, PY>, grid, dim3(256), s, y2, coef2, r, coefr, weight, bias, out, Cin, H, W); break;
+        case 3: launch_profiled(PK_CONV_SMALL_COUT, bytes, conv3x3_small_cout_norm2_kernel<3, PY>, grid, dim3(256), s, y2, coef2, r, coefr, weight, bias, out, Cin, H, W); break;
+        default: launch_profiled(PK_CONV_SMALL_COUT, bytes, conv3x3_small_cout_norm2_kernel<4, PY>, grid, dim3(256), s, y2, coef2, r, coefr, weight, bias, out, Cin, H, W); break;
+    }
     CF_CHECK_LAUNCH();
     return CF_OK;
 }

@@ -407,6 +407,23 @@ int cf_conv2d_small_cin(const float* x, const float* weight, const float* bias, 
  * bias and res may be NULL. */
 int cf_conv2d_small_cout(const float* x, const float* weight, const float* bias, const float* res, float* out, int B, int Cin, int H, int W,
                          int Cout, void* stream);
+/* The same head directly behind a DoubleConv (nnunet/lib/utils.py:1182-1215) whose last apply pass is left out: the head's input
+ * GELU((y2 - m2) * s2 + b2) + ((r - mr) * sr + br) is formed from the block's two raw maps while the tile is staged -- y2 = conv2's output
+ * with coef2, r = the 1x1 downsample branch's output with coefr, both coefficient tables float [B][3][Cin] from cf_group_norm_coef.
+ * out = conv(that) + bias, same summation order as cf_conv2d_small_cout.  cf_conv2d_small_cout_norm2_ok (host code, no launch) returns 1
+ * when the kernel takes the shape (1..4 output channels, one input sample below 2 GiB); the call fails with CF_ERR_ARG otherwise. */
+int cf_conv2d_small_cout_norm2_ok(int B, int Cin, int H, int W, int Cout);
+int cf_conv2d_small_cout_norm2(const float* y2, const float* coef2, const float* r, const float* coefr, const float* weight, const float* bias,
+                               float* out, int B, int Cin, int H, int W, int Cout, void* stream);
+/* The stem DoubleConv of the flow encoders (nnunet/lib/utils.py:1182-1215 with a 1x1 downsample; Cin 1 or 6) in ONE launch over the
+ * input: y = conv3x3(x; w3, b3) (pad 1) and r = conv1x1(x; w1, b1), both raw, dense [B][Cout][H][W], exact fp32 with the summation order
+ * of cf_conv2d_small_cin, and the GroupNorm statistics of each ({sum, sum of squares} per (sample, group), fp64 [B][gn_groups][2]) in
+ * ws_y / ws_r.  gn_groups <= 64 divides Cout; negative gn_groups declares both workspaces already zeroed, otherwise they are zeroed
+ * here.  b3 / b1 may be NULL.  cf_stem_block_ok (host code, no launch) returns 1 when the kernel takes the shape, and the call fails
+ * with CF_ERR_ARG otherwise. */
+int cf_stem_block_ok(int B, int Cin, int H, int W, int Cout, int gn_groups);
+int cf_stem_block(const float* x, const float* w3, const float* b3, const float* w1, const float* b1, float* y, float* r, int B, int Cin,
+                  int H, int W, int Cout, double* ws_y, double* ws_r, int gn_groups, void* stream);
 
 /* ---------------------------------------------------------------- test-time preprocessing (the step before the path)
  * create_nonzero_mask, nnunet/preprocessing/cropping.py:25-32: mask[v] = any_c data[c][v] != 0 (uint8 [V]). */

@@ -46,6 +46,10 @@ def shape_key(name, args, kw):
         x, w = args[0], args[1]
         B, C, H, W = x.shape
         return "conv2d_small_cin B%d C%d %dx%d -> %d k%d" % (B, C, H, W, w.shape[0], w.shape[2]), 2.0 * B * H * W * w.shape[0] * C * w.shape[2] * w.shape[3]
+    if name == "stem_block":                # (x, w3, b3, w1, b1, groups): both maps of the stem block
+        x, w3 = args[0], args[1]
+        B, C, H, W = x.shape
+        return "stem_block B%d C%d %dx%d -> 2 x %d" % (B, C, H, W, w3.shape[0]), 2.0 * B * H * W * w3.shape[0] * C * 10
     if name.startswith("conv_transpose"):
         x = args[0]
         B, C, H, W = x.shape
@@ -87,9 +91,10 @@ def main():
     lab[:, 100:156, 100:156] = 1
     bench.run_step(fnet, snet, frames, lab)
     torch.cuda.synchronize()
-    for n in ("conv2d_f16s", "conv2d_f16s_prenorm", "conv2d_wino", "conv2d_wino_prenorm", "conv2d_small_cin", "group_norm_coef", "conv_transpose2d_k2s2_f16s", "group_norm_apply", "group_norm", "layer_norm_cf", "attention_cf", "corr_volume",
+    for n in ("conv2d_f16s", "conv2d_f16s_prenorm", "conv2d_wino", "conv2d_wino_prenorm", "conv2d_small_cin", "stem_block", "conv2d_small_cout", "conv2d_small_cout_norm2", "group_norm_coef", "conv_transpose2d_k2s2_f16s", "group_norm_apply", "group_norm", "layer_norm_cf", "attention_cf", "corr_volume",
               "warp_bilinear", "binary", "copy_channels", "gru_reset_mul", "gru_blend", "tta_accumulate", "warp_labels", "memory_input"):
-        wrap(n)
+        if hasattr(ops, n):
+            wrap(n)
     # modules bound `ops.X` at call time through the module attribute, so the wrappers are picked up
     bench.run_step(fnet, snet, frames, lab)
     torch.cuda.synchronize()
