@@ -1,15 +1,19 @@
 """Who picks the kernel: one object owns a convolution's device-side weight forms and chooses the kernel of every call.
 
-`PackedConv` (Conv2d, _Linear, the attention projections, the depth taps of the composed Conv3d, the fused SepConvGRU gates) and
-`PackedConvT` (the k2s2 transposed convolution, per depth tap for ConvTranspose3d) are the only places outside the deferred-norm decisions
-that read ops.CONV_MODE and ops.f16s_dynamic_ok.  The layer classes of nn.py / models.py / mtl.py hold one of these per weight and never
-touch another layer's packed tensors.  Route of a PackedConv call, first match:
+`PackedConv` (Conv2d, _Linear, the attention projections, the depth taps of the composed Conv3d, the fused SepConvGRU gates),
+`PackedConvT` (the k2s2 transposed convolution, per depth tap for ConvTranspose3d) and `PackedConv3d` (Conv3d's two native kernels) are the
+only places outside ops.py that read ops.CONV_MODE and ops.f16s_dynamic_ok (the probes of the deferred-norm decisions test the mode inside
+ops.py).  The layer classes of nn.py / models.py / mtl.py hold one of these per weight and never touch another layer's packed tensors.
+Route of a PackedConv call, first match:
+    0. direct fp32 (conv_direct.hip)   built with direct=True (Conv2d alone), set_conv_mode("f16s"), a plain call (no x2 / act / out / alpha /
+                                      bias override): ops.small_cout_supported shapes without statistics, ops.small_cin_supported ones without res
     1. row Winograd (conv_wino.hip)   built with wino=True, 3x3 / stride 1 / pad 1, Cout in whole 128-channel blocks (or a last block >= 96),
                                       16-byte aligned inputs, ops.wino_ok for the call's shape
     2. f16 hi/lo split (conv_f16s.hip) ops.f16s_supported kernel shape, set_conv_mode("f16s"), ops.f16s_dynamic_ok for the inputs AND the
                                       destination (all channels of `out`): an oversized destination sample takes 3 instead of raising in the library
     3. exact fp32 MFMA (conv.hip)      everything else
-Conv2d alone tries the direct small_cin / small_cout kernels ahead of this object (nn.Conv2d.forward_plain).
+Route of a PackedConv3d call: cf_conv3d_f16s for (1|3, 3, 3) kernels, cf_conv3d_pw_f16s for a (1, 1, 1) kernel without x2, each under
+set_conv_mode("f16s") and its ops.*_ok probe; None otherwise (Conv3d then runs its composition of 2-D convolutions).
 """
 from . import ops
 
@@ -24,10 +28,11 @@ def split_key(x, x2, chunk):
 
 class PackedConv:
     """weight [Cout,Cin,KH,KW] in every form a kernel reads: the fp32 transposed matrix, the f16-split packing per split key (the plain one
-    at construction, split ones on first use) and, for wino=True layers of an eligible shape, the Winograd packing per split key (on first use)"""
+    at construction, split ones on first use) and, for wino=True layers of an eligible shape, the Winograd packing per split key (on first use).
+    direct=True: a plain call tries the two direct fp32 kernels (HBM-bound layers: the stems, the flow heads) on the checkpoint layout first"""
 
-    def __init__(self, weight, bias=None, stride=1, pad=(0, 0), wino=False):
-        self.weight, self.bias, self.stride, self.pad = weight, bias, stride, tuple(pad)
+    def __init__(self, weight, bias=None, stride=1, pad=(0, 0), wino=False, direct=False):
+        self.weight, self.bias, self.stride, self.pad, self.direct = weight, bias, stride, tuple(pad), direct
         self.cout, self.cin, self.kh, self.kw = weight.shape
         self.wt = ops.prep_conv_weight(weight)
         self.f16s = ops.f16s_supported(self.kh, self.kw, stride, self.pad)
@@ -59,9 +64,14 @@ class PackedConv:
     def __call__(self, x, x2=None, act=None, res=None, out=None, out_coff=0, alpha=1.0, bias=OWN, stats_groups=None):
         """act(alpha * conv(cat[x, x2]) + bias) + res into channels [out_coff, out_coff + Cout) of `out`.  stats_groups=G: returns (out, ws)
         with the GroupNorm statistics of `out` when an f16 kernel fused them, else (out, None)."""
+        kh, kw, cout = self.kh, self.kw, self.cout
+        if self.direct and ops.CONV_MODE == "f16s" and x2 is None and act is None and out is None and alpha == 1.0 and bias is OWN:
+            if not stats_groups and ops.small_cout_supported(cout, kh, kw, self.stride, self.pad):
+                return ops.conv2d_small_cout(x, self.weight, self.bias, res)                          # the flow heads
+            if res is None and ops.small_cin_supported(self.cin, kh, kw, self.stride, self.pad, stats_groups):
+                return ops.conv2d_small_cin(x, self.weight, self.bias, stats_groups)                  # the stems
         if bias is OWN:
             bias = self.bias
-        kh, kw, cout = self.kh, self.kw, self.cout
         if self.f16s and ops.CONV_MODE == "f16s":
             ohw = ((x.shape[2] + 2 * self.pad[0] - kh) // self.stride + 1) * ((x.shape[3] + 2 * self.pad[1] - kw) // self.stride + 1)
             if ops.f16s_dynamic_ok(x, x2, kh, out_sample_elems=(cout if out is None else out.shape[1]) * ohw, out_hw=ohw):
@@ -111,3 +121,32 @@ class PackedConvT:
             return ops.conv_transpose2d_k2s2_f16s(x, self.wpk, self.scale, self.bias, self.cout, out=out, out_coff=out_coff, stats_groups=stats_groups)
         y = ops.conv_transpose2d_k2s2(x, self.weight, self.bias, out=out, out_coff=out_coff)
         return (y, None) if stats_groups else y
+
+
+class PackedConv3d:
+    """weight [Cout,Cin,KD,KH,KW] of a Conv3d on the native 3-D kernels: the f16-split packing of conv3d_f16s.hip per split key and the one of
+    conv3d_pw_f16s.hip, each on first use"""
+
+    def __init__(self, weight, bias, stride):
+        self.weight, self.bias, self.stride = weight, bias, tuple(stride)
+        self.cout, self.ks = weight.shape[0], tuple(weight.shape[2:])
+        self._pk, self._pw = {}, None
+
+    def __call__(self, x, x2=None, stats_groups=None):
+        """conv(cat[x, x2]) + bias on NCDHW tensors: (out, ws) with stats_groups, else out -- or None: neither kernel takes the call
+        (set_conv_mode("f32"), one-term mode, declined shapes)"""
+        if ops.CONV_MODE != "f16s":
+            return None
+        B, C, D, H, W = x.shape
+        if self.ks[1:] == (3, 3) and ops.conv3d_f16s_ok(B, C, 0 if x2 is None else x2.shape[1], D, H, W, self.cout, self.ks, self.stride):
+            key = split_key(x, x2, 16)
+            if key not in self._pk:
+                self._pk[key] = ops.pack_conv3d_weight_f16s(self.weight, c1=key)
+            wpk, s = self._pk[key]
+            return ops.conv3d_f16s(x, wpk, s, self.bias, self.cout, self.ks, self.stride, x2=x2, stats_groups=stats_groups)
+        if self.ks == (1, 1, 1) and x2 is None and ops.conv3d_pw_f16s_ok(B, C, D, H, W, self.cout, self.stride):
+            if self._pw is None:
+                self._pw = ops.pack_conv3d_pw_weight_f16s(self.weight)
+            wpk, s = self._pw
+            return ops.conv3d_pw_f16s(x, wpk, s, self.bias, self.cout, self.stride, stats_groups=stats_groups)
+        return None

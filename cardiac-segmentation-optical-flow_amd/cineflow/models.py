@@ -10,7 +10,7 @@ import torch
 
 from . import ops
 from .convroute import PackedConv
-from .nn import (Module, conv_norm, Conv2d, ConvTranspose2d, GroupNorm, Conv3d, ConvTranspose3d, InstanceNorm3d, ResidualLayer3D, ConvBlocks2DGroupLegacy, Encoder2D, Decoder2D, CrossAttentionLayer,
+from .nn import (Module, RawMap, conv_norm, Conv2d, ConvTranspose2d, GroupNorm, Conv3d, ConvTranspose3d, InstanceNorm3d, ResidualLayer3D, ConvBlocks2DGroupLegacy, Encoder2D, Decoder2D, CrossAttentionLayer,
                  TransformerFlowEncoderSuccessiveNoEmb, ConvGRUCell, SpatialTransformer, VecInt)
 
 
@@ -464,28 +464,22 @@ class StackedConvLayers(Module):
     def forward(self, x, x2=None, pending=None, defer_last=None):
         """A block whose output feeds only the next convolution leaves its InstanceNorm + LeakyReLU to that convolution (applied while the
         tile is staged, ops.conv2d_f16s_prenorm): one 8-byte-per-element pass less per pair.
-        pending = (raw conv output, its statistics, its norm module) handed over by the PREVIOUS stack (x is then ignored);
+        pending = the nn.RawMap (raw conv output, its statistics, its norm module) handed over by the PREVIOUS stack (x is then ignored);
         defer_last = the convolution that will consume this stack's output alone: when it qualifies, the last block's norm is handed on
         as the returned `pending` instead of being applied.  Returns x, or (x, pending) when defer_last is given."""
         for i, b in enumerate(self.blocks):
             last = i == len(self.blocks) - 1
             if pending is not None:
-                raw, ws, norm = pending
-                B, C, H, W = raw.shape
-                coef = ops.group_norm_coef(ws, norm._p["weight"], norm._p["bias"], norm.groups, B, C, H * W, norm.eps)
-                y, ws_b = b.conv.prenorm(raw, coef, 0.01, stats_groups=b.instnorm.groups)
+                y = b.conv.prenorm(pending.raw, pending.coef(), 0.01, stats_groups=b.instnorm.groups)
             else:
-                kw = {} if (x2 is None or i > 0) else {"x2": x2}
-                y, ws_b = b.conv(x, stats_groups=b.instnorm.groups, **kw)
+                y = b.conv(x, x2=x2 if i == 0 else None, stats_groups=b.instnorm.groups)
+            pending = RawMap(*y, b.instnorm)
             nxt = defer_last if last else self.blocks[i + 1].conv
-            if nxt is not None and ws_b is not None and ops.CONV_MODE == "f16s" and nxt.ks == (3, 3) and nxt.prenorm_ok(y):
-                pending = (y, ws_b, b.instnorm)
+            if nxt is not None and pending.ws is not None and nxt.ks == (3, 3) and nxt.prenorm_ok(pending.raw):
                 continue
-            if last and nxt is not None and ws_b is not None and nxt.ks == (1, 1) and nxt.stride == 1 and ops.norm_head_ok(y, nxt.cout):
-                pending = (y, ws_b, b.instnorm)      # a 1x1 head takes the norm + LeakyReLU itself (ops.norm_head_1x1)
-                continue
-            pending = None
-            x = b.instnorm(y, act="lrelu", ws=ws_b)
+            if last and nxt is not None and pending.ws is not None and nxt.ks == (1, 1) and nxt.stride == 1 and ops.norm_head_ok(pending.raw, nxt.cout):
+                continue                             # a 1x1 head takes the norm + LeakyReLU itself (ops.norm_head_1x1)
+            x, pending = pending.apply("lrelu"), None
         return (x, pending) if defer_last is not None else x
 
     def first_conv(self):
@@ -561,10 +555,7 @@ class Generic_UNet(Module):
                 # the last stack hands its norm to the 1x1 head: one pass over the raw map instead of apply + 1x1 convolution
                 x, pend = blk[1](x, pending=pend, defer_last=head)
                 if pend is not None:
-                    raw, ws, norm = pend
-                    B, C, H, W = raw.shape
-                    coef = ops.group_norm_coef(ws, norm._p["weight"], norm._p["bias"], norm.groups, B, C, H * W, norm.eps)
-                    return ops.norm_head_1x1(raw, coef, 0.01, head._p["weight"], head._p.get("bias"))
+                    return ops.norm_head_1x1(pend.raw, pend.coef(), 0.01, head._p["weight"], head._p.get("bias"))
             else:
                 x = blk[1](x, pending=pend)
         return head(x)
@@ -580,8 +571,7 @@ class ConvDropoutNormNonlin3D(Module):
         self.instnorm = InstanceNorm3d(cout)
 
     def forward(self, x, x2=None):
-        y, ws = self.conv(x, x2=x2, stats_groups=self.instnorm.channels)
-        return self.instnorm(y, act="lrelu", ws=ws)
+        return conv_norm(self.conv, self.instnorm, x, x2=x2, act="lrelu")
 
 
 class StackedConvLayers3D(Module):
@@ -653,8 +643,7 @@ class ConvDropoutNormReLU3D(Module):
         self.norm = InstanceNorm3d(cout)
 
     def forward(self, x, x2=None):
-        y, ws = self.conv(x, x2=x2, stats_groups=self.norm.channels)
-        return self.norm(y, act="lrelu", ws=ws)
+        return conv_norm(self.conv, self.norm, x, x2=x2, act="lrelu")
 
 
 class PlainStackedConvLayers3D(Module):
@@ -689,8 +678,7 @@ class ResidualUNetEncoder3D(Module):
             cin = cout
 
     def forward(self, x):
-        y, ws = self.initial_conv(x, stats_groups=self.initial_norm.channels)
-        x = self.initial_norm(y, act="lrelu", ws=ws)
+        x = conv_norm(self.initial_conv, self.initial_norm, x, act="lrelu")
         skips = []
         for s in self.stages:
             x = s(x)

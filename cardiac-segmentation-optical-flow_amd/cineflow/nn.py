@@ -7,11 +7,12 @@ channel-first ([B,C,N]) so the reference's permute/contiguous round trips never 
 1x1 convolution on the same implicit-GEMM kernel.  `file:line` citations are relative to /root/reference.
 """
 import math
+from typing import NamedTuple
 
 import torch
 
 from . import ops
-from .convroute import OWN, PackedConv, PackedConvT, split_key
+from .convroute import OWN, PackedConv, PackedConv3d, PackedConvT
 
 
 class Module:
@@ -108,7 +109,7 @@ class Conv2d(Module):
 
     def _prepare(self):
         if "weight" in self._p:
-            self._packed = PackedConv(self._p["weight"], self._p.get("bias"), self.stride, self.pad, wino=self.sub is None)
+            self._packed = PackedConv(self._p["weight"], self._p.get("bias"), self.stride, self.pad, wino=self.sub is None, direct=True)
 
     @property
     def _ws(self):
@@ -126,18 +127,9 @@ class Conv2d(Module):
         """stats_groups=G: returns (out, ws) with the GroupNorm statistics of `out` when the f16 kernel can fuse them, else (out, None)."""
         if self.sub is not None:
             assert act is None and res is None and out is None, "per-axis strides: plain convolution only"
-            y = self.forward_plain(x, x2, alpha=alpha, bias=bias)
+            y = self._packed(x, x2, alpha=alpha, bias=bias)
             y = y[:, :, ::self.sub[0], ::self.sub[1]].contiguous()
             return (y, None) if stats_groups else y
-        return self.forward_plain(x, x2, act, res, out, out_coff, stats_groups, alpha, bias)
-
-    def forward_plain(self, x, x2=None, act=None, res=None, out=None, out_coff=0, stats_groups=None, alpha=1.0, bias=OWN):
-        # the direct fp32 kernels (HBM-bound layers) take a plain call of this layer class only; everything else is PackedConv's choice
-        if ops.CONV_MODE == "f16s" and x2 is None and act is None and out is None and alpha == 1.0 and bias is OWN:
-            if not stats_groups and ops.small_cout_supported(self.cout, self.ks[0], self.ks[1], self.stride, self.pad):
-                return ops.conv2d_small_cout(x, self._p["weight"], self._p.get("bias"), res)          # the flow heads
-            if res is None and ops.small_cin_supported(self.cin, self.ks[0], self.ks[1], self.stride, self.pad, stats_groups):
-                return ops.conv2d_small_cin(x, self._p["weight"], self._p.get("bias"), stats_groups)      # the stems
         return self._packed(x, x2, act, res, out, out_coff, alpha, bias, stats_groups)
 
 
@@ -179,7 +171,7 @@ class ConvTranspose2d(Module):
 
 class GroupNorm(Module):
     """nn.GroupNorm(groups, C) (eps 1e-5) fused with the following activation / residual add.
-    groups == C gives nn.InstanceNorm2d(C, affine=True)."""
+    groups == C gives nn.InstanceNorm2d(C, affine=True) -- and, on an NCDHW tensor, nn.InstanceNorm3d: statistics over (D, H, W)."""
 
     def __init__(self, groups, channels, eps=1e-5):
         super().__init__()
@@ -189,7 +181,12 @@ class GroupNorm(Module):
 
     def forward(self, x, act=None, res=None, res_mode=None, inplace=True, ws=None, res_norm=None):
         """ws: statistics already accumulated by the producing convolution's epilogue -> apply pass only.
-        res_norm=(raw residual's statistics, its GroupNorm module): that norm is applied to `res` inside this pass."""
+        res_norm=(raw residual's statistics, its GroupNorm module): that norm is applied to `res` inside this pass.
+        x (and res) NCDHW: the same pass on the [B, C, D*H, W] views."""
+        if x.dim() == 5:
+            B, C, D, H, W = x.shape
+            y = self.forward(x.view(B, C, D * H, W), act, None if res is None else res.view(B, C, D * H, W), res_mode, inplace, ws, res_norm)
+            return y.view(B, C, D, H, W)
         if res_norm is not None:
             ws_r, norm_r = res_norm
             if ws is not None and ws_r is not None and norm_r.groups == self.groups and norm_r.eps == self.eps:
@@ -203,11 +200,37 @@ class GroupNorm(Module):
                               out=x if inplace else None)
 
 
-def conv_norm(conv, norm, x, x2=None, act=None, res=None, res_mode=None, res_norm=None):
-    """norm(conv(x)) with the GroupNorm statistics accumulated in the convolution's epilogue when possible."""
+class InstanceNorm3d(GroupNorm):
+    """nn.InstanceNorm3d(C, affine=True): GroupNorm with groups = C on the NCDHW tensor"""
+
+    def __init__(self, channels, eps=1e-5):
+        super().__init__(channels, channels, eps)
+
+
+class RawMap(NamedTuple):
+    """a normalisation that has not run yet: a convolution's raw output, its statistics from the convolution's epilogue (None: not fused)
+    and the norm module.  Whoever holds it applies the norm -- as a pass (`apply`) or while staging the map (`coef`)."""
+    raw: torch.Tensor
+    ws: torch.Tensor
+    norm: GroupNorm
+
+    def coef(self):
+        """the [B, 3, C] table {mean, rstd * gamma, beta} a consumer that normalises while staging reads"""
+        B, C = self.raw.shape[:2]
+        n = self.norm
+        return ops.group_norm_coef(self.ws, n._p["weight"], n._p["bias"], n.groups, B, C, self.raw.numel() // (B * C), n.eps)
+
+    def apply(self, act=None, res=None, res_mode=None, inplace=True):
+        """act(norm(raw)) with the residual inside the pass; a residual that is itself a RawMap gets its norm in the same pass"""
+        if isinstance(res, RawMap):
+            return self.norm(self.raw, act=act, res=res.raw, res_mode=res_mode, inplace=inplace, ws=self.ws, res_norm=(res.ws, res.norm))
+        return self.norm(self.raw, act=act, res=res, res_mode=res_mode, inplace=inplace, ws=self.ws)
+
+
+def conv_norm(conv, norm, x, x2=None, act=None, res=None, res_mode=None):
+    """norm(conv(x)) with the GroupNorm statistics accumulated in the convolution's epilogue when possible; res as RawMap.apply's"""
     kw = {} if x2 is None else {"x2": x2}
-    y, ws = conv(x, stats_groups=norm.groups, **kw)
-    return norm(y, act=act, res=res, res_mode=res_mode, ws=ws, res_norm=res_norm)
+    return RawMap(*conv(x, stats_groups=norm.groups, **kw), norm).apply(act, res, res_mode)
 
 
 class LayerNormCF(Module):
@@ -231,7 +254,7 @@ class Conv3d(Module):
     NCDHW tensors, the InstanceNorm statistics of the output from its epilogue (stats_groups).  The (1, 1, 1) / stride-1 heads are a 1x1
     Conv2d on the [B, C, D*H, W] view.  A (1, 1, 1) kernel with a stride above 1 -- the skip projection of BasicResidualBlock3D -- runs
     on cf_conv3d_pw_f16s (conv3d_pw_f16s.hip) where ops.conv3d_pw_f16s_ok takes the shape, statistics likewise.
-    Everything else -- set_conv_mode("f32"), one-term mode, declined shapes -- runs the composition:
+    Everything else -- its convroute.PackedConv3d answers None: set_conv_mode("f32"), one-term mode, declined shapes -- runs the composition:
     a (kd, k, k) convolution is the sum over the kd depth taps of 2-D (k, k) convolutions of depth-shifted planes, so it
     runs on the same MFMA implicit-GEMM kernels: the volume is re-laid as [B, D, C, H, W] planes, the centre tap writes
     every output plane (with the bias), the other taps accumulate through the kernel's residual input.  Kernel sizes 1 or 3
@@ -254,20 +277,9 @@ class Conv3d(Module):
             # the segmentation heads: a 1x1 convolution on the [B, C, D*H, W] view of the NCDHW tensor, no re-layout
             self._head = Conv2d.from_tensors(self._p["weight"].reshape(self.cout, self.cin, 1, 1), self._p.get("bias"), self.cin, self.cout, 1)
             return
-        # the native kernel (conv3d_f16s.hip) takes (1|3, 3, 3) kernels; packed per channel split on first use
-        self._native = self.ks[1:] == (3, 3)
-        self._pk3 = {}
-        # a strided (1, 1, 1) kernel: the gathered pointwise kernel (conv3d_pw_f16s.hip); packed on first use
-        self._pointwise = self.ks == (1, 1, 1)
-        self._pkpw = None
+        self._packed = PackedConv3d(self._p["weight"], self._p.get("bias"), self.stride)      # the native and the pointwise kernel
         # the composed route: one 2-D convolution per depth tap (the layer's bias rides on the centre tap's call; never Winograd)
         self._taps = [PackedConv(self._p["weight"][:, :, dz].contiguous(), None, self.stride[1], pad) for dz in range(self.ks[0])]
-
-    def _packed3(self, x, x2):
-        key = split_key(x, x2, 16)
-        if key not in self._pk3:
-            self._pk3[key] = ops.pack_conv3d_weight_f16s(self._p["weight"], c1=key)
-        return self._pk3[key]
 
     def forward(self, x, x2=None, stats_groups=None):
         """stats_groups=G: returns (out, ws) with the GroupNorm / InstanceNorm statistics of `out` when the native kernel ran, else (out, None)."""
@@ -276,16 +288,9 @@ class Conv3d(Module):
             assert x2 is None
             y = self._head(x.view(B, self.cin, D * H, W)).view(B, self.cout, D, H, W)
             return (y, None) if stats_groups else y
-        if (self._native and ops.CONV_MODE == "f16s"
-                and ops.conv3d_f16s_ok(B, x.shape[1], 0 if x2 is None else x2.shape[1], D, H, W, self.cout, self.ks, self.stride)):
-            wpk, wsc = self._packed3(x, x2)
-            return ops.conv3d_f16s(x, wpk, wsc, self._p.get("bias"), self.cout, self.ks, self.stride, x2=x2, stats_groups=stats_groups)
-        if (self._pointwise and x2 is None and ops.CONV_MODE == "f16s"
-                and ops.conv3d_pw_f16s_ok(B, x.shape[1], D, H, W, self.cout, self.stride)):
-            if self._pkpw is None:
-                self._pkpw = ops.pack_conv3d_pw_weight_f16s(self._p["weight"])
-            wpk, wsc = self._pkpw
-            return ops.conv3d_pw_f16s(x, wpk, wsc, self._p.get("bias"), self.cout, self.stride, stats_groups=stats_groups)
+        y = self._packed(x, x2, stats_groups)
+        if y is not None:
+            return y
         y = self._forward_composed(x, x2)          # set_conv_mode("f32"), one-term mode and declined shapes
         return (y, None) if stats_groups else y
 
@@ -341,39 +346,6 @@ class ConvTranspose3d(Module):
         return outp.view(B, D * kd, self.cout, 2 * H, 2 * W).permute(0, 2, 1, 3, 4).contiguous()
 
 
-class InstanceNorm3d(Module):
-    """nn.InstanceNorm3d(C, affine=True) fused with the following LeakyReLU: statistics over (D, H, W) per (sample, channel) --
-    the NCDHW tensor viewed as [B, C, D*H, W] on the GroupNorm kernels with groups = C."""
-
-    def __init__(self, channels, eps=1e-5):
-        super().__init__()
-        self.channels, self.eps = channels, eps
-        self._param("weight", (channels,))
-        self._param("bias", (channels,))
-
-    def forward(self, x, act=None, ws=None, res=None, res_mode=None, res_norm=None):
-        """ws: statistics already accumulated by the producing convolution (Conv3d with stats_groups) -> apply pass only.
-        res / res_mode / res_norm as GroupNorm.forward: a residual added before or after the activation inside the pass;
-        res_norm=(raw residual's statistics, its InstanceNorm3d module): that norm is applied to `res` inside this pass."""
-        B, C, D, H, W = x.shape
-        v = x.view(B, C, D * H, W)
-        if res is not None:
-            assert res.shape == x.shape
-            res = res.view(B, C, D * H, W)
-        if res_norm is not None:
-            ws_r, norm_r = res_norm
-            if ws is not None and ws_r is not None and norm_r.eps == self.eps:
-                y = ops.group_norm_apply(v, self._p["weight"], self._p["bias"], C, ws, self.eps, act=act, res=res, res_mode=res_mode, out=v,
-                                         res_norm=(ws_r, norm_r._p["weight"], norm_r._p["bias"]))
-                return y.view(B, C, D, H, W)
-            res = norm_r(res.view(B, C, D, H, W), ws=ws_r).view(B, C, D * H, W)          # the branch's own pass (statistics not fused)
-        if ws is not None:
-            y = ops.group_norm_apply(v, self._p["weight"], self._p["bias"], C, ws, self.eps, act=act, res=res, res_mode=res_mode, out=v)
-            return y.view(B, C, D, H, W)
-        y = ops.group_norm(v, self._p["weight"], self._p["bias"], C, self.eps, act=act, res=res, res_mode=res_mode, out=v)
-        return y.view(B, C, D, H, W)
-
-
 class BasicResidualBlock3D(Module):
     """custom_modules/conv_blocks.py:86-145 with conv_op = nn.Conv3d, InstanceNorm3d(affine), LeakyReLU(0.01), no dropout:
     lrelu(IN2(conv2(lrelu(IN1(conv1 x)))) + skip(x)), skip = identity or IN(conv1x1x1 at conv1's stride, no bias) -- the projection exists
@@ -393,13 +365,13 @@ class BasicResidualBlock3D(Module):
             self.downsample_skip = {0: Conv3d(cin, cout, (1, 1, 1), st, bias=False), 1: InstanceNorm3d(cout)}
 
     def forward(self, x):
-        t, ws1 = self.conv1(x, stats_groups=self.norm1.channels)
-        t = self.norm1(t, act="lrelu", ws=ws1)
-        y, ws2 = self.conv2(t, stats_groups=self.norm2.channels)
-        if not self.has_skip:
-            return self.norm2(y, act="lrelu", ws=ws2, res=x, res_mode="before_act")
-        r, ws_r = self.downsample_skip[0](x, stats_groups=self.downsample_skip[1].channels)
-        return self.norm2(y, act="lrelu", ws=ws2, res=r, res_mode="before_act", res_norm=(ws_r, self.downsample_skip[1]))
+        t = conv_norm(self.conv1, self.norm1, x, act="lrelu")
+        y = RawMap(*self.conv2(t, stats_groups=self.norm2.groups), self.norm2)
+        res = x
+        if self.has_skip:      # launched behind conv2 (profiles/layer_library_refactor.md pins the order; as conv_norm's argument it would lead)
+            proj, norm = self.downsample_skip[0], self.downsample_skip[1]
+            res = RawMap(*proj(x, stats_groups=norm.groups), norm)
+        return y.apply("lrelu", res=res, res_mode="before_act")
 
 
 class ResidualLayer3D(Module):
@@ -431,52 +403,47 @@ class DoubleConv(Module):
         if self.has_ds:
             self.downsample = {0: Conv2d(in_dim, out_dim, 1, stride=stride), 1: GroupNorm(8, out_dim)}
 
-    def _conv2(self, t_raw, ws1):
-        """conv2 on GELU(GN1(t_raw)) with the normalisation applied while conv2 stages its input -> (raw conv2 output, its statistics)"""
-        B, C, H, W = t_raw.shape
-        coef = ops.group_norm_coef(ws1, self.norm1._p["weight"], self.norm1._p["bias"], self.norm1.groups, B, C, H * W, self.norm1.eps)
-        return self.conv2.prenorm(t_raw, coef, -1.0, stats_groups=self.norm2.groups)
-
     def _stem_ok(self, x, x2):
         """conv1 and the 1x1 downsample convolution read the same few-channel input: one launch writes both raw maps (ops.stem_block)"""
         c1 = self.conv1
         return (x2 is None and self.has_ds and c1.sub is None and c1.stride == 1 and c1.cin <= 8 and c1.ks == (3, 3) and c1.pad == (1, 1)
                 and self.downsample[1].groups == self.norm1.groups and ops.stem_block_ok(x, c1.cout, self.norm1.groups))
 
+    def _shortcut(self, x, x2):
+        """the 1x1 shortcut convolution's raw map (its GroupNorm rides in the block's final pass); None for a block without one"""
+        if not self.has_ds:
+            return None
+        conv, norm = self.downsample[0], self.downsample[1]
+        return RawMap(*conv(x, x2=x2, stats_groups=norm.groups), norm)
+
     def forward(self, x, x2=None, defer_last=None):
         """defer_last = the 3x3 head convolution that will consume this block's output alone (Decoder2D.final_conv): when it can form
         GELU(GN2(y2)) + GN_ds(r) itself while staging (ops.conv2d_small_cout_norm2), the final apply pass is left to it and the pending
-        norms are handed on as ((y2, ws2, norm2), (r, ws_r, norm_ds)).  Returns x, or (x, pending) when defer_last is given (one of the
-        two is None)."""
-        kw1 = {} if x2 is None else {"x2": x2}
-        r = ws_r = None
+        norms are handed on as the RawMaps (y2, r).  Returns x, or (x, pending) when defer_last is given (one of the two is None)."""
+        short = None
         if self._stem_ok(x, x2):
             ds = self.downsample[0]
             t, ws1, r, ws_r = ops.stem_block(x, self.conv1._p["weight"], self.conv1._p.get("bias"), ds._p["weight"], ds._p.get("bias"), self.norm1.groups)
+            short = RawMap(r, ws_r, self.downsample[1])
         else:
-            t, ws1 = self.conv1(x, stats_groups=self.norm1.groups, **kw1)
-        pre = ws1 is not None and ops.CONV_MODE == "f16s" and self.conv2.prenorm_ok(t)
-        y2 = ws2 = None
+            t, ws1 = self.conv1(x, x2=x2, stats_groups=self.norm1.groups)
+        # conv2 applies GELU(GN1(t)) itself while it stages its input where it can, else norm1 runs as a pass.  The shortcut convolution
+        # is launched behind a conv2 that took the norm and ahead of a plain one (the order profiles/layer_library_refactor.md pins).
+        pre = ws1 is not None and self.conv2.prenorm_ok(t)
         if pre:
-            y2, ws2 = self._conv2(t, ws1)
-            conv2 = lambda **k: self.norm2(y2, act="gelu", ws=ws2, **k)                       # noqa: E731
+            y2 = RawMap(*self.conv2.prenorm(t, RawMap(t, ws1, self.norm1).coef(), -1.0, stats_groups=self.norm2.groups), self.norm2)
+            short = short or self._shortcut(x, x2)
         else:
             t = self.norm1(t, act="gelu", ws=ws1)
-            conv2 = lambda **k: conv_norm(self.conv2, self.norm2, t, act="gelu", **k)          # noqa: E731
-        done = (lambda out: out) if defer_last is None else (lambda out: (out, None))          # noqa: E731
-        if not self.residual:
-            return done(conv2())
-        if self.has_ds:
-            # the branch's GroupNorm rides in the final apply pass: GELU(GN2(conv2(t))) + GN_ds(conv1x1(x)) in one kernel
-            if r is None:
-                kw = {} if x2 is None else {"x2": x2}
-                r, ws_r = self.downsample[0](x, stats_groups=self.downsample[1].groups, **kw)
-            if (defer_last is not None and ws2 is not None and ws_r is not None and defer_last.sub is None
-                    and ops.small_cout_norm2_ok(y2, defer_last.cout, defer_last.ks[0], defer_last.ks[1], defer_last.stride, defer_last.pad)):
-                return None, ((y2, ws2, self.norm2), (r, ws_r, self.downsample[1]))
-            return done(conv2(res=r, res_mode="after_act", res_norm=(ws_r, self.downsample[1])))
-        assert x2 is None
-        return done(conv2(res=x, res_mode="after_act"))
+            short = short or self._shortcut(x, x2)
+            y2 = RawMap(*self.conv2(t, stats_groups=self.norm2.groups), self.norm2)
+        if (short is not None and defer_last is not None and pre and y2.ws is not None and short.ws is not None and defer_last.sub is None
+                and ops.small_cout_norm2_ok(y2.raw, defer_last.cout, defer_last.ks[0], defer_last.ks[1], defer_last.stride, defer_last.pad)):
+            return None, (y2, short)
+        assert not self.residual or self.has_ds or x2 is None
+        res = short if self.has_ds else x if self.residual else None          # added after the second GELU
+        out = y2.apply("gelu", res=res, res_mode="after_act")
+        return out if defer_last is None else (out, None)
 
 
 class SingleConv(Module):
@@ -603,12 +570,8 @@ class Decoder2D(Module):
                 x = layer(skip, x2=up(x))
         if pending is None:
             return self.final_conv(x)
-        coefs = []
-        for raw, ws, norm in pending:
-            B, C, H, W = raw.shape
-            coefs.append(ops.group_norm_coef(ws, norm._p["weight"], norm._p["bias"], norm.groups, B, C, H * W, norm.eps))
-        (y2, _, _), (r, _, _) = pending
-        return ops.conv2d_small_cout_norm2(y2, coefs[0], r, coefs[1], self.final_conv._p["weight"], self.final_conv._p.get("bias"))
+        y2, r = pending
+        return ops.conv2d_small_cout_norm2(y2.raw, y2.coef(), r.raw, r.coef(), self.final_conv._p["weight"], self.final_conv._p.get("bias"))
 
 
 # --------------------------------------------------------------------------------------------- transformers

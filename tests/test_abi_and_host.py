@@ -311,3 +311,117 @@ def test_wino_form_query_follows_the_route_level():
             assert ops.wino_form(2, 128, 0, 12, 32, 128) == (0 if level in (0, 4) else level if level > 1 else 2)   # H % 8 != 0: no NTW 4
     finally:
         h.cf_conv_wino_enable(prev)
+
+
+class _FakeTensor:
+    """what the route decisions read of a tensor: its shape, its element count and an aligned address"""
+
+    def __init__(self, *shape):
+        self.shape = shape
+
+    def numel(self):
+        n = 1
+        for v in self.shape:
+            n *= v
+        return n
+
+    def data_ptr(self):
+        return 0
+
+
+def test_packed_conv_direct_takes_the_small_kernels_for_a_plain_call_only(monkeypatch):
+    """convroute.PackedConv(direct=True) -- what nn.Conv2d builds -- sends a plain call of a 1 -> 32 3x3 stem to conv2d_small_cin and of a
+    64 -> 2 3x3 head to conv2d_small_cout; any one of x2 / act / out / alpha != 1 / an overriding bias / set_conv_mode("f32") sends it back
+    to the MFMA call.  res goes with small_cout only, stats_groups with small_cin only.  The same weights with direct=False (every other
+    user of PackedConv) never take a direct kernel.  Host logic only: fake tensors, the ops launch functions replaced by recorders."""
+    from cineflow import ops
+    from cineflow.convroute import PackedConv
+    calls = []
+    for name in ("conv2d_small_cin", "conv2d_small_cout", "conv2d_f16s", "conv2d", "conv2d_wino"):
+        monkeypatch.setattr(ops, name, lambda *a, _n=name, **k: calls.append((_n, a, k)) or _n)
+    monkeypatch.setattr(ops, "CONV_MODE", "f16s")
+    g = torch.Generator().manual_seed(0)
+    B, H, W = 2, 32, 48
+    layers = {"stem": (torch.randn(32, 1, 3, 3, generator=g), torch.randn(32, generator=g)),
+              "head": (torch.randn(2, 64, 3, 3, generator=g), torch.randn(2, generator=g))}
+    direct_of = {"stem": "conv2d_small_cin", "head": "conv2d_small_cout"}
+    for which, (w, b) in layers.items():
+        cout, cin = w.shape[:2]
+        conv = PackedConv(w, b, 1, (1, 1), wino=True, direct=True)
+        plain = PackedConv(w, b, 1, (1, 1), wino=True)
+        x, other = _FakeTensor(B, cin, H, W), _FakeTensor(B, cout, H, W)
+        assert conv(x) == direct_of[which]
+        name, a, k = calls[-1]
+        assert a[0] is x and a[1] is w and a[2] is b, "the direct kernels read the checkpoint layout and the layer's own bias"
+        back = [dict(x2=_FakeTensor(B, cin, H, W)), dict(act="relu"), dict(out=other), dict(alpha=0.5), dict(bias=None),
+                dict(bias=torch.zeros(cout))]
+        for kw in back:
+            assert conv(x, **kw) == "conv2d_f16s", (which, kw)
+        if which == "stem":
+            assert conv(x, stats_groups=8) == "conv2d_small_cin" and calls[-1][1][3] == 8
+            assert conv(x, stats_groups=128) == "conv2d_f16s"                        # more statistics groups than the direct kernel holds
+            assert conv(x, res=other) == "conv2d_f16s"
+        else:
+            assert conv(x, res=other) == "conv2d_small_cout" and calls[-1][1][3] is other
+            assert conv(x, stats_groups=2) == "conv2d_f16s"
+        for kw in [{}] + back + [dict(res=other), dict(stats_groups=8)]:
+            assert plain(x, **kw) == "conv2d_f16s", (which, kw)
+        monkeypatch.setattr(ops, "CONV_MODE", "f32")
+        assert conv(x) == "conv2d" and conv(x, stats_groups=8) == ("conv2d", None) and plain(x) == "conv2d"
+        monkeypatch.setattr(ops, "CONV_MODE", "f16s")
+    assert not [c for c in calls if c[0] == "conv2d_wino"]
+
+
+def test_packed_conv3d_asks_native_then_pointwise_and_packs_once_per_split(monkeypatch):
+    """convroute.PackedConv3d: the native kernel's probe is checked first and the pointwise one second, each for its own kernel shape (a
+    (1|3, 3, 3) layer asks ops.conv3d_f16s_ok alone; a (1, 1, 1) layer asks ops.conv3d_pw_f16s_ok alone, and only without x2); None when the
+    asked probe declines, when the shape is neither's, and under set_conv_mode("f32") (no probe is asked then).  The native packing is
+    made once per distinct split key, the pointwise one once.  Host logic only: fake tensors, probes and launches replaced by recorders."""
+    from cineflow import ops
+    from cineflow.convroute import PackedConv3d
+    log, answer = [], {"conv3d_f16s_ok": True, "conv3d_pw_f16s_ok": True}
+    for name in answer:
+        monkeypatch.setattr(ops, name, lambda *a, _n=name: log.append((_n, a)) or answer[_n])
+    for name in ("conv3d_f16s", "conv3d_pw_f16s"):
+        monkeypatch.setattr(ops, name, lambda *a, _n=name, **k: log.append((_n, a, k)) or _n)
+    monkeypatch.setattr(ops, "pack_conv3d_weight_f16s", lambda w, c1=None: log.append(("pack", c1)) or (("native", c1), 3))
+    monkeypatch.setattr(ops, "pack_conv3d_pw_weight_f16s", lambda w: log.append(("pack_pw",)) or ("pw", 5))
+    monkeypatch.setattr(ops, "CONV_MODE", "f16s")
+    names = lambda: [e[0] for e in log]          # noqa: E731
+    g = torch.Generator().manual_seed(0)
+    bias = torch.randn(8, generator=g)
+
+    conv = PackedConv3d(torch.randn(8, 32, 3, 3, 3, generator=g), bias, (1, 2, 2))
+    x, x24, x8 = _FakeTensor(2, 32, 4, 8, 8), _FakeTensor(2, 24, 4, 8, 8), _FakeTensor(2, 8, 4, 8, 8)
+    assert conv(x, None, 8) == "conv3d_f16s"
+    assert log[0] == ("conv3d_f16s_ok", (2, 32, 0, 4, 8, 8, 8, (3, 3, 3), (1, 2, 2))) and names() == ["conv3d_f16s_ok", "pack", "conv3d_f16s"]
+    name, a, k = log[-1]
+    assert a[0] is x and a[1:] == (("native", None), 3, bias, 8, (3, 3, 3), (1, 2, 2)) and k == dict(x2=None, stats_groups=8)
+    for x1, x2 in ((x24, x8), (x24, x8), (x, x8), (x, None)):          # split keys 24, 24, None (32 is whole chunks), None
+        assert conv(x1, x2) == "conv3d_f16s"
+    assert [e for e in log if e[0] == "pack"] == [("pack", None), ("pack", 24)]
+    assert log[-1][1][1] == ("native", None) and "conv3d_pw_f16s_ok" not in names()
+    del log[:]
+    answer["conv3d_f16s_ok"] = False
+    assert conv(x) is None and names() == ["conv3d_f16s_ok"]            # declined: the pointwise probe is not for this kernel shape
+    monkeypatch.setattr(ops, "CONV_MODE", "f32")
+    answer["conv3d_f16s_ok"] = True
+    assert conv(x) is None and names() == ["conv3d_f16s_ok"]            # nothing more was asked
+    monkeypatch.setattr(ops, "CONV_MODE", "f16s")
+
+    del log[:]
+    pw = PackedConv3d(torch.randn(8, 32, 1, 1, 1, generator=g), None, (2, 2, 2))
+    assert pw(x, None, 8) == "conv3d_pw_f16s" and pw(x) == "conv3d_pw_f16s"
+    assert names() == ["conv3d_pw_f16s_ok", "pack_pw", "conv3d_pw_f16s", "conv3d_pw_f16s_ok", "conv3d_pw_f16s"]
+    assert log[0][1] == (2, 32, 4, 8, 8, 8, (2, 2, 2))
+    assert log[2][1][1:] == ("pw", 5, None, 8, (2, 2, 2)) and log[2][2] == dict(stats_groups=8)
+    del log[:]
+    assert pw(x24, x8) is None and names() == []                        # cat[x, x2]: the pointwise kernel reads one input
+    answer["conv3d_pw_f16s_ok"] = False
+    assert pw(x) is None and names() == ["conv3d_pw_f16s_ok"]
+    answer["conv3d_pw_f16s_ok"] = True
+    monkeypatch.setattr(ops, "CONV_MODE", "f32")
+    assert pw(x) is None and names() == ["conv3d_pw_f16s_ok"]
+    monkeypatch.setattr(ops, "CONV_MODE", "f16s")
+    del log[:]
+    assert PackedConv3d(torch.randn(8, 32, 3, 1, 1, generator=g), None, (1, 1, 1))(x) is None and names() == []      # neither kernel's shape
