@@ -54,6 +54,7 @@ SIGNATURES = {
     "cf_norm_head_1x1": [P, P, F, P, P, P, I, I, I, I, P],
     "cf_conv2d_f16s_prenorm_ok": [I, I, I, I, I],
     "cf_conv_stream_enable": [I],
+    "cf_conv2d_f16s_route": [I] * 16 + [P],
     "cf_conv2d_f16s_prenorm": [P, I, P, F, P, P, P, I, I, I, I, F, P, I, P],
     "cf_conv_terms": [I],
     "cf_conv_wino_enable": [I],

@@ -4,7 +4,9 @@ PyTorch is used for device memory (torch.empty on the caching allocator) and the
 number is produced by a hand-written HIP kernel in libcineflow_hip.so.  Inputs must be CUDA(=HIP) tensors; nothing
 here runs on the CPU and nothing falls back to torch operators.
 """
+import collections
 import contextlib
+import ctypes
 import math
 import os
 
@@ -387,6 +389,23 @@ def conv2d_f16s(x1, wpk, wscale, bias, cout, kh, kw, stride=1, pad=(0, 0), x2=No
                                cout, kh, kw, stride, pad[0], pad[1], ACT[act], float(alpha) * (2.0 ** -wscale),
                                ws_ptr, ws_groups, _stream()), "cf_conv2d_f16s")
     return (out, ws) if stats_groups else out
+
+
+F16sRoute = collections.namedtuple("F16sRoute", "route tup terms nimg fused part")
+
+
+def conv2d_f16s_route(x1, cout, kh, kw, stride=1, pad=(0, 0), x2=None, prenorm=False, transposed=False, stats_groups=None):
+    """The plan conv2d_f16s (conv2d_f16s_prenorm with prenorm=True, conv_transpose2d_k2s2_f16s with transposed=True) executes for a plain
+    call on these tensors in the current conv_terms mode (cf_conv2d_f16s_route; host code, launches nothing): route 0 declined / 1
+    conv_f16s_kernel / 2 conv_stream_kernel, tup = the instantiation <KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL> (route 1), TERMS, images
+    per workgroup, whether the epilogue accumulates the statistics, samples per launch."""
+    B, C1, H, W = x1.shape
+    C2 = 0 if x2 is None else x2.shape[1]
+    plan = (ctypes.c_int * 15)()
+    route = lib().cf_conv2d_f16s_route(B, C1, C2, H, W, cout, kh, kw, stride, pad[0], pad[1], x1.data_ptr() & 15,
+                                       0 if x2 is None else x2.data_ptr() & 15, int(prenorm), int(transposed), stats_groups or 0, plan)
+    check(min(route, 0), "cf_conv2d_f16s_route")
+    return F16sRoute(route, tuple(plan[1:11]), plan[11], plan[12], bool(plan[13]), plan[14])
 
 
 # ---- 3-D convolution (conv3d_f16s.hip) -----------------------------------------------------------------------------------

@@ -27,7 +27,6 @@ struct ConvParams {
     float in_slope = 1.0f;   // LeakyReLU slope; in_slope < 0 selects GELU (erf form) instead
     int terms = 3;          // f16-split kernels: 3 = hi/lo split, three MFMAs per k-step (f32-class, the default); 1 = hi x hi only ("mixed precision":
                             // operands rounded to fp16, fp32 accumulation -- the segmentation path under mixed_precision=True, cf_conv_terms)
-    int probe = 0;          // 1: run the dispatch and its checks only, launch nothing (capability query)
     int profile_kid = -1;   // >= 0: time this launch under that profile id with `profile_work` instead of the conv's own id / flops
     double profile_work = 0.0;
 };

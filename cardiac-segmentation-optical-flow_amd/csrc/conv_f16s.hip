@@ -27,6 +27,8 @@
 //   * wave tile: one 32-channel m-tile x NTW n-tiles of 32 pixels, one fp32 accumulator per tile.
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
+#include <string.h>
+#include <algorithm>
 
 #include "conv.h"
 #include "profile.h"
@@ -565,7 +567,7 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
     // Stores go through a buffer resource over the NIMG output samples of this workgroup: one 32-bit add per store, and a pixel outside the
     // tile / a channel beyond Cout is an out-of-range offset (the store is dropped by the range check) instead of a branch around the store
     // and a 64-bit address per element.  Two parking values so that "both invalid" cannot wrap back into range; the host keeps
-    // NIMG x (output sample bytes) below 1 GiB (launch_f16s_v).
+    // NIMG x (output sample bytes) below 1 GiB (f16s_finish).
     constexpr unsigned OOB_PX = 0x80000000u, OOB_CH = 0x40000000u;
     const unsigned up4 = p.scatter2x2 ? 4u : 1u;
     const unsigned osample = (unsigned)p.out_ctotal * (unsigned)HoWo * up4;                    // elements per output sample
@@ -680,138 +682,53 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Host half: the table of built instantiations (CF_F16S_SHAPES), the plan (f16s_plan: pure host arithmetic naming route, table row, geometry,
+// grid and LDS size of one launch, or why it is declined) and the launcher that executes a plan (launch_conv_f16s_part).  The queries
+// cf_conv2d_f16s_prenorm_ok and cf_conv2d_f16s_route ask the plan; nothing else decides.
+
 // cf_conv_terms: per-thread product mode of the f16-split convolutions launched from this thread (3 = hi/lo split, 1 = hi x hi only)
 static thread_local int t_conv_terms = 3;
 int conv_terms() { return t_conv_terms; }
 
-template <int KH, int KW, int CK, int WM, int NTW, int MAXT, int NW, int VEC, int PRE = 0, int WL = 0>
-static int launch_f16s_v(const ConvParams& p, F16sGeom g, const _Float16* wpk, hipStream_t s);
+// Every <KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL> that is built, each with TERMS = 3 and 1: the plan can only name a row of this table,
+// and the launch functions are instantiated from it and from nothing else.
+//   VEC: 1 for the 3x3 shapes (one 4x4 task per staging thread); the 1x5 / 5x1 shapes (CK = 32, wider patches) take 2.  1x1 layers measured
+//        6-17 % slower with it -- their scalar loads are already whole rows -- so spatial kernels only; the stride-2 3x3 shapes, MAXT 3 and
+//        5, never qualify at run time (two tasks per thread for their (2 TH + 1) x (2 TW + 1) patches: equal or 2 % slower, not built).
+//   PRE: the stride-1 3x3 four-wave shapes are also built with the deferred input normalisation; not the 8-wave shape of the small maps
+//        (< 1024 workgroups): its short workgroups lose more to the table fill + barrier than the apply pass costs (256 channels at 32x32,
+//        B = 32: 192 us vs 120 + 15 us, tools/prenorm_ab.py).
+#define CF_F16S_SHAPES(X)                                                                                                                \
+    /* 3x3 stride 1: weights through LDS (8 waves, 256 pixels); register fragments, 4 waves x 32 / 64 / 128 channels; 128 channels, 8 waves */ \
+    X(3, 3, 16, 1, 1, 2, 8, 1, 0, 1) X(3, 3, 16, 1, 1, 2, 8, 1, 1, 1) X(3, 3, 16, 2, 2, 2, 8, 1, 0, 1) X(3, 3, 16, 2, 2, 2, 8, 1, 1, 1)  \
+    X(3, 3, 16, 1, 1, 2, 4, 0, 0, 0) X(3, 3, 16, 1, 1, 2, 4, 1, 0, 0) X(3, 3, 16, 1, 1, 2, 4, 1, 1, 0) X(3, 3, 16, 2, 2, 2, 4, 0, 0, 0)  \
+    X(3, 3, 16, 2, 2, 2, 4, 1, 0, 0) X(3, 3, 16, 2, 2, 2, 4, 1, 1, 0) X(3, 3, 16, 4, 4, 2, 4, 0, 0, 0) X(3, 3, 16, 4, 4, 2, 4, 1, 0, 0)  \
+    X(3, 3, 16, 4, 4, 2, 4, 1, 1, 0) X(3, 3, 16, 4, 2, 2, 8, 0, 0, 0) X(3, 3, 16, 4, 2, 2, 8, 1, 0, 0)                                   \
+    /* 3x3 stride 2; 1x1 (also the transposed 2x2 convolution's GEMM); 1x5 / 5x1 of the SepConvGRU */                                    \
+    X(3, 3, 16, 1, 1, 5, 4, 0, 0, 0) X(3, 3, 16, 2, 1, 3, 4, 0, 0, 0) X(3, 3, 16, 4, 2, 3, 4, 0, 0, 0)                                   \
+    X(1, 1, 32, 1, 1, 2, 4, 0, 0, 0) X(1, 1, 32, 2, 2, 2, 4, 0, 0, 0) X(1, 1, 32, 4, 4, 2, 4, 0, 0, 0) X(1, 1, 32, 4, 2, 2, 8, 0, 0, 0)  \
+    X(1, 5, 32, 2, 2, 4, 4, 0, 0, 0) X(1, 5, 32, 2, 2, 4, 4, 2, 0, 0) X(1, 5, 32, 4, 2, 4, 8, 0, 0, 0) X(1, 5, 32, 4, 2, 4, 8, 2, 0, 0)  \
+    X(5, 1, 32, 2, 2, 4, 4, 0, 0, 0) X(5, 1, 32, 2, 2, 4, 4, 2, 0, 0) X(5, 1, 32, 4, 2, 4, 8, 0, 0, 0) X(5, 1, 32, 4, 2, 4, 8, 2, 0, 0)
 
-// picks the vector-staging instantiation when the layer qualifies (stride 1, W % 4 == 0, 16-byte aligned inputs, VT 4x4 tasks per
-// staging thread), else the scalar one.  VT = 1 for the 3x3 shapes; the 1x5 / 5x1 shapes (CK = 32, wider patches) take VT = 2.
-template <int KH, int KW, int CK, int WM, int NTW, int MAXT, int NW = 4>
-static int launch_f16s(const ConvParams& p, F16sGeom g, const _Float16* wpk, hipStream_t s) {
-    constexpr int KHW = KH * KW;
-    g.NQ = 0;
-    // (1x1 layers measured 6-17 % slower with it -- their scalar loads are already whole rows -- so spatial kernels only; the stride-2
-    // 3x3 shapes, MAXT 3 and 5, never qualify at run time and are not built with it)
-    if constexpr (KHW > 1 && !(KHW == 9 && MAXT > 2)) {
-    if (p.stride == 1 && (p.W & 3) == 0 && (g.TW & 3) == 0 &&
-        ((reinterpret_cast<uintptr_t>(p.x1) | reinterpret_cast<uintptr_t>(p.x2)) & 15) == 0) {
-        const int a = (-p.pad_w) & 3;                       // ix_org mod 4 (tile origins are multiples of 4)
-        const int nq = ((a + g.PW - 1) >> 2) + 1;
-        const int tasks = (CK / 4) * g.NIMG * g.PH * nq;
-        g.NQ = nq;
-        if constexpr (KHW == 9) {
-            if (tasks <= 64 * NW) {
-                // the stride-1 3x3 four-wave shapes are also built with the deferred input normalisation; not the 8-wave shape of the small
-                // maps (< 1024 workgroups): its short workgroups lose more to the table fill + barrier than the apply pass costs
-                // (256 channels at 32x32, B = 32: 192 us vs 120 + 15 us, tools/prenorm_ab.py)
-                if constexpr (MAXT == 2 && NW == 4) {
-                    if (p.in_norm && g.NIMG == 1 && p.C2 == 0 && (reinterpret_cast<uintptr_t>(p.in_norm) & 3) == 0)
-                        return launch_f16s_v<KH, KW, CK, WM, NTW, MAXT, NW, 1, 1>(p, g, wpk, s);
-                }
-                if (p.in_norm) { set_error("conv_f16s: deferred input normalisation is not built for this layer shape"); return CF_ERR_ARG; }
-                return launch_f16s_v<KH, KW, CK, WM, NTW, MAXT, NW, 1>(p, g, wpk, s);
-            }
-            // (two tasks per thread for the (2 TH + 1) x (2 TW + 1) patches of the stride-2 shapes: measured equal or 2 % slower, not built)
-        } else if constexpr (KHW > 1) {
-            if (!p.in_norm && tasks <= 2 * 64 * NW) return launch_f16s_v<KH, KW, CK, WM, NTW, MAXT, NW, 2>(p, g, wpk, s);
-        }
-        g.NQ = 0;
-    }
-    }
-    if (p.in_norm) { set_error("conv_f16s: deferred input normalisation needs the vector staging path (3x3, stride 1, W % 4 == 0)"); return CF_ERR_ARG; }
-    return launch_f16s_v<KH, KW, CK, WM, NTW, MAXT, NW, 0>(p, g, wpk, s);
-}
+struct F16sShape { int KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL; };
+#define CF_F16S_ROW(...) {__VA_ARGS__},
+static constexpr F16sShape k_f16s_shapes[] = {CF_F16S_SHAPES(CF_F16S_ROW)};
+#undef CF_F16S_ROW
 
-template <int KH, int KW, int CK, int WM, int NTW, int MAXT, int NW, int VEC, int PRE, int WL>
-static int launch_f16s_v(const ConvParams& p, F16sGeom g, const _Float16* wpk, hipStream_t s) {
-    constexpr int REC = CK * 4 + 16;
-    constexpr int WGRP = (KH * KW == 9) ? 3 : ((KH * KW == 1) ? CK / 16 : 5);      // k-steps per LDS weight slot (kernel: G)
-    constexpr int NSTAGE = 64 * NW;
-    const int nrec = g.NIMG * g.PH * g.PW;
-#ifdef CF_F16S_ABLATION_BUILD
-    { static int ab = -1; if (ab < 0) { const char* e = getenv("CF_F16S_ABLATE"); ab = e ? atoi(e) : 0; } g.ablate = ab; }
-#else
-    g.ablate = 0;
-#endif
-    g.m_tx = f16s_magic(g.tiles_x);
-    g.m_ty = f16s_magic(g.tiles_y);
-    g.m_percg = f16s_magic(g.NIMG * g.PH * g.NQ);
-    g.m_phnq = f16s_magic(g.PH * g.NQ);
-    g.m_nq = f16s_magic(g.NQ);
-    g.m_nrec = f16s_magic(nrec);
-    g.m_phpw = f16s_magic(g.PH * g.PW);
-    g.m_pw = f16s_magic(g.PW);
-    g.m_thtw = f16s_magic(g.TH * g.TW);
-    g.m_tw = f16s_magic(g.TW);
-    if ((long)g.tiles_x * g.tiles_y * g.bgroups >= (1L << 31) / (g.tiles_x > g.tiles_y ? g.tiles_x : g.tiles_y)) {
-        set_error("conv_f16s: grid too large for the index decode");
-        return CF_ERR_ARG;
-    }
-    if (!VEC && (nrec * (CK / 8) + NSTAGE - 1) / NSTAGE > MAXT) {
-        set_error("conv_f16s: staging tasks exceed MAXT");
-        return CF_ERR_ARG;
-    }
-    size_t lds_bytes = (size_t)2 * g.NIMG * g.PH * g.PWR * REC + (PRE ? (size_t)3 * g.nchunk * CK * sizeof(float) : 0) +
-                             (WL ? (size_t)2 * WM * WGRP * 2 * 1024 : 0);
-    if (p.gn_ws && lds_bytes < (size_t)WM * 64 * sizeof(double)) lds_bytes = (size_t)WM * 64 * sizeof(double);   // the statistics epilogue's fp64 totals
-#ifdef CF_F16S_ABLATION_BUILD
-    { static long pad = -1; if (pad < 0) { const char* e = getenv("CF_F16S_LDSPAD"); pad = e ? atol(e) : 0; }   // timing builds: fewer resident workgroups
-      if (pad > (long)lds_bytes) lds_bytes = (size_t)pad; }
-#endif
-    if ((double)g.NIMG * p.out_ctotal * p.Ho * p.Wo * (p.scatter2x2 ? 4.0 : 1.0) * 4.0 >= 1073741824.0) {
-        set_error("conv_f16s: one workgroup's output samples must stay below 1 GiB (32-bit store offsets)");
-        return CF_ERR_ARG;
-    }
-    if (lds_bytes > 160 * 1024) {
-        set_error("conv_f16s: LDS tile too large");
-        return CF_ERR_ARG;
-    }
-    if (p.probe) return CF_OK;
-    auto kern = p.terms == 1 ? conv_f16s_kernel<KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL, 1> : conv_f16s_kernel<KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL, 3>;
-    static bool attr_set[64][2] = {};       // per device and variant
-    const int dev = current_device_slot();
-    if (!attr_set[dev][p.terms == 1]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set[dev][p.terms == 1] = true;
-    }
-    dim3 grid((unsigned)(g.tiles_x * g.tiles_y * g.bgroups), (unsigned)((p.Cout + 32 * WM - 1) / (32 * WM)));
-    dim3 block(64 * NW);
-    const double flops = 2.0 * (double)p.B * p.Ho * p.Wo * p.Cout * (p.C1 + p.C2) * p.KH * p.KW;
-    hipEvent_t e0, e1;
-    if (profile_on() && profile_events(PK_CONV_F16S, flops, &e0, &e1))
-        hipExtLaunchKernelGGL(kern, grid, block, lds_bytes, s, e0, e1, 0, p, g, wpk);
-    else
-        hipLaunchKernelGGL(kern, grid, block, lds_bytes, s, p, g, wpk);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string("conv_f16s launch failed: ") + hipGetErrorString(e));
-        return CF_ERR_LAUNCH;
-    }
-    return CF_OK;
-}
+enum { F16S_DECLINED = 0, F16S_KERNEL = 1, F16S_STREAM = 2 };
 
-// The weights-through-LDS shapes (3x3, stride 1, vector staging, one sample per workgroup, 8 waves).  Returns -1 when the layer does not
-// qualify (the caller then takes the register-fragment shapes).
-template <int WM, int NTW>
-static int launch_f16s_wl(const ConvParams& p, F16sGeom g, const _Float16* wpk, hipStream_t s, bool* probe_single) {
-    constexpr int CK = 16, NW = 8;
-    if (!(p.stride == 1 && (p.W & 3) == 0 && (g.TW & 3) == 0 && g.NIMG == 1 &&
-          ((reinterpret_cast<uintptr_t>(p.x1) | reinterpret_cast<uintptr_t>(p.x2)) & 15) == 0))
-        return -1;
-    const int a = (-p.pad_w) & 3;
-    const int nq = ((a + g.PW - 1) >> 2) + 1;
-    if ((CK / 4) * g.NIMG * g.PH * nq > 64 * NW) return -1;
-    g.NQ = nq;
-    if (probe_single) { *probe_single = true; return CF_OK; }      // geometry probe: the layer takes this shape, one sample per workgroup
-    if (p.in_norm) {
-        if (p.C2 != 0 || (reinterpret_cast<uintptr_t>(p.in_norm) & 3) != 0) return -1;
-        return launch_f16s_v<3, 3, CK, WM, NTW, 2, NW, 1, 1, 1>(p, g, wpk, s);
-    }
-    return launch_f16s_v<3, 3, CK, WM, NTW, 2, NW, 1, 0, 1>(p, g, wpk, s);
-}
+// What one launch on a (sub-)batch will be: a pure function of the ConvParams (pointers are read for their alignment, never dereferenced;
+// p.terms is this thread's product mode) and of the cf_conv_stream_enable level.
+struct F16sPlan {
+    int route = F16S_DECLINED;
+    int shape = -1;              // F16S_KERNEL: row of k_f16s_shapes
+    F16sGeom g = {};             // F16S_KERNEL: the kernel's geometry argument, complete
+    unsigned grid_x = 0, grid_y = 0;
+    size_t lds_bytes = 0;        // dynamic LDS of the launch
+    bool fusable = false;        // the epilogue can accumulate the GroupNorm statistics: one sample per workgroup, or the stream route
+    const char* why = nullptr;   // F16S_DECLINED: the message for set_error
+};
+static F16sPlan f16s_declined(const char* why) { F16sPlan pl; pl.why = why; return pl; }
 
 // kernel shapes of the f16-split kernel: 3x3 pad 1 and 1x1 pad 0 at stride 1 / 2, and the separable 1x5 (pad 0,2) / 5x1 (pad 2,0)
 // convolutions of RAFT's SepConvGRU at stride 1
@@ -823,13 +740,14 @@ static int f16s_kind(const ConvParams& p) {
     return 0;
 }
 
-// One sample of each input must stay below 2 GiB (32-bit buffer offsets); larger batches are split by launch_conv_f16s itself.
+// The argument-level gate.  One sample of each input must stay below 2 GiB (32-bit buffer offsets); larger batches are split by f16s_parts.
 bool conv_f16s_supported(const ConvParams& p) {
     if (p.w_bstride) return false;
     if (!f16s_kind(p)) return false;
     const long HW = (long)p.H * p.W;
     if ((long)p.C1 * HW * 4 >= (1L << 31) || (long)p.C2 * HW * 4 >= (1L << 31)) return false;
-    // the epilogue's buffer-resource stores address the output samples of one workgroup with 32-bit offsets below 1 GiB (launch_f16s_v):
+    // the epilogue's buffer-resource stores address the output samples of one workgroup with 32-bit offsets below 1 GiB (f16s_finish
+    // checks the same with the plan's own images per workgroup: a backstop, no exported call gets past this gate with more):
     // up to 8 whole images per workgroup when an image fits one tile (<= 256 pixels), else one
     const double osample = (double)p.out_ctotal * p.Ho * p.Wo * (p.scatter2x2 ? 4.0 : 1.0) * 4.0;
     if (osample * ((long)p.Ho * p.Wo <= 256 ? 8.0 : 1.0) >= 1073741824.0) return false;
@@ -842,97 +760,84 @@ bool conv_f16s_supported(const ConvParams& p) {
 // weights whose stores the epilogue drops.
 static bool f16s_cout_wide(int cout) { return cout % 128 == 0 || (cout > 128 && cout % 128 >= 96); }
 
-static int launch_conv_f16s_impl(const ConvParams& p, const _Float16* wpk, hipStream_t s, bool* one_sample_per_wg);
+// a deferred input normalisation beside the conditions of vector staging: a single input and a 4-byte aligned table
+static bool f16s_pre_ok(const ConvParams& p) { return p.C2 == 0 && (reinterpret_cast<uintptr_t>(p.in_norm) & 3) == 0; }
 
-// Runs the convolution on a batch whose inputs fit 32-bit buffer offsets; when p.gn_ws is set the workspace ends up holding the
-// GroupNorm statistics of the output -- from the fused epilogue when every workgroup covers a single sample, otherwise from the
-// separate statistics pass.
-static int launch_conv_f16s_part(const ConvParams& p, const _Float16* wpk, hipStream_t s) {
+// 16-byte column quads per patch row when the layer qualifies for vector staging (stride 1, W % 4 == 0, tile columns in whole quads,
+// 16-byte aligned inputs), else 0
+static int f16s_quads(const ConvParams& p, const F16sGeom& g) {
+    if (p.stride != 1 || (p.W & 3) || (g.TW & 3) || ((reinterpret_cast<uintptr_t>(p.x1) | reinterpret_cast<uintptr_t>(p.x2)) & 15)) return 0;
+    const int a = (-p.pad_w) & 3;                       // ix_org mod 4 (tile origins are multiples of 4)
+    return ((a + g.PW - 1) >> 2) + 1;
+}
+
+// The staging form of a register-fragment shape: vector staging (t.VEC, g.NQ) when the layer qualifies and its 4x4 tasks fit VEC per staging
+// thread, else scalar; the deferred input normalisation (t.PRE) where it is built.  Returns the reason when p.in_norm cannot be served.
+static const char* f16s_staging(const ConvParams& p, F16sShape& t, F16sGeom& g) {
+    const int KHW = t.KH * t.KW;
+    const int nq = (KHW > 1 && !(KHW == 9 && t.MAXT > 2)) ? f16s_quads(p, g) : 0;       // CF_F16S_SHAPES: which shapes have a vector form
+    const int tasks = (t.CK / 4) * g.NIMG * g.PH * nq;
+    if (nq && KHW == 9 && tasks <= 64 * t.NW) {
+        g.NQ = nq; t.VEC = 1; t.PRE = p.in_norm ? 1 : 0;
+        const bool pre_built = t.MAXT == 2 && t.NW == 4 && g.NIMG == 1 && f16s_pre_ok(p);
+        return p.in_norm && !pre_built ? "conv_f16s: deferred input normalisation is not built for this layer shape" : nullptr;
+    }
+    if (p.in_norm) return "conv_f16s: deferred input normalisation needs the vector staging path (3x3, stride 1, W % 4 == 0)";
+    if (nq && KHW != 9 && tasks <= 2 * 64 * t.NW) { g.NQ = nq; t.VEC = 2; }
+    return nullptr;
+}
+
+// Completes the plan of a chosen shape: the table row, the index-decode multipliers, every limit of the kernel, LDS size and grid.
+static F16sPlan f16s_finish(const ConvParams& p, const F16sShape& t, F16sGeom g) {
+    F16sPlan pl;
+    for (int i = 0; i < (int)(sizeof(k_f16s_shapes) / sizeof(F16sShape)) && pl.shape < 0; ++i)
+        if (memcmp(&k_f16s_shapes[i], &t, sizeof(F16sShape)) == 0) pl.shape = i;
+    if (pl.shape < 0) return f16s_declined("conv_f16s: the dispatch named a kernel shape that is not built");
+    const int REC = t.CK * 4 + 16;
+    const int WGRP = (t.KH * t.KW == 9) ? 3 : ((t.KH * t.KW == 1) ? t.CK / 16 : 5);      // k-steps per LDS weight slot (kernel: G)
+    const int NSTAGE = 64 * t.NW;
+    const int nrec = g.NIMG * g.PH * g.PW;
+    g.m_tx = f16s_magic(g.tiles_x);
+    g.m_ty = f16s_magic(g.tiles_y);
+    g.m_percg = f16s_magic(g.NIMG * g.PH * g.NQ);
+    g.m_phnq = f16s_magic(g.PH * g.NQ);
+    g.m_nq = f16s_magic(g.NQ);
+    g.m_nrec = f16s_magic(nrec);
+    g.m_phpw = f16s_magic(g.PH * g.PW);
+    g.m_pw = f16s_magic(g.PW);
+    g.m_thtw = f16s_magic(g.TH * g.TW);
+    g.m_tw = f16s_magic(g.TW);
+    if ((long)g.tiles_x * g.tiles_y * g.bgroups >= (1L << 31) / (g.tiles_x > g.tiles_y ? g.tiles_x : g.tiles_y))
+        return f16s_declined("conv_f16s: grid too large for the index decode");
+    if (!t.VEC && (nrec * (t.CK / 8) + NSTAGE - 1) / NSTAGE > t.MAXT) return f16s_declined("conv_f16s: staging tasks exceed MAXT");
+    pl.fusable = g.NIMG == 1;
+    pl.lds_bytes = (size_t)2 * g.NIMG * g.PH * g.PWR * REC + (t.PRE ? (size_t)3 * g.nchunk * t.CK * sizeof(float) : 0) +
+                   (t.WL ? (size_t)2 * t.WM * WGRP * 2 * 1024 : 0);
+    const size_t stats_lds = (size_t)t.WM * 64 * sizeof(double);      // the statistics epilogue's fp64 totals
+    if (p.gn_ws && pl.fusable && pl.lds_bytes < stats_lds) pl.lds_bytes = stats_lds;
+    if ((double)g.NIMG * p.out_ctotal * p.Ho * p.Wo * (p.scatter2x2 ? 4.0 : 1.0) * 4.0 >= 1073741824.0)
+        return f16s_declined("conv_f16s: one workgroup's output samples must stay below 1 GiB (32-bit store offsets)");
+    if (pl.lds_bytes > 160 * 1024) return f16s_declined("conv_f16s: LDS tile too large");
+    pl.route = F16S_KERNEL;
+    pl.g = g;
+    pl.grid_x = (unsigned)(g.tiles_x * g.tiles_y * g.bgroups), pl.grid_y = (unsigned)((p.Cout + 32 * t.WM - 1) / (32 * t.WM));
+    return pl;
+}
+
+// The plan of one launch on a batch whose inputs fit 32-bit buffer offsets (conv_f16s_supported(p) holds; f16s_parts cuts larger batches).
+static F16sPlan f16s_plan(const ConvParams& p) {
     // short-K layers on large maps (<= 64 output channels, 3x3, stride 1, >= 1024 tiles): the persistent pipelined kernel of conv_stream.hip,
     // same arithmetic and packed weights (CF_CONV_STREAM=0 keeps this file's shapes: A/B knob)
-    if (conv_stream_applicable(p)) {
-        if (p.probe) return CF_OK;
-        if (p.gn_ws && !p.gn_prezeroed &&
-            hipMemsetAsync(p.gn_ws, 0, sizeof(double) * 2 * (size_t)p.B * p.gn_groups, s) != hipSuccess) { set_error("conv_stream: memset failed"); return CF_ERR_LAUNCH; }
-        return launch_conv_stream(p, wpk, s);
-    }
-    if (!p.gn_ws) return launch_conv_f16s_impl(p, wpk, s, nullptr);
-    bool fusable = false;
-    launch_conv_f16s_impl(p, nullptr, s, &fusable);  // geometry probe only
-    ConvParams q = p;
-    // (the transposed convolution's scatter qualifies too: its GEMM rows are co * 4 + dy * 2 + dx, so a group of Cout / groups output
-    // channels is a run of 4 * Cout / groups consecutive rows -- the same `co / cpg` with cpg = p.Cout / groups = 4 * Cout / groups)
-    if (fusable) {
-        // the fused statistics accumulate with atomics: the workspace must start at zero (gn_prezeroed: the caller hands out slices
-        // of a pool it zeroed with ONE memset -- the per-launch memsets were 1.2 % of the step)
-        if (!p.gn_prezeroed &&
-            hipMemsetAsync(p.gn_ws, 0, sizeof(double) * 2 * (size_t)p.B * p.gn_groups, s) != hipSuccess) { set_error("conv_f16s: memset failed"); return CF_ERR_LAUNCH; }
-        return launch_conv_f16s_impl(q, wpk, s, nullptr);
-    }
-    q.gn_ws = nullptr;
-    int rc = launch_conv_f16s_impl(q, wpk, s, nullptr);
-    if (rc != CF_OK) return rc;
-    const int up = p.scatter2x2 ? 2 : 1;
-    const int cout = p.scatter2x2 ? p.Cout / 4 : p.Cout;
-    if (p.out_coff != 0 || p.out_ctotal != cout) { set_error("conv_f16s: GroupNorm statistics need a dense output tensor"); return CF_ERR_ARG; }
-    return launch_gn_stats(p.out, p.gn_ws, p.B, cout, p.Ho * up * p.Wo * up, p.gn_groups, s);
-}
-
-// The kernel addresses its inputs with 32-bit buffer offsets (< 2 GiB per descriptor).  A batch whose input tensors are larger is
-// cut into sub-batches HERE (same kernel, same numbers, a few more launches) instead of being handed to another kernel: the batch
-// axis is the outermost one of every operand, so a sub-batch is a pointer offset.
-// Samples per sub-batch: the batch is cut into the FEWEST parts that fit and the parts are made equal (the last one at most parts - 1
-// samples smaller) -- a greedy cut could leave a remainder of one sample, for which the dispatch picks another kernel shape than for the
-// large parts (one that e.g. lacks the deferred input normalisation although the capability probe, asked with the whole batch, said yes).
-static long f16s_sub_batch(const ConvParams& p) {
-    const long HW = (long)p.H * p.W;
-    const long per1 = (long)p.C1 * HW * 4, per2 = (long)p.C2 * HW * 4;
-    const long lim = (1L << 31) - 1;
-    const long nb = lim / (per1 > per2 ? per1 : per2);
-    if (nb < 1) return 0;
-    if (p.B <= nb) return p.B;
-    const long parts = (p.B + nb - 1) / nb;
-    return (p.B + parts - 1) / parts;
-}
-
-int launch_conv_f16s(const ConvParams& p, const _Float16* wpk, hipStream_t s) {
-    if (conv_stream_applicable(p)) return launch_conv_f16s_part(p, wpk, s);      // per-sample buffer resources: no 2 GiB limit on the batch
-    const long HW = (long)p.H * p.W;
-    const long nb = f16s_sub_batch(p);
-    if (nb < 1) { set_error("conv_f16s: one sample of the input exceeds 2 GiB"); return CF_ERR_ARG; }
-    if (p.B <= nb) return launch_conv_f16s_part(p, wpk, s);
-    const int up = p.scatter2x2 ? 2 : 1;
-    const long HoWo = (long)p.Ho * p.Wo;
-    for (long b0 = 0; b0 < p.B; b0 += nb) {
-        ConvParams q = p;
-        q.B = (int)(p.B - b0 < nb ? p.B - b0 : nb);
-        q.x1 = p.x1 + b0 * p.C1 * HW;
-        if (p.x2) q.x2 = p.x2 + b0 * p.C2 * HW;
-        if (p.res) q.res = p.res + b0 * p.Cout * HoWo;
-        q.out = p.out + b0 * p.out_ctotal * HoWo * up * up;
-        if (p.gn_ws) q.gn_ws = p.gn_ws + 2 * b0 * p.gn_groups;
-        if (p.in_norm) q.in_norm = p.in_norm + b0 * 3 * p.C1;
-        int rc = launch_conv_f16s_part(q, wpk, s);
-        if (rc != CF_OK) return rc;
-    }
-    return CF_OK;
-}
-
-static int launch_conv_f16s_impl(const ConvParams& p, const _Float16* wpk, hipStream_t s, bool* one_sample_per_wg) {
+    if (conv_stream_applicable(p)) { F16sPlan pl; pl.route = F16S_STREAM; pl.fusable = true; return pl; }
     const int kind = f16s_kind(p);
-    const bool k3 = kind == 33;
-    const bool sep = kind == 15 || kind == 51;           // 1x5 / 5x1
-    const bool spatial = k3 || sep;
+    const bool k3 = kind == 33, sep = kind == 15 || kind == 51, spatial = k3 || sep;      // sep: 1x5 / 5x1
     const int CK = k3 ? 16 : 32;
-    const bool narrow = p.Cout <= 32;
-    const bool s2 = k3 && p.stride == 2;
+    const bool narrow = p.Cout <= 32, s2 = k3 && p.stride == 2;
     // Cout = 3 x 128 + 96 and the like ride on the 128-channel shapes with a partly empty last m-tile -- where the four-wave shape runs
     // (>= 1024 workgroups); a small launch keeps the 64-channel shapes (and with them the deferred input normalisation)
     bool cout_wide = f16s_cout_wide(p.Cout);
     if (cout_wide && p.Cout % 128 != 0 && !s2) {
-        const int tw = p.Wo < 32 ? p.Wo : 32;
-        int th = 128 / tw;
-        if (th > p.Ho) th = p.Ho;
+        const int tw = std::min(p.Wo, 32), th = std::min(128 / tw, p.Ho);
         const long nwg = (long)((p.Wo + tw - 1) / tw) * ((p.Ho + th - 1) / th) * p.B * ((p.Cout + 127) / 128);
         if (nwg < 1024) cout_wide = false;
     }
@@ -940,35 +845,20 @@ static int launch_conv_f16s_impl(const ConvParams& p, const _Float16* wpk, hipSt
     // n-tiles (of 32 output pixels) per workgroup: 128-pixel tiles (64 for the stride-2 shapes of more than 32 channels) keep 4 waves
     // per SIMD to hide the staging latency; 256-pixel tiles at 2 waves/SIMD were 15-60 % slower and were removed
     const int NT_WG = (s2 && !narrow) ? 2 : 4;
-    F16sGeom g;
+    F16sGeom g = {};
     auto geometry = [&](int npx) {
-    g.TW = p.Wo < 32 ? p.Wo : 32;
-    g.TH = npx / g.TW;
-    if (g.TH > p.Ho) g.TH = p.Ho;
-    g.NIMG = 1;
-    if (g.TH == p.Ho && g.TW == p.Wo) {
-        g.NIMG = npx / (g.TH * g.TW);
-        if (g.NIMG > 8) g.NIMG = 8;
-        if (g.NIMG > p.B) g.NIMG = p.B;
-        if (g.NIMG < 1) g.NIMG = 1;
-    }
-    if (spatial) {
-        g.pstep = 1;
-        g.ostep = p.stride;
-        g.PH = (g.TH - 1) * p.stride + p.KH;
-        g.PW = (g.TW - 1) * p.stride + p.KW;
-    } else {
-        g.pstep = p.stride;
-        g.ostep = 1;
-        g.PH = g.TH;
-        g.PW = g.TW;
-    }
+    g.TW = std::min(p.Wo, 32);
+    g.TH = std::min(npx / g.TW, p.Ho);
+    g.NIMG = 1;      // several whole images per workgroup when one fits the tile: up to 8, and no more than the batch has
+    if (g.TH == p.Ho && g.TW == p.Wo) g.NIMG = std::max(1, std::min(npx / (g.TH * g.TW), std::min(8, p.B)));
+    g.pstep = spatial ? 1 : p.stride;      // a 1x1 layer takes its stride while staging: its patch is its tile
+    g.ostep = spatial ? p.stride : 1;
+    g.PH = spatial ? (g.TH - 1) * p.stride + p.KH : g.TH;
+    g.PW = spatial ? (g.TW - 1) * p.stride + p.KW : g.TW;
     // keep the staging work within the per-thread task budget of the variant (MAXT x 256 eight-channel tasks)
-    {
-        const int maxt = sep ? 4 : (s2 ? (narrow ? 5 : 3) : 2);
-        const int nstage = (wide && !sep) ? 512 : 256;
-        while (g.NIMG > 1 && (g.NIMG * g.PH * g.PW * (CK / 8) + nstage - 1) / nstage > maxt) --g.NIMG;
-    }
+    const int maxt = sep ? 4 : (s2 ? (narrow ? 5 : 3) : 2);
+    const int nstage = (wide && !sep) ? 512 : 256;
+    while (g.NIMG > 1 && (g.NIMG * g.PH * g.PW * (CK / 8) + nstage - 1) / nstage > maxt) --g.NIMG;
     // Stride 2: output-pixel lanes read every second input column; with plain row-major records (80 B apart) their 160-byte lane
     // stride lands 16 lanes on 8 of the 16 LDS slots (2-way conflicts on every B-fragment read).  The patch rows are therefore stored
     // de-interleaved -- even columns, then odd columns -- so a tap's 32 lanes read consecutive records again.
@@ -982,45 +872,180 @@ static int launch_conv_f16s_impl(const ConvParams& p, const _Float16* wpk, hipSt
     g.nchunk = p.C2 > 0 ? g.c1_pad / CK + (p.C2 + CK - 1) / CK : (p.C1 + CK - 1) / CK;
     };
     // The weights-through-LDS shapes come first (3x3, stride 1, not a 128-channel layer): 8 waves, 256 output pixels x 64 (or 32)
-    // channels; they need one sample per workgroup and the vector staging path, else the register-fragment shapes below take the layer.
+    // channels; they need one sample per workgroup and the vector staging path within one task per thread, else the register-fragment
+    // shapes below take the layer -- as they do when the layer exceeds a limit of the kernel in this shape (their LDS footprint lacks
+    // the 12 / 24 KiB weight ring, which decides for a deferred normalisation of ~13000 channels).
     // Measured (profiles/r02_conv_weight_path.md, B = 16): 64 -> 64 at 256x256 234 -> 263 TF, 32 -> 32 195 -> 205, 81 -> 64 208 -> 222; the
     // 128-channel form of it (4 m-tiles x 2 pixel tiles per wave, 8 waves) lost to the four-wave shape whose fragments feed 12 MFMAs
     // (128 -> 128 at 128x128: 294 vs 343 TF) and was removed.
     if (k3 && p.stride == 1 && !cout_wide) {
         geometry(256);
-        if (g.NIMG == 1) {
-            const int rc = narrow ? launch_f16s_wl<1, 1>(p, g, one_sample_per_wg ? nullptr : wpk, s, one_sample_per_wg)
-                                  : launch_f16s_wl<2, 2>(p, g, one_sample_per_wg ? nullptr : wpk, s, one_sample_per_wg);
-            if (rc != -1) return rc;
+        g.NQ = g.NIMG == 1 ? f16s_quads(p, g) : 0;
+        if (g.NQ && (16 / 4) * g.PH * g.NQ <= 64 * 8 && (!p.in_norm || f16s_pre_ok(p))) {
+            const int wm = narrow ? 1 : 2;
+            const F16sPlan pl = f16s_finish(p, F16sShape{3, 3, 16, wm, wm, 2, 8, 1, p.in_norm ? 1 : 0, 1}, g);
+            if (pl.route != F16S_DECLINED) return pl;
         }
     }
     geometry(NT_WG * 32);
-    if (one_sample_per_wg) {  // geometry probe
-        *one_sample_per_wg = g.NIMG == 1;
-        return CF_OK;
-    }
+    g.NQ = 0;
+    F16sShape t = {p.KH, p.KW, CK, 2, 2, 2, 4, 0, 0, 0};      // 64-channel workgroups: four waves, 2 m-tiles x 2 pixel groups
     if (sep) {
         // RAFT's SepConvGRU (384 -> 128 / 256 at 1/8 resolution): CK = 32 (10 k-steps per chunk keep the 2-slot fragment ring static);
         // 128-pixel tiles; 128-channel workgroups when Cout allows (8 waves: 4 m-tiles x 2 pixel groups), else 64-channel ones
-        if (kind == 15) return (p.Cout % 128 == 0) ? launch_f16s<1, 5, 32, 4, 2, 4, 8>(p, g, wpk, s) : launch_f16s<1, 5, 32, 2, 2, 4>(p, g, wpk, s);
-        return (p.Cout % 128 == 0) ? launch_f16s<5, 1, 32, 4, 2, 4, 8>(p, g, wpk, s) : launch_f16s<5, 1, 32, 2, 2, 4>(p, g, wpk, s);
-    }
-    if (wide) {
+        t.MAXT = 4;
+        if (p.Cout % 128 == 0) { t.WM = 4; t.NW = 8; }
+    } else if (wide) {
         // Two 128-channel shapes.  Four waves, each ONE m-tile x FOUR pixel tiles: a weight fragment feeds 12 MFMAs instead of 6, which
         // halves the per-wave weight re-reads from L1/L2 -- the resource the time stamps and the persistent-kernel experiment pointed at
         // (+9-15 % on the 128- and 256-channel layers at 64x64 and above); 148 VGPRs (no scratch under a 2-workgroup launch bound; a bound of 3 made the allocator spill 168 B/lane for the same speed), 3 waves/SIMD.  With few workgroups (32x32 maps)
         // the 8-wave shape (4 m-tiles x 2 pixel groups, 4 waves/SIMD) keeps more of the chip busy.  1x1 layers make the same choice.
         const long nwg = (long)g.tiles_x * g.tiles_y * g.bgroups * ((p.Cout + 127) / 128);
         const bool four = nwg >= 1024 && g.NIMG == 1 && (g.NIMG * g.PH * g.PW * (CK / 8) + 255) / 256 <= 2;
-        if (k3) return four ? launch_f16s<3, 3, 16, 4, 4, 2>(p, g, wpk, s) : launch_f16s<3, 3, 16, 4, 2, 2, 8>(p, g, wpk, s);
-        return four ? launch_f16s<1, 1, 32, 4, 4, 2>(p, g, wpk, s) : launch_f16s<1, 1, 32, 4, 2, 2, 8>(p, g, wpk, s);
+        t.WM = 4;
+        if (four) t.NTW = 4; else t.NW = 8;
+    } else if (narrow) {
+        t.WM = t.NTW = 1;
+        if (s2) t.MAXT = 5;      // stride-2 3x3 to <= 32 channels
+    } else if (s2) {
+        // stride 2 with Cout % 128 == 0: four m-tiles x two pixel tiles per wave -- every weight fragment is loaded once per workgroup and
+        // feeds 6 MFMAs (the 64-channel shape: loaded twice, 3 MFMAs each)
+        t.MAXT = 3;
+        if (f16s_cout_wide(p.Cout)) t.WM = 4; else t.NTW = 1;
     }
-    if (narrow && !s2) return k3 ? launch_f16s<3, 3, 16, 1, 1, 2>(p, g, wpk, s) : launch_f16s<1, 1, 32, 1, 1, 2>(p, g, wpk, s);
-    if (narrow) return launch_f16s<3, 3, 16, 1, 1, 5>(p, g, wpk, s);      // stride-2 3x3 to <= 32 channels
-    // stride 2 with Cout % 128 == 0: four m-tiles x two pixel tiles per wave -- every weight fragment is loaded once per workgroup and
-    // feeds 6 MFMAs (the 64-channel shape below: loaded twice, 3 MFMAs each)
-    if (s2) return f16s_cout_wide(p.Cout) ? launch_f16s<3, 3, 16, 4, 2, 3>(p, g, wpk, s) : launch_f16s<3, 3, 16, 2, 1, 3>(p, g, wpk, s);
-    return k3 ? launch_f16s<3, 3, 16, 2, 2, 2>(p, g, wpk, s) : launch_f16s<1, 1, 32, 2, 2, 2>(p, g, wpk, s);
+    if (const char* why = f16s_staging(p, t, g)) return f16s_declined(why);
+    return f16s_finish(p, t, g);
+}
+
+// Executes the kernel route of a plan; what belongs to the launch stays here: the 160 KiB opt-in, the profile events, the ablation-build hooks.
+template <int KH, int KW, int CK, int WM, int NTW, int MAXT, int NW, int VEC, int PRE, int WL>
+static int launch_f16s_shape(const ConvParams& p, const F16sPlan& pl, const _Float16* wpk, hipStream_t s) {
+    F16sGeom g = pl.g;
+    size_t lds_bytes = pl.lds_bytes;
+#ifdef CF_F16S_ABLATION_BUILD
+    { static int ab = -1; if (ab < 0) { const char* e = getenv("CF_F16S_ABLATE"); ab = e ? atoi(e) : 0; } g.ablate = ab; }
+    { static long pad = -1; if (pad < 0) { const char* e = getenv("CF_F16S_LDSPAD"); pad = e ? atol(e) : 0; }   // timing builds: fewer resident workgroups
+      if (pad > (long)lds_bytes) lds_bytes = (size_t)pad; }
+    if (lds_bytes > 160 * 1024) { set_error("conv_f16s: LDS tile too large"); return CF_ERR_ARG; }
+#endif
+    auto kern = p.terms == 1 ? conv_f16s_kernel<KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL, 1> : conv_f16s_kernel<KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL, 3>;
+    static bool attr_set[64][2] = {};       // per device and variant
+    const int dev = current_device_slot();
+    if (!attr_set[dev][p.terms == 1]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set[dev][p.terms == 1] = true;
+    }
+    const dim3 grid(pl.grid_x, pl.grid_y), block(64 * NW);
+    const double flops = 2.0 * (double)p.B * p.Ho * p.Wo * p.Cout * (p.C1 + p.C2) * p.KH * p.KW;
+    hipEvent_t e0, e1;
+    if (profile_on() && profile_events(PK_CONV_F16S, flops, &e0, &e1))
+        hipExtLaunchKernelGGL(kern, grid, block, lds_bytes, s, e0, e1, 0, p, g, wpk);
+    else
+        hipLaunchKernelGGL(kern, grid, block, lds_bytes, s, p, g, wpk);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error(std::string("conv_f16s launch failed: ") + hipGetErrorString(e)); return CF_ERR_LAUNCH; }
+    return CF_OK;
+}
+
+#define CF_F16S_ROW(...) launch_f16s_shape<__VA_ARGS__>,
+static int (*const k_f16s_launch[])(const ConvParams&, const F16sPlan&, const _Float16*, hipStream_t) = {CF_F16S_SHAPES(CF_F16S_ROW)};
+#undef CF_F16S_ROW
+
+// Runs the convolution on a batch whose inputs fit 32-bit buffer offsets; when p.gn_ws is set the workspace ends up holding the
+// GroupNorm statistics of the output -- from the fused epilogue when every workgroup covers a single sample, otherwise from the
+// separate statistics pass.  (The transposed convolution's scatter fuses too: its GEMM rows are co * 4 + dy * 2 + dx, so a group of
+// Cout / groups output channels is a run of 4 * Cout / groups consecutive rows -- the same `co / cpg` with cpg = p.Cout / groups.)
+static int launch_conv_f16s_part(const ConvParams& p, const _Float16* wpk, hipStream_t s) {
+    const F16sPlan pl = f16s_plan(p);
+    if (pl.route == F16S_DECLINED) { set_error(pl.why); return CF_ERR_ARG; }
+    const bool fused = p.gn_ws && pl.fusable;
+    // the fused statistics accumulate with atomics: the workspace must start at zero (gn_prezeroed: the caller hands out slices
+    // of a pool it zeroed with ONE memset -- the per-launch memsets were 1.2 % of the step)
+    const bool zero = fused && !p.gn_prezeroed;
+    const size_t ws_bytes = sizeof(double) * 2 * (size_t)p.B * p.gn_groups;
+    if (zero && hipMemsetAsync(p.gn_ws, 0, ws_bytes, s) != hipSuccess) {
+        set_error(pl.route == F16S_STREAM ? "conv_stream: memset failed" : "conv_f16s: memset failed");
+        return CF_ERR_LAUNCH;
+    }
+    if (pl.route == F16S_STREAM) return launch_conv_stream(p, wpk, s);
+    ConvParams q = p;
+    if (!fused) q.gn_ws = nullptr;
+    const int rc = k_f16s_launch[pl.shape](q, pl, wpk, s);
+    if (rc != CF_OK || !p.gn_ws || fused) return rc;
+    const int up = p.scatter2x2 ? 2 : 1;
+    const int cout = p.scatter2x2 ? p.Cout / 4 : p.Cout;
+    if (p.out_coff != 0 || p.out_ctotal != cout) { set_error("conv_f16s: GroupNorm statistics need a dense output tensor"); return CF_ERR_ARG; }
+    return launch_gn_stats(p.out, p.gn_ws, p.B, cout, p.Ho * up * p.Wo * up, p.gn_groups, s);
+}
+
+// The kernel addresses its inputs with 32-bit buffer offsets (< 2 GiB per descriptor).  A batch whose input tensors are larger is
+// cut into sub-batches HERE (same kernel, same numbers, a few more launches) instead of being handed to another kernel: the batch
+// axis is the outermost one of every operand, so a sub-batch is a pointer offset.
+// Samples per sub-batch: the batch is cut into the FEWEST parts that fit and the parts are made equal (the last one at most parts - 1
+// samples smaller) -- a greedy cut could leave a remainder of one sample, for which the plan picks another kernel shape than for the
+// large parts (e.g. one without the deferred input normalisation).  Plans are made per part: n samples, `last` in the remainder; n == 0:
+// one sample of an input exceeds 2 GiB.
+struct F16sParts { long n, last; };
+static F16sParts f16s_parts(const ConvParams& p) {
+    if (conv_stream_applicable(p)) return {p.B, p.B};      // per-sample buffer resources: no 2 GiB limit on the batch
+    const long HW = (long)p.H * p.W;
+    const long per1 = (long)p.C1 * HW * 4, per2 = (long)p.C2 * HW * 4;
+    const long nb = ((1L << 31) - 1) / (per1 > per2 ? per1 : per2);
+    if (nb < 1) return {0, 0};
+    if (p.B <= nb) return {p.B, p.B};
+    const long parts = (p.B + nb - 1) / nb;
+    const long n = (p.B + parts - 1) / parts;
+    return {n, p.B - (p.B - 1) / n * n};
+}
+
+int launch_conv_f16s(const ConvParams& p, const _Float16* wpk, hipStream_t s) {
+    const long nb = f16s_parts(p).n;
+    if (nb < 1) { set_error("conv_f16s: one sample of the input exceeds 2 GiB"); return CF_ERR_ARG; }
+    const long HW = (long)p.H * p.W, HoWo = (long)p.Ho * p.Wo;
+    const int up = p.scatter2x2 ? 2 : 1;
+    for (long b0 = 0; b0 < p.B; b0 += nb) {      // one turn unless the inputs exceed 2 GiB
+        ConvParams q = p;
+        q.B = (int)(p.B - b0 < nb ? p.B - b0 : nb);
+        q.x1 = p.x1 + b0 * p.C1 * HW;
+        if (p.x2) q.x2 = p.x2 + b0 * p.C2 * HW;
+        if (p.res) q.res = p.res + b0 * p.Cout * HoWo;
+        q.out = p.out + b0 * p.out_ctotal * HoWo * up * up;
+        if (p.gn_ws) q.gn_ws = p.gn_ws + 2 * b0 * p.gn_groups;
+        if (p.in_norm) q.in_norm = p.in_norm + b0 * 3 * p.C1;
+        if (const int rc = launch_conv_f16s_part(q, wpk, s)) return rc;
+    }
+    return CF_OK;
+}
+
+// The ConvParams of a plain call on a layer of this shape, in this thread's product mode: no tensors yet, dense output of Cout channels, no
+// activation, no statistics.  The exports assign what they have by name.
+static ConvParams f16s_layer(int B, int C1, int C2, int H, int W, int Cout, int KH, int KW, int stride, int pad_h, int pad_w) {
+    ConvParams p;
+    p.x1 = p.x2 = p.wt = p.bias = p.res = nullptr; p.out = nullptr; p.w_bstride = 0;
+    p.C1 = C1; p.C2 = C2; p.B = B; p.H = H; p.W = W; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride;
+    p.pad_h = pad_h; p.pad_w = pad_w; p.Ho = (H + 2 * pad_h - KH) / stride + 1; p.Wo = (W + 2 * pad_w - KW) / stride + 1;
+    p.out_ctotal = Cout; p.out_coff = 0; p.act = CF_ACT_NONE; p.alpha = 1.f; p.scatter2x2 = 0;
+    p.gn_ws = nullptr; p.gn_groups = 0; p.gn_prezeroed = 0;
+    p.terms = conv_terms();
+    return p;
+}
+// gn_groups < 0 declares gn_ws already zeroed
+static void f16s_stats(ConvParams& p, double* gn_ws, int gn_groups) {
+    p.gn_ws = gn_ws; p.gn_groups = gn_groups < 0 ? -gn_groups : gn_groups; p.gn_prezeroed = gn_groups < 0;
+}
+// the transposed 2x2 / stride 2 convolution as the kernel sees it: a 1x1 GEMM to 4 * Cout rows (co, dy, dx), scattered by the epilogue
+static ConvParams f16s_layer_transposed(int B, int Cin, int H, int W, int Cout) {
+    ConvParams p = f16s_layer(B, Cin, 0, H, W, 4 * Cout, 1, 1, 1, 0, 0);
+    p.scatter2x2 = 1; p.out_ctotal = Cout;
+    return p;
+}
+static const char* const k_f16s_unsupported =
+    "unsupported configuration for the f16-split kernel (3x3 pad 1 or 1x1 pad 0 at stride 1/2, 1x5 pad (0,2) or 5x1 pad (2,0) at stride 1; one sample < 2 GiB)";
+
+// An address with the given low four bits for the queries, which have no tensors: the plan reads alignment only.
+static const float* f16s_address(int low4) {
+    alignas(16) static const unsigned char anchor[32] = {};
+    return reinterpret_cast<const float*>(anchor + (low4 & 15));
 }
 
 }  // namespace cf
@@ -1044,16 +1069,13 @@ extern "C" int cf_conv2d_f16s(const float* x1, int C1, const float* x2, int C2, 
     CF_REQUIRE(out_coff >= 0 && out_coff + Cout <= out_ctotal, "output channel slice out of range");
     CF_REQUIRE(act >= CF_ACT_NONE && act <= CF_ACT_SIGMOID, "bad activation %d", act);
     CF_REQUIRE((reinterpret_cast<uintptr_t>(wpk) & 15) == 0, "packed weights must be 16-byte aligned");
-    ConvParams p;
-    p.x1 = x1; p.x2 = C2 ? x2 : nullptr; p.wt = nullptr; p.bias = bias; p.res = res; p.out = out; p.w_bstride = 0;
-    p.C1 = C1; p.C2 = C2; p.B = B; p.H = H; p.W = W; p.Cout = Cout; p.KH = KH; p.KW = KW; p.stride = stride;
-    p.pad_h = pad_h; p.pad_w = pad_w; p.Ho = (H + 2 * pad_h - KH) / stride + 1; p.Wo = (W + 2 * pad_w - KW) / stride + 1;
-    p.out_ctotal = out_ctotal; p.out_coff = out_coff; p.act = act; p.alpha = alpha; p.scatter2x2 = 0;
-    p.gn_ws = gn_ws; p.gn_groups = gn_groups < 0 ? -gn_groups : gn_groups; p.gn_prezeroed = gn_groups < 0;
-    p.terms = conv_terms();
+    ConvParams p = f16s_layer(B, C1, C2, H, W, Cout, KH, KW, stride, pad_h, pad_w);
+    p.x1 = x1; p.x2 = C2 ? x2 : nullptr; p.bias = bias; p.res = res; p.out = out;
+    p.out_ctotal = out_ctotal; p.out_coff = out_coff; p.act = act; p.alpha = alpha;
+    f16s_stats(p, gn_ws, gn_groups);
     CF_REQUIRE(!gn_ws || (p.gn_groups > 0 && Cout % p.gn_groups == 0 && out_coff == 0 && out_ctotal == Cout), "bad GroupNorm statistics request");
     CF_REQUIRE(p.Ho > 0 && p.Wo > 0, "empty output");
-    CF_REQUIRE(conv_f16s_supported(p), "unsupported configuration for the f16-split kernel (3x3 pad 1 or 1x1 pad 0 at stride 1/2, 1x5 pad (0,2) or 5x1 pad (2,0) at stride 1; one sample < 2 GiB)");
+    CF_REQUIRE(conv_f16s_supported(p), "%s", k_f16s_unsupported);
     return launch_conv_f16s(p, reinterpret_cast<const _Float16*>(wpk), as_stream(stream));
 }
 
@@ -1061,33 +1083,18 @@ extern "C" int cf_conv2d_f16s(const float* x1, int C1, const float* x2, int C2, 
 // (the second convolution of a Generic_UNet stage): in_norm = float [B][3][C] {mean, scale, shift} from cf_group_norm_coef, applied
 // as lrelu((x - mean) * scale + shift, in_slope) while the tile is staged -- the producer's apply pass (8 B per element) disappears.
 // Built for 3x3 / stride 1 / pad 1 layers on the vector staging path (W % 4 == 0, one sample per workgroup, single input);
-// cf_conv2d_f16s_prenorm_ok answers whether a shape qualifies (1) or not (0).
-static void prenorm_params(ConvParams& p, const float* x, int C, const float* bias, float* out, int B, int H, int W, int Cout, float alpha,
-                           double* gn_ws, int gn_groups, const float* in_norm, float in_slope) {
-    p.x1 = x; p.x2 = nullptr; p.wt = nullptr; p.bias = bias; p.res = nullptr; p.out = out; p.w_bstride = 0;
-    p.C1 = C; p.C2 = 0; p.B = B; p.H = H; p.W = W; p.Cout = Cout; p.KH = 3; p.KW = 3; p.stride = 1;
-    p.pad_h = 1; p.pad_w = 1; p.Ho = H; p.Wo = W; p.out_ctotal = Cout; p.out_coff = 0; p.act = CF_ACT_NONE; p.alpha = alpha; p.scatter2x2 = 0;
-    p.gn_ws = gn_ws; p.gn_groups = gn_groups < 0 ? -gn_groups : gn_groups; p.gn_prezeroed = gn_groups < 0;
-    p.in_norm = in_norm; p.in_slope = in_slope;
-    p.terms = conv_terms();
-}
-
+// cf_conv2d_f16s_prenorm_ok answers whether a shape qualifies (1) or not (0): every sub-batch's plan is a PRE shape or the stream route.
 extern "C" int cf_conv2d_f16s_prenorm_ok(int B, int C, int H, int W, int Cout) {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-    ConvParams p;
-    float* dummy = reinterpret_cast<float*>(uintptr_t(256));      // never dereferenced: probe mode launches nothing
-    prenorm_params(p, dummy, C, nullptr, dummy, B, H, W, Cout, 1.f, nullptr, 0, dummy, 0.01f);
-    p.probe = 1;
+    ConvParams p = f16s_layer(B, C, 0, H, W, Cout, 3, 3, 1, 1, 1);
+    p.x1 = p.in_norm = f16s_address(0);
     if (!conv_f16s_supported(p)) return 0;
-    // the shapes are chosen per sub-batch (launch_conv_f16s): ask for the sizes that will actually be launched
-    const long nb = f16s_sub_batch(p);
-    if (nb < 1) return 0;
-    const long last = B - (B - 1) / nb * nb;
-    p.B = (int)nb;
-    if (!conv_stream_applicable(p) && launch_conv_f16s_impl(p, reinterpret_cast<const _Float16*>(dummy), nullptr, nullptr) != CF_OK) return 0;
-    if (last != nb) {
-        p.B = (int)last;
-        if (!conv_stream_applicable(p) && launch_conv_f16s_impl(p, reinterpret_cast<const _Float16*>(dummy), nullptr, nullptr) != CF_OK) return 0;
+    const F16sParts parts = f16s_parts(p);
+    if (parts.n < 1) return 0;
+    for (const long b : {parts.n, parts.last}) {
+        p.B = (int)b;
+        const F16sPlan pl = f16s_plan(p);
+        if (!(pl.route == F16S_STREAM || (pl.route == F16S_KERNEL && k_f16s_shapes[pl.shape].PRE))) return 0;
     }
     return 1;
 }
@@ -1097,8 +1104,9 @@ extern "C" int cf_conv2d_f16s_prenorm(const float* x, int C, const float* in_nor
     CF_REQUIRE(x && wpk && out && in_norm, "null pointer");
     CF_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && Cout > 0, "bad shape B=%d C=%d H=%d W=%d Cout=%d", B, C, H, W, Cout);
     CF_REQUIRE((reinterpret_cast<uintptr_t>(wpk) & 15) == 0, "packed weights must be 16-byte aligned");
-    ConvParams p;
-    prenorm_params(p, x, C, bias, out, B, H, W, Cout, alpha, gn_ws, gn_groups, in_norm, in_slope);
+    ConvParams p = f16s_layer(B, C, 0, H, W, Cout, 3, 3, 1, 1, 1);
+    p.x1 = x; p.bias = bias; p.out = out; p.alpha = alpha; p.in_norm = in_norm; p.in_slope = in_slope;
+    f16s_stats(p, gn_ws, gn_groups);
     CF_REQUIRE(!gn_ws || (p.gn_groups > 0 && Cout % p.gn_groups == 0), "bad GroupNorm statistics request");
     CF_REQUIRE(conv_f16s_supported(p), "unsupported configuration for the f16-split kernel");
     return launch_conv_f16s(p, reinterpret_cast<const _Float16*>(wpk), as_stream(stream));
@@ -1111,15 +1119,44 @@ extern "C" int cf_conv_transpose2d_k2s2_f16s(const float* x, const void* wpk, co
     CF_REQUIRE(B > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0, "bad shape");
     CF_REQUIRE(out_coff >= 0 && out_coff + Cout <= out_ctotal, "output channel slice out of range");
     CF_REQUIRE((reinterpret_cast<uintptr_t>(wpk) & 15) == 0, "packed weights must be 16-byte aligned");
-    ConvParams p;
-    p.x1 = x; p.x2 = nullptr; p.wt = nullptr; p.bias = bias; p.res = nullptr; p.out = out; p.w_bstride = 0;
-    p.C1 = Cin; p.C2 = 0; p.B = B; p.H = H; p.W = W; p.Cout = Cout * 4; p.KH = 1; p.KW = 1; p.stride = 1;
-    p.pad_h = 0; p.pad_w = 0; p.Ho = H; p.Wo = W; p.out_ctotal = out_ctotal; p.out_coff = out_coff; p.act = CF_ACT_NONE;
-    p.alpha = alpha; p.scatter2x2 = 1; p.gn_ws = gn_ws; p.gn_groups = gn_groups < 0 ? -gn_groups : gn_groups; p.gn_prezeroed = gn_groups < 0;
-    p.terms = conv_terms();
+    ConvParams p = f16s_layer_transposed(B, Cin, H, W, Cout);
+    p.x1 = x; p.bias = bias; p.out = out; p.out_ctotal = out_ctotal; p.out_coff = out_coff; p.alpha = alpha;
+    f16s_stats(p, gn_ws, gn_groups);
     CF_REQUIRE(!gn_ws || (p.gn_groups > 0 && Cout % p.gn_groups == 0 && out_coff == 0 && out_ctotal == Cout), "bad GroupNorm statistics request");
     CF_REQUIRE(conv_f16s_supported(p), "unsupported configuration for the f16-split kernel (one sample of the input must stay below 2 GiB)");
     return launch_conv_f16s(p, reinterpret_cast<const _Float16*>(wpk), as_stream(stream));
+}
+
+// The plan of the first sub-batch of a plain call (dense output, no activation, no residual), exported: include/cineflow.h.
+extern "C" int cf_conv2d_f16s_route(int B, int C1, int C2, int H, int W, int Cout, int KH, int KW, int stride, int pad_h, int pad_w, int x1_low4,
+                                    int x2_low4, int prenorm, int transposed, int stats_groups, int* plan15) {
+    if (plan15) memset(plan15, 0, 15 * sizeof(int));
+    CF_REQUIRE(C1 > 0 && C2 >= 0 && B > 0 && H > 0 && W > 0 && Cout > 0 && stride > 0, "bad shape B=%d C=%d+%d H=%d W=%d Cout=%d", B, C1, C2, H, W, Cout);
+    CF_REQUIRE(stats_groups >= 0 && (stats_groups == 0 || Cout % stats_groups == 0), "bad GroupNorm statistics request");
+    ConvParams p = transposed ? f16s_layer_transposed(B, C1, H, W, Cout) : f16s_layer(B, C1, C2, H, W, Cout, KH, KW, stride, pad_h, pad_w);
+    p.x1 = f16s_address(x1_low4);
+    if (p.C2) p.x2 = f16s_address(x2_low4);
+    if (prenorm && !transposed) { p.in_norm = f16s_address(0); p.in_slope = 0.01f; }
+    static double stats;      // stands for a workspace: the plan asks only whether there is one
+    if (stats_groups) f16s_stats(p, &stats, stats_groups);
+    CF_REQUIRE(p.Ho > 0 && p.Wo > 0, "empty output");
+    F16sPlan pl;
+    F16sParts parts = {0, 0};
+    if (!conv_f16s_supported(p)) {
+        pl = f16s_declined(k_f16s_unsupported);
+    } else {
+        parts = f16s_parts(p);
+        p.B = (int)parts.n;
+        pl = parts.n < 1 ? f16s_declined("conv_f16s: one sample of the input exceeds 2 GiB") : f16s_plan(p);
+    }
+    if (pl.route == F16S_DECLINED) { set_error(pl.why); return F16S_DECLINED; }
+    if (plan15) {
+        const F16sShape t = pl.route == F16S_KERNEL ? k_f16s_shapes[pl.shape] : F16sShape{};
+        const int nimg = pl.route == F16S_KERNEL ? pl.g.NIMG : 1;
+        const int v[15] = {pl.route, t.KH, t.KW, t.CK, t.WM, t.NTW, t.MAXT, t.NW, t.VEC, t.PRE, t.WL, p.terms, nimg, pl.fusable, (int)parts.n};
+        memcpy(plan15, v, sizeof(v));
+    }
+    return pl.route;
 }
 
 #ifdef CF_F16S_ABLATION_BUILD

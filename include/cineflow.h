@@ -244,6 +244,20 @@ int cf_conv_stream_enable(int on);
 int cf_conv2d_f16s_prenorm_ok(int B, int C, int H, int W, int Cout);
 int cf_conv2d_f16s_prenorm(const float* x, int C, const float* in_norm, float in_slope, const void* wpk, const float* bias, float* out,
                            int B, int H, int W, int Cout, float alpha, double* gn_ws, int gn_groups, void* stream);
+/* The launch plan of the f16-split convolution, exported (host code, launches nothing, needs no GPU): what cf_conv2d_f16s (prenorm 0,
+ * transposed 0), cf_conv2d_f16s_prenorm (prenorm 1; KH = KW = 3, stride 1, pad 1, C2 = 0) or cf_conv_transpose2d_k2s2_f16s (transposed 1:
+ * C1 = Cin, Cout as passed there; KH, KW, stride >= 1 and the pads are ignored) does with a plain call -- dense output, no activation, no
+ * residual -- of this shape in the calling thread's cf_conv_terms mode and at the current cf_conv_stream_enable level.  x1_low4 / x2_low4
+ * are the low four bits of the input addresses (the vector staging forms need 16-byte alignment), stats_groups the gn_groups of the
+ * call (0: no statistics).  prenorm 1 with another kernel, stride or C2 > 0 is planned as given -- no call can issue it, the plan declines it.
+ * Returns the route: 0 = declined (cf_last_error holds the reason the call would fail with), 1 = conv_f16s_kernel,
+ * 2 = conv_stream_kernel; CF_ERR_ARG for arguments no call accepts.  plan15 (nullable, 15 ints) receives
+ *   [0] the route, [1..10] the instantiation <KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL> (route 1, else zeros), [11] TERMS,
+ *   [12] images per workgroup, [13] 1 when the epilogue accumulates the GroupNorm statistics (one sample per workgroup, or route 2;
+ *   otherwise a statistics pass follows the convolution), [14] samples per launch: B, or ceil(B / parts) with the fewest parts whose
+ *   inputs stay below 2 GiB -- the plan is that of such a part; ask with B = the last part's size for the route of the remainder. */
+int cf_conv2d_f16s_route(int B, int C1, int C2, int H, int W, int Cout, int KH, int KW, int stride, int pad_h, int pad_w, int x1_low4,
+                         int x2_low4, int prenorm, int transposed, int stats_groups, int* plan15);
 
 /* The same operator (nn.Conv2d 3x3 / stride 1 / padding 1 of DoubleConv, nnunet/lib/utils.py:1182-1215; ConvDropoutNormNonlin,
  * generic_UNet.py:26-69; ConvGRUCell's gate convolutions, convGRU.py:57-66) as a ROW Winograd F(2,3) on the f16 MFMA with the 3-term hi/lo

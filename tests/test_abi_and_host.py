@@ -93,6 +93,114 @@ def test_corr_volume_route_probe_needs_no_gpu():
         h.cf_corr_mfma_enable(before)
 
 
+def test_conv2d_f16s_route_plan_needs_no_gpu():
+    """cf_conv2d_f16s_route is the plan the f16-split launcher executes, as host code: the instantiation of every row of
+    test_gpu_conv_f16s_routes.py in both product modes, and the conditions no GPU test can afford -- sub-batches, the 1024-workgroup and
+    1024-tile lines, the stream knob, every decline of a deferred normalisation, and the limits that used to be found at launch."""
+    from collections import namedtuple
+    from cineflow import _lib
+    from _conv_f16s_rows import CONVT_ROWS, PAD, PRE_ROWS, ROWS
+    h = _lib.lib()
+    Plan = namedtuple("Plan", "route tup terms nimg fused part")
+
+    def route(B, C1, H, W, cout, k=(3, 3), stride=1, C2=0, lo1=0, lo2=0, prenorm=0, transposed=0, groups=0):
+        plan = (ctypes.c_int * 15)()
+        r = h.cf_conv2d_f16s_route(B, C1, C2, H, W, cout, k[0], k[1], stride, PAD[k][0], PAD[k][1], lo1, lo2, prenorm, transposed, groups, plan)
+        assert r == plan[0] and r in (0, 1, 2), r
+        return Plan(r, tuple(plan[1:11]), plan[11], plan[12], bool(plan[13]), plan[14])
+
+    def declined(why, *a, **k):
+        p = route(*a, **k)
+        assert p.route == 0 and p.tup == (0,) * 10 and why in h.cf_last_error(), (a, k, p, h.cf_last_error())
+
+    WL32, WL64 = (3, 3, 16, 1, 1, 2, 8, 1, 0, 1), (3, 3, 16, 2, 2, 2, 8, 1, 0, 1)
+    knob, mode = h.cf_conv_stream_enable(1), h.cf_conv_terms(3)
+    try:
+        assert len(ROWS) + len(PRE_ROWS) + len(CONVT_ROWS) == 34 and len({r.tup for r in ROWS + PRE_ROWS}) == 30
+        for terms in (3, 1):
+            h.cf_conv_terms(terms)
+            for r in ROWS:
+                groups = 8 if r.Cout % 8 == 0 else r.Cout
+                for g in (0, groups):
+                    assert route(r.B, r.C, r.H, r.W, r.Cout, r.k, r.stride, lo1=4 if r.view else 0, groups=g) == \
+                        (1, r.tup, terms, r.nimg, r.nimg == 1, r.B), (r, terms)
+            for r in PRE_ROWS:
+                assert route(r.B, r.C, r.H, r.W, r.Cout, prenorm=1, groups=r.Cout) == (1, r.tup, terms, 1, True, r.B), (r, terms)
+            for r in CONVT_ROWS:
+                assert route(r.B, r.Cin, r.H, r.W, r.Cout, (1, 1), transposed=1, groups=4) == (1, r.tup, terms, r.nimg, r.nimg == 1, r.B), (r, terms)
+        h.cf_conv_terms(3)
+        # sub-batches: a sample of 4000 x 32 x 64 floats is 31.25 MiB, 65 of them stay below 2 GiB; 127 samples are cut into the fewest parts
+        # that fit, 2, made equal: 64 + 63 (a greedy cut: 65 + 62).  64 samples x 16 tiles reach the 1024 workgroups of the four-wave shape,
+        # the 63 of the last part do not: asking with B = 63 names the eight-wave shape that part runs on.
+        four, eight = (3, 3, 16, 4, 4, 2, 4, 1, 0, 0), (3, 3, 16, 4, 2, 2, 8, 1, 0, 0)
+        assert route(65, 4000, 32, 64, 128) == (1, four, 3, 1, True, 65)
+        assert route(127, 4000, 32, 64, 128) == (1, four, 3, 1, True, 64)
+        assert route(63, 4000, 32, 64, 128) == (1, eight, 3, 1, True, 63)
+        assert route(131, 4000, 32, 64, 128).part == 44          # ceil(131 / 3): three parts, the last one 43
+        declined(b"unsupported configuration", 1, 2 ** 19, 32, 64, 128)          # one sample of the input at 4 GiB: the argument-level gate
+        # 480 = 3 x 128 + 96 output channels on 32x32 maps: 8 tiles x 4 channel blocks per sample.  32 samples make the 1024 workgroups at which
+        # the layer rides on the 128-channel four-wave shape; 31 keep the 64-channel one (weights through LDS)
+        assert route(32, 40, 32, 32, 480) == (1, four, 3, 1, True, 32)
+        assert route(31, 40, 32, 32, 480) == (1, WL64, 3, 1, True, 31)
+        # the stream route: 3x3 / stride 1 to 32 or 64 channels, an even number of 16-channel chunks, >= 1024 tiles (8 rows x 32 at 64
+        # channels, 16 rows x 32 at 32: 16 / 8 tiles per 64x64 sample).  Level 0 keeps conv_f16s_kernel, level 1 leaves it the 64-channel
+        # layers with a deferred normalisation, level 2 takes every shape; the one-term mode is built in conv_f16s_kernel only
+        stream = (2, (0,) * 10, 3, 1, True)
+        PRE64 = WL64[:8] + (1, 1)
+        for level in (0, 1, 2):
+            h.cf_conv_stream_enable(level)
+            on = level > 0
+            assert route(64, 32, 64, 64, 64, groups=8) == (stream + (64,) if on else (1, WL64, 3, 1, True, 64)), level
+            assert route(63, 32, 64, 64, 64, groups=8) == (1, WL64, 3, 1, True, 63), level
+            assert route(128, 32, 64, 64, 32) == (stream + (128,) if on else (1, WL32, 3, 1, True, 128)), level
+            assert route(127, 32, 64, 64, 32) == (1, WL32, 3, 1, True, 127), level
+            assert route(64, 32, 64, 64, 64, prenorm=1) == (stream + (64,) if level == 2 else (1, PRE64, 3, 1, True, 64)), level
+            assert route(128, 32, 64, 64, 32, prenorm=1) == (stream + (128,) if on else (1, WL32[:8] + (1, 1), 3, 1, True, 128)), level
+            assert route(64, 40, 64, 64, 64).route == 1 and route(64, 32, 64, 64, 64, lo1=4).route == 1, level       # 3 chunks; misaligned
+            h.cf_conv_terms(1)
+            assert route(64, 32, 64, 64, 64) == (1, WL64, 1, 1, True, 64), level
+            h.cf_conv_terms(3)
+        h.cf_conv_stream_enable(1)
+        # a deferred normalisation is declined, with the message the call fails with
+        assert route(2, 40, 20, 36, 48, prenorm=1).tup == PRE64
+        declined(b"not built for this layer shape", 2, 40, 20, 36, 48, C2=8, prenorm=1)
+        declined(b"needs the vector staging path", 2, 40, 20, 36, 48, lo1=4, prenorm=1)
+        declined(b"needs the vector staging path", 2, 40, 20, 34, 48, prenorm=1)             # W % 4 != 0
+        declined(b"needs the vector staging path", 2, 40, 20, 36, 48, stride=2, prenorm=1)
+        declined(b"needs the vector staging path", 2, 40, 20, 36, 48, k=(1, 1), prenorm=1)
+        declined(b"not built for this layer shape", 2, 40, 32, 32, 128, prenorm=1)           # the eight-wave shape of the small launches
+        # the limits that were found only at launch: the plan declines, and the call fails with the same message.  The calls get made-up
+        # addresses, so each is made only after `declined` has asserted that the plan -- the one the call executes -- queues nothing.
+        # One workgroup's output at 1 GiB is caught by the argument-level gate of the call, as before (the plan's own check is a backstop).
+        a = 4096
+        conv = lambda B, C, H, W, cout: h.cf_conv2d_f16s(a, C, None, 0, a, None, None, a, cout, 0, B, H, W, cout, 3, 3, 1, 1, 1, 0, 1.0, None, 0, None)
+        declined(b"conv_f16s: staging tasks exceed MAXT", 2, 8, 200, 1, 24)                   # a one-column map taller than the staging budget
+        assert conv(2, 8, 200, 1, 24) == -1 and h.cf_last_error() == b"conv_f16s: staging tasks exceed MAXT"
+        declined(b"unsupported configuration", 1, 4, 4096, 4096, 16)                          # 16 x 4096 x 4096 floats = 1 GiB
+        assert conv(1, 4, 4096, 4096, 16) == -1 and b"unsupported configuration for the f16-split kernel" in h.cf_last_error()
+        declined(b"conv_f16s: LDS tile too large", 1, 14000, 4, 4, 24, prenorm=1)             # 3 x 14000 floats of coefficients beside the patch
+        assert h.cf_conv2d_f16s_prenorm(a, 14000, a, 0.01, a, None, a, 1, 4, 4, 24, 1.0, None, 0, None) == -1
+        assert h.cf_last_error() == b"conv_f16s: LDS tile too large"
+        assert h.cf_conv2d_f16s_prenorm_ok(1, 14000, 4, 4, 24) == 0 and h.cf_conv2d_f16s_prenorm_ok(2, 40, 20, 36, 48) == 1
+        # the plan names rows of the table only: no layer of a grid over every routing condition is declined for "a shape that is not built"
+        n = 0
+        for terms in (3, 1):
+            h.cf_conv_terms(terms)
+            for k, strides in (((3, 3), (1, 2)), ((1, 1), (1, 2)), ((1, 5), (1,)), ((5, 1), (1,))):
+                for stride in strides:
+                    for cout in (8, 32, 48, 64, 96, 128, 224, 256, 480):
+                        for H, W in ((4, 5), (6, 12), (10, 8), (8, 12), (20, 36), (32, 32), (33, 45), (64, 64), (200, 1), (12, 40)):
+                            for B in (1, 3, 11, 128):
+                                for C2, lo1, pre in ((0, 0, 0), (13, 0, 0), (0, 4, 0), (0, 0, 1)):
+                                    p = route(B, 40, H, W, cout, k, stride, C2=C2, lo1=lo1, prenorm=pre, groups=8)
+                                    assert p.route or b"not built" not in h.cf_last_error().replace(b"not built for this layer shape", b""), (k, stride, cout, H, W, B)
+                                    n += 1
+        assert n == 2 * 6 * 9 * 10 * 4 * 4
+    finally:
+        h.cf_conv_stream_enable(knob)
+        h.cf_conv_terms(mode)
+
+
 def test_product_fails_loudly_without_library(monkeypatch):
     from cineflow import _lib
     monkeypatch.setattr(_lib, "_lib", None)
