@@ -100,6 +100,9 @@ SIGNATURES = {
     "cf_conv2d_small_cout_norm2": [P, P, P, P, P, P, P, I, I, I, I, I, P],
     "cf_stem_block_ok": [I, I, I, I, I, I],
     "cf_stem_block": [P, P, P, P, P, P, P, I, I, I, I, I, P, P, I, P],
+    "cf_stem_block_y": [P, P, P, P, P, P, I, I, I, I, I, P, P, I, P],
+    "cf_group_norm_apply_res_stem_ok": [I, I, I, I, I, I],
+    "cf_group_norm_apply_res_stem": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, I, P],
     "cf_nonzero_mask": [P, I, L, P, P],
     "cf_fill_holes": [P, P, P, I, I, I, I, P],
     "cf_mask_bbox": [P, I, I, I, P, P],

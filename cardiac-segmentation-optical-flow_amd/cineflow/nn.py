@@ -420,11 +420,16 @@ class DoubleConv(Module):
         """defer_last = the 3x3 head convolution that will consume this block's output alone (Decoder2D.final_conv): when it can form
         GELU(GN2(y2)) + GN_ds(r) itself while staging (ops.conv2d_small_cout_norm2), the final apply pass is left to it and the pending
         norms are handed on as the RawMaps (y2, r).  Returns x, or (x, pending) when defer_last is given (one of the two is None)."""
-        short = None
+        short = ws_r = None          # ws_r alone: the stem's shortcut map was summed but not stored (the final pass rebuilds it from x)
         if self._stem_ok(x, x2):
-            ds = self.downsample[0]
-            t, ws1, r, ws_r = ops.stem_block(x, self.conv1._p["weight"], self.conv1._p.get("bias"), ds._p["weight"], ds._p.get("bias"), self.norm1.groups)
-            short = RawMap(r, ws_r, self.downsample[1])
+            ds, dn = self.downsample[0], self.downsample[1]
+            stem = (x, self.conv1._p["weight"], self.conv1._p.get("bias"), ds._p["weight"], ds._p.get("bias"), self.norm1.groups)
+            if (defer_last is None and dn.groups == self.norm2.groups and dn.eps == self.norm2.eps
+                    and ops.group_norm_apply_res_stem_ok(x, self.conv1.cout, self.norm2.groups)):
+                t, ws1, ws_r = ops.stem_block_y(*stem)
+            else:
+                t, ws1, r, ws_s = ops.stem_block(*stem)
+                short = RawMap(r, ws_s, dn)
         else:
             t, ws1 = self.conv1(x, x2=x2, stats_groups=self.norm1.groups)
         # conv2 applies GELU(GN1(t)) itself while it stages its input where it can, else norm1 runs as a pass.  The shortcut convolution
@@ -432,11 +437,17 @@ class DoubleConv(Module):
         pre = ws1 is not None and self.conv2.prenorm_ok(t)
         if pre:
             y2 = RawMap(*self.conv2.prenorm(t, RawMap(t, ws1, self.norm1).coef(), -1.0, stats_groups=self.norm2.groups), self.norm2)
-            short = short or self._shortcut(x, x2)
+            short = short or (self._shortcut(x, x2) if ws_r is None else None)
         else:
             t = self.norm1(t, act="gelu", ws=ws1)
-            short = short or self._shortcut(x, x2)
+            short = short or (self._shortcut(x, x2) if ws_r is None else None)
             y2 = RawMap(*self.conv2(t, stats_groups=self.norm2.groups), self.norm2)
+        if ws_r is not None:
+            if y2.ws is not None:
+                n2, ds, dn = self.norm2, self.downsample[0], self.downsample[1]
+                return ops.group_norm_apply_res_stem(y2.raw, n2._p["weight"], n2._p["bias"], n2.groups, y2.ws, x, ds._p["weight"], ds._p.get("bias"), ws_r,
+                                                     dn._p["weight"], dn._p["bias"], n2.eps, act="gelu", res_mode="after_act", out=y2.raw)
+            short = self._shortcut(x, x2)          # conv2's statistics were not fused: the shortcut map is needed after all
         if (short is not None and defer_last is not None and pre and y2.ws is not None and short.ws is not None and defer_last.sub is None
                 and ops.small_cout_norm2_ok(y2.raw, defer_last.cout, defer_last.ks[0], defer_last.ks[1], defer_last.stride, defer_last.pad)):
             return None, (y2, short)

@@ -574,6 +574,41 @@ def stem_block(x, w3, b3, w1, b1, groups):
     return y, ws_y, r, ws_r
 
 
+def stem_block_y(x, w3, b3, w1, b1, groups):
+    """stem_block without the shortcut map: -> (y, ws_y, ws_r).  r = conv1x1(x; w1, b1) is summed into ws_r but never stored; the block's
+    final pass rebuilds it from x (group_norm_apply_res_stem)."""
+    B, Cin, H, W = x.shape
+    cout = w3.shape[0]
+    assert tuple(w3.shape) == (cout, Cin, 3, 3) and tuple(w1.shape) == (cout, Cin, 1, 1)
+    y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+    ws = _zeroed_stats_ws(4 * B * groups, x.device)
+    ws_y, ws_r = ws[:2 * B * groups], ws[2 * B * groups:]
+    check(lib().cf_stem_block_y(_f32(x), _f32(w3), _opt(b3), _f32(w1), _opt(b1), _f32(y), B, Cin, H, W, cout, ws_y.data_ptr(), ws_r.data_ptr(), -groups,
+                                _stream()), "cf_stem_block_y")
+    return y, ws_y, ws_r
+
+
+def group_norm_apply_res_stem_ok(x, c, groups):
+    """can cf_group_norm_apply_res_stem rebuild a `c`-channel 1x1 shortcut of x [B,Cin,H,W] inside the apply pass?"""
+    B, Cin, H, W = x.shape
+    return bool(CONV_MODE == "f16s" and x.data_ptr() % 16 == 0 and lib().cf_group_norm_apply_res_stem_ok(B, Cin, c, H, W, groups) == 1)
+
+
+def group_norm_apply_res_stem(y2, gamma, beta, groups, ws, x, w1, b1, ws_r, gamma_r, beta_r, eps=1e-5, act=None, res_mode="after_act", out=None):
+    """group_norm_apply(y2, ..., res=r, res_norm=(ws_r, gamma_r, beta_r)) with r = conv1x1(x; w1, b1) rebuilt inside the pass instead of
+    read: the same bits as that call on the r stem_block stores."""
+    B, C, H, W = y2.shape
+    Cin = x.shape[1]
+    assert tuple(x.shape) == (B, Cin, H, W) and tuple(w1.shape) == (C, Cin, 1, 1) and res_mode in ("before_act", "after_act")
+    assert ws.dtype == torch.float64 and ws.numel() >= 2 * B * groups and ws_r.dtype == torch.float64 and ws_r.numel() >= 2 * B * groups
+    if out is None:
+        out = torch.empty_like(y2)
+    check(lib().cf_group_norm_apply_res_stem(_f32(y2), _opt(gamma), _opt(beta), ws.data_ptr(), _f32(x), _f32(w1), _opt(b1), ws_r.data_ptr(),
+                                             _opt(gamma_r), _opt(beta_r), _f32(out), B, Cin, C, H, W, groups, float(eps), ACT[act], RES[res_mode],
+                                             _stream()), "cf_group_norm_apply_res_stem")
+    return out
+
+
 def prenorm_ok(x, cout):
     """can cf_conv2d_f16s_prenorm take this input (raw conv output [B,C,H,W]) for a 3x3 / stride 1 convolution to `cout` channels?"""
     B, C, H, W = x.shape

@@ -3,7 +3,7 @@
 // neighbourhood once and writes both raw maps with the GroupNorm statistics of each.  Same thread layout as conv_small_cin_kernel
 // (conv_direct.hip): a thread owns one output column of PY rows, its (PY + 2) x 3 x CIN neighbourhood sits in registers (the 1x1 branch
 // reads its centre column), the weights of the current output channel are wave-uniform scalar loads, every store is a 256-byte row segment
-// per wave, statistics go registers -> shuffles -> LDS -> ONE fp64 atomic pair per (group, map) and block.  Exact fp32; the 3x3 sum of an
+// per wave, statistics go registers -> shuffles -> LDS (a slot per wave, summed in wave order) -> ONE fp64 atomic pair per (group, map) and block.  Exact fp32; the 3x3 sum of an
 // output is formed in conv_small_cin_kernel's order (bias, then ci / ky / kx), the 1x1 sum likewise (bias, then ci), so each map is
 // bit-equal to that kernel's.  Roofline: the two Cout-channel writes (algorithmic bytes = 4 * B * H * W * (Cin + 2 * Cout)).  Measured at
 // 256 x 256 -> 2 x 64 (profiles/flow_stem_head_bench.md): CIN = 1 moves its 2.16 GB (B = 64) at 5.1-6.4 TB/s, 0.34-0.42 ms against 0.41 ms for
@@ -16,21 +16,21 @@
 
 namespace cf {
 
-template <int CIN, int PY>
+// STORE_R false (cf_stem_block_y): r is formed and summed into ws_r as before but never written -- its one consumer, the block's final
+// apply pass, recomputes it from x (cf_group_norm_apply_res_stem, norm.hip), so the launch writes one Cout-channel map instead of two.
+template <int CIN, int PY, bool STORE_R>
 __global__ void __launch_bounds__(256) stem_block_kernel(const float* __restrict__ x, const float* __restrict__ w3, const float* __restrict__ b3,
                                                          const float* __restrict__ w1, const float* __restrict__ b1, float* __restrict__ y,
                                                          float* __restrict__ r, int H, int W, int Cout, int groups,
                                                          double* __restrict__ ws_y, double* __restrict__ ws_r) {
     constexpr int NR = PY + 2;
-    __shared__ float red[2][64 * 2];          // [map][group (<= 64)]: sum, sum of squares of this block
+    __shared__ float red[2][4][64 * 2];       // [map][wave][group (<= 64)]: sum, sum of squares of each wave
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int x0 = blockIdx.x * 64 + tx, y0 = (blockIdx.y * 4 + ty) * PY, b = blockIdx.z;
     const long HW = (long)H * W;
     const float* xb = x + (long)b * CIN * HW;
     float* yb = y + (long)b * Cout * HW;
-    float* rb = r + (long)b * Cout * HW;
-    for (int k = threadIdx.x; k < 2 * groups; k += 256) red[0][k] = red[1][k] = 0.f;
-    __syncthreads();
+    float* rb = STORE_R ? r + (long)b * Cout * HW : nullptr;
     float in[CIN][NR][3];
 #pragma unroll
     for (int ci = 0; ci < CIN; ++ci)
@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(256) stem_block_kernel(const float* __restrict
                 if (ok[rr]) {
                     const long o = (long)co * HW + (long)(y0 + rr) * W + x0;
                     yb[o] = acc;
-                    rb[o] = pacc;
+                    if (STORE_R) rb[o] = pacc;
                     ys += acc;
                     yq += acc * acc;
                     rs += pacc;
@@ -86,24 +86,26 @@ __global__ void __launch_bounds__(256) stem_block_kernel(const float* __restrict
             rq += __shfl_xor(rq, o, 64);
         }
         if (tx == 0) {
-            atomicAdd(&red[0][2 * g], ys);
-            atomicAdd(&red[0][2 * g + 1], yq);
-            atomicAdd(&red[1][2 * g], rs);
-            atomicAdd(&red[1][2 * g + 1], rq);
+            red[0][ty][2 * g] = ys;
+            red[0][ty][2 * g + 1] = yq;
+            red[1][ty][2 * g] = rs;
+            red[1][ty][2 * g + 1] = rq;
         }
     }
     __syncthreads();
     for (int k = threadIdx.x; k < 4 * groups; k += 256) {
         const int m = k >= 2 * groups, j = k - m * 2 * groups;
-        atomicAdd(&(m ? ws_r : ws_y)[2L * b * groups + j], (double)red[m][j]);
+        // the four waves' sums in wave order, whichever finished first: a block's contribution is the same bits in every run and in both
+        // forms of the kernel, so two runs differ by the order of the fp64 atomics alone
+        atomicAdd(&(m ? ws_r : ws_y)[2L * b * groups + j], (double)(((red[m][0][j] + red[m][1][j]) + red[m][2][j]) + red[m][3][j]));
     }
 }
 
-template <int CIN, int PY>
+template <int CIN, int PY, bool STORE_R>
 static void launch_stem_block(const float* x, const float* w3, const float* b3, const float* w1, const float* b1, float* y, float* r, int B, int H,
                               int W, int Cout, int groups, double* ws_y, double* ws_r, hipStream_t s) {
     dim3 grid((unsigned)((W + 63) / 64), (unsigned)((H + 4 * PY - 1) / (4 * PY)), (unsigned)B);
-    hipLaunchKernelGGL((stem_block_kernel<CIN, PY>), grid, dim3(256), 0, s, x, w3, b3, w1, b1, y, r, H, W, Cout, groups, ws_y, ws_r);
+    hipLaunchKernelGGL((stem_block_kernel<CIN, PY, STORE_R>), grid, dim3(256), 0, s, x, w3, b3, w1, b1, y, r, H, W, Cout, groups, ws_y, ws_r);
 }
 
 }  // namespace cf
@@ -116,22 +118,48 @@ extern "C" int cf_stem_block_ok(int B, int Cin, int H, int W, int Cout, int gn_g
                ? 1 : 0;
 }
 
+static int stem_block_call(const char* who, const float* x, const float* w3, const float* b3, const float* w1, const float* b1, float* y, float* r, int B,
+                           int Cin, int H, int W, int Cout, double* ws_y, double* ws_r, int gn_groups, void* stream) {
+    const int groups = gn_groups < 0 ? -gn_groups : gn_groups;      // negative: the caller's workspaces are already zero
+    if (cf_stem_block_ok(B, Cin, H, W, Cout, groups) != 1) {
+        char msg[384];
+        snprintf(msg, sizeof(msg),
+                 "%s: built for Cin 1 or 6, <= 64 statistics groups dividing Cout, one output sample below 2^31 elements: B=%d Cin=%d H=%d W=%d Cout=%d groups=%d",
+                 who, B, Cin, H, W, Cout, groups);
+        set_error(msg);
+        return CF_ERR_ARG;
+    }
+    hipStream_t s = as_stream(stream);
+    if (gn_groups > 0 && (hipMemsetAsync(ws_y, 0, 2L * B * groups * sizeof(double), s) != hipSuccess ||
+                          hipMemsetAsync(ws_r, 0, 2L * B * groups * sizeof(double), s) != hipSuccess)) {
+        set_error(std::string(who) + ": memset failed");
+        return CF_ERR_LAUNCH;
+    }
+    if (r) {
+        if (Cin == 1) launch_stem_block<1, 8, true>(x, w3, b3, w1, b1, y, r, B, H, W, Cout, groups, ws_y, ws_r, s);
+        else launch_stem_block<6, 4, true>(x, w3, b3, w1, b1, y, r, B, H, W, Cout, groups, ws_y, ws_r, s);
+    } else {
+        if (Cin == 1) launch_stem_block<1, 8, false>(x, w3, b3, w1, b1, y, nullptr, B, H, W, Cout, groups, ws_y, ws_r, s);
+        else launch_stem_block<6, 4, false>(x, w3, b3, w1, b1, y, nullptr, B, H, W, Cout, groups, ws_y, ws_r, s);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error(std::string(who) + ": launch failed: " + hipGetErrorString(e));
+        return CF_ERR_LAUNCH;
+    }
+    return CF_OK;
+}
+
 extern "C" int cf_stem_block(const float* x, const float* w3, const float* b3, const float* w1, const float* b1, float* y, float* r, int B, int Cin,
                              int H, int W, int Cout, double* ws_y, double* ws_r, int gn_groups, void* stream) {
     CF_REQUIRE(x && w3 && w1 && y && r && ws_y && ws_r, "null pointer");
     CF_REQUIRE(x != y && x != r && y != r && ws_y != ws_r, "aliased pointers");
-    const int groups = gn_groups < 0 ? -gn_groups : gn_groups;      // negative: the caller's workspaces are already zero
-    CF_REQUIRE(cf_stem_block_ok(B, Cin, H, W, Cout, groups) == 1,
-               "built for Cin 1 or 6, <= 64 statistics groups dividing Cout, one output sample below 2^31 elements: B=%d Cin=%d H=%d W=%d Cout=%d groups=%d", B,
-               Cin, H, W, Cout, groups);
-    hipStream_t s = as_stream(stream);
-    if (gn_groups > 0 && (hipMemsetAsync(ws_y, 0, 2L * B * groups * sizeof(double), s) != hipSuccess ||
-                          hipMemsetAsync(ws_r, 0, 2L * B * groups * sizeof(double), s) != hipSuccess)) {
-        set_error("cf_stem_block: memset failed");
-        return CF_ERR_LAUNCH;
-    }
-    if (Cin == 1) launch_stem_block<1, 8>(x, w3, b3, w1, b1, y, r, B, H, W, Cout, groups, ws_y, ws_r, s);
-    else launch_stem_block<6, 4>(x, w3, b3, w1, b1, y, r, B, H, W, Cout, groups, ws_y, ws_r, s);
-    CF_CHECK_LAUNCH();
-    return CF_OK;
+    return stem_block_call("cf_stem_block", x, w3, b3, w1, b1, y, r, B, Cin, H, W, Cout, ws_y, ws_r, gn_groups, stream);
+}
+
+extern "C" int cf_stem_block_y(const float* x, const float* w3, const float* b3, const float* w1, const float* b1, float* y, int B, int Cin, int H,
+                               int W, int Cout, double* ws_y, double* ws_r, int gn_groups, void* stream) {
+    CF_REQUIRE(x && w3 && w1 && y && ws_y && ws_r, "null pointer");
+    CF_REQUIRE(x != y && ws_y != ws_r, "aliased pointers");
+    return stem_block_call("cf_stem_block_y", x, w3, b3, w1, b1, y, nullptr, B, Cin, H, W, Cout, ws_y, ws_r, gn_groups, stream);
 }

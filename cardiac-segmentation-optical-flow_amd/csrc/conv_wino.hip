@@ -22,7 +22,7 @@
 //   * LDS holds V (not the raw patch): [patch row][position][unit] records of 80 bytes ([hi c0..15 | lo c0..15 | 16 B pad]); the odd
 //     multiple of 16 B keeps every ds_read_b128 lane group on 16 distinct slots.  Two buffers, one barrier per chunk.
 //   * staging: a lane loads one aligned quad of columns for 4 channels (buffer_load_dwordx4), its two neighbour columns come from the
-//     adjacent lanes by DPP row shifts (the tile's outermost columns from one extra dword load of the edge lanes), the transform is
+//     adjacent lanes by DPP row shifts (the tile's outermost columns from one extra dword load of the row's first / last lane; in the persistent kernel from edge lanes of their own, see its lane map), the transform is
 //     7 additions per quad and channel, then the usual split and two ds_write_b64 per (position, unit).
 //   * weights: packed on the host in fragment order [m-tile][chunk][ky][position][hi|lo], loaded L2 -> registers two steps ahead.
 // Reference layers: DoubleConv / ConvBlocks (nnunet/lib/utils.py:1182-1215), ConvDropoutNormNonlin (generic_UNet.py:26-69), ConvGRUCell
@@ -451,9 +451,7 @@ conv_wino_kernel(const ConvParams p, const WinoGeom g, const _Float16* __restric
 // band cross samples).
 struct StageRegs {
     f32x4v stg[4];
-    float edg[4];
     f32x4v cm, ca, cs;
-    bool evalid;
 };
 
 template <int PRE>
@@ -493,27 +491,38 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
 
     if (wave >= 4) {
         // ============================================================================================================ staging waves (4 .. 7)
-        constexpr int VT = 1;                             // tasks per thread: 256 threads cover the <= 256 (row, quad, channel group) tasks of a chunk
+        // Lane map.  Each of the four waves takes a quarter of the 4 PH (patch row, channel group) rows = PH rows: PH * QW MAIN lanes (q
+        // fastest, as in conv_wino_kernel, so a row of quads sits inside a 16-lane DPP row) and behind them 2 PH EDGE lanes, one per row and side.
+        //   TW = 32: 6 rows x 8 quads = lanes 0 .. 47, edge lanes 48 .. 59;   TW = 16: 10 rows x 4 quads = lanes 0 .. 39, edge lanes 40 .. 59.
+        // An edge lane loads the aligned quad that holds its row's edge column (left: x0 - 4 .. x0 - 1, right: x0 + TW .. x0 + TW + 3) with the
+        // offsets of a main lane, so the activations every lane issues for its four columns activate the edge value too; it writes nothing to
+        // LDS.  The row's first / last quad lane fetches the activated value with ds_bpermute_b32.  (Before: every lane loaded and activated
+        // a fifth "edge" value per channel that only first / last lanes use -- one GELU in five -- and with ntask = 192 wave 7 had no task.)
+        constexpr int VT = 1;
+        const int nmain = g.PH * g.QW, el = lane - nmain;
+        const bool is_main = lane < nmain, is_edge = !is_main && el < 2 * g.PH;
+        const bool eleft = is_edge && (el & 1) == 0;
         bool has[VT], first[VT], last[VT];
         unsigned c4[VT];
-        int v_lds[VT], t_py[VT], t_q[VT];
+        int v_lds[VT], t_py[VT], t_q[VT], e_src[VT];
 #pragma unroll
         for (int t = 0; t < VT; ++t) {
-            const int task = (tid - 256) + t * 256;
-            has[t] = task < g.ntask;
-            const int q = task % g.QW;                    // lane order (q, channel group, patch row): see conv_wino_kernel
-            const int r = task / g.QW;
+            const int q = is_main ? lane % g.QW : 0;
+            const int lr = is_main ? lane / g.QW : (is_edge ? el >> 1 : 0);
+            const int r = (wave - 4) * g.PH + lr;
             const int cg = r & 3, py = r >> 2;
-            first[t] = q == 0;
-            last[t] = q == g.QW - 1;
+            has[t] = is_main;
+            first[t] = is_main && q == 0;
+            last[t] = is_main && q == g.QW - 1;
             c4[t] = (unsigned)cg * 4u;
             v_lds[t] = py * g.ROWP + 2 * q * REC + cg * 8;
             t_py[t] = py;
             t_q[t] = q;
+            e_src[t] = (nmain + 2 * lr + (last[t] ? 1 : 0)) * 4;        // ds_bpermute address of the row's edge lane (left; right for the last quad)
         }
 
         int ld_i = 0, ld_c = 0, ld_b = 0;                 // the next chunk to load: item, chunk, its sample
-        unsigned v_off[VT], e_off[VT];
+        unsigned v_off[VT];
         __amdgpu_buffer_rsrc_t rsrc1, rsrc2;
         auto setup = [&](int i) __attribute__((always_inline)) {
             int cb, b, y0, x0;
@@ -521,10 +530,11 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
 #pragma unroll
             for (int t = 0; t < VT; ++t) {
                 const int iy = y0 - 1 + t_py[t];
-                const bool row_ok = has[t] && (unsigned)iy < (unsigned)p.H;
-                v_off[t] = row_ok ? (unsigned)(iy * p.W + x0 + 4 * t_q[t]) * 4u + c4[t] * HW4 : OOB;
-                const int ecol = first[t] ? x0 - 1 : x0 + g.TW;
-                e_off[t] = (row_ok && (first[t] || last[t]) && (unsigned)ecol < (unsigned)p.W) ? (unsigned)(iy * p.W + ecol) * 4u + c4[t] * HW4 : OOB;
+                // an edge lane's quad lies wholly inside the row or wholly outside it (W % TW == 0): outside, the lane is parked like a row
+                // outside the image -- load offset AND coefficient offsets out of range, so its value stays (0 - 0) * 0 + 0 = 0 through both activations
+                const int col = is_main ? x0 + 4 * t_q[t] : (eleft ? x0 - 4 : x0 + g.TW);
+                const bool ok = (is_main || is_edge) && (unsigned)iy < (unsigned)p.H && (unsigned)col < (unsigned)p.W;
+                v_off[t] = ok ? (unsigned)(iy * p.W + col) * 4u + c4[t] * HW4 : OOB;
             }
             // per-sample resources: offsets at or past C * HW * 4 (the zero-weight channel tail of a chunk, parked lanes) read as 0
             rsrc1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x1 + (long)b * p.C1 * HW), 0, (int)((long)p.C1 * HW * 4), 0x00020000);
@@ -546,24 +556,21 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
                     const unsigned ch = (cb + (unsigned)j) * HW4;               // scalar
                     if (in1) {
                         R[t].stg[j] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rsrc1, v_off[t] + ch, 0, 0));
-                        R[t].edg[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc1, e_off[t] + ch, 0, 0));
                     } else {
                         R[t].stg[j] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rsrc2, v_off[t] + ch, 0, 0));
-                        R[t].edg[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc2, e_off[t] + ch, 0, 0));
                     }
                 }
                 if (PRE) {
                     const int c = c0 + (int)c4[t];                               // C1 % 4 == 0 (host): a quad is wholly inside or wholly the padded tail
                     const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in_norm + (long)ld_b * 3 * p.C1), 0,
                                                                                         3 * p.C1 * 4, 0x00020000);
-                    // rows outside the image take ZERO coefficients: their loads read 0, (0 - 0) * 0 + 0 = 0 and both activations map 0 to 0, so the
-                    // padding stays exactly zero without a select per value
+                    // rows (and edge quads) outside the image take ZERO coefficients: their loads read 0, (0 - 0) * 0 + 0 = 0 and both activations
+                    // map 0 to 0, so the padding stays exactly zero without a select per value
                     const unsigned o = (c < p.C1 && v_off[t] < OOB) ? (unsigned)c * 4u : OOB;
                     R[t].cm = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rn, o, 0, 0));
                     R[t].ca = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rn, o + (unsigned)p.C1 * 4u, 0, 0));
                     R[t].cs = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(rn, o + (unsigned)p.C1 * 8u, 0, 0));
                 }
-                R[t].evalid = e_off[t] < OOB;
             }
             if (ld_c + 1 < g.nchunk) ++ld_c;
             else if (ld_i + 1 < n_my) { ld_c = 0; ++ld_i; setup(ld_i); }
@@ -584,14 +591,15 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
                 float va[4][4], vb[4][4];      // [position][channel]
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    float c0 = R.stg[j][0], c1 = R.stg[j][1], c2 = R.stg[j][2], c3 = R.stg[j][3], e = R.edg[j];
+                    float c0 = R.stg[j][0], c1 = R.stg[j][1], c2 = R.stg[j][2], c3 = R.stg[j][3];
                     if (PRE) {
                         c0 = pre_apply(c0, R.cm[j], R.ca[j], R.cs[j]);
                         c1 = pre_apply(c1, R.cm[j], R.ca[j], R.cs[j]);
                         c2 = pre_apply(c2, R.cm[j], R.ca[j], R.cs[j]);
                         c3 = pre_apply(c3, R.cm[j], R.ca[j], R.cs[j]);
-                        e = R.evalid ? pre_apply(e, R.cm[j], R.ca[j], R.cs[j]) : 0.f;      // (a column outside an inside row: the coefficients are live)
                     }
+                    // the row's edge lane holds the column beside the tile: last of its quad on the left, first on the right
+                    const float e = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(e_src[t], __builtin_bit_cast(int, eleft ? c3 : c0)));
                     float left = from_lane_below(c3), right = from_lane_above(c0);
                     left = first[t] ? e : left;
                     right = last[t] ? e : right;
@@ -939,7 +947,8 @@ int launch_wino_ps(const ConvParams& p, const WinoGeom& g, const _Float16* wpk, 
 int wino_pick_ntw(const ConvParams& p, WinoGeom& g) {
     const int lvl = wino_level();
     const long cblocks = (p.Cout + 127) / 128;
-    if ((lvl == 1 || lvl == 8) && wino_geometry(p, 2, g) && g.ntask <= 256 && wino_ps_lds_bytes(g) <= 160 * 1024 &&
+    // (PH * QW main + 2 PH edge lanes per staging wave: 60 of 64 in both geometries)
+    if ((lvl == 1 || lvl == 8) && wino_geometry(p, 2, g) && g.PH * (g.QW + 2) <= 64 && wino_ps_lds_bytes(g) <= 160 * 1024 &&
         (!p.in_norm || ((p.C1 & 3) == 0 && (reinterpret_cast<uintptr_t>(p.in_norm) & 15) == 0))) {
         const long nitems = (long)g.tiles_x * g.tiles_y * p.B * cblocks;
         if (lvl == 8 || nitems >= 2L * wino_num_cus()) return 8;

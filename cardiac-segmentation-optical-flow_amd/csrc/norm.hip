@@ -219,6 +219,90 @@ __global__ void __launch_bounds__(256) gn_apply_small_kernel(const float* __rest
     }
 }
 
+// The final apply pass of a stem DoubleConv (Cin 1 or 6) whose 1x1 shortcut map r was never stored (cf_stem_block_y, conv_stem.hip):
+//   out = act(GN2(y2) [+ r']) [+ r'],  r' = (r - rm) * ra + rb,  r[c] = b1[c] + sum_ci w1[c][ci] * x[ci]
+// r is rebuilt per element with stem_block_kernel's fmaf chain (bias first, then ci in order), so it is that kernel's r bit for bit, and
+// everything behind it is gn_apply_kernel's expression with ResNorm: the output equals the stored-r pass for the same workspaces.
+// 8 bytes per output element instead of 12.  Blocking: a workgroup owns 1024 consecutive pixels of ONE sample -- a float4 per thread,
+// whose CIN input values stay in registers -- and walks all C channels, so x is read once per block and not once per channel; the
+// per-channel scalars (both norms' coefficients from the fp64 sums, the 1x1 weights) are formed once per block in LDS.  y2 is loaded
+// four channels ahead of the stores: out may be y2 itself (a thread reads only the elements it writes), so neither is __restrict__.
+constexpr int STEM_APPLY_MAXC = 128, STEM_APPLY_CB = 4;
+template <int CIN>
+__global__ void __launch_bounds__(256) gn_apply_stem_kernel(const float* y2, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            const double* __restrict__ ws, const float* __restrict__ x,
+                                                            const float* __restrict__ w1, const float* __restrict__ b1, float* out, int C, int HW,
+                                                            int groups, float eps, int act, int res_mode, ResNorm rn) {
+    __shared__ float tab[STEM_APPLY_MAXC][8 + CIN];       // mean, rstd, gamma, beta, rm, ra, rb, b1, w1[CIN]
+    const int b = blockIdx.y;
+    const int cpg = C / groups;
+    const double invL = 1.0 / ((double)cpg * HW);
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const long slab = (long)b * groups + c / cpg;
+        const double mean_d = ws[2 * slab] * invL;
+        double var = ws[2 * slab + 1] * invL - mean_d * mean_d;
+        if (var < 0.0) var = 0.0;
+        const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+        const float mean = (float)mean_d;
+        const float g = gamma ? gamma[c] : 1.f, bb = beta ? beta[c] : 0.f;
+        const double rmean = rn.ws[2 * slab] * invL;
+        double rvar = rn.ws[2 * slab + 1] * invL - rmean * rmean;
+        if (rvar < 0.0) rvar = 0.0;
+        const float rrstd = (float)(1.0 / sqrt(rvar + (double)eps)), rg = rn.gamma ? rn.gamma[c] : 1.f;
+        float* t = tab[c];
+        t[0] = mean;
+        t[1] = rstd;
+        t[2] = g;
+        t[3] = bb;
+        t[4] = (float)rmean;
+        t[5] = rrstd * rg;
+        t[6] = rn.beta ? rn.beta[c] : 0.f;
+        t[7] = b1 ? b1[c] : 0.f;
+#pragma unroll
+        for (int ci = 0; ci < CIN; ++ci) t[8 + ci] = w1[c * CIN + ci];
+    }
+    __syncthreads();
+    const int i = blockIdx.x * 256 + threadIdx.x;          // float4 of the plane
+    if (i >= (HW >> 2)) return;
+    float xin[CIN][4];
+#pragma unroll
+    for (int ci = 0; ci < CIN; ++ci) {
+        const float4 v = *reinterpret_cast<const float4*>(x + ((long)b * CIN + ci) * HW + 4L * i);
+        xin[ci][0] = v.x, xin[ci][1] = v.y, xin[ci][2] = v.z, xin[ci][3] = v.w;
+    }
+    const long base = (long)b * C * HW + 4L * i;
+    for (int c0 = 0; c0 < C; c0 += STEM_APPLY_CB) {
+        float4 v[STEM_APPLY_CB];
+#pragma unroll
+        for (int j = 0; j < STEM_APPLY_CB; ++j)
+            if (c0 + j < C) v[j] = NT_LOAD4(y2 + base + (long)(c0 + j) * HW);
+#pragma unroll
+        for (int j = 0; j < STEM_APPLY_CB; ++j) {
+            if (c0 + j >= C) break;
+            const float* tc = tab[c0 + j];
+            const float mean = tc[0], rstd = tc[1], g = tc[2], bb = tc[3], rm = tc[4], ra = tc[5], rb = tc[6], bv1 = tc[7];
+            float t[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
+            float rr[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float pacc = bv1;
+#pragma unroll
+                for (int ci = 0; ci < CIN; ++ci) pacc = fmaf(tc[8 + ci], xin[ci][k], pacc);
+                rr[k] = (pacc - rm) * ra + rb;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float y = (t[k] - mean) * rstd * g + bb;
+                if (res_mode == CF_RES_BEFORE_ACT) y += rr[k];
+                y = act_apply(y, act);
+                if (res_mode == CF_RES_AFTER_ACT) y += rr[k];
+                t[k] = y;
+            }
+            NT_STORE4(out + base + (long)(c0 + j) * HW, t[0], t[1], t[2], t[3]);
+        }
+    }
+}
+
 // LayerNorm over C of channel-first tokens [B, C, N].  Block = 64 consecutive tokens (lanes: coalesced along N) x 8 waves,
 // wave g owning channels g, g+8, ...: fp64 partial sums per thread, one LDS combine, then the affine pass.  Up to 32
 // channels per thread stay in registers between the two passes (C <= 256); larger C re-reads (L2 hits).
@@ -427,6 +511,40 @@ extern "C" int cf_group_norm_apply_res_norm(const float* x, const float* gamma, 
     CF_REQUIRE(res_mode == CF_RES_BEFORE_ACT || res_mode == CF_RES_AFTER_ACT, "a normalised residual needs a residual mode, got %d", res_mode);
     CF_REQUIRE(act >= CF_ACT_NONE && act <= CF_ACT_SIGMOID, "bad activation %d", act);
     return gn_apply_launch(x, gamma, beta, res, out, B, C, HW, groups, eps, act, res_mode, ws, as_stream(stream), ResNorm{res_ws, res_gamma, res_beta});
+}
+
+// cf_group_norm_apply_res_norm for a stem DoubleConv whose shortcut map was never stored: the residual r = conv1x1(x; w1, b1) is rebuilt
+// from the block's Cin-channel input inside the pass (gn_apply_stem_kernel); res_ws holds r's statistics from cf_stem_block_y.
+extern "C" int cf_group_norm_apply_res_stem_ok(int B, int Cin, int C, int H, int W, int groups) {
+    const double hw = (double)H * W;
+    return (Cin == 1 || Cin == 6) && B > 0 && B < 65536 && H > 0 && W > 0 && C > 0 && C <= STEM_APPLY_MAXC && groups > 0 && C % groups == 0 &&
+                   hw >= 2048.0 && hw < 2147483648.0 && ((long)H * W & 3) == 0 && (double)(C / groups) * hw < 2147483648.0
+               ? 1 : 0;
+}
+
+extern "C" int cf_group_norm_apply_res_stem(const float* y2, const float* gamma, const float* beta, const double* ws, const float* x, const float* w1,
+                                            const float* b1, const double* res_ws, const float* res_gamma, const float* res_beta, float* out, int B,
+                                            int Cin, int C, int H, int W, int groups, float eps, int act, int res_mode, void* stream) {
+    CF_REQUIRE(y2 && ws && x && w1 && res_ws && out, "null pointer");
+    CF_REQUIRE(x != y2 && x != out, "the block's input aliases a map");
+    CF_REQUIRE(cf_group_norm_apply_res_stem_ok(B, Cin, C, H, W, groups) == 1,
+               "built for Cin 1 or 6, C <= %d, groups dividing C, H * W >= 2048 and a multiple of 4: B=%d Cin=%d C=%d H=%d W=%d groups=%d", STEM_APPLY_MAXC,
+               B, Cin, C, H, W, groups);
+    CF_REQUIRE(((reinterpret_cast<uintptr_t>(y2) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+               "y2, x and out must be 16-byte aligned");
+    CF_REQUIRE(res_mode == CF_RES_BEFORE_ACT || res_mode == CF_RES_AFTER_ACT, "a normalised residual needs a residual mode, got %d", res_mode);
+    CF_REQUIRE(act >= CF_ACT_NONE && act <= CF_ACT_SIGMOID, "bad activation %d", act);
+    const int HW = H * W;
+    const dim3 grid((unsigned)((HW / 4 + 255) / 256), (unsigned)B);
+    const ResNorm rn{res_ws, res_gamma, res_beta};
+    if (Cin == 1)
+        hipLaunchKernelGGL((gn_apply_stem_kernel<1>), grid, dim3(256), 0, as_stream(stream), y2, gamma, beta, ws, x, w1, b1, out, C, HW, groups, eps, act,
+                           res_mode, rn);
+    else
+        hipLaunchKernelGGL((gn_apply_stem_kernel<6>), grid, dim3(256), 0, as_stream(stream), y2, gamma, beta, ws, x, w1, b1, out, C, HW, groups, eps, act,
+                           res_mode, rn);
+    CF_CHECK_LAUNCH();
+    return CF_OK;
 }
 
 static int gn_apply_launch(const float* x, const float* gamma, const float* beta, const float* res, float* out, int B, int C, int HW,

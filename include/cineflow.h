@@ -438,6 +438,21 @@ int cf_conv2d_small_cout_norm2(const float* y2, const float* coef2, const float*
 int cf_stem_block_ok(int B, int Cin, int H, int W, int Cout, int gn_groups);
 int cf_stem_block(const float* x, const float* w3, const float* b3, const float* w1, const float* b1, float* y, float* r, int B, int Cin,
                   int H, int W, int Cout, double* ws_y, double* ws_r, int gn_groups, void* stream);
+/* cf_stem_block without the store of r, for a block whose output is applied by cf_group_norm_apply_res_stem: the same kernel writes y
+ * and ws_y and accumulates r's statistics into ws_r, but r itself is never written (its one consumer recomputes it from x).  y is bit
+ * equal to cf_stem_block's; same shapes (cf_stem_block_ok), same zeroing rule for gn_groups. */
+int cf_stem_block_y(const float* x, const float* w3, const float* b3, const float* w1, const float* b1, float* y, int B, int Cin, int H, int W,
+                    int Cout, double* ws_y, double* ws_r, int gn_groups, void* stream);
+/* The final apply pass of that block: out = act(GN(y2) [+ r']) [+ r'] as cf_group_norm_apply_res_norm forms it, with the raw residual
+ * r = conv1x1(x; w1, b1) rebuilt per element from the block's input x [B][Cin][H][W] (w1 fp32 [C][Cin], b1 may be NULL) in cf_stem_block's
+ * summation order, so that out is bit equal to cf_group_norm_apply_res_norm fed with the r cf_stem_block stores and the same workspaces.
+ * ws / res_ws: the statistics of y2 / of r (fp64 [B][groups][2]); out may be y2.  cf_group_norm_apply_res_stem_ok (host code, no
+ * launch) returns 1 when the kernel takes the shape: Cin 1 or 6, C <= 128, H * W >= 2048 and a multiple of 4; the call fails with
+ * CF_ERR_ARG otherwise, and the caller keeps the stored-r pass. */
+int cf_group_norm_apply_res_stem_ok(int B, int Cin, int C, int H, int W, int groups);
+int cf_group_norm_apply_res_stem(const float* y2, const float* gamma, const float* beta, const double* ws, const float* x, const float* w1,
+                                 const float* b1, const double* res_ws, const float* res_gamma, const float* res_beta, float* out, int B, int Cin,
+                                 int C, int H, int W, int groups, float eps, int act, int res_mode, void* stream);
 
 /* ---------------------------------------------------------------- test-time preprocessing (the step before the path)
  * create_nonzero_mask, nnunet/preprocessing/cropping.py:25-32: mask[v] = any_c data[c][v] != 0 (uint8 [V]). */

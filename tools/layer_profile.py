@@ -50,6 +50,13 @@ def shape_key(name, args, kw):
         x, w3 = args[0], args[1]
         B, C, H, W = x.shape
         return "stem_block B%d C%d %dx%d -> 2 x %d" % (B, C, H, W, w3.shape[0]), 2.0 * B * H * W * w3.shape[0] * C * 10
+    if name == "stem_block_y":              # (x, w3, b3, w1, b1, groups): the 3x3 map stored, the 1x1 map only summed
+        x, w3 = args[0], args[1]
+        B, C, H, W = x.shape
+        return "stem_block_y B%d C%d %dx%d -> %d" % (B, C, H, W, w3.shape[0]), 2.0 * B * H * W * w3.shape[0] * C * 10
+    if name == "group_norm_apply_res_stem":  # (y2, gamma, beta, groups, ws, x, w1, ...): the final pass that rebuilds the 1x1 map
+        y2, x = args[0], args[5]
+        return "group_norm_apply_res_stem %s Cin%d" % ("x".join(str(s) for s in y2.shape), x.shape[1]), 2.0 * y2.numel() * x.shape[1]
     if name.startswith("conv_transpose"):
         x = args[0]
         B, C, H, W = x.shape
@@ -91,7 +98,7 @@ def main():
     lab[:, 100:156, 100:156] = 1
     bench.run_step(fnet, snet, frames, lab)
     torch.cuda.synchronize()
-    for n in ("conv2d_f16s", "conv2d_f16s_prenorm", "conv2d_wino", "conv2d_wino_prenorm", "conv2d_small_cin", "stem_block", "conv2d_small_cout", "conv2d_small_cout_norm2", "group_norm_coef", "conv_transpose2d_k2s2_f16s", "group_norm_apply", "group_norm", "layer_norm_cf", "attention_cf", "corr_volume",
+    for n in ("conv2d_f16s", "conv2d_f16s_prenorm", "conv2d_wino", "conv2d_wino_prenorm", "conv2d_small_cin", "stem_block", "stem_block_y", "conv2d_small_cout", "conv2d_small_cout_norm2", "group_norm_coef", "conv_transpose2d_k2s2_f16s", "group_norm_apply", "group_norm_apply_res_stem", "group_norm", "layer_norm_cf", "attention_cf", "corr_volume",
               "warp_bilinear", "binary", "copy_channels", "gru_reset_mul", "gru_blend", "tta_accumulate", "warp_labels", "memory_input"):
         if hasattr(ops, n):
             wrap(n)
