@@ -5,6 +5,8 @@ Mirrors nnunet/evaluation/metrics.py (ConfusionMatrix and the metric functions, 
 per-frame statistics of nnunet/compute_jacobian.py.  numpy arrays or device tensors in, Python floats out like the reference.
 Counting, border extraction, nearest-border distances and reductions are HIP kernels (csrc/metrics.hip); the 95th percentile of
 hausdorff_distance_95 is taken by numpy on the downloaded distance vector (a few thousand values).
+cine_label_scores / cine_jacobian_table (csrc/score.hip) give the same figures for all frames, classes and slices of a patient in one
+device visit; cineflow.score writes the scripts' tables from them.
 """
 import numpy as np
 import torch
@@ -385,6 +387,134 @@ def gradient_means(slice_flow):
     check(lib().cf_slab_abs_sum(_f32(g), 6, 1, T, H * W, sums.data_ptr(), _stream()), "cf_slab_abs_sum")
     s = sums.cpu().numpy().reshape(2, 3, T)
     return s[:, 2].sum(0) / (2 * H * W), s[:, :2].sum((0, 1)) / (4 * H * W)
+
+
+# ------------------------------------------------------------------------------------------------ one visit per patient
+def _labels_u8(a):
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.to(_dev()).to(torch.uint8).contiguous()
+
+
+def label_surface_table(test, reference, num_classes, voxel_spacing=None):
+    """All frames and classes of a patient in two library calls (cf_label_surface_count, cf_label_surface_table) and three reads.
+
+    test / reference: label stacks [N, H, W] (2-D frames) or [N, D, H, W] (3-D frames), labels < num_classes <= 16.  Returns
+    (table, dist, offsets): table float64 [N, K, 9] = {TP, FP, FN, border voxels of test, of reference, max test->ref, max ref->test,
+    sum test->ref, sum ref->test} of `test == c` vs `reference == c` (row 0, the background, is not scored and stays zero); dist the
+    directed nearest-border distances of every border voxel; offsets int [N, K, 2, 2]: the distances of (n, c, side) -- side 0 test->ref,
+    1 ref->test -- are dist[offsets[n, c, side, 0]:offsets[n, c, side, 1]], in compaction order.  Where one side of a pair has no border the
+    other side's distances are not computed (NaN).  The distance search is brute force: cine-sized objects, not hundreds of thousands of
+    border voxels."""
+    t, r = _labels_u8(test), _labels_u8(reference)
+    assert_shape(t, r)
+    assert t.dim() in (3, 4), "label stacks are [N, H, W] or [N, D, H, W]"
+    nd = t.dim() - 1
+    N = t.shape[0]
+    D, H, W = (1,) * (3 - nd) + tuple(t.shape[1:])
+    K = int(num_classes)
+    sp = np.ones(nd) if voxel_spacing is None else np.asarray(voxel_spacing, dtype=np.float64) * np.ones(nd)
+    sz, sy, sx = ([1.0] * (3 - nd) + [float(v) for v in sp])
+    ws = torch.empty(11 * N * K + 3, dtype=torch.int32, device=t.device)
+    table = torch.empty(9 * N * K + 1, dtype=torch.float64, device=t.device)
+    check(lib().cf_label_surface_count(_u8(t), _u8(r), N, D, H, W, nd, K, ws.data_ptr(), table.data_ptr(), _stream()), "cf_label_surface_count")
+    S = 2 * N * K
+    scans = ws[5 * N * K + 1:5 * N * K + 1 + 2 * (S + 1)].cpu().numpy()
+    offs, blk = scans[:S + 1].astype(np.int64), scans[S + 1:]
+    total, nblocks = int(offs[S]), int(blk[S])
+    coords = torch.empty(3 * max(total, 1), dtype=torch.int32, device=t.device)
+    dist = torch.full((max(total, 1),), float("nan"), dtype=torch.float64, device=t.device)
+    check(lib().cf_label_surface_table(_u8(t), _u8(r), N, D, H, W, nd, K, sz, sy, sx, ws.data_ptr(), total, nblocks, coords.data_ptr(), dist.data_ptr(),
+                                       table.data_ptr(), _stream()), "cf_label_surface_table")
+    tab = table.cpu().numpy()
+    if tab[-1]:
+        raise ValueError("label_surface_table: %d voxels carry a label >= num_classes=%d" % (int(tab[-1]), K))
+    d = dist.cpu().numpy()[:total]
+    return tab[:-1].reshape(N, K, 9), d, np.stack([offs[:-1], offs[1:]], -1).reshape(N, K, 2, 2)
+
+
+def cine_label_scores(test, reference, num_classes, voxel_spacing=None, reproducible=True):
+    """Dice, Hausdorff distance and surface distances of every frame and class of a patient from one label_surface_table visit: what
+    nnunet/compute_metrics.py:96-106 asks of dice / hausdorff_distance / avg_surface_distance_symmetric frame by frame and class by class.
+
+    Returns a dict of float64 arrays [N, K]: dice, hd, asd_test_to_ref, asd_ref_to_test, assd, hd95 (column 0, the background, is NaN).
+    The existence rules are those of `dice` and `_surface_metric`: Dice is NaN when both masks are empty, the surface metrics when a mask
+    is empty or fills the frame.  reproducible=True takes the means from each segment's distances sorted on the host (the rule of
+    _mean_distance), so a value does not depend on the order of the border compaction; False divides the device sums.  Brute-force
+    distance search: cine-sized objects only."""
+    tab, dist, offs = label_surface_table(test, reference, num_classes, voxel_spacing)
+    N, K = tab.shape[:2]
+    V = int(np.prod(np.shape(test)[1:]))
+    out = {k: np.full((N, K), np.nan) for k in ("dice", "hd", "asd_test_to_ref", "asd_ref_to_test", "assd", "hd95")}
+    for n in range(N):
+        for c in range(1, K):
+            tp, fp, fn = (int(v) for v in tab[n, c, :3])
+            nt, nr = tp + fp, tp + fn
+            if nt or nr:
+                out["dice"][n, c] = float(2. * tp / (2 * tp + fp + fn))
+            if nt in (0, V) or nr in (0, V):
+                continue
+            d1, d2 = (dist[offs[n, c, s, 0]:offs[n, c, s, 1]] for s in (0, 1))
+            if reproducible:
+                m1, m2 = float(np.sum(np.sort(d1)) / d1.size), float(np.sum(np.sort(d2)) / d2.size)
+            else:
+                m1, m2 = float(tab[n, c, 7] / d1.size), float(tab[n, c, 8] / d2.size)
+            out["hd"][n, c] = max(float(tab[n, c, 5]), float(tab[n, c, 6]))
+            out["asd_test_to_ref"][n, c], out["asd_ref_to_test"][n, c] = m1, m2
+            out["assd"][n, c] = float(np.mean((m1, m2)))
+            out["hd95"][n, c] = float(np.percentile(np.hstack((d1, d2)), 95))
+    return out
+
+
+def flow_regularity_table(flow, labels, num_classes):
+    """cf_flow_regularity_table: flow [T, H, W, D, 2] (the stacked `flow` arrays of a patient's .npz files), labels [T, H, W, D] ->
+    float64 [T, D, 5 + 3 K]: {sum |d/dt|, sum |d/dy| + |d/dx|} of both components, then {sum J, count, #(J < 0)} per label k < K and for
+    the whole slice.  One call and one read; the same bits on every run."""
+    f = (flow if torch.is_tensor(flow) else torch.from_numpy(np.ascontiguousarray(flow))).to(_dev(), dtype=torch.float32)
+    assert f.dim() == 5 and f.shape[-1] == 2, "flow has to be [T, H, W, D, 2]"
+    T, H, W, D, _ = f.shape
+    g = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(labels))
+    assert tuple(g.shape) == (T, H, W, D), "Shape mismatch: flow {} and labels {}".format(tuple(f.shape), tuple(g.shape))
+    g = g.to(_dev())
+    K = int(num_classes)
+    if g.dtype != torch.uint8:
+        g = torch.where((g >= 0) & (g < K), g, torch.full_like(g, 255)).to(torch.uint8)
+    f = f.permute(0, 3, 4, 1, 2).contiguous()                                   # [T, D, 2, H, W]
+    g = g.permute(0, 3, 1, 2).contiguous()                                      # [T, D, H, W]
+    cols = 5 + 3 * K
+    part = torch.empty(T * D * (-(-H // 32)) * (-(-W // 64)) * cols, dtype=torch.float64, device=f.device)
+    table = torch.empty(T * D * cols, dtype=torch.float64, device=f.device)
+    check(lib().cf_flow_regularity_table(_f32(f), _u8(g), T, D, H, W, K, part.data_ptr(), table.data_ptr(), _stream()), "cf_flow_regularity_table")
+    return table.cpu().numpy().reshape(T, D, cols)
+
+
+def cine_jacobian_table(flow, labels, names=("RV", "MYO", "LV")):
+    """compute_jacobian.py:141-198 for one patient: flow [T, H, W, D, 2], labels [T, H, W, D] (structures = labels 1..len(names)) -> one
+    dict per (slice, frame), slices outermost like the script, holding `Temporal gradient`, `Spatial gradient` (gradient_means) and the
+    keys of jacobian_frame_stats."""
+    K = len(names) + 1
+    tab = flow_regularity_table(flow, labels, K)
+    T, D = tab.shape[:2]
+    H, W = int(np.shape(flow)[1]), int(np.shape(flow)[2])
+    rows = []
+    for d in range(D):
+        for t in range(T):
+            v = tab[t, d]
+            res = {"Temporal gradient": float(v[0] / (2 * H * W)), "Spatial gradient": float(v[1] / (4 * H * W))}
+            for i, k in enumerate(names, 1):
+                s, total, neg = v[2 + 3 * i:5 + 3 * i]
+                res["abs(Mean jacobian - 1)_" + k] = float(abs(s / total - 1)) if total else float("nan")
+                res["total_" + k] = float(total)
+                res["negative_" + k] = float(neg)
+                res["negative_%_" + k] = float((neg / total) * 100) if total else float("nan")
+            res["abs(Mean jacobian - 1)_average"] = sum(res["abs(Mean jacobian - 1)_" + k] for k in names) / 3
+            res["negative_%_average"] = sum(res["negative_%_" + k] for k in names) / 3
+            s, total, neg = v[2 + 3 * K:5 + 3 * K]
+            res["abs(Mean jacobian - 1)"] = float(abs(s / total - 1))
+            res["total"] = float(total)
+            res["negative"] = float(neg)
+            res["negative_%"] = float((neg / total) * 100)
+            rows.append(res)
+    return rows
 
 
 # ------------------------------------------------------------------------------------------------ compute_SSIM*.py

@@ -1,0 +1,377 @@
+"""The tables the reference's users read after a cine prediction, from this project's output folders, one device visit per patient.
+
+    python -m cineflow.score seg      -pred FOLDER -ref GT_FOLDER    [-i INPUT_FOLDER] [--gt frame|ed] [--layout predict|saver]
+    python -m cineflow.score jacobian -flow FOLDER -l LABEL_FOLDER   [-i INPUT_FOLDER] [--layout predict|saver]
+
+`seg` writes what nnunet/compute_metrics.py writes -- segmentation_metrics.json, segmentation_metrics.csv, segmentation_metrics_es.csv:
+Dice, Hausdorff distance and average symmetric surface distance of the propagated labels (RV = 1, MYO = 2, LV = 3) per frame --
+and `jacobian` what nnunet/compute_jacobian.py writes -- jacobian.json, jacobian_metrics.csv: the Jacobian statistics and flow
+gradients per slice and frame.  Both are written from the scripts' behaviour, not transcribed: the scripts' hard-coded paths, pickles
+and `patient029` special cases are arguments or gone, and the numbers of a patient come from cineflow.metrics.cine_label_scores /
+cine_jacobian_table (csrc/score.hip) instead of one call chain per frame and class.
+
+Layouts (one sub-folder per patient either way):
+    predict   <FOLDER>/<patient>/Registered/<case>.nii.gz, <FOLDER>/<patient>/Flow/<case>.npz          (cineflow.predict)
+    saver     <FOLDER>/Postprocessed/Registered/<patient>/[temp_allClasses/]<case>.nii.gz,
+              <FOLDER>/Postprocessed/Flow/<patient>/<case>.npz                                          (cineflow.voxelmorph_saver)
+A case's frame number is int(stem[-2:]); cases are sorted by it.  ED / ES indices come from INPUT_FOLDER/<patient>/<patient>.csv
+(cineflow.predict.get_ed_es_indices), both 0 without -i; the frame number of index k is k + 1.
+
+A thread pool reads and inflates the next patient's files while the current one is scored; one patient is resident on the device at a
+time and only this process opens the GPU.  Turning per-case rows into the json / csv documents is host code (segmentation_tables,
+jacobian_tables).
+"""
+import collections
+import csv
+import json
+import os
+import warnings
+import zipfile
+import zlib
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+from .nifti import read_nifti
+
+join = os.path.join
+
+STRUCTURES = ("RV", "MYO", "LV")
+SEG_METRICS = ("Dice", "HD", "ASSD")
+SEG_COLUMNS = ["Name", "Average_Dice", "Average_HD", "Average_ASSD"] + ["%s_%s" % (s, m) for s in STRUCTURES for m in SEG_METRICS]
+READERS = 8
+
+# one file of a patient: `name` the stem, `frame` its number (int(stem[-2:])), `path` the file, `other` its reference / label file
+Case = collections.namedtuple("Case", "name frame path other")
+
+
+# ------------------------------------------------------------------------------------------------ discovery
+def frame_number(stem):
+    return int(stem[-2:])
+
+
+def _stem(fname, suffix):
+    return os.path.basename(fname)[:-len(suffix)]
+
+
+def patient_folders(folder, layout, kind):
+    """{patient: folder holding its `kind` ('Registered' or 'Flow') files}, patients sorted"""
+    if layout == "predict":
+        found = {p: join(folder, p, kind) for p in sorted(os.listdir(folder))}
+    elif layout == "saver":
+        root = join(folder, "Postprocessed", kind)
+        if not os.path.isdir(root):
+            raise ValueError("%s: no Postprocessed/%s folder (the saver layout)" % (folder, kind))
+        found = {p: join(root, p) for p in sorted(os.listdir(root))}
+        if kind == "Registered":
+            found = {p: join(d, "temp_allClasses") if os.path.isdir(join(d, "temp_allClasses")) else d for p, d in found.items()}
+    else:
+        raise ValueError("layout must be 'predict' or 'saver', got %r" % (layout,))
+    return collections.OrderedDict((p, d) for p, d in found.items() if os.path.isdir(d))
+
+
+def sorted_cases(folder, suffix):
+    """the stems of the `suffix` files of a folder, sorted by frame number"""
+    return sorted((_stem(f, suffix) for f in os.listdir(folder) if f.endswith(suffix)), key=frame_number)
+
+
+def ed_es_indices(input_folder, patient):
+    if input_folder is None:
+        return 0, 0
+    from .predict import get_ed_es_indices
+    return get_ed_es_indices(join(input_folder, patient, patient + ".csv"))
+
+
+def reference_name(stem, gt_mode, ed_index):
+    """the GT case a predicted case is scored against: its own frame, or the ED frame's (frame digits <- ed_index + 1, zero-filled)"""
+    if gt_mode == "frame":
+        return stem
+    if gt_mode == "ed":
+        return stem[:-2] + str(ed_index + 1).zfill(2)
+    raise ValueError("--gt must be 'frame' or 'ed', got %r" % (gt_mode,))
+
+
+def pair_segmentation_cases(pred_folder, gt_folder, gt_mode="frame", ed_index=0):
+    """Cases of one patient folder with their GT files, sorted by frame number; cases without a GT file are skipped."""
+    cases = []
+    for stem in sorted_cases(pred_folder, ".nii.gz"):
+        gt = join(gt_folder, reference_name(stem, gt_mode, ed_index) + ".nii.gz")
+        if os.path.isfile(gt):
+            cases.append(Case(stem, frame_number(stem), join(pred_folder, stem + ".nii.gz"), gt))
+    return cases
+
+
+def label_file(label_folder, patient, stem):
+    for cand in (join(label_folder, stem + ".nii.gz"), join(label_folder, patient, stem + ".nii.gz"),
+                 join(label_folder, patient, "Segmentation", stem + ".nii.gz")):
+        if os.path.isfile(cand):
+            return cand
+    return None
+
+
+def _nifti_shape(path):
+    """(Z, Y, X) from the header alone"""
+    with open(path, "rb") as f:
+        raw = f.read()
+    head = zlib.decompressobj(wbits=31).decompress(raw, 352) if str(path).endswith(".gz") else raw[:352]
+    dim = np.frombuffer(head, dtype="<i2", count=8, offset=40)
+    return (max(int(dim[3]), 1) if dim[0] >= 3 else 1, max(int(dim[2]), 1), int(dim[1]))
+
+
+def _npz_shape(path, key):
+    with zipfile.ZipFile(path) as z, z.open(key + ".npy") as f:
+        version = np.lib.format.read_magic(f)
+        read = np.lib.format.read_array_header_1_0 if version == (1, 0) else np.lib.format.read_array_header_2_0
+        return tuple(read(f)[0])
+
+
+def pair_jacobian_cases(flow_folder, label_folder, patient, ed_index=None):
+    """Flow files of one patient with their label volumes, sorted by frame number, the ED frame's file (frame number ed_index + 1) left out
+    when ed_index is known.  A missing or mis-shaped label volume is a ValueError naming the case (headers only: nothing is inflated)."""
+    cases = []
+    for stem in sorted_cases(flow_folder, ".npz"):
+        if ed_index is not None and frame_number(stem) == ed_index + 1:
+            continue
+        lab = label_file(label_folder, patient, stem)
+        if lab is None:
+            raise ValueError("case %s: no label volume %s.nii.gz in %s (flat, per patient or <patient>/Segmentation)" % (stem, stem, label_folder))
+        fshape = _npz_shape(join(flow_folder, stem + ".npz"), "flow")
+        if len(fshape) != 4 or fshape[3] != 2:
+            raise ValueError("case %s: flow of shape %s, expected [H, W, D, 2]" % (stem, fshape))
+        Z, Y, X = _nifti_shape(lab)
+        if (Y, X, Z) != fshape[:3]:
+            raise ValueError("case %s: label volume %s is [Z, Y, X] = %s, the flow [H, W, D] = %s" % (stem, lab, (Z, Y, X), fshape[:3]))
+        cases.append(Case(stem, frame_number(stem), join(flow_folder, stem + ".npz"), lab))
+    return cases
+
+
+# ------------------------------------------------------------------------------------------------ host tables
+def segmentation_row(name, scores):
+    """one csv row (the thirteen columns) from {'RV': {'Dice', 'HD', 'ASSD'}, 'MYO': ..., 'LV': ...}"""
+    row = {"Name": name}
+    for m in SEG_METRICS:
+        row["Average_" + m] = (scores["RV"][m] + scores["MYO"][m] + scores["LV"][m]) / 3
+    for s in STRUCTURES:
+        for m in SEG_METRICS:
+            row["%s_%s" % (s, m)] = scores[s][m]
+    return {k: row[k] for k in SEG_COLUMNS}
+
+
+def segmentation_tables(cases):
+    """cases: per-case dicts {'patient', 'name', 'test', 'reference', 'is_es', 'scores': {structure: {'Dice', 'HD', 'ASSD'}}} in patient and
+    frame order -> (json document, csv rows, ES csv rows).  mean is np.nanmean over all cases, std is np.std (NaN as soon as one case is)."""
+    doc = {"all": collections.OrderedDict(), "mean": {}, "std": {}}
+    rows, es_rows, flat = [], [], []
+    for c in cases:
+        entry = {s: {m: float(c["scores"][s][m]) for m in SEG_METRICS} for s in STRUCTURES}
+        entry["test"], entry["reference"] = c["test"], c["reference"]
+        doc["all"].setdefault(c["patient"], []).append(entry)
+        flat.append(entry)
+        row = segmentation_row(c["name"], entry)
+        rows.append(row)
+        if c["is_es"]:
+            es_rows.append(row)
+    for s in STRUCTURES:
+        doc["mean"][s], doc["std"][s] = {}, {}
+        for m in SEG_METRICS:
+            col = np.array([e[s][m] for e in flat], dtype=np.float64)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", category=RuntimeWarning)                    # an all-NaN or empty column: NaN, like numpy
+                doc["mean"][s][m] = float(np.nanmean(col)) if col.size else float("nan")
+                doc["std"][s][m] = float(np.std(col)) if col.size else float("nan")
+    return doc, rows, es_rows
+
+
+JACOBIAN_ES_KEYS = (("ES_negative_%", "negative_%"), ("ES_negative_%_average", "negative_%_average")) + \
+    tuple(("ES_negative_%_average_" + k, "negative_%_" + k) for k in STRUCTURES)
+
+
+def jacobian_rows(names, stats, es_position):
+    """names[t]: case of frame position t; stats: cine_jacobian_table's dicts (slices outermost); es_position: position of the ES frame in
+    `names` (None: no row is the ES row) -> the script's rows: Name, Slice nb, Frame nb, the gradients and statistics, and the five ES_*
+    columns, which hold the row's own figures on the ES frame and NaN elsewhere."""
+    T = len(names)
+    assert len(stats) % T == 0
+    rows = []
+    for i, st in enumerate(stats):
+        d, t = divmod(i, T)
+        row = collections.OrderedDict([("Name", names[t]), ("Slice nb", float(d)), ("Frame nb", float(t))])
+        row.update(st)
+        for es_key, key in JACOBIAN_ES_KEYS:
+            row[es_key] = row[key] if t == es_position else float("nan")
+        rows.append(row)
+    return rows
+
+
+def jacobian_tables(rows):
+    """rows of every patient -> the json document {'all': rows, 'mean': ...} with the script's `mean` keys: plain means (NaN as soon as one
+    row is -- so the per-structure ES_negative_%_average_* means are NaN whenever a non-ES row exists), nanmeans for the two ES_*_mean
+    keys, and the negative_% of the summed counts."""
+    col = lambda k: np.array([r[k] for r in rows], dtype=np.float64)          # noqa: E731
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        mean = collections.OrderedDict()
+        mean["Temporal gradient"] = float(col("Temporal gradient").mean())
+        mean["Spatial gradient"] = float(col("Spatial gradient").mean())
+        mean["abs(Mean jacobian - 1)"] = float(col("abs(Mean jacobian - 1)").mean())
+        mean["total_sum"] = float(col("total").sum())
+        mean["negative_sum"] = float(col("negative").sum())
+        mean["negative_%"] = float(np.float64(mean["negative_sum"]) / np.float64(mean["total_sum"]) * 100)
+        mean["ES_negative_%_mean"] = float(np.nanmean(col("ES_negative_%")))
+        mean["negative_%_mean"] = float(col("negative_%").mean())
+        mean["negative_%_mean_average"] = float(col("negative_%_average").mean())
+        mean["abs(Mean jacobian - 1)_average"] = float(col("abs(Mean jacobian - 1)_average").mean())
+        mean["ES_negative_%_mean_average"] = float(np.nanmean(col("ES_negative_%_average")))
+        for k in STRUCTURES:
+            mean["negative_sum_" + k] = float(col("negative_" + k).sum())
+            mean["total_sum_" + k] = float(col("total_" + k).sum())
+            mean["negative_%_" + k] = float(np.float64(mean["negative_sum_" + k]) / np.float64(mean["total_sum_" + k]) * 100)
+            mean["negative_%_mean_" + k] = float(col("negative_%_" + k).mean())
+            mean["abs(Mean jacobian - 1)_" + k] = float(col("abs(Mean jacobian - 1)_" + k).mean())
+            mean["ES_negative_%_average_" + k] = float(col("ES_negative_%_average_" + k).mean())
+    return {"all": [dict(r) for r in rows], "mean": dict(mean)}
+
+
+def save_json(obj, file):
+    with open(file, "w") as f:
+        json.dump(obj, f, sort_keys=True, indent=4)
+
+
+def write_csv(file, columns, rows):
+    with open(file, "w", newline="") as f:
+        writer = csv.DictWriter(f, fieldnames=list(columns))
+        writer.writeheader()
+        writer.writerows(rows)
+
+
+# ------------------------------------------------------------------------------------------------ readers (thread pool)
+def _structure_labels(a, what):
+    """label volume -> uint8 with every value other than 1, 2, 3 set to 0 (the scripts only ever ask `== 1`, `== 2`, `== 3`)"""
+    a = np.asarray(a)
+    if a.dtype.kind == "f" and not np.array_equal(a, np.rint(a)):
+        raise ValueError("%s: not a label volume (non-integer values)" % what)
+    return np.where((a >= 1) & (a <= len(STRUCTURES)), a, 0).astype(np.uint8)
+
+
+def _read_seg_case(case):
+    test, _ = read_nifti(case.path)
+    ref, props = read_nifti(case.other)
+    if test.shape != ref.shape:
+        raise ValueError("case %s: prediction %s and reference %s differ in shape" % (case.name, test.shape, ref.shape))
+    spacing = tuple(float(v) for v in props["itk_spacing"][::-1])                        # the GT header's zooms, in array order (z, y, x)
+    return _structure_labels(test, case.path), _structure_labels(ref, case.other), spacing
+
+
+def _read_jacobian_case(case):
+    with np.load(case.path) as z:
+        flow = np.asarray(z["flow"], dtype=np.float32)
+    lab, _ = read_nifti(case.other)
+    lab = _structure_labels(lab, case.other).transpose(1, 2, 0)                         # [Z, Y, X] -> the flow's [H, W, D]
+    if lab.shape != flow.shape[:3] or flow.shape[3:] != (2,):
+        raise ValueError("case %s: label volume %s and flow %s do not match" % (case.name, lab.shape, flow.shape))
+    return flow, lab
+
+
+def _prefetched(patients, read):
+    """yields (patient, cases, [read(case)]) in order; the files of the next patient are read while the caller works on this one"""
+    with ThreadPoolExecutor(READERS) as pool:
+        submit = lambda i: [pool.submit(read, c) for c in patients[i][1]] if i < len(patients) else None          # noqa: E731
+        ahead = submit(0)
+        for i, (patient, cases) in enumerate(patients):
+            loaded = [f.result() for f in ahead]
+            ahead = submit(i + 1)
+            yield patient, cases, loaded
+
+
+# ------------------------------------------------------------------------------------------------ drivers
+def score_segmentation_patient(loaded):
+    """loaded: [(test, reference, spacing)] of one patient -> per case {structure: {'Dice', 'HD', 'ASSD'}}.  One device visit per group of
+    frames that share shape and spacing (one group for a cine)."""
+    from . import metrics
+    groups = collections.OrderedDict()
+    for i, (t, r, sp) in enumerate(loaded):
+        groups.setdefault((t.shape, sp), []).append(i)
+    out = [None] * len(loaded)
+    for (_, sp), idx in groups.items():
+        sc = metrics.cine_label_scores(np.stack([loaded[i][0] for i in idx]), np.stack([loaded[i][1] for i in idx]), len(STRUCTURES) + 1,
+                                       voxel_spacing=sp, reproducible=True)
+        for n, i in enumerate(idx):
+            out[i] = {s: {"Dice": float(sc["dice"][n, c]), "HD": float(sc["hd"][n, c]), "ASSD": float(sc["assd"][n, c])}
+                      for c, s in enumerate(STRUCTURES, 1)}
+    return out
+
+
+def score_segmentation(pred, ref, input_folder=None, gt="frame", layout="predict"):
+    """The `seg` sub-command.  Returns the json document; the three files are written into `pred`.  The ES row is the case whose frame
+    number is es_index + 1."""
+    patients, es_frame = [], {}
+    for patient, folder in patient_folders(pred, layout, "Registered").items():
+        ed, es = ed_es_indices(input_folder, patient)
+        cases = pair_segmentation_cases(folder, ref, gt, ed)
+        if cases:
+            patients.append((patient, cases))
+            es_frame[patient] = es + 1
+    per_case = []
+    for patient, cases, loaded in _prefetched(patients, _read_seg_case):
+        for case, scores in zip(cases, score_segmentation_patient(loaded)):
+            per_case.append({"patient": patient, "name": case.name, "test": case.path, "reference": case.other,
+                             "is_es": case.frame == es_frame[patient], "scores": scores})
+    doc, rows, es_rows = segmentation_tables(per_case)
+    save_json(doc, join(pred, "segmentation_metrics.json"))
+    write_csv(join(pred, "segmentation_metrics.csv"), SEG_COLUMNS, rows)
+    write_csv(join(pred, "segmentation_metrics_es.csv"), SEG_COLUMNS, es_rows)
+    return doc
+
+
+def score_jacobian(flow, labels, input_folder=None, layout="predict"):
+    """The `jacobian` sub-command.  Returns the json document; jacobian.json and jacobian_metrics.csv are written into `flow`."""
+    from . import metrics
+    patients, es_frame = [], {}
+    for patient, folder in patient_folders(flow, layout, "Flow").items():
+        ed, es = ed_es_indices(input_folder, patient)
+        cases = pair_jacobian_cases(folder, labels, patient, ed if input_folder is not None else None)
+        if cases:
+            patients.append((patient, cases))
+            es_frame[patient] = es + 1
+    rows = []
+    for patient, cases, loaded in _prefetched(patients, _read_jacobian_case):
+        if len({f.shape for f, _ in loaded}) != 1:
+            raise ValueError("patient %s: the flow files differ in shape" % patient)
+        stats = metrics.cine_jacobian_table(np.stack([f for f, _ in loaded]), np.stack([g for _, g in loaded]), STRUCTURES)
+        frames = [c.frame for c in cases]
+        es_position = frames.index(es_frame[patient]) if es_frame[patient] in frames else None
+        rows += jacobian_rows([c.name for c in cases], stats, es_position)
+    if not rows:
+        raise ValueError("%s: no flow files found (layout %r)" % (flow, layout))
+    doc = jacobian_tables(rows)
+    save_json(doc, join(flow, "jacobian.json"))
+    write_csv(join(flow, "jacobian_metrics.csv"), list(rows[0].keys()), rows)
+    return doc
+
+
+def build_parser():
+    import argparse
+    parser = argparse.ArgumentParser(description="Score the folders of a cine prediction on the device, one visit per patient.")
+    sub = parser.add_subparsers(dest="command", required=True)
+    seg = sub.add_parser("seg", help="Dice / HD / ASSD of the propagated labels: segmentation_metrics.{json,csv}, segmentation_metrics_es.csv")
+    seg.add_argument("-pred", required=True, help="output folder of the prediction (one sub-folder per patient); the tables are written here")
+    seg.add_argument("-ref", required=True, help="folder of the ground-truth label files <case>.nii.gz")
+    seg.add_argument("--gt", choices=("frame", "ed"), default="frame", help="score a frame against its own GT, or every frame against the ED frame's")
+    jac = sub.add_parser("jacobian", help="Jacobian statistics and flow gradients per slice and frame: jacobian.json, jacobian_metrics.csv")
+    jac.add_argument("-flow", required=True, help="output folder of the prediction (one sub-folder per patient); the tables are written here")
+    jac.add_argument("-l", required=True, help="folder of the label volumes <case>.nii.gz, flat or per patient")
+    for p in (seg, jac):
+        p.add_argument("-i", default=None, help="input folder with <patient>/<patient>.csv (ed_index, es_index); without it both are 0")
+        p.add_argument("--layout", choices=("predict", "saver"), default="predict")
+    return parser
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    if a.command == "seg":
+        return score_segmentation(a.pred, a.ref, a.i, a.gt, a.layout)
+    return score_jacobian(a.flow, a.l, a.i, a.layout)
+
+
+if __name__ == "__main__":
+    main()

@@ -528,6 +528,32 @@ int cf_slab_abs_sum(const float* x, int C, int A, int S, long B, double* sums, v
  * cov_norm = NP / (NP - 1).  The mean over the interior (cf_region_stats on the cropped map) is the score. */
 int cf_ssim_map(const double* im1, const double* im2, int H, int W, int win, double C1, double C2, double cov_norm, double* S, void* stream);
 
+/* ---------------------------------------------------------------- cine tables: one device visit per patient (csrc/score.hip)
+ * nnunet/compute_metrics.py:96-106 for all frames and classes of a patient.  test / reference: uint8 label stacks [N][D][H][W]
+ * (N <= 65535 frames, N D H W < 2^30), K in 2..16 labels, ndim 3, or 2 with D == 1 (no z-face rule, as cf_surface_border).  For every
+ * frame n and class 1 <= c < K the masks are `label == c`; a border voxel has a face neighbour that is not c or lies outside the frame's
+ * own volume (frames never see each other).  Everything is caller-owned:
+ *   ws      int32 [11 N K + 3]:  counts [N K 5] | bad [1] | offs [2 N K + 1] | blk [2 N K + 1] | cursors [2 N K]
+ *   table   fp64  [N K 9 + 1]:   per (n, c) {TP, FP, FN, border voxels of test, of reference, max test->ref, max ref->test,
+ *                                sum test->ref, sum ref->test}; the last element counts the voxels whose label is >= K
+ * cf_label_surface_count classifies every voxel once, scans the 2 N K border counts on the device and fills the table's count columns.
+ * Segment s = (n K + c) 2 + side (0: test border, 1: reference border) owns the points offs[s] .. offs[s + 1]; blk is the same scan over
+ * the distance workgroups (256 points of a segment each; none where either side of the pair is empty).  The caller reads offs / blk once,
+ * allocates coords int32 [3 total] and dist fp64 [total] for total = offs[2 N K], and calls cf_label_surface_table with nblocks =
+ * blk[2 N K]: a fill pass compacts the border coordinates (z, y, x), one distance launch writes dist[p] = min_q || spacing (p - q) ||
+ * over the partner segment (fp64, squares summed z, y, x as cf_surface_min_dist) and reduces maxima and sums into the table.  The order
+ * of the points inside a segment follows the compaction; the distance search is brute force (cine-sized objects). */
+int cf_label_surface_count(const uint8_t* test, const uint8_t* reference, int N, int D, int H, int W, int ndim, int K, int* ws, double* table,
+                           void* stream);
+int cf_label_surface_table(const uint8_t* test, const uint8_t* reference, int N, int D, int H, int W, int ndim, int K, double sz, double sy, double sx,
+                           int* ws, int total, int nblocks, int* coords, double* dist, double* table, void* stream);
+/* nnunet/compute_jacobian.py:141-198 for a whole cine.  flow fp32 [T][D][2][H][W] (component 0 along H), labels uint8 [T][D][H][W],
+ * K <= 16, H, W >= 2, T D <= 65535.  table fp64 [T][D][5 + 3 K]: {sum |d/dt|, sum (|d/dy| + |d/dx|)} over both components with
+ * kornia's replicate-padded 0.5 (x[+1] - x[-1]) in fp32, then {sum J, count, #(J < 0)} per label k < K and for the whole slice, J the
+ * determinant of cf_jacobian_det_2d.  part: fp64 workspace [T D ceil(H / 32) ceil(W / 64) (5 + 3 K)] of per-tile totals, added in tile
+ * order by a second launch, so the table has the same bits on every run.  Labels >= K count for the whole slice only. */
+int cf_flow_regularity_table(const float* flow, const uint8_t* labels, int T, int D, int H, int W, int K, double* part, double* table, void* stream);
+
 /* SwinCrossAttention (nnunet/lib/swin_cross_attention.py:13-112) after the projections: qk [B][2C][H][W] = the q and k maps of the
  * "rescaler" input, v [B][C][H][W] the value map of the "rescaled" input, bias_table [(2w-1)^2][heads] the learned relative position
  * bias; out [B][C][H][W] = softmax(q k^T / sqrt(C/heads) + bias + shift mask) v per window of w x w tokens (w <= 8 dividing H and W),
