@@ -67,6 +67,7 @@ SIGNATURES = {
     "cf_layer_norm_cf": [P, P, P, P, I, I, I, F, P],
     "cf_attention_cf": [P, L, P, L, P, L, P, I, I, I, I, I, P],
     "cf_attention_cf_masked": [P, L, P, L, P, L, P, I, I, I, I, I, I, P],
+    "cf_attention_cf_route": [P, L, I, I],
     "cf_gru_reset_mul": [P, P, P, I, I, I, P],
     "cf_gru_blend": [P, P, P, P, I, I, I, P],
     "cf_binary": [I, P, P, P, L, L, P],

@@ -782,6 +782,22 @@ def attention_cf(q, k, v, heads):
     return out
 
 
+def attention_route(v, heads, Nq=None):
+    """the kernel attention_cf launches for this v [B,C,Nk] (Nq: the query count of the call, when it is known): 0 attention_cf_kernel<d>
+    (fp32 MFMA), 1 attention_cf_f16s_kernel<d> (f16 hi/lo split); launches nothing.  A ragged call (Nk or Nq not a multiple of 32) runs on
+    attention_cf's zero-padded copy of v -- a fresh contiguous buffer of Nk rounded up to 32 --, so there only the head dimension decides."""
+    B, C, Nk = v.shape
+    assert C % heads == 0
+    if Nk % 32 or (Nq is not None and Nq % 32):
+        vp, vbs, Nk = 0, C * ((Nk + 31) // 32 * 32), (Nk + 31) // 32 * 32
+    else:
+        vp, vbs = _cf_slice(v, "v")
+    r = lib().cf_attention_cf_route(vp, vbs, C // heads, Nk)
+    if r < 0:
+        check(r, "cf_attention_cf_route")
+    return r
+
+
 # ------------------------------------------------------------------------------------------------ plumbing kernels
 def gru_reset_mul(gates, h):
     B, C = h.shape[0], h.shape[1]

@@ -302,8 +302,34 @@ extern "C" int cf_attention_cf(const float* q, long q_bs, const float* k, long k
     return cf_attention_cf_masked(q, q_bs, k, k_bs, v, v_bs, out, B, heads, d, Nq, Nk, Nk, stream);
 }
 
+// The kernel cf_attention_cf / cf_attention_cf_masked launch for this V pointer, batch stride (floats), head dimension and key count: host
+// code, launches nothing, needs no GPU.  0 = attention_cf_kernel<d> (fp32 MFMA), 1 = attention_cf_f16s_kernel<d> (f16 hi/lo split), -1 with
+// cf_last_error set for a head dimension that is not built.  Head dims >= 16 run on the f16-split kernel; it reads V with 16-byte loads, so
+// every 8-key group must be 16-byte aligned (the pointer, the batch stride in bytes, Nk % 8).  The exact fp32-MFMA kernel takes d == 8 and
+// misaligned V.  This is the only statement of the condition: the launcher below dispatches on this value.
+extern "C" int cf_attention_cf_route(const float* v, long v_bs, int d, int Nk) {
+    CF_REQUIRE(d == 8 || d == 16 || d == 32 || d == 64, "head dim %d unsupported (8,16,32,64)", d);
+    const bool valign = ((reinterpret_cast<uintptr_t>(v) | (uintptr_t)(v_bs * 4)) & 15) == 0 && (Nk & 7) == 0;
+    return d >= 16 && valign ? 1 : 0;
+}
+
+template <int D>
+static void launch_attention(int route, dim3 grid, hipStream_t s, const float* q, long q_bs, const float* k, long k_bs, const float* v, long v_bs,
+                             float* out, int heads, int Nq, int Nk, float scale, int nk_valid) {
+    if constexpr (D >= 16) {
+        if (route == 1) {
+            hipLaunchKernelGGL((attention_cf_f16s_kernel<D>), grid, dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((attention_cf_kernel<D>), grid, dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid);
+}
+
 // The same with only the first nk_valid keys taking part in the softmax: a sequence whose length is not a multiple of 32 is padded by
-// the caller (q, k, v zero-filled up to Nq, Nk; the padded query rows of `out` are discarded).
+// the caller (q, k, v up to Nq, Nk; the padded query rows of `out` are discarded).  The padded keys need only be finite, not zero: their
+// score is replaced by -inf before the softmax, so their weight is exactly 0 and adds exactly 0 x V to the output (0 x Inf or a NaN
+// would not).  Range: the f16-split kernel clamps q / sqrt(d), k and v to +-60000 before the hi/lo split (split_h8), so a finite value above
+// the f16 range saturates instead of turning into Inf; the fp32 kernel has the fp32 range.
 extern "C" int cf_attention_cf_masked(const float* q, long q_bs, const float* k, long k_bs, const float* v, long v_bs, float* out, int B,
                                       int heads, int d, int Nq, int Nk, int nk_valid, void* stream) {
     CF_REQUIRE(q && k && v && out, "null pointer");
@@ -315,21 +341,13 @@ extern "C" int cf_attention_cf_masked(const float* q, long q_bs, const float* k,
     const float scale = (float)(1.0 / sqrt((double)d));
     dim3 grid((unsigned)(B * heads * ((Nq + 127) / 128)));
     hipStream_t s = as_stream(stream);
-    // head dims >= 16 run on the f16 hi/lo-split kernel; it reads V with 16-byte loads: 8-key groups must be 16-byte aligned.  The exact
-    // fp32-MFMA kernel takes d == 8 and misaligned V
-    const bool valign = ((reinterpret_cast<uintptr_t>(v) | (uintptr_t)(v_bs * 4)) & 15) == 0 && (Nk & 7) == 0;
-    if (d >= 16 && valign) {
-        if (d == 16) hipLaunchKernelGGL((attention_cf_f16s_kernel<16>), grid, dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid);
-        else if (d == 32) hipLaunchKernelGGL((attention_cf_f16s_kernel<32>), grid, dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid);
-        else hipLaunchKernelGGL((attention_cf_f16s_kernel<64>), grid, dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid);
-        CF_CHECK_LAUNCH();
-        return CF_OK;
-    }
+    const int route = cf_attention_cf_route(v, v_bs, d, Nk);
+    if (route < 0) return CF_ERR_ARG;
     switch (d) {
-        case 8: hipLaunchKernelGGL((attention_cf_kernel<8>), grid, dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid); break;
-        case 16: hipLaunchKernelGGL((attention_cf_kernel<16>), grid, dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid); break;
-        case 32: hipLaunchKernelGGL((attention_cf_kernel<32>), grid, dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid); break;
-        default: hipLaunchKernelGGL((attention_cf_kernel<64>), grid, dim3(256), 0, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid); break;
+        case 8: launch_attention<8>(route, grid, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid); break;
+        case 16: launch_attention<16>(route, grid, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid); break;
+        case 32: launch_attention<32>(route, grid, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid); break;
+        default: launch_attention<64>(route, grid, s, q, q_bs, k, k_bs, v, v_bs, out, heads, Nq, Nk, scale, nk_valid); break;
     }
     CF_CHECK_LAUNCH();
     return CF_OK;

@@ -296,9 +296,17 @@ int cf_layer_norm_cf(const float* x, const float* gamma, const float* beta, floa
 int cf_attention_cf(const float* q, long q_bs, const float* k, long k_bs, const float* v, long v_bs, float* out, int B,
                     int heads, int d, int Nq, int Nk, void* stream);
 /* cf_attention_cf for sequences whose length is not a multiple of 32: the caller zero-pads q / k / v to Nq, Nk (multiples of 32); only
- * the first nk_valid keys take part in the softmax (nk_valid in the last 32-key block); padded query rows of `out` are garbage. */
+ * the first nk_valid keys take part in the softmax (nk_valid in the last 32-key block); padded query rows of `out` are garbage.
+ * The padded keys need only be finite, not zero: their weight is exactly 0, and the result is bit-identical whatever finite values they hold.
+ * Range: the f16-split kernel (route 1 below) clamps q / sqrt(d), k and v to +-60000 before its f16 hi/lo split, so a finite value above the
+ * f16 range saturates there instead of becoming Inf; the fp32 kernel (route 0) has the fp32 range. */
 int cf_attention_cf_masked(const float* q, long q_bs, const float* k, long k_bs, const float* v, long v_bs, float* out, int B,
                            int heads, int d, int Nq, int Nk, int nk_valid, void* stream);
+/* The kernel cf_attention_cf / cf_attention_cf_masked launch for this V pointer, batch stride, head dimension and key count (host code,
+ * launches nothing, needs no GPU; the launcher dispatches on this very value): 0 = attention_cf_kernel<d>, fp32 MFMA (d == 8, or a V whose
+ * 8-key groups are not 16-byte aligned: pointer, v_bs * 4 or Nk % 8), 1 = attention_cf_f16s_kernel<d>, f16 hi/lo split (d in {16, 32, 64},
+ * aligned V), -1 with cf_last_error set for any other d. */
+int cf_attention_cf_route(const float* v, long v_bs, int d, int Nk);
 
 /* ---------------------------------------------------------------- ConvGRU gating (convGRU.py:60-68)
  * gates [B,2C,HW] = sigmoid(conv_gates(...)) with channels [0,C) = reset, [C,2C) = update. */

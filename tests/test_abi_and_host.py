@@ -93,6 +93,36 @@ def test_corr_volume_route_probe_needs_no_gpu():
         h.cf_corr_mfma_enable(before)
 
 
+def test_attention_route_probe_needs_no_gpu():
+    """cf_attention_cf_route is host code: the dispatch of cf_attention_cf / cf_attention_cf_masked (0 attention_cf_kernel<d>, 1
+    attention_cf_f16s_kernel<d>) on the head dimension and on whether every 8-key group of V is 16-byte aligned -- the pointer, the batch
+    stride and the key count --, asked here with made-up addresses"""
+    from cineflow import _lib
+    h = _lib.lib()
+    a = 4096                                                       # a 16-byte aligned address
+    route = h.cf_attention_cf_route
+    for Nk in (32, 64, 96, 1024):
+        for v_bs in (4 * Nk, 64 * Nk, 192 * Nk, 64 * Nk + 4, 64 * Nk + 1024):      # multiples of 4 floats: every sample stays aligned
+            assert v_bs % 4 == 0
+            assert route(a, v_bs, 8, Nk) == 0, (v_bs, Nk)
+            for d in (16, 32, 64):
+                assert route(a, v_bs, d, Nk) == 1, (d, v_bs, Nk)
+                for off in (4, 8, 12):                             # V one, two, three floats off
+                    assert route(a + off, v_bs, d, Nk) == 0, (d, off, v_bs, Nk)
+        for v_bs in (64 * Nk + 1, 64 * Nk + 2, 64 * Nk + 3, 64 * Nk + 5, 64 * Nk + 7):      # odd, and even but no multiple of 4: sample 1 is off
+            for d in (8, 16, 32, 64):
+                assert route(a, v_bs, d, Nk) == 0 and route(a + 4, v_bs, d, Nk) == 0, (d, v_bs, Nk)
+    for Nk in (4, 12, 36):                                         # Nk % 8 != 0 (the launcher refuses these; the probe has the whole condition)
+        for d in (8, 16, 32, 64):
+            assert route(a, 64 * 40, d, Nk) == 0, (d, Nk)
+    for d in (0, 4, 12, 24, 48, 128, -8):
+        h.cf_attention_cf_route(a, 4096, 8, 32)
+        assert route(a, 64 * 64, d, 64) == -1 and b"head dim %d unsupported" % d in h.cf_last_error(), d
+        assert route(a + 4, 64 * 64 + 1, d, 64) == -1, d           # whatever the alignment
+    # the launcher asks the probe: the same unsupported d fails there before anything is queued
+    assert h.cf_attention_cf(a, 4096, a, 4096, a, 4096, a, 1, 1, 24, 32, 32, None) == -1 and b"head dim 24 unsupported" in h.cf_last_error()
+
+
 def test_conv2d_f16s_route_plan_needs_no_gpu():
     """cf_conv2d_f16s_route is the plan the f16-split launcher executes, as host code: the instantiation of every row of
     test_gpu_conv_f16s_routes.py in both product modes, and the conditions no GPU test can afford -- sub-batches, the 1024-workgroup and
