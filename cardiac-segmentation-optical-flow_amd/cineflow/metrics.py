@@ -548,3 +548,84 @@ def structural_similarity(im1, im2, *, win_size=None, data_range=None, full=Fals
     if full:
         return mssim, (S if torch.is_tensor(im1) else S.cpu().numpy())
     return mssim
+
+
+def _tensor(a):
+    return a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+
+
+def ssim_sums_table(fixed, moving, flow, labels=None, num_classes=0, win_size=7, K1=0.01, K2=0.03, registered=None):
+    """cf_cine_ssim_table: fixed [H, W, D], moving [T, H, W, D], flow [T, H, W, D, 2] (component 0 along H), labels [H, W, D] or None ->
+    (table, registered): table float64 [T, D, 2 + 2 K] = {sum S, count} over the interior of the SSIM map of (frame, slice), then {sum S,
+    count} over all pixels with labels == k for each k < K = num_classes (0 without labels); registered the fp32 device tensor [T, D, H, W]
+    that was scored: every frame warped onto ED by ONE cf_warp_bilinear_2d call (B = T D), or the `registered` argument (fp32
+    [T, H, W, D]; moving and flow are not read then).  Two library calls and one read; the same bits on every run."""
+    win = int(win_size)
+    fx = _tensor(fixed).to(_dev(), dtype=torch.float64)
+    assert fx.dim() == 3, "fixed has to be [H, W, D]"
+    H, W, D = fx.shape
+    if registered is None:
+        m = _tensor(moving).to(_dev(), dtype=torch.float32)
+        f = _tensor(flow).to(_dev(), dtype=torch.float32)
+        assert m.dim() == 4 and tuple(m.shape[1:]) == (H, W, D), "Shape mismatch: fixed {} and moving {}".format(tuple(fx.shape), tuple(m.shape))
+        T = m.shape[0]
+        assert tuple(f.shape) == (T, H, W, D, 2), "Shape mismatch: moving {} and flow {}".format(tuple(m.shape), tuple(f.shape))
+        f = f.permute(0, 3, 4, 1, 2).reshape(T * D, 2, H, W).contiguous()
+        m = m.permute(0, 3, 1, 2).reshape(T * D, 1, H, W).contiguous()
+        reg = ops.warp_bilinear(f, m).reshape(T, D, H, W)
+    else:
+        reg = _tensor(registered).to(_dev(), dtype=torch.float32)
+        assert reg.dim() == 4 and tuple(reg.shape[1:]) == (H, W, D), "Shape mismatch: fixed {} and registered {}".format(tuple(fx.shape), tuple(reg.shape))
+        T = reg.shape[0]
+        reg = reg.permute(0, 3, 1, 2).contiguous()
+    fx = fx.permute(2, 0, 1).contiguous()
+    K, g = 0, None
+    if labels is not None:
+        K = int(num_classes)
+        g = _tensor(labels).to(_dev())
+        assert tuple(g.shape) == (H, W, D), "Shape mismatch: fixed {} and labels {}".format((H, W, D), tuple(g.shape))
+        if g.dtype != torch.uint8:
+            g = torch.where((g >= 0) & (g < K), g, torch.full_like(g, 255)).to(torch.uint8)
+        g = g.permute(2, 0, 1).contiguous()
+    cols = 2 + 2 * K
+    NP = win * win
+    rng = torch.empty(T * D * 2, dtype=torch.float32, device=fx.device)
+    part = torch.empty(T * D * (-(-H // 32)) * (-(-W // 64)) * cols, dtype=torch.float64, device=fx.device)
+    table = torch.empty(T * D * cols, dtype=torch.float64, device=fx.device)
+    check(lib().cf_cine_ssim_table(fx.data_ptr(), _f32(reg), None if g is None else _u8(g), T, D, H, W, K, win, float(K1), float(K2), NP / (NP - 1.0),
+                                   rng.data_ptr(), part.data_ptr(), table.data_ptr(), _stream()), "cf_cine_ssim_table")
+    return table.cpu().numpy().reshape(T, D, cols), reg
+
+
+def cine_ssim_table(fixed, moving, flow, labels=None, names=("RV", "MYO", "LV"), win_size=7, K1=0.01, K2=0.03, registered=None,
+                    return_registered=False):
+    """compute_SSIM.py:74-104 and compute_SSIM_crop_per_structure.py:70-127 for one patient, from one ssim_sums_table visit.
+
+    fixed [H, W, D]: the ED frame's image (scored in fp64); moving [T, H, W, D]: the other frames; flow [T, H, W, D, 2]: their flows onto
+    ED (the stacked `flow` arrays of the .npz files, as flow_regularity_table takes them); labels [H, W, D]: the ED segmentation
+    (structures = labels 1..len(names)) or None.  Every (frame, slice) is scored against the ED slice with data_range = max - min of the
+    registered slice.  registered= (fp32 [T, H, W, D]) takes the place of the warp: the scripts' `'registered' in data.files` branch.
+
+    Returns one dict per (slice, frame), slices outermost like cine_jacobian_table: `SSIM_whole`, the mean of the SSIM map over the
+    interior, and with labels `SSIM_rv`, `SSIM_myo`, `SSIM_lv` -- the map's mean over ALL pixels of the structure, NaN where the slice
+    has none -- and `SSIM_mean`, their plain mean.  return_registered=True returns (rows, registered): the fp32 [T, H, W, D] images that
+    were scored (a device tensor when the image given was one, numpy otherwise)."""
+    K = len(names) + 1 if labels is not None else 0
+    tab, reg = ssim_sums_table(fixed, moving, flow, labels, K, win_size, K1, K2, registered)
+    T, D = tab.shape[:2]
+    rows = []
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for d in range(D):
+            for t in range(T):
+                v = tab[t, d]
+                res = {"SSIM_whole": float(v[0] / v[1])}
+                if K:
+                    per = [float(v[2 + 2 * i] / v[3 + 2 * i]) if v[3 + 2 * i] else float("nan") for i in range(1, K)]
+                    for k, s in zip(names, per):
+                        res["SSIM_" + k.lower()] = s
+                    res["SSIM_mean"] = sum(per) / len(per)
+                rows.append(res)
+    if return_registered:
+        out = reg.permute(0, 2, 3, 1).contiguous()
+        return rows, (out if torch.is_tensor(moving if registered is None else registered) else out.cpu().numpy())
+    return rows

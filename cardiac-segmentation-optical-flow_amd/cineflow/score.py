@@ -2,11 +2,15 @@
 
     python -m cineflow.score seg      -pred FOLDER -ref GT_FOLDER    [-i INPUT_FOLDER] [--gt frame|ed] [--layout predict|saver]
     python -m cineflow.score jacobian -flow FOLDER -l LABEL_FOLDER   [-i INPUT_FOLDER] [--layout predict|saver]
+    python -m cineflow.score ssim     -flow FOLDER -i INPUT_FOLDER   [-l LABEL_FOLDER] [--layout predict|saver] [--win 7]
 
 `seg` writes what nnunet/compute_metrics.py writes -- segmentation_metrics.json, segmentation_metrics.csv, segmentation_metrics_es.csv:
 Dice, Hausdorff distance and average symmetric surface distance of the propagated labels (RV = 1, MYO = 2, LV = 3) per frame --
 and `jacobian` what nnunet/compute_jacobian.py writes -- jacobian.json, jacobian_metrics.csv: the Jacobian statistics and flow
-gradients per slice and frame.  Both are written from the scripts' behaviour, not transcribed: the scripts' hard-coded paths, pickles
+gradients per slice and frame.  `ssim` writes what nnunet/compute_SSIM.py writes -- ssim_metrics.json, ssim_metrics.csv: the structural
+similarity of every frame's image INPUT_FOLDER/<patient>/<case>_0000.nii.gz, warped onto the ED frame with the case's flow, to the ED
+image, per slice -- and with -l what nnunet/compute_SSIM_crop_per_structure.py writes -- ssim_metrics_all.json, ssim_metrics_all.csv: the
+SSIM map's means over the RV, MYO and LV of the ED label volume as well (cineflow.metrics.cine_ssim_table).  All are written from the scripts' behaviour, not transcribed: the scripts' hard-coded paths, pickles
 and `patient029` special cases are arguments or gone, and the numbers of a patient come from cineflow.metrics.cine_label_scores /
 cine_jacobian_table (csrc/score.hip) instead of one call chain per frame and class.
 
@@ -19,7 +23,7 @@ A case's frame number is int(stem[-2:]); cases are sorted by it.  ED / ES indice
 
 A thread pool reads and inflates the next patient's files while the current one is scored; one patient is resident on the device at a
 time and only this process opens the GPU.  Turning per-case rows into the json / csv documents is host code (segmentation_tables,
-jacobian_tables).
+jacobian_tables, ssim_tables).
 """
 import collections
 import csv
@@ -145,6 +149,50 @@ def pair_jacobian_cases(flow_folder, label_folder, patient, ed_index=None):
     return cases
 
 
+def pair_ssim_cases(flow_folder, input_folder, patient, ed_index, label_folder=None):
+    """-> [ED case] + the flow files of one patient sorted by frame number, the ED frame's own flow file (frame number ed_index + 1) left
+    out as pair_jacobian_cases leaves it out; [] without flow files.  A flow case's `other` is its image
+    INPUT/<patient>/<case>_0000.nii.gz; the ED case's `path` is the ED image and its `other` the ED label volume (label_file under the ED
+    case's stem; None without a label folder).  A missing image, a missing ED label volume or an image / label volume whose [Z, Y, X] is
+    not the flow's [H, W, D] is a ValueError naming the case (headers only: nothing is inflated)."""
+    stems = [s for s in sorted_cases(flow_folder, ".npz") if frame_number(s) != ed_index + 1]
+    if not stems:
+        return []
+    ed_stem = stems[0][:-2] + str(ed_index + 1).zfill(2)
+
+    def image_of(stem):
+        img = join(input_folder, patient, stem + "_0000.nii.gz")
+        if not os.path.isfile(img):
+            raise ValueError("case %s: no image %s" % (stem, img))
+        return img
+    lab = None
+    if label_folder is not None:
+        lab = label_file(label_folder, patient, ed_stem)
+        if lab is None:
+            raise ValueError("case %s: no label volume %s.nii.gz of the ED frame in %s (flat, per patient or <patient>/Segmentation)"
+                             % (ed_stem, ed_stem, label_folder))
+    cases = [Case(ed_stem, ed_index + 1, image_of(ed_stem), lab)]
+    for stem in stems:
+        cases.append(Case(stem, frame_number(stem), join(flow_folder, stem + ".npz"), image_of(stem)))
+    want = None
+    for c in cases[1:]:
+        fshape = _npz_shape(c.path, "flow")
+        if len(fshape) != 4 or fshape[3] != 2:
+            raise ValueError("case %s: flow of shape %s, expected [H, W, D, 2]" % (c.name, fshape))
+        if want is not None and fshape[:3] != want:
+            raise ValueError("case %s: flow [H, W, D] = %s, the patient's other flows %s" % (c.name, fshape[:3], want))
+        want = fshape[:3]
+        Z, Y, X = _nifti_shape(c.other)
+        if (Y, X, Z) != want:
+            raise ValueError("case %s: image %s is [Z, Y, X] = %s, the flow [H, W, D] = %s" % (c.name, c.other, (Z, Y, X), want))
+    for what, f in (("image", cases[0].path), ("label volume", lab)):
+        if f is not None:
+            Z, Y, X = _nifti_shape(f)
+            if (Y, X, Z) != want:
+                raise ValueError("case %s: %s %s is [Z, Y, X] = %s, the flow [H, W, D] = %s" % (ed_stem, what, f, (Z, Y, X), want))
+    return cases
+
+
 # ------------------------------------------------------------------------------------------------ host tables
 def segmentation_row(name, scores):
     """one csv row (the thirteen columns) from {'RV': {'Dice', 'HD', 'ASSD'}, 'MYO': ..., 'LV': ...}"""
@@ -232,6 +280,47 @@ def jacobian_tables(rows):
     return {"all": [dict(r) for r in rows], "mean": dict(mean)}
 
 
+SSIM_KEYS = ("SSIM_mean",) + tuple("SSIM_" + k.lower() for k in STRUCTURES) + ("SSIM_whole",)
+SSIM_COLUMNS = ["Name", "slice_number", "SSIM"]
+SSIM_ALL_COLUMNS = ["Name", "slice_number"] + list(SSIM_KEYS) + ["ES_" + k for k in SSIM_KEYS]
+
+
+def ssim_rows(patient, frames, stats, ed_frame, es_frame):
+    """frames[t]: frame number of position t (ascending, the ED frame not among them); stats: cine_ssim_table's dicts (slices outermost)
+    -> (entries, entries_all), one entry per slice.  The lists run over the frames by number, rotated to start with the first frame after
+    ed_frame (the scripts' `indices >= ed` then `< ed`).  entries: Name, slice_number, SSIM (the whole-slice scores); entries_all (empty
+    when the stats carry no structures): the five SSIM_* lists and ES_SSIM_*, the values of the frame numbered es_frame, NaN when that
+    frame is not among `frames`."""
+    T = len(frames)
+    assert T and len(stats) % T == 0
+    order = [t for t in range(T) if frames[t] > ed_frame] + [t for t in range(T) if frames[t] < ed_frame]
+    es_position = frames.index(es_frame) if es_frame in frames else None
+    entries, entries_all = [], []
+    for d in range(len(stats) // T):
+        st = stats[d * T:(d + 1) * T]
+        entries.append(collections.OrderedDict([("Name", patient), ("slice_number", d), ("SSIM", [float(st[t]["SSIM_whole"]) for t in order])]))
+        if "SSIM_mean" in st[0]:
+            e = collections.OrderedDict([("Name", patient), ("slice_number", d)])
+            for k in SSIM_KEYS:
+                e[k] = [float(st[t][k]) for t in order]
+            for k in SSIM_KEYS:
+                e["ES_" + k] = float(st[es_position][k]) if es_position is not None else float("nan")
+            entries_all.append(e)
+    return entries, entries_all
+
+
+def ssim_tables(entries, key="SSIM"):
+    """entries of every patient -> (json document {'all': entries, 'mean': ...}, csv rows).  A csv row is the entry with every list
+    replaced by its plain mean; `mean` is the plain mean over the entries of the per-entry means of `key` (NaN as soon as one value is)."""
+    rows = []
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        for e in entries:
+            rows.append(collections.OrderedDict((k, float(np.array(v, dtype=np.float64).mean()) if isinstance(v, list) else v) for k, v in e.items()))
+        mean = float(np.array([r[key] for r in rows], dtype=np.float64).mean()) if rows else float("nan")
+    return {"all": [dict(e) for e in entries], "mean": mean}, rows
+
+
 def save_json(obj, file):
     with open(file, "w") as f:
         json.dump(obj, f, sort_keys=True, indent=4)
@@ -270,6 +359,23 @@ def _read_jacobian_case(case):
     if lab.shape != flow.shape[:3] or flow.shape[3:] != (2,):
         raise ValueError("case %s: label volume %s and flow %s do not match" % (case.name, lab.shape, flow.shape))
     return flow, lab
+
+
+def _read_ssim_case(case):
+    """a flow case -> (flow fp32 [H, W, D, 2], image fp32 [H, W, D]); the ED case -> (image fp64 [H, W, D], labels uint8 [H, W, D] or None)"""
+    if case.path.endswith(".npz"):
+        with np.load(case.path) as z:
+            flow = np.asarray(z["flow"], dtype=np.float32)
+        img, _ = read_nifti(case.other)
+        img = np.asarray(img).transpose(1, 2, 0).astype(np.float32)                     # [Z, Y, X] -> the flow's [H, W, D]
+        if img.shape != flow.shape[:3] or flow.shape[3:] != (2,):
+            raise ValueError("case %s: image %s and flow %s do not match" % (case.name, img.shape, flow.shape))
+        return flow, img
+    img, _ = read_nifti(case.path)
+    lab = None
+    if case.other is not None:
+        lab = _structure_labels(read_nifti(case.other)[0], case.other).transpose(1, 2, 0)
+    return np.asarray(img).transpose(1, 2, 0).astype(np.float64), lab
 
 
 def _prefetched(patients, read):
@@ -349,6 +455,37 @@ def score_jacobian(flow, labels, input_folder=None, layout="predict"):
     return doc
 
 
+def score_ssim(flow, input_folder, labels=None, layout="predict", win=7):
+    """The `ssim` sub-command.  Returns the json document of ssim_metrics.json; ssim_metrics.{json,csv} are written into `flow`, and with
+    a label folder ssim_metrics_all.{json,csv} as well.  Every frame with a flow file is warped onto the ED frame with that file's flow
+    and scored against the ED image: two library calls per patient."""
+    from . import metrics
+    patients, es_frame = [], {}
+    for patient, folder in patient_folders(flow, layout, "Flow").items():
+        ed, es = ed_es_indices(input_folder, patient)
+        cases = pair_ssim_cases(folder, input_folder, patient, ed, labels)
+        if cases:
+            patients.append((patient, cases))
+            es_frame[patient] = es + 1
+    entries, entries_all = [], []
+    for patient, cases, loaded in _prefetched(patients, _read_ssim_case):
+        (fixed, lab), moving = loaded[0], loaded[1:]
+        stats = metrics.cine_ssim_table(fixed, np.stack([m for _, m in moving]), np.stack([f for f, _ in moving]), lab, STRUCTURES, win)
+        e, ea = ssim_rows(patient, [c.frame for c in cases[1:]], stats, cases[0].frame, es_frame[patient])
+        entries += e
+        entries_all += ea
+    if not entries:
+        raise ValueError("%s: no flow files found (layout %r)" % (flow, layout))
+    doc, rows = ssim_tables(entries, "SSIM")
+    save_json(doc, join(flow, "ssim_metrics.json"))
+    write_csv(join(flow, "ssim_metrics.csv"), SSIM_COLUMNS, rows)
+    if labels is not None:
+        doc_all, rows_all = ssim_tables(entries_all, "SSIM_mean")
+        save_json(doc_all, join(flow, "ssim_metrics_all.json"))
+        write_csv(join(flow, "ssim_metrics_all.csv"), SSIM_ALL_COLUMNS, rows_all)
+    return doc
+
+
 def build_parser():
     import argparse
     parser = argparse.ArgumentParser(description="Score the folders of a cine prediction on the device, one visit per patient.")
@@ -363,6 +500,12 @@ def build_parser():
     for p in (seg, jac):
         p.add_argument("-i", default=None, help="input folder with <patient>/<patient>.csv (ed_index, es_index); without it both are 0")
         p.add_argument("--layout", choices=("predict", "saver"), default="predict")
+    ssim = sub.add_parser("ssim", help="SSIM of every frame warped onto the ED frame: ssim_metrics.{json,csv}, with -l ssim_metrics_all.{json,csv}")
+    ssim.add_argument("-flow", required=True, help="output folder of the prediction (one sub-folder per patient); the tables are written here")
+    ssim.add_argument("-i", required=True, help="input folder with <patient>/<case>_0000.nii.gz and <patient>/<patient>.csv (ed_index, es_index)")
+    ssim.add_argument("-l", default=None, help="folder of the label volumes <case>.nii.gz, flat or per patient: per-structure scores on the ED labels")
+    ssim.add_argument("--layout", choices=("predict", "saver"), default="predict")
+    ssim.add_argument("--win", type=int, default=7, help="side of the uniform SSIM window (odd, 3..15)")
     return parser
 
 
@@ -370,7 +513,9 @@ def main(argv=None):
     a = build_parser().parse_args(argv)
     if a.command == "seg":
         return score_segmentation(a.pred, a.ref, a.i, a.gt, a.layout)
-    return score_jacobian(a.flow, a.l, a.i, a.layout)
+    if a.command == "jacobian":
+        return score_jacobian(a.flow, a.l, a.i, a.layout)
+    return score_ssim(a.flow, a.i, a.l, a.layout, a.win)
 
 
 if __name__ == "__main__":

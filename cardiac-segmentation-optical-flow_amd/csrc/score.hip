@@ -8,6 +8,9 @@
 //     |d/dy| + |d/dx| of both flow components (kornia's replicate-padded 0.5 * (x[+1] - x[-1])) and sum / count / negatives of the
 //     2-D Jacobian determinant per label and for the whole slice (the arithmetic of jacobian_det_2d_kernel in warp.hip).  No
 //     determinant image and no gradient tensor is stored.
+//   * cf_cine_ssim_table: nnunet/compute_SSIM.py / compute_SSIM_crop_per_structure.py for a whole cine -- per (frame, slice) the sum of
+//     skimage's SSIM map (the arithmetic of ssim_map_kernel in metrics.hip) over the interior and over each label of the ED
+//     segmentation, the windows summed separably from an LDS-staged halo.  No SSIM map is stored.
 // The file is built with -ffp-contract=off (Makefile): the fp64 products and sums round one by one, as in scipy / numpy.
 #include "common.h"
 
@@ -278,6 +281,142 @@ __global__ void __launch_bounds__(64) flow_regularity_reduce_kernel(const double
     table[(long)slice * cols + c] = s;
 }
 
+// ------------------------------------------------------------------------------------------------ cine SSIM
+constexpr int CS_TW = 64, CS_TH = 32, CS_ROWS = CS_TH / 4, CS_MAXWIN = 15, CS_MAXCOLS = 2 + 2 * 16;
+
+// scipy's 'reflect' (d c b a | a b c d | d c b a), as ssim_map_kernel resolves it; the clamp keeps the halo of a partial tile's dead pixels in bounds
+__device__ __forceinline__ int reflect_index(int i, int n) {
+    i = i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i);
+    return min(max(i, 0), n - 1);
+}
+
+// one workgroup of 1024 per slice: range[slice] = {min, max} of the registered slice, NaN when a value is (numpy's min / max)
+__global__ void __launch_bounds__(1024) cine_ssim_range_kernel(const float* __restrict__ reg, long HW, float* __restrict__ range) {
+    __shared__ float rmin[16], rmax[16];
+    __shared__ int rbad[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* p = reg + (long)blockIdx.x * HW;
+    float mn = INFINITY, mx = -INFINITY;
+    int bad = 0;
+    for (long i = tid; i < HW; i += 1024) {
+        const float v = p[i];
+        mn = fminf(mn, v);
+        mx = fmaxf(mx, v);
+        bad |= v != v;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        mn = fminf(mn, __shfl_xor(mn, o, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+        bad |= __shfl_xor(bad, o, 64);
+    }
+    if (lane == 0) { rmin[wave] = mn; rmax[wave] = mx; rbad[wave] = bad; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int k = 1; k < 16; ++k) { mn = fminf(mn, rmin[k]); mx = fmaxf(mx, rmax[k]); bad |= rbad[k]; }
+        range[2L * blockIdx.x] = bad ? NAN : mn;
+        range[2L * blockIdx.x + 1] = bad ? NAN : mx;
+    }
+}
+
+// grid (tiles, T * D); a workgroup owns a 32 x 64 tile of one slice of one frame, a wave 8 rows of it, a thread those 8 rows of one column.
+// The (32 + win - 1) x (64 + win - 1) halo of both images is staged once (fixed fp64, registered fp32), reflection resolved on the way in.
+// Window sums are separable: for each of the 8 + win - 1 halo rows of its strip a thread forms the five row sums over win columns from LDS
+// (lane = column: every wave read is one contiguous run, free of bank conflicts at 4 and at 8 bytes) and adds them to those of its 8 pixels
+// whose window holds the row -- the column sums stay in registers: five fp64 row-sum planes of a strip do not fit beside the halo.  That is
+// 2 win (8 + win - 1) / 8 LDS reads per pixel for all five quantities where ssim_map_kernel reads 2 win^2 values from global memory.  The
+// window is a template argument (one instantiation per odd win 3..15): the halo arrays have their exact size (31.9 KB at win 7, 43.1 KB at
+// win 15), both loops unroll, a row's LDS reads are issued together and which pixel takes which row sum is known at compile time.
+// S is ssim_map_kernel's expression; the sums go over the wave by a fixed butterfly and over the four waves in order.
+template <int WIN>
+__global__ void __launch_bounds__(256) cine_ssim_tile_kernel(const double* __restrict__ fixed, const float* __restrict__ reg, const uint8_t* __restrict__ lab,
+                                                             int D, int H, int W, int K, double K1, double K2, double cov_norm, int tiles_x,
+                                                             const float* __restrict__ range, double* __restrict__ part) {
+    constexpr int win = WIN, pad = WIN / 2, hh = CS_TH + WIN - 1, hw = CS_TW + WIN - 1;
+    __shared__ double A[hh * hw];
+    __shared__ float B[hh * hw];
+    __shared__ double red[4][CS_MAXCOLS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int slice = blockIdx.y, d = slice % D;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const long HW = (long)H * W;
+    const double* fs = fixed + (long)d * HW;
+    const float* rs = reg + (long)slice * HW;
+    const int y0 = ty * CS_TH - pad, x0 = tx * CS_TW - pad;
+    for (int i = tid; i < hh * hw; i += 256) {
+        const int r = i / hw, c = i - r * hw;
+        const long g = (long)reflect_index(y0 + r, H) * W + reflect_index(x0 + c, W);
+        A[i] = fs[g];
+        B[i] = rs[g];
+    }
+    __syncthreads();
+
+    const int row0 = wave * CS_ROWS;                             // the strip's first row inside the tile, and its first halo row
+    double ax[CS_ROWS], ay[CS_ROWS], axx[CS_ROWS], ayy[CS_ROWS], axy[CS_ROWS];
+#pragma unroll
+    for (int o = 0; o < CS_ROWS; ++o) ax[o] = ay[o] = axx[o] = ayy[o] = axy[o] = 0.0;
+    const bool strip_live = ty * CS_TH + row0 < H;               // wave-uniform
+    if (strip_live) {
+#pragma unroll
+        for (int hr = 0; hr < CS_ROWS + win - 1; ++hr) {
+            const double* ar = A + (row0 + hr) * hw + lane;
+            const float* br = B + (row0 + hr) * hw + lane;
+            double sx = 0.0, sy = 0.0, sxx = 0.0, syy = 0.0, sxy = 0.0;
+#pragma unroll
+            for (int dx = 0; dx < win; ++dx) {
+                const double u = ar[dx], v = (double)br[dx];
+                sx += u; sy += v; sxx += u * u; syy += v * v; sxy += u * v;
+            }
+#pragma unroll
+            for (int o = 0; o < CS_ROWS; ++o)
+                if (hr >= o && hr < o + win) {                            // halo row hr lies in the window of the strip's pixel row o: known at compile time
+                    ax[o] += sx; ay[o] += sy; axx[o] += sxx; ayy[o] += syy; axy[o] += sxy;
+                }
+        }
+    }
+
+    // C1 = (K1 R)^2, C2 = (K2 R)^2 with R = max - min subtracted in fp32, as on a float32 array
+    const double R = (double)(range[2L * slice + 1] - range[2L * slice]);
+    const double C1 = (K1 * R) * (K1 * R), C2 = (K2 * R) * (K2 * R);
+    const double inv = 1.0 / ((double)win * win);
+    const uint8_t* ls = lab ? lab + (long)d * HW : nullptr;
+    double sw = 0.0, sk[16];
+    unsigned cw = 0, ck[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { sk[k] = 0.0; ck[k] = 0; }
+    const int x = tx * CS_TW + lane;
+    if (strip_live && x < W) {
+#pragma unroll
+        for (int o = 0; o < CS_ROWS; ++o) {
+            const int y = ty * CS_TH + row0 + o;
+            if (y < H) {
+                const double ux = ax[o] * inv, uy = ay[o] * inv;
+                const double vx = cov_norm * (axx[o] * inv - ux * ux), vy = cov_norm * (ayy[o] * inv - uy * uy), vxy = cov_norm * (axy[o] * inv - ux * uy);
+                const double S = ((2.0 * ux * uy + C1) * (2.0 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2));
+                if (y >= pad && y < H - pad && x >= pad && x < W - pad) { sw += S; cw += 1; }
+                const int k = ls ? ls[(long)y * W + x] : 255;
+#pragma unroll
+                for (int q = 0; q < 16; ++q)
+                    if (q < K) {                                      // uniform: labels >= K count nowhere
+                        sk[q] += q == k ? S : 0.0;
+                        ck[q] += q == k ? 1u : 0u;
+                    }
+            }
+        }
+    }
+    auto put = [&](int col, double v) {
+        v = wave_sum_d(v);
+        if (lane == 0) red[wave][col] = v;
+    };
+    put(0, sw);
+    put(1, (double)cw);
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+        if (k < K) { put(2 + 2 * k, sk[k]); put(3 + 2 * k, (double)ck[k]); }
+    __syncthreads();
+    const int cols = 2 + 2 * K;
+    if (tid < cols) part[((long)slice * gridDim.x + blockIdx.x) * cols + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
 }  // namespace cf
 
 using namespace cf;
@@ -363,6 +502,35 @@ extern "C" int cf_flow_regularity_table(const float* flow, const uint8_t* labels
     hipLaunchKernelGGL(flow_regularity_tile_kernel, dim3((unsigned)ntiles, (unsigned)(T * D)), dim3(256), 0, s, flow, labels, T, D, H, W, K, tiles_x, part);
     CF_CHECK_LAUNCH();
     hipLaunchKernelGGL(flow_regularity_reduce_kernel, dim3((unsigned)(T * D)), dim3(64), 0, s, (const double*)part, (int)ntiles, 5 + 3 * K, table);
+    CF_CHECK_LAUNCH();
+    return CF_OK;
+}
+
+extern "C" int cf_cine_ssim_table(const double* fixed, const float* registered, const uint8_t* labels, int T, int D, int H, int W, int K, int win,
+                                  double K1, double K2, double cov_norm, float* range, double* part, double* table, void* stream) {
+    CF_REQUIRE(fixed && registered && range && part && table, "null pointer");
+    CF_REQUIRE(K >= 0 && K <= 16, "K must be 0..16, got %d", K);
+    CF_REQUIRE(labels || K == 0, "labels may be null only with K = 0, got K=%d", K);
+    CF_REQUIRE(T > 0 && D > 0 && H > 0 && W > 0, "bad shape T=%d D=%d H=%d W=%d", T, D, H, W);
+    CF_REQUIRE((long)T * D <= 65535, "T * D = %ld slices exceed one grid dimension (65535)", (long)T * D);
+    CF_REQUIRE((win & 1) && win >= 3 && win <= CS_MAXWIN, "win must be odd and 3..%d, got %d", CS_MAXWIN, win);
+    CF_REQUIRE(win <= H && win <= W, "win=%d exceeds the image (H=%d W=%d)", win, H, W);
+    const int tiles_x = cdiv(W, CS_TW), tiles_y = cdiv(H, CS_TH);
+    const long ntiles = (long)tiles_x * tiles_y;
+    CF_REQUIRE(ntiles < (1L << 24), "map too large");
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(cine_ssim_range_kernel, dim3((unsigned)(T * D)), dim3(1024), 0, s, registered, (long)H * W, range);
+    CF_CHECK_LAUNCH();
+    const dim3 grid((unsigned)ntiles, (unsigned)(T * D));
+#define CS_TILE(WIN)                                                                                                                              \
+    case WIN:                                                                                                                                     \
+        hipLaunchKernelGGL(cine_ssim_tile_kernel<WIN>, grid, dim3(256), 0, s, fixed, registered, labels, D, H, W, K, K1, K2, cov_norm, tiles_x, \
+                           (const float*)range, part);                                                                                            \
+        break;
+    switch (win) { CS_TILE(3) CS_TILE(5) CS_TILE(7) CS_TILE(9) CS_TILE(11) CS_TILE(13) CS_TILE(15) }
+#undef CS_TILE
+    CF_CHECK_LAUNCH();
+    hipLaunchKernelGGL(flow_regularity_reduce_kernel, dim3((unsigned)(T * D)), dim3(64), 0, s, (const double*)part, (int)ntiles, 2 + 2 * K, table);
     CF_CHECK_LAUNCH();
     return CF_OK;
 }

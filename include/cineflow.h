@@ -561,6 +561,17 @@ int cf_label_surface_table(const uint8_t* test, const uint8_t* reference, int N,
  * determinant of cf_jacobian_det_2d.  part: fp64 workspace [T D ceil(H / 32) ceil(W / 64) (5 + 3 K)] of per-tile totals, added in tile
  * order by a second launch, so the table has the same bits on every run.  Labels >= K count for the whole slice only. */
 int cf_flow_regularity_table(const float* flow, const uint8_t* labels, int T, int D, int H, int W, int K, double* part, double* table, void* stream);
+/* nnunet/compute_SSIM.py and compute_SSIM_crop_per_structure.py for a whole cine: cf_ssim_map's S of every frame against the ED frame,
+ * summed, without storing a map.  fixed fp64 [D][H][W] (the ED image), registered fp32 [T][D][H][W] (every other frame warped onto ED),
+ * labels uint8 [D][H][W] (the ED segmentation; NULL with K = 0).  win odd, 3 <= win <= 15, win <= min(H, W); K <= 16; T D <= 65535.
+ * table fp64 [T][D][2 + 2 K]: {sum S, count} over the interior [pad, H - pad) x [pad, W - pad), pad = (win - 1) / 2, then {sum S, count}
+ * over ALL pixels of the slice with labels == k for each k < K (S with scipy's 'reflect' boundary there, as cf_ssim_map; labels >= K count
+ * nowhere).  Per slice data_range R = (double)(max - min) of the registered slice, subtracted in fp32; C1 = (K1 R)^2, C2 = (K2 R)^2 in
+ * fp64.  range: fp32 workspace [T][D][2] (min, max); part: fp64 workspace [T D ceil(H / 32) ceil(W / 64) (2 + 2 K)] of per-tile totals,
+ * added in tile order, so the table has the same bits on every run.  Three launches, no allocation, no synchronisation.  NaN propagates:
+ * a slice where both images are constant zero has R = 0, S = 0 / 0 and NaN sums, as numpy's. */
+int cf_cine_ssim_table(const double* fixed, const float* registered, const uint8_t* labels, int T, int D, int H, int W, int K, int win,
+                       double K1, double K2, double cov_norm, float* range, double* part, double* table, void* stream);
 
 /* SwinCrossAttention (nnunet/lib/swin_cross_attention.py:13-112) after the projections: qk [B][2C][H][W] = the q and k maps of the
  * "rescaler" input, v [B][C][H][W] the value map of the "rescaled" input, bias_table [(2w-1)^2][heads] the learned relative position
