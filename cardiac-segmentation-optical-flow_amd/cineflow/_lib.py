@@ -64,6 +64,8 @@ SIGNATURES = {
     "cf_conv2d_wino_prenorm": [P, I, P, F, P, P, P, I, I, I, I, F, P, I, P],
     "cf_group_norm_apply_res_norm": [P, P, P, P, P, I, I, I, I, F, I, I, P, P, P, P, P],
     "cf_group_norm": [P, P, P, P, P, I, I, I, I, F, I, I, P, P],
+    "cf_group_norm_stats": [P, P, I, I, I, I, P],
+    "cf_group_norm_route": [P, P, P, I, I, I, I, P],
     "cf_layer_norm_cf": [P, P, P, P, I, I, I, F, P],
     "cf_attention_cf": [P, L, P, L, P, L, P, I, I, I, I, I, P],
     "cf_attention_cf_masked": [P, L, P, L, P, L, P, I, I, I, I, I, I, P],

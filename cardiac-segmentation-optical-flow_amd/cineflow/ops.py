@@ -738,6 +738,29 @@ def group_norm_apply(x, gamma, beta, groups, ws, eps=1e-5, act=None, res=None, r
     return out
 
 
+def group_norm_stats(x, groups):
+    """The statistics pass of group_norm alone -> a fresh fp64 workspace [B, groups, 2] of {sum, sum of squares} per slab."""
+    B, C = x.shape[0], x.shape[1]
+    HW = x.numel() // (B * C)
+    ws = torch.empty((B, groups, 2), dtype=torch.float64, device=x.device)
+    check(lib().cf_group_norm_stats(_f32(x), ws.data_ptr(), B, C, HW, groups, _stream()), "cf_group_norm_stats")
+    return ws
+
+
+GroupNormRoute = collections.namedtuple("GroupNormRoute", "stats_block segs stats_blocks apply_large vec ppb apply_blocks last_np")
+
+
+def group_norm_route(x, out=None, res=None, groups=1):
+    """The plan group_norm / group_norm_apply execute for these tensors (out None: a fresh, aligned tensor); launches nothing.
+    stats_block: 0 gn_stats_wave_kernel, 1 gn_stats_block_kernel (segs blocks per slab); apply_large: 0 gn_apply_small_kernel (ppb planes
+    per block, last_np in the last), 1 gn_apply_kernel (ppb blocks per plane); vec: the float4 instantiation."""
+    B, C = x.shape[0], x.shape[1]
+    HW = x.numel() // (B * C)
+    plan = (ctypes.c_int * 8)()
+    check(lib().cf_group_norm_route(_f32(x), _opt(out), _opt(res), B, C, HW, groups, ctypes.addressof(plan)), "cf_group_norm_route")
+    return GroupNormRoute(*plan)
+
+
 def layer_norm_cf(x, gamma, beta, eps=1e-5, out=None):
     B, C, N = x.shape
     if out is None:

@@ -1,8 +1,13 @@
 // GroupNorm / InstanceNorm (+activation, +residual) and channel-first LayerNorm.  HBM-bound.
 //
-// Statistics are accumulated in fp64 (sum, sum of squares): E[x^2]-E[x]^2 is then exact to ~1e-16 relative, so the
-// result matches PyTorch's two-pass/Welford CPU kernels to fp32 rounding.  In NCHW a (sample, group) slab is one
-// contiguous run of (C/groups)*HW floats, so the statistics pass is a plain segmented reduction.
+// Statistics are accumulated in fp64 (sum, sum of squares).  On the wave route every value is widened first: the sums are within
+// 2^-36 of (sum |x|, sum x^2), E[x^2]-E[x]^2 loses only (mean/std)^2 * 1e-16 relative, and the result matches PyTorch's two-pass/Welford
+// CPU kernels to fp32 rounding.  The block route adds the pairs of a float4 in fp32 before widening (one rounding per pair sum, two per
+// pair of squares): the sums are within 2^-24 sum |x| and 2^-23 sum x^2 to first order, the variance within 2^-22 (mean/std)^2 relative in
+// the worst case -- invisible for normalised activations (mean/std ~ 0.5), 1e-3 at mean/std = 64.  Measured on the MI355X at
+// mean/std = 64 (tests/test_gpu_norm_routes.py, profiles/norm_route_table.md): relative variance error 1.9e-13 on the wave route
+// (L = 1024), 8.8e-6 on the block route (L = 8192).  In NCHW a (sample, group) slab is one contiguous run of (C/groups)*HW floats, so the
+// statistics pass is a plain segmented reduction.
 #include "conv.h"
 
 namespace cf {
@@ -63,6 +68,11 @@ typedef float nt_f32x4 __attribute__((ext_vector_type(4)));
 #define NT_LOAD4(p) ([&]() { const nt_f32x4 _v = __builtin_nontemporal_load(reinterpret_cast<const nt_f32x4*>(p)); return make_float4(_v.x, _v.y, _v.z, _v.w); }())
 #define NT_STORE4(p, a, b, c, d) __builtin_nontemporal_store(nt_f32x4{a, b, c, d}, reinterpret_cast<nt_f32x4*>(p))
 
+// act_apply for the apply passes, with a ReLU that keeps NaN as torch.relu does (act_apply's `v > 0.f ? v : 0.f` turns it into 0; every
+// other activation returns NaN).  Every other value, -0 and the infinities included, gives act_apply's bits.  Free in these HBM-bound
+// passes; in the MFMA epilogues the second instruction per accumulator cost 0.1 % of bench.py, so act_apply itself is left as it is.
+__device__ __forceinline__ float norm_act(float v, int act) { return act == CF_ACT_RELU ? (v <= 0.f ? 0.f : v) : act_apply(v, act); }
+
 // optional normalisation of the residual operand (all NULL: the residual is added as it is)
 struct ResNorm {
     const double* ws;
@@ -117,7 +127,7 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const float* __restrict__
             for (int k = 0; k < 4; ++k) {
                 float y = (t[k] - mean) * rstd * g + bb;
                 if (res_mode == CF_RES_BEFORE_ACT) y += rr[k];
-                y = act_apply(y, act);
+                y = norm_act(y, act);
                 if (res_mode == CF_RES_AFTER_ACT) y += rr[k];
                 t[k] = y;
             }
@@ -128,7 +138,7 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const float* __restrict__
             float y = (x[base + i] - mean) * rstd * g + bb;
             const float r = res_mode != CF_RES_NONE ? (res[base + i] - rm) * ra + rb : 0.f;
             if (res_mode == CF_RES_BEFORE_ACT) y += r;
-            y = act_apply(y, act);
+            y = norm_act(y, act);
             if (res_mode == CF_RES_AFTER_ACT) y += r;
             out[base + i] = y;
         }
@@ -197,7 +207,7 @@ __global__ void __launch_bounds__(256) gn_apply_small_kernel(const float* __rest
             for (int k = 0; k < 4; ++k) {
                 float y = (t[k] - mean) * rstd * g + bb;
                 if (res_mode == CF_RES_BEFORE_ACT) y += rr[k];
-                y = act_apply(y, act);
+                y = norm_act(y, act);
                 if (res_mode == CF_RES_AFTER_ACT) y += rr[k];
                 t[k] = y;
             }
@@ -212,7 +222,7 @@ __global__ void __launch_bounds__(256) gn_apply_small_kernel(const float* __rest
             float y = (x[base + i] - coef[pl][0]) * coef[pl][1] * coef[pl][2] + coef[pl][3];
             const float r = res_mode != CF_RES_NONE ? (res[base + i] - rcoef[pl][0]) * rcoef[pl][1] + rcoef[pl][2] : 0.f;
             if (res_mode == CF_RES_BEFORE_ACT) y += r;
-            y = act_apply(y, act);
+            y = norm_act(y, act);
             if (res_mode == CF_RES_AFTER_ACT) y += r;
             out[base + i] = y;
         }
@@ -294,7 +304,7 @@ __global__ void __launch_bounds__(256) gn_apply_stem_kernel(const float* y2, con
             for (int k = 0; k < 4; ++k) {
                 float y = (t[k] - mean) * rstd * g + bb;
                 if (res_mode == CF_RES_BEFORE_ACT) y += rr[k];
-                y = act_apply(y, act);
+                y = norm_act(y, act);
                 if (res_mode == CF_RES_AFTER_ACT) y += rr[k];
                 t[k] = y;
             }
@@ -367,17 +377,73 @@ __global__ void __launch_bounds__(64 * LN_G) layer_norm_cf_kernel(const float* _
 }  // namespace cf
 
 namespace cf {
-int launch_gn_stats(const float* x, double* ws, int B, int C, int HW, int groups, hipStream_t s) {
-    const long nslabs = (long)B * groups;
+// The launch plan of both passes: every condition on which launch_gn_stats and gn_apply_launch choose a kernel or a geometry lives here
+// and nowhere else (cf_group_norm_route exports it; the launchers execute it).  out / res may be NULL: the statistics half needs x only.
+struct GnPlan {
+    int stats_block;   // 0 gn_stats_wave_kernel, 1 gn_stats_block_kernel
+    int segs;          // blocks per slab of the block kernel (0: wave kernel)
+    int stats_blocks;  // grid of the statistics kernel
+    int apply_large;   // 0 gn_apply_small_kernel, 1 gn_apply_kernel
+    int vec;           // the float4 instantiation
+    int ppb;           // small: planes per block; large: blocks per plane (asegs)
+    int apply_blocks;  // grid of the apply kernel
+    int last_np;       // small: planes of the last block; large: 0
+};
+
+static int gn_plan(const float* x, const float* out, const float* res, int B, int C, int HW, int groups, GnPlan* p) {
+    CF_REQUIRE(B > 0 && C > 0 && HW > 0 && groups > 0 && C % groups == 0, "bad shape B=%d C=%d HW=%d groups=%d", B, C, HW, groups);
+    CF_REQUIRE((long)(C / groups) * HW < (1L << 31), "slab too large");
+    const long nslabs = (long)B * groups, planes = (long)B * C;
     const int L = (C / groups) * HW;
     if (L <= 4096 || (L & 3) || (reinterpret_cast<uintptr_t>(x) & 15)) {
-        hipLaunchKernelGGL(gn_stats_wave_kernel, dim3(cdiv(nslabs, 4)), dim3(256), 0, s, x, ws, nslabs, L);
+        CF_REQUIRE((nslabs + 3) / 4 < (1L << 31), "grid too large");
+        p->stats_block = 0;
+        p->segs = 0;
+        p->stats_blocks = cdiv(nslabs, 4);
     } else {
-        if (hipMemsetAsync(ws, 0, sizeof(double) * 2 * nslabs, s) != hipSuccess) { set_error("gn stats: memset failed"); return CF_ERR_LAUNCH; }
         int segs = (int)((L / 4 + 256 * 8 - 1) / (256 * 8));  // ~8 float4 per thread
         if (segs < 1) segs = 1;
         if (segs > 64) segs = 64;
-        hipLaunchKernelGGL(gn_stats_block_kernel, dim3((unsigned)(nslabs * segs)), dim3(256), 0, s, x, ws, L, segs);
+        CF_REQUIRE(nslabs * segs < (1L << 31), "grid too large");
+        p->stats_block = 1;
+        p->segs = segs;
+        p->stats_blocks = (int)(nslabs * segs);
+    }
+    p->vec = (HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(res)) & 15) == 0;
+    if (HW < 2048) {
+        int ppb = 4096 / HW;
+        if (ppb < 1) ppb = 1;
+        if (ppb > GN_SMALL_MAXP) ppb = GN_SMALL_MAXP;
+        const long nblk = (planes + ppb - 1) / ppb;
+        CF_REQUIRE(nblk < (1L << 31), "grid too large");
+        p->apply_large = 0;
+        p->ppb = ppb;
+        p->apply_blocks = (int)nblk;
+        p->last_np = (int)(planes - (nblk - 1) * ppb);
+    } else {
+        const int per_block = p->vec ? 256 * 4 * 4 : 256 * 4;  // ~4 vector (or scalar) elements per thread
+        int asegs = (HW + per_block - 1) / per_block;
+        if (asegs < 1) asegs = 1;
+        CF_REQUIRE(planes * asegs < (1L << 31), "grid too large");
+        p->apply_large = 1;
+        p->ppb = asegs;
+        p->apply_blocks = (int)(planes * asegs);
+        p->last_np = 0;
+    }
+    return CF_OK;
+}
+
+int launch_gn_stats(const float* x, double* ws, int B, int C, int HW, int groups, hipStream_t s) {
+    GnPlan p;
+    const int rc = gn_plan(x, nullptr, nullptr, B, C, HW, groups, &p);
+    if (rc != CF_OK) return rc;
+    const long nslabs = (long)B * groups;
+    const int L = (C / groups) * HW;
+    if (!p.stats_block) {
+        hipLaunchKernelGGL(gn_stats_wave_kernel, dim3((unsigned)p.stats_blocks), dim3(256), 0, s, x, ws, nslabs, L);
+    } else {
+        if (hipMemsetAsync(ws, 0, sizeof(double) * 2 * nslabs, s) != hipSuccess) { set_error("gn stats: memset failed"); return CF_ERR_LAUNCH; }
+        hipLaunchKernelGGL(gn_stats_block_kernel, dim3((unsigned)p.stats_blocks), dim3(256), 0, s, x, ws, L, p.segs);
     }
     if (hipGetLastError() != hipSuccess) { set_error("gn stats: launch failed"); return CF_ERR_LAUNCH; }
     return CF_OK;
@@ -396,7 +462,6 @@ extern "C" int cf_group_norm(const float* x, const float* gamma, const float* be
     CF_REQUIRE(res_mode == CF_RES_NONE || res, "residual mode %d without residual tensor", res_mode);
     CF_REQUIRE(act >= CF_ACT_NONE && act <= CF_ACT_SIGMOID, "bad activation %d", act);
     hipStream_t s = as_stream(stream);
-    CF_REQUIRE((long)(C / groups) * HW < (1L << 31), "slab too large");
     int rc = launch_gn_stats(x, ws, B, C, HW, groups, s);
     if (rc != CF_OK) return rc;
     return gn_apply_launch(x, gamma, beta, res, out, B, C, HW, groups, eps, act, res_mode, ws, s);
@@ -410,6 +475,26 @@ extern "C" int cf_group_norm_apply(const float* x, const float* gamma, const flo
     CF_REQUIRE(res_mode == CF_RES_NONE || res, "residual mode %d without residual tensor", res_mode);
     CF_REQUIRE(act >= CF_ACT_NONE && act <= CF_ACT_SIGMOID, "bad activation %d", act);
     return gn_apply_launch(x, gamma, beta, res, out, B, C, HW, groups, eps, act, res_mode, ws, as_stream(stream));
+}
+
+// The plan cf_group_norm / cf_group_norm_apply / cf_group_norm_apply_res_norm execute for these pointers and this shape, as host code:
+// launches nothing, needs no GPU.  plan8 (nullable): {statistics kernel (0 wave, 1 block), segs (0 on the wave kernel), statistics blocks,
+// apply kernel (0 small, 1 large), VEC, ppb (small) or asegs (large), apply blocks, planes of the last small block (0 on the large kernel)}.
+extern "C" int cf_group_norm_route(const float* x, const float* out, const float* res, int B, int C, int HW, int groups, int* plan8) {
+    GnPlan p;
+    const int rc = gn_plan(x, out, res, B, C, HW, groups, &p);
+    if (rc != CF_OK) return rc;
+    if (plan8) {
+        const int v[8] = {p.stats_block, p.segs, p.stats_blocks, p.apply_large, p.vec, p.ppb, p.apply_blocks, p.last_np};
+        for (int i = 0; i < 8; ++i) plan8[i] = v[i];
+    }
+    return CF_OK;
+}
+
+// The statistics pass of cf_group_norm alone: ws[2 * (b * groups + g)] = {sum, sum of squares} of the slab.
+extern "C" int cf_group_norm_stats(const float* x, double* ws, int B, int C, int HW, int groups, void* stream) {
+    CF_REQUIRE(x && ws, "null pointer");
+    return launch_gn_stats(x, ws, B, C, HW, groups, as_stream(stream));
 }
 
 // {mean, scale, shift} per (sample, channel) from the fp64 sums: what a consumer needs to apply the normalisation itself
@@ -549,35 +634,23 @@ extern "C" int cf_group_norm_apply_res_stem(const float* y2, const float* gamma,
 
 static int gn_apply_launch(const float* x, const float* gamma, const float* beta, const float* res, float* out, int B, int C, int HW,
                            int groups, float eps, int act, int res_mode, const double* ws, hipStream_t s, ResNorm rn) {
-    if (HW < 2048) {
-        const long planes_s = (long)B * C;
-        int ppb = 4096 / HW;
-        if (ppb < 1) ppb = 1;
-        if (ppb > GN_SMALL_MAXP) ppb = GN_SMALL_MAXP;
-        const long nblk = (planes_s + ppb - 1) / ppb;
-        CF_REQUIRE(nblk < (1L << 31), "grid too large");
-        const bool vec_s = (HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(res)) & 15) == 0;
-        if (vec_s)
-            hipLaunchKernelGGL((gn_apply_small_kernel<true>), dim3((unsigned)nblk), dim3(256), 0, s, x, gamma, beta, res, out, ws, C, HW, groups, eps,
-                               act, res_mode, planes_s, ppb, rn);
+    GnPlan p;
+    const int rc = gn_plan(x, out, res, B, C, HW, groups, &p);
+    if (rc != CF_OK) return rc;
+    const dim3 grid((unsigned)p.apply_blocks);
+    if (!p.apply_large) {
+        const long planes = (long)B * C;
+        if (p.vec)
+            hipLaunchKernelGGL((gn_apply_small_kernel<true>), grid, dim3(256), 0, s, x, gamma, beta, res, out, ws, C, HW, groups, eps, act, res_mode,
+                               planes, p.ppb, rn);
         else
-            hipLaunchKernelGGL((gn_apply_small_kernel<false>), dim3((unsigned)nblk), dim3(256), 0, s, x, gamma, beta, res, out, ws, C, HW, groups, eps,
-                               act, res_mode, planes_s, ppb, rn);
-        CF_CHECK_LAUNCH();
-        return CF_OK;
+            hipLaunchKernelGGL((gn_apply_small_kernel<false>), grid, dim3(256), 0, s, x, gamma, beta, res, out, ws, C, HW, groups, eps, act, res_mode,
+                               planes, p.ppb, rn);
+    } else if (p.vec) {
+        hipLaunchKernelGGL((gn_apply_kernel<true>), grid, dim3(256), 0, s, x, gamma, beta, res, out, ws, C, HW, groups, eps, act, res_mode, p.ppb, rn);
+    } else {
+        hipLaunchKernelGGL((gn_apply_kernel<false>), grid, dim3(256), 0, s, x, gamma, beta, res, out, ws, C, HW, groups, eps, act, res_mode, p.ppb, rn);
     }
-    const long planes = (long)B * C;
-    const bool vec = (HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(res)) & 15) == 0;
-    const int per_block = vec ? 256 * 4 * 4 : 256 * 4;  // ~4 vector (or scalar) elements per thread
-    int asegs = (HW + per_block - 1) / per_block;
-    if (asegs < 1) asegs = 1;
-    CF_REQUIRE(planes * asegs < (1L << 31), "grid too large");
-    if (vec)
-        hipLaunchKernelGGL((gn_apply_kernel<true>), dim3((unsigned)(planes * asegs)), dim3(256), 0, s, x, gamma, beta, res, out, ws, C, HW, groups,
-                           eps, act, res_mode, asegs, rn);
-    else
-        hipLaunchKernelGGL((gn_apply_kernel<false>), dim3((unsigned)(planes * asegs)), dim3(256), 0, s, x, gamma, beta, res, out, ws, C, HW, groups,
-                           eps, act, res_mode, asegs, rn);
     CF_CHECK_LAUNCH();
     return CF_OK;
 }

@@ -214,6 +214,14 @@ int cf_group_norm(const float* x, const float* gamma, const float* beta, const f
 /* The apply pass of cf_group_norm alone; `ws` holds the statistics (from cf_conv2d_f16s' fused epilogue). */
 int cf_group_norm_apply(const float* x, const float* gamma, const float* beta, const float* res, float* out, int B, int C,
                         int HW, int groups, float eps, int act, int res_mode, const double* ws, void* stream);
+/* The statistics pass of cf_group_norm alone: ws[2 * (b * groups + g)] = {sum, sum of squares} of the slab, in fp64. */
+int cf_group_norm_stats(const float* x, double* ws, int B, int C, int HW, int groups, void* stream);
+/* The launch plan of the three calls above and of cf_group_norm_apply_res_norm, exported (host code, launches nothing, needs no GPU): the
+ * launchers execute exactly this plan.  x, out, res: the pointers of the call (only their 16-byte alignment matters; out / res may be
+ * NULL).  plan8 (nullable) receives {statistics kernel: 0 gn_stats_wave_kernel, 1 gn_stats_block_kernel; blocks per slab of the block
+ * kernel, or 0; statistics grid; apply kernel: 0 gn_apply_small_kernel, 1 gn_apply_kernel; VEC; planes per block (small) or blocks per
+ * plane (large); apply grid; planes of the last small block, or 0}.  Returns CF_OK, or CF_ERR_ARG for a shape the calls refuse. */
+int cf_group_norm_route(const float* x, const float* out, const float* res, int B, int C, int HW, int groups, int* plan8);
 /* The same apply pass when the residual is a raw convolution output that still awaits ITS OWN GroupNorm (the 1x1 conv + GroupNorm
  * `downsample` branch of DoubleConv, nnunet/lib/utils.py:1192-1195, :1208-1213): res is normalised on the fly with res_ws (its
  * {sum, sum of squares} pairs, same groups and eps) and res_gamma / res_beta, saving that branch's own apply pass. */

@@ -123,6 +123,68 @@ def test_attention_route_probe_needs_no_gpu():
     assert h.cf_attention_cf(a, 4096, a, 4096, a, 4096, a, 1, 1, 24, 32, 32, None) == -1 and b"head dim 24 unsupported" in h.cf_last_error()
 
 
+def test_group_norm_route_plan_needs_no_gpu():
+    """cf_group_norm_route is the plan launch_gn_stats and gn_apply_launch execute, as host code: the plan of every row of
+    test_gpu_norm_routes.py (written out by hand in _norm_refs.py), asked with made-up addresses -- one 16-byte aligned, one 4 bytes off --,
+    the lines either side of each row, and the error returns of every norm entry, none of which reaches a launch"""
+    import _norm_refs as R
+    from cineflow import _lib
+    h = _lib.lib()
+    a, m = 4096, 4096 + 4
+
+    def plan(x, out, res, B, C, HW, groups):
+        p = (ctypes.c_int * 8)()
+        assert h.cf_group_norm_route(x, out, res, B, C, HW, groups, ctypes.addressof(p)) == 0, h.cf_last_error()
+        return tuple(p)
+
+    for row in R.STATS_ROWS:
+        x = m if row.view else a
+        assert plan(x, None, None, row.B, row.C, row.HW, row.groups)[:3] == row.plan, row.name
+    for row in R.APPLY_ROWS:
+        x, res = (m if row.view == "x" else a), (m if row.view == "res" else a)
+        out = x if row.inplace else a
+        assert plan(x, out, res, row.B, row.C, row.HW, row.groups) == row.plan, row.name
+        if row.view != "res":
+            assert plan(x, out, None, row.B, row.C, row.HW, row.groups) == row.plan, row.name
+    # the statistics line: L = 4096 | 4100, a misaligned or odd L of any size, the clamp of segs at 64 and the last L below it
+    assert plan(a, a, None, 1, 1, 4096, 1)[:3] == (0, 0, 1) and plan(a, a, None, 1, 1, 4100, 1)[:3] == (1, 1, 1)
+    assert plan(m, a, None, 1, 1, 1 << 20, 1)[:3] == (0, 0, 1) and plan(a, a, None, 5, 1, (1 << 20) + 2, 1)[:3] == (0, 0, 2)
+    assert plan(a, a, None, 1, 1, 64 * 8192, 1)[:3] == (1, 64, 64) and plan(a, a, None, 1, 1, 64 * 8192 + 4, 1)[:3] == (1, 64, 64)
+    assert plan(a, a, None, 3, 1, 63 * 8192 + 4, 1)[:3] == (1, 64, 192) and plan(a, a, None, 3, 1, 63 * 8192, 1)[:3] == (1, 63, 189)
+    # the apply line: HW = 2047 | 2048, every pointer's alignment on its own, the ppb clamp at HW = 8 | 9
+    assert plan(a, a, a, 1, 3, 2047, 1)[3:] == (0, 0, 2, 2, 1) and plan(a, a, a, 1, 3, 2048, 1)[3:] == (1, 1, 1, 3, 0)
+    for x, out, res in ((m, a, a), (a, m, a), (a, a, m)):
+        assert plan(x, out, res, 1, 3, 2048, 1)[3:] == (1, 0, 2, 6, 0) and plan(x, out, res, 1, 3, 512, 1)[3:] == (0, 0, 8, 1, 3)
+    assert plan(a, a, None, 1, 1030, 8, 1)[3:] == (0, 1, 512, 3, 6) and plan(a, a, None, 1, 1030, 9, 1)[3:] == (0, 0, 455, 3, 120)
+    assert plan(a, a, None, 1, 1, 4096 * 4 + 4, 1)[3:] == (1, 1, 5, 5, 0)
+    assert h.cf_group_norm_route(a, a, None, 2, 8, 36, 4, None) == 0                        # plan8 is nullable
+
+    def err(rc, text):
+        assert rc == -1 and text in h.cf_last_error(), (rc, h.cf_last_error())
+
+    err(h.cf_group_norm_route(a, a, None, 2, 12, 16, 8, None), b"bad shape")                # groups does not divide C
+    err(h.cf_group_norm_route(a, a, None, 1, 2, 1 << 30, 1, None), b"slab too large")
+    err(h.cf_group_norm_stats(a, a, 2, 12, 16, 8, None), b"bad shape")
+    err(h.cf_group_norm_stats(None, a, 2, 8, 16, 8, None), b"null pointer")
+    err(h.cf_group_norm(a, None, None, None, a, 2, 12, 16, 8, 1e-5, 0, 0, a, None), b"bad shape")
+    err(h.cf_group_norm(a, None, None, None, a, 2, 8, 16, 8, 1e-5, 1, 1, a, None), b"without residual")
+    err(h.cf_group_norm_apply(a, None, None, None, a, 2, 12, 16, 8, 1e-5, 0, 0, a, None), b"bad shape")
+    err(h.cf_group_norm_apply(a, None, None, None, a, 2, 8, 16, 8, 1e-5, 0, 2, a, None), b"without residual")
+    err(h.cf_group_norm_apply(a, None, None, None, a, 2, 8, 16, 8, 1e-5, 6, 0, a, None), b"bad activation")
+    err(h.cf_group_norm_apply_res_norm(a, None, None, a, a, 2, 8, 16, 8, 1e-5, 1, 0, a, a, None, None, None), b"needs a residual mode")
+    err(h.cf_group_norm_apply_res_norm(a, None, None, None, a, 2, 8, 16, 8, 1e-5, 1, 1, a, a, None, None, None), b"null pointer")
+    err(h.cf_group_norm_apply_res_norm(a, None, None, a, a, 2, 12, 16, 8, 1e-5, 1, 1, a, a, None, None, None), b"bad shape")
+    err(h.cf_group_norm_coef(a, None, None, 2, 12, 16, 8, 1e-5, a, None), b"bad shape")
+    err(h.cf_layer_norm_cf(a, a, a, a, 2, 0, 16, 1e-5, None), b"bad shape")
+    err(h.cf_layer_norm_cf(a, None, a, a, 2, 8, 16, 1e-5, None), b"null pointer")
+    err(h.cf_norm_head_1x1(a, a, 0.01, a, None, a, 2, 8, 18, 4, None), b"HW % 4 == 0")      # HW % 4
+    err(h.cf_norm_head_1x1(a, a, 0.01, a, None, a, 2, 8, 16, 3, None), b"K=3")
+    err(h.cf_norm_head_1x1(a, a, 0.01, a, None, a, 2, 1025, 16, 4, None), b"C=1025")
+    err(h.cf_norm_head_1x1(a, a, -0.01, a, None, a, 2, 8, 16, 4, None), b"slope must be >= 0")
+    err(h.cf_norm_head_1x1(m, a, 0.01, a, None, a, 2, 8, 16, 4, None), b"16-byte aligned")
+    err(h.cf_norm_head_1x1(a, a, 0.01, a, None, m, 2, 8, 16, 4, None), b"16-byte aligned")
+
+
 def test_conv2d_f16s_route_plan_needs_no_gpu():
     """cf_conv2d_f16s_route is the plan the f16-split launcher executes, as host code: the instantiation of every row of
     test_gpu_conv_f16s_routes.py in both product modes, and the conditions no GPU test can afford -- sub-batches, the 1024-workgroup and
