@@ -133,6 +133,8 @@ SIGNATURES = {
     "cf_label_surface_table": [P, P, I, I, I, I, I, I, DBL, DBL, DBL, P, I, I, P, P, P, P],
     "cf_flow_regularity_table": [P, P, I, I, I, I, I, P, P, P],
     "cf_cine_ssim_table": [P, P, P, I, I, I, I, I, I, DBL, DBL, DBL, P, P, P, P],
+    "cf_contour_track_table": [P, P, P, P, I, I, I, I, I, I, P, P, P],
+    "cf_contour_strain_table": [P, P, L, P, P, I, I, I, DBL, DBL, P, P],
     "cf_window_attention": [P, P, P, P, I, I, I, I, I, I, I, P],
     "cf_frame_boxes": [P, I, P, I, I, I, P],
     "cf_sample_points_2d": [P, P, P, I, I, I, I, I, P],

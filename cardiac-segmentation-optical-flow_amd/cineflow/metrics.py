@@ -629,3 +629,70 @@ def cine_ssim_table(fixed, moving, flow, labels=None, names=("RV", "MYO", "LV"),
         out = reg.permute(0, 2, 3, 1).contiguous()
         return rows, (out if torch.is_tensor(moving if registered is None else registered) else out.cpu().numpy())
     return rows
+
+
+# ------------------------------------------------------------------------------------------------ compute_contour_metrics.py / get_strain.py
+CONTOUR_MODES = ("from_ed", "from_ed_accumulation", "to_ed_accumulation", "to_ed")          # cf_contour_track_table's mode numbers
+
+
+def contour_counts(counts, D, Pmax, strain=False):
+    """counts [D, 3] (endo, epi, RV points per slice) -> contiguous int32 numpy array, checked on the host before any device work"""
+    c = np.ascontiguousarray(counts.cpu().numpy() if torch.is_tensor(counts) else counts)
+    if c.shape != (D, 3) or c.dtype.kind not in "iu":
+        raise ValueError("counts has to be an integer array [D, 3] = %s, got %s %s" % ((D, 3), c.dtype, c.shape))
+    if (c < 0).any() or (c.sum(1) > Pmax).any():
+        raise ValueError("counts %s: negative, or more points than the padded row of %d" % (c.tolist(), Pmax))
+    if strain and (c[:, 0] != c[:, 1]).any():
+        d = int(np.argmax(c[:, 0] != c[:, 1]))
+        raise ValueError("slice %d: %d endo and %d epi points: strain needs equal counts" % (d, c[d, 0], c[d, 1]))
+    return c.astype(np.int32)
+
+
+def contour_track_table(flow, pts, counts, mode, out=None, counts_dev=None):
+    """cf_contour_track_table: flow [D, T, 2, A, B] (ED first, as strain.prepare_flow returns it; frame 0 is never read), pts
+    [D, T, Pmax, 2] (0-based ground-truth points in the same frame order: endo, epi, RV, padded), counts [D, 3] on the host, mode a name
+    of CONTOUR_MODES or its number -> (pos, table), device tensors: pos fp32 [D, T - 1, Pmax, 2], the tracked positions (from_ed*) or
+    predicted deltas (to_ed*) with the bits of chained ops.sample_points calls, and table fp64 [D, T - 1, 3], the mean point error of
+    ENDO, EPI, RV per frame in the order strain.contour_tracking_error returns (NaN without points).  One library call whatever T;
+    `out` (fp64 device tensor of D (T - 1) 3 elements) receives the table."""
+    mode = CONTOUR_MODES.index(mode) if isinstance(mode, str) else int(mode)
+    f = _tensor(flow)
+    p = _tensor(pts)
+    if f.dim() != 5 or f.shape[2] != 2 or p.dim() != 4 or p.shape[3] != 2 or tuple(p.shape[:2]) != tuple(f.shape[:2]):
+        raise ValueError("flow has to be [D, T, 2, A, B] and pts [D, T, Pmax, 2], got %s and %s" % (tuple(f.shape), tuple(p.shape)))
+    D, T, _, A, B = f.shape
+    Pmax = p.shape[2]
+    c = contour_counts(counts, D, Pmax)
+    f = f.to(_dev(), dtype=torch.float32).contiguous()
+    p = p.to(_dev(), dtype=torch.float32).contiguous()
+    cd = torch.from_numpy(c).to(f.device) if counts_dev is None else counts_dev
+    pos = torch.empty((D, T - 1, Pmax, 2), dtype=torch.float32, device=f.device)
+    table = torch.empty(D * (T - 1) * 3, dtype=torch.float64, device=f.device) if out is None else out
+    assert table.dtype == torch.float64 and table.numel() == D * (T - 1) * 3 and table.is_contiguous()
+    check(lib().cf_contour_track_table(_f32(f), _f32(p), c.ctypes.data, cd.data_ptr(), D, T, A, B, Pmax, mode, _f32(pos), table.data_ptr(), _stream()),
+          "cf_contour_track_table")
+    return pos, table.view(D, T - 1, 3)
+
+
+def contour_strain_table(pos, ed_pts, counts, zoom, out=None, counts_dev=None):
+    """cf_contour_strain_table: pos fp32 [D, T - 1, Pmax, 2] (contour_track_table's from_ed positions), ed_pts [D, Pmax, 2] (the ED points;
+    a view pts[:, 0] of the [D, T, Pmax, 2] array is read in place), counts [D, 3] on the host with equal endo and epi counts, zoom =
+    (mm, mm) for the two coordinates -> fp64 device tensor [D, T, 2]: radial and circumferential strain per frame, ED first (row 0 is
+    the ED frame against itself).  `out` (fp64, D T 2 elements) receives it."""
+    ps = _tensor(pos)
+    e = _tensor(ed_pts)
+    if ps.dim() != 4 or ps.shape[3] != 2 or e.dim() != 3 or (e.shape[0], e.shape[1], e.shape[2]) != (ps.shape[0], ps.shape[2], 2):
+        raise ValueError("pos has to be [D, T - 1, Pmax, 2] and ed_pts [D, Pmax, 2], got %s and %s" % (tuple(ps.shape), tuple(e.shape)))
+    D, T, Pmax = ps.shape[0], ps.shape[1] + 1, ps.shape[2]
+    c = contour_counts(counts, D, Pmax, strain=True)
+    ps = ps.to(_dev(), dtype=torch.float32).contiguous()
+    e = e.to(_dev(), dtype=torch.float32)
+    if e.stride(2) != 1 or e.stride(1) != 2 or (D > 1 and (e.stride(0) < 2 * Pmax or e.stride(0) % 2)):
+        e = e.contiguous()
+    stride = e.stride(0) if D > 1 else 2 * Pmax
+    cd = torch.from_numpy(c).to(ps.device) if counts_dev is None else counts_dev
+    table = torch.empty(D * T * 2, dtype=torch.float64, device=ps.device) if out is None else out
+    assert table.dtype == torch.float64 and table.numel() == D * T * 2 and table.is_contiguous()
+    check(lib().cf_contour_strain_table(_f32(ps), e.data_ptr(), stride, c.ctypes.data, cd.data_ptr(), D, T, Pmax, float(zoom[0]), float(zoom[1]),
+                                        table.data_ptr(), _stream()), "cf_contour_strain_table")
+    return table.view(D, T, 2)

@@ -3,6 +3,8 @@
     python -m cineflow.score seg      -pred FOLDER -ref GT_FOLDER    [-i INPUT_FOLDER] [--gt frame|ed] [--layout predict|saver]
     python -m cineflow.score jacobian -flow FOLDER -l LABEL_FOLDER   [-i INPUT_FOLDER] [--layout predict|saver]
     python -m cineflow.score ssim     -flow FOLDER -i INPUT_FOLDER   [-l LABEL_FOLDER] [--layout predict|saver] [--win 7]
+    python -m cineflow.score contour  -flow FOLDER -c CONTOUR_FOLDER -i INPUT_FOLDER [--layout predict|saver]
+                                      [--mode from_ed|from_ed_accumulation|to_ed|to_ed_accumulation]
 
 `seg` writes what nnunet/compute_metrics.py writes -- segmentation_metrics.json, segmentation_metrics.csv, segmentation_metrics_es.csv:
 Dice, Hausdorff distance and average symmetric surface distance of the propagated labels (RV = 1, MYO = 2, LV = 3) per frame --
@@ -12,7 +14,13 @@ similarity of every frame's image INPUT_FOLDER/<patient>/<case>_0000.nii.gz, war
 image, per slice -- and with -l what nnunet/compute_SSIM_crop_per_structure.py writes -- ssim_metrics_all.json, ssim_metrics_all.csv: the
 SSIM map's means over the RV, MYO and LV of the ED label volume as well (cineflow.metrics.cine_ssim_table).  All are written from the scripts' behaviour, not transcribed: the scripts' hard-coded paths, pickles
 and `patient029` special cases are arguments or gone, and the numbers of a patient come from cineflow.metrics.cine_label_scores /
-cine_jacobian_table (csrc/score.hip) instead of one call chain per frame and class.
+cine_jacobian_table (csrc/score.hip) instead of one call chain per frame and class.  `contour` writes what
+nnunet/compute_contour_metrics.py writes -- contour_metrics.json, contour_metrics.csv: the tracking error of the ground-truth endo-, epi-
+and RV contour points CONTOUR_FOLDER/contour/{LV,RV}/<patient>_sliceNN.npy ([4, P, T] and [2, P2, T], 1-based, NN = slice + 1) under the
+predicted flow, per slice and frame, in one of the script's four modes (the script picks one from the training config; from_ed is its
+fallback and the default here) -- and in mode from_ed also strain_metrics.json: the radial and circumferential strain curves of
+nnunet/get_strain.py and their smoothness, with the pixel spacing of the ED image INPUT_FOLDER/<patient>/<case>_0000.nii.gz
+(cineflow.strain.track_patient, csrc/contour.hip).
 
 Layouts (one sub-folder per patient either way):
     predict   <FOLDER>/<patient>/Registered/<case>.nii.gz, <FOLDER>/<patient>/Flow/<case>.npz          (cineflow.predict)
@@ -23,7 +31,7 @@ A case's frame number is int(stem[-2:]); cases are sorted by it.  ED / ES indice
 
 A thread pool reads and inflates the next patient's files while the current one is scored; one patient is resident on the device at a
 time and only this process opens the GPU.  Turning per-case rows into the json / csv documents is host code (segmentation_tables,
-jacobian_tables, ssim_tables).
+jacobian_tables, ssim_tables, contour_tables, strain_tables).
 """
 import collections
 import csv
@@ -193,6 +201,64 @@ def pair_ssim_cases(flow_folder, input_folder, patient, ed_index, label_folder=N
     return cases
 
 
+def _nifti_zooms(path):
+    """pixdim[1:3] from the header alone: nibabel's header.get_zooms()[:2]"""
+    with open(path, "rb") as f:
+        raw = f.read()
+    head = zlib.decompressobj(wbits=31).decompress(raw, 352) if str(path).endswith(".gz") else raw[:352]
+    pixdim = np.frombuffer(head, dtype="<f4", count=8, offset=76)
+    return float(pixdim[1]), float(pixdim[2])
+
+
+def _npy_shape(path):
+    with open(path, "rb") as f:
+        version = np.lib.format.read_magic(f)
+        read = np.lib.format.read_array_header_1_0 if version == (1, 0) else np.lib.format.read_array_header_2_0
+        return tuple(read(f)[0])
+
+
+def pair_contour_cases(flow_folder, contour_folder, input_folder, patient, ed_index):
+    """-> (cases, zoom): the flow files of one patient sorted by frame number, the ED frame's own flow file (frame number ed_index + 1)
+    left out, then one case per slice d whose `path` / `other` are contour/LV/<patient>_slice<d+1>.npy ([4, P, T]: endo x, y, epi x, y)
+    and contour/RV/<patient>_slice<d+1>.npy ([2, P2, T]); zoom the in-plane spacing of the ED image INPUT/<patient>/<ED case>_0000.nii.gz.
+    ([], None) without flow files.  With T - 1 flow files the frame numbers have to be 1 .. T without ed_index + 1 and every contour
+    file has to hold T frames; a missing or mis-shaped file is a ValueError naming it (headers only: nothing is read)."""
+    stems = [s for s in sorted_cases(flow_folder, ".npz") if frame_number(s) != ed_index + 1]
+    if not stems:
+        return [], None
+    T = len(stems) + 1
+    if [frame_number(s) for s in stems] != [t + 1 for t in range(T) if t != ed_index]:
+        raise ValueError("patient %s: flow files of frames %s, expected 1 .. %d without the ED frame %d (ed_index %d)"
+                         % (patient, [frame_number(s) for s in stems], T, ed_index + 1, ed_index))
+    cases, want = [], None
+    for stem in stems:
+        path = join(flow_folder, stem + ".npz")
+        fshape = _npz_shape(path, "flow")
+        if len(fshape) != 4 or fshape[3] != 2:
+            raise ValueError("case %s: flow of shape %s, expected [H, W, D, 2]" % (stem, fshape))
+        if want is not None and fshape[:3] != want:
+            raise ValueError("case %s: flow [H, W, D] = %s, the patient's other flows %s" % (stem, fshape[:3], want))
+        want = fshape[:3]
+        cases.append(Case(stem, frame_number(stem), path, None))
+    for d in range(want[2]):
+        name = "%s_slice%s" % (patient, str(d + 1).zfill(2))
+        files = [join(contour_folder, "contour", k, name + ".npy") for k in ("LV", "RV")]
+        for f, rows in zip(files, (4, 2)):
+            if not os.path.isfile(f):
+                raise ValueError("patient %s: no contour file %s (slice %d of %d)" % (patient, f, d, want[2]))
+            shape = _npy_shape(f)
+            if len(shape) != 3 or shape[0] != rows:
+                raise ValueError("contour file %s: shape %s, expected [%d, P, T]%s" % (f, shape, rows, " (endo and epi points pair up)" if rows == 4 else ""))
+            if shape[2] != T:
+                raise ValueError("contour file %s: %d frames, but %d flow files + the ED frame = %d" % (f, shape[2], T - 1, T))
+        cases.append(Case(name, d, files[0], files[1]))
+    ed_stem = stems[0][:-2] + str(ed_index + 1).zfill(2)
+    img = join(input_folder, patient, ed_stem + "_0000.nii.gz")
+    if not os.path.isfile(img):
+        raise ValueError("case %s: no image %s (the pixel spacing of the strain curves)" % (ed_stem, img))
+    return cases, _nifti_zooms(img)
+
+
 # ------------------------------------------------------------------------------------------------ host tables
 def segmentation_row(name, scores):
     """one csv row (the thirteen columns) from {'RV': {'Dice', 'HD', 'ASSD'}, 'MYO': ..., 'LV': ...}"""
@@ -321,6 +387,62 @@ def ssim_tables(entries, key="SSIM"):
     return {"all": [dict(e) for e in entries], "mean": mean}, rows
 
 
+CONTOUR_STRUCTURES = ("ENDO", "EPI", "RV")
+CONTOUR_COLUMNS = ["Name", "slice_number"] + list(CONTOUR_STRUCTURES) + ["Average"]
+CONTOUR_MODES = ("from_ed", "from_ed_accumulation", "to_ed", "to_ed_accumulation")
+
+
+def contour_rows(patient, errors):
+    """errors [D, T - 1, 3] (strain.track_patient) -> the script's per-slice entries: Name, slice_number and the per-frame lists"""
+    return [collections.OrderedDict([("Name", patient), ("slice_number", d)] + [(k, [float(v) for v in e[:, i]]) for i, k in enumerate(CONTOUR_STRUCTURES)])
+            for d, e in enumerate(np.asarray(errors))]
+
+
+def contour_tables(per_patient):
+    """{patient: contour_rows} -> (json document, csv rows) as compute_contour_metrics.py:615-653 builds them: a csv row is the entry with
+    every list replaced by its plain mean over the frames plus Average = (ENDO + EPI + RV) / 3; `mean` and `std` are numpy's plain mean
+    and std of those per-slice means over all slices of all patients (NaN as soon as one slice has no points of the structure)."""
+    rows = []
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        for entries in per_patient.values():
+            for e in entries:
+                row = collections.OrderedDict((k, float(np.array(v, dtype=np.float64).mean()) if isinstance(v, list) else v) for k, v in e.items())
+                row["Average"] = (row["ENDO"] + row["EPI"] + row["RV"]) / 3
+                rows.append(row)
+        col = lambda k: np.array([r[k] for r in rows], dtype=np.float64)          # noqa: E731
+        doc = {"all": collections.OrderedDict((p, [dict(e) for e in entries]) for p, entries in per_patient.items()),
+               "mean": {k: float(col(k).mean()) if rows else float("nan") for k in CONTOUR_STRUCTURES},
+               "std": {k: float(col(k).std()) if rows else float("nan") for k in CONTOUR_STRUCTURES}}
+    return doc, rows
+
+
+def strain_rows(patient, curves, to_roll):
+    """curves [D, T, 2] (strain.track_patient: radial, circumferential, ED first) -> per-slice entries with the curves rolled back by
+    `to_roll` frames to the acquisition order (get_strain.py:588-589) and `smooth`, the mean of the two curvature variances (:596-599)."""
+    from .strain import smoothness_measure
+    entries = []
+    with warnings.catch_warnings(), np.errstate(invalid="ignore", divide="ignore"):
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        for d, c in enumerate(np.asarray(curves, dtype=np.float64)):
+            radial, circ = np.roll(c[:, 0], -to_roll), np.roll(c[:, 1], -to_roll)
+            x = np.arange(len(radial))
+            smooth = (smoothness_measure(x, radial) + smoothness_measure(x, circ)) / 2
+            entries.append(collections.OrderedDict([("Name", patient), ("slice_number", d), ("radial_strain", [float(v) for v in radial]),
+                                                    ("circ_strain", [float(v) for v in circ]), ("smooth", float(smooth))]))
+    return entries
+
+
+def strain_tables(per_patient):
+    """{patient: strain_rows} -> {'all': ..., 'mean'}: `mean` the mean over the patients of each patient's mean smoothness over its slices
+    (what get_strain.py:604 returns per patient and :681 prints)"""
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        per = [float(np.array([e["smooth"] for e in entries], dtype=np.float64).mean()) for entries in per_patient.values()]
+        mean = float(np.array(per, dtype=np.float64).mean()) if per else float("nan")
+    return {"all": collections.OrderedDict((p, [dict(e) for e in entries]) for p, entries in per_patient.items()), "mean": mean}
+
+
 def save_json(obj, file):
     with open(file, "w") as f:
         json.dump(obj, f, sort_keys=True, indent=4)
@@ -376,6 +498,20 @@ def _read_ssim_case(case):
     if case.other is not None:
         lab = _structure_labels(read_nifti(case.other)[0], case.other).transpose(1, 2, 0)
     return np.asarray(img).transpose(1, 2, 0).astype(np.float64), lab
+
+
+def _read_contour_case(case):
+    """a flow case -> flow fp32 [H, W, D, 2]; a slice's contour case -> (lv [T, P, 4], rv [T, P2, 2]) as the script transposes them"""
+    if case.path.endswith(".npz"):
+        with np.load(case.path) as z:
+            flow = np.asarray(z["flow"], dtype=np.float32)
+        if flow.ndim != 4 or flow.shape[3] != 2:
+            raise ValueError("case %s: flow of shape %s, expected [H, W, D, 2]" % (case.name, flow.shape))
+        return flow
+    lv, rv = np.load(case.path).transpose((2, 1, 0)), np.load(case.other).transpose((2, 1, 0))
+    if lv.ndim != 3 or lv.shape[2] != 4 or rv.ndim != 3 or rv.shape[2] != 2 or len(lv) != len(rv):
+        raise ValueError("contours %s: LV %s and RV %s, expected [4, P, T] and [2, P2, T]" % (case.name, lv.shape[::-1], rv.shape[::-1]))
+    return lv, rv
 
 
 def _prefetched(patients, read):
@@ -486,6 +622,53 @@ def score_ssim(flow, input_folder, labels=None, layout="predict", win=7):
     return doc
 
 
+def contour_arrays(flows, contours, ed_index):
+    """flows: the T - 1 arrays [H, W, D, 2] by frame number without the ED frame; contours: per slice (lv [T, P, 4], rv [T, P2, 2]),
+    1-based, in acquisition order -> (flow [D, T, 2, W, H], pts [D, T, Pmax, 2], counts [D, 3]) in ED-first order, the points 0-based:
+    what every mode of compute_contour_metrics.py prepares before its loops."""
+    from . import strain
+    flow, idx = strain.prepare_flow(flows, ed_index)
+    if len(contours) != len(flow):
+        raise ValueError("%d contour slices for a flow of %d slices" % (len(contours), len(flow)))
+    per_slice = [(lv[idx, :, :2] - 1, lv[idx, :, 2:] - 1, rv[idx] - 1) for lv, rv in contours]
+    pts, counts = strain.pack_contours(per_slice)
+    return flow, pts, counts
+
+
+def score_contour(flow, contours, input_folder, layout="predict", mode="from_ed"):
+    """The `contour` sub-command.  Returns the json document of contour_metrics.json; contour_metrics.{json,csv} are written into `flow`,
+    and strain_metrics.json in mode from_ed.  One upload, at most two library calls and one download per patient (strain.track_patient)."""
+    from . import metrics, strain
+    if mode not in CONTOUR_MODES:
+        raise ValueError("--mode must be one of %s, got %r" % (", ".join(CONTOUR_MODES), mode))
+    patients, info = [], {}
+    for patient, folder in patient_folders(flow, layout, "Flow").items():
+        ed, _ = ed_es_indices(input_folder, patient)
+        cases, zoom = pair_contour_cases(folder, contours, input_folder, patient, ed)
+        if cases:
+            patients.append((patient, cases))
+            info[patient] = (ed, zoom)
+    errors, curves = collections.OrderedDict(), collections.OrderedDict()
+    for patient, cases, loaded in _prefetched(patients, _read_contour_case):
+        nflow = sum(1 for c in cases if c.path.endswith(".npz"))
+        ed, zoom = info[patient]
+        f, pts, counts = contour_arrays(loaded[:nflow], loaded[nflow:], ed)
+        with_strain = mode == "from_ed"
+        metrics.contour_counts(counts, len(pts), pts.shape[2], strain=with_strain)          # refusals before any device work
+        res = strain.track_patient(f, pts, counts, mode, np.asarray(zoom, dtype=np.float32) if with_strain else None)
+        errors[patient] = contour_rows(patient, res["errors"])
+        if with_strain:
+            curves[patient] = strain_rows(patient, res["strain"], pts.shape[1] - ed)
+    if not errors:
+        raise ValueError("%s: no flow files found (layout %r)" % (flow, layout))
+    doc, rows = contour_tables(errors)
+    save_json(doc, join(flow, "contour_metrics.json"))
+    write_csv(join(flow, "contour_metrics.csv"), CONTOUR_COLUMNS, rows)
+    if curves:
+        save_json(strain_tables(curves), join(flow, "strain_metrics.json"))
+    return doc
+
+
 def build_parser():
     import argparse
     parser = argparse.ArgumentParser(description="Score the folders of a cine prediction on the device, one visit per patient.")
@@ -506,6 +689,13 @@ def build_parser():
     ssim.add_argument("-l", default=None, help="folder of the label volumes <case>.nii.gz, flat or per patient: per-structure scores on the ED labels")
     ssim.add_argument("--layout", choices=("predict", "saver"), default="predict")
     ssim.add_argument("--win", type=int, default=7, help="side of the uniform SSIM window (odd, 3..15)")
+    con = sub.add_parser("contour", help="tracking error of the ground-truth contour points under the flow: contour_metrics.{json,csv}; "
+                                         "in mode from_ed also the strain curves: strain_metrics.json")
+    con.add_argument("-flow", required=True, help="output folder of the prediction (one sub-folder per patient); the tables are written here")
+    con.add_argument("-c", required=True, help="folder with contour/LV/<patient>_sliceNN.npy [4, P, T] and contour/RV/<patient>_sliceNN.npy [2, P2, T]")
+    con.add_argument("-i", required=True, help="input folder with <patient>/<case>_0000.nii.gz and <patient>/<patient>.csv (ed_index, es_index)")
+    con.add_argument("--layout", choices=("predict", "saver"), default="predict")
+    con.add_argument("--mode", choices=CONTOUR_MODES, default="from_ed", help="the script's motion model (from_ed: its fallback without a training config)")
     return parser
 
 
@@ -515,6 +705,8 @@ def main(argv=None):
         return score_segmentation(a.pred, a.ref, a.i, a.gt, a.layout)
     if a.command == "jacobian":
         return score_jacobian(a.flow, a.l, a.i, a.layout)
+    if a.command == "contour":
+        return score_contour(a.flow, a.c, a.i, a.layout, a.mode)
     return score_ssim(a.flow, a.i, a.l, a.layout, a.win)
 
 

@@ -9,6 +9,10 @@ get_strain.py reads `Postprocessed/Flow/<patient>/*.npz['flow']` ([H, W, D, 2] p
 The one device operation is SpatialTransformerContour (network_architecture/integration.py:5-34): the flow field sampled bilinearly at
 the contour points (cf_sample_points_2d); everything after it is arithmetic on a few hundred points, kept in torch on the host exactly as
 the reference writes it.  File plumbing (.mat / nibabel / pickle readers, matplotlib) is not mirrored: the functions take arrays.
+
+track_patient is the patient-level form: every slice, frame and point of a patient in one cf_contour_track_table call (and one
+cf_contour_strain_table call for the strain curves), the chains walked on the device (csrc/contour.hip); `python -m cineflow.score
+contour` writes the scripts' documents from it.  The per-launch functions above it stay as the small-scale form of the same arithmetic.
 """
 import numpy as np
 import torch
@@ -99,6 +103,8 @@ def contour_tracking_error(slice_flow, contours, split_index, mode="from_ed_accu
 
     slice_flow [T,2,A,B] (ED first, frame 0 NaN), contours [T,P,2] (0-based ground-truth points in the same frame order),
     split_index: np.cumsum([P_endo, P_epi]).  mode:
+      'from_ed'              (compute_contour_metrics.py:478-527): points of frame 0 displaced once by the flow of frame t, the
+                             position held against the ground truth of frame t;
       'from_ed_accumulation' (:100-129): points of frame 0 pushed through the flows of frames 1..t one after the other;
       'to_ed_accumulation'   (:190-221): frames reversed, points of frame t pushed through flows t .. T-2;
       'to_ed'                (:283-306): frames reversed, one flow per frame.
@@ -107,7 +113,13 @@ def contour_tracking_error(slice_flow, contours, split_index, mode="from_ed_accu
     con = torch.as_tensor(np.ascontiguousarray(contours)).float()
     st = SpatialTransformerContour(size=flow.shape[-2:])
     errs = []
-    if mode == "from_ed_accumulation":
+    if mode == "from_ed":
+        first = con[0].transpose(1, 0)[None, :, None, :]
+        for t in range(1, len(flow)):
+            new = (first + st(torch.clone(first), flow[t][None])).squeeze(2)[0].permute(1, 0).numpy()
+            errs.append(np.linalg.norm(con[t].numpy() - new, axis=1))
+        e = np.stack(errs, axis=0)
+    elif mode == "from_ed_accumulation":
         for t in range(1, len(flow)):
             cur = con[0].transpose(1, 0)[None, :, None, :]
             init = cur
@@ -129,3 +141,45 @@ def contour_tracking_error(slice_flow, contours, split_index, mode="from_ed_accu
         e = np.flip(np.stack(errs, axis=0), axis=0)
     parts = np.split(e, indices_or_sections=split_index, axis=1)
     return np.stack([x.mean(-1) for x in parts], axis=-1)
+
+
+def pack_contours(contours):
+    """contours: per slice (endo [T,P,2], epi [T,P2,2], rv [T,P3,2]) 0-based, ED-first -> (pts fp32 [D,T,Pmax,2], counts int32 [D,3]):
+    the structures one after the other (the reference's np.concatenate, split_index = cumsum(counts[:2])), zero-padded to the longest."""
+    rows = [np.concatenate([np.asarray(c, dtype=np.float32).reshape(len(s[0]), -1, 2) for c in s], axis=1) for s in contours]
+    counts = np.array([[np.shape(c)[1] for c in s] for s in contours], dtype=np.int32).reshape(len(rows), 3)
+    pts = np.zeros((len(rows), len(rows[0]), max(max(r.shape[1] for r in rows), 1), 2), np.float32)
+    for d, r in enumerate(rows):
+        pts[d, :, :r.shape[1]] = r
+    return pts, counts
+
+
+def track_patient(flow, contours, counts, mode="from_ed", zoom=None):
+    """compute_contour_metrics.py (and, with zoom, get_strain.py:531-599) for one patient in one device visit.
+
+    flow [D,T,2,A,B]: prepare_flow's array (ED first, frame 0 NaN); contours [D,T,Pmax,2]: the 0-based ground-truth points in the same
+    frame order, endo, epi, RV one after the other, padded (pack_contours); counts [D,3]; mode one of metrics.CONTOUR_MODES.
+    Returns {'errors': float64 [D,T-1,3] (ENDO, EPI, RV per frame, contour_tracking_error's order)} and, when zoom = (mm, mm) is given
+    (mode 'from_ed' only, equal endo / epi counts), 'strain': float64 [D,T,2], radial and circumferential strain per frame, ED first.
+    One upload, one library call (two with strain), one download, whatever T."""
+    from . import metrics
+    if mode not in metrics.CONTOUR_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (", ".join(metrics.CONTOUR_MODES), mode))
+    if zoom is not None and mode != "from_ed":
+        raise ValueError("strain curves come from the from_ed positions: mode %r takes no zoom" % (mode,))
+    D, T, Pmax = (int(v) for v in np.shape(contours)[:3])
+    c = metrics.contour_counts(counts, D, Pmax, strain=zoom is not None)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    f = torch.as_tensor(flow).to(dev, dtype=torch.float32)
+    p = torch.as_tensor(contours).to(dev, dtype=torch.float32).contiguous()
+    cd = torch.from_numpy(c).to(dev)
+    ne, ns = D * (T - 1) * 3, D * T * 2 if zoom is not None else 0
+    out = torch.empty(ne + ns, dtype=torch.float64, device=dev)                    # both tables, read back together
+    pos, _ = metrics.contour_track_table(f, p, c, mode, out=out[:ne], counts_dev=cd)
+    if zoom is not None:
+        metrics.contour_strain_table(pos, p[:, 0], c, zoom, out=out[ne:], counts_dev=cd)
+    host = out.cpu().numpy()
+    res = {"errors": host[:ne].reshape(D, T - 1, 3)}
+    if zoom is not None:
+        res["strain"] = host[ne:].reshape(D, T, 2)
+    return res

@@ -580,6 +580,32 @@ int cf_flow_regularity_table(const float* flow, const uint8_t* labels, int T, in
  * a slice where both images are constant zero has R = 0, S = 0 / 0 and NaN sums, as numpy's. */
 int cf_cine_ssim_table(const double* fixed, const float* registered, const uint8_t* labels, int T, int D, int H, int W, int K, int win,
                        double K1, double K2, double cov_norm, float* range, double* part, double* table, void* stream);
+/* nnunet/compute_contour_metrics.py for a whole patient (csrc/contour.hip).  flow fp32 [D][T][2][A][B]: the flows of every slice in
+ * ED-first frame order (cineflow.strain.prepare_flow; frame 0 is the ED placeholder and is never read), component 0 along B.  pts fp32
+ * [D][T][Pmax][2]: the 0-based ground-truth points (x along B, y along A) in the same frame order, each slice's endo, epi and RV points
+ * one after the other, padded to Pmax.  counts int [D][3] = the numbers of endo, epi and RV points per slice, TWICE: `counts` in HOST
+ * memory, which the argument checks read (non-negative, sum <= Pmax), and `counts_dev` the same numbers in device memory for the kernels
+ * (they clamp what they read to Pmax).  mode:
+ *   0 from_ed               pos[d][t-1][p] = pts[d][0][p] + flow[d][t](pts[d][0][p]);  error against pts[d][t][p]
+ *   1 from_ed_accumulation  one chain per point from pts[d][0][p] through flows 1 .. t, pos[d][t-1] the position after flow t;  error
+ *                           against pts[d][t][p]
+ *   2 to_ed_accumulation    one chain per (frame t, point) from pts[d][t][p] through flows t, t-1 .. 1, pos[d][t-1][p] = end - start;
+ *                           error against pts[d][0][p] - pts[d][t][p]
+ *   3 to_ed                 pos[d][t-1][p] = flow[d][t](pts[d][t][p]);  error against pts[d][0][p] - pts[d][t][p]
+ * A sample is cf_sample_points_2d's on both components (zeros outside the map), a chain step one rounded fp32 add: pos fp32
+ * [D][T-1][Pmax][2] holds the bits of chained cf_sample_points_2d calls (padding points: 0).  table fp64 [D][T-1][3]: the mean over the
+ * endo, epi and RV points of the Euclidean norm of (ground truth - pos), fp64 from the fp32 values; NaN for a structure without points.
+ * T >= 2, A, B >= 2, D <= 65535.  Two launches, no allocation, no atomics: the same bits on every run. */
+int cf_contour_track_table(const float* flow, const float* pts, const int* counts, const int* counts_dev, int D, int T, int A, int B, int Pmax,
+                           int mode, float* pos, double* table, void* stream);
+/* nnunet/get_strain.py:531-599 for all slices.  pos: the mode-0 positions of cf_contour_track_table, [D][T-1][Pmax][2]; ed_pts: the ED
+ * points, slice d at ed_pts + d * ed_stride floats (the pts array itself with ed_stride = 2 T Pmax); counts / counts_dev as above, with
+ * counts[d][0] == counts[d][1] (endo point p pairs with epi point p) or the call is refused.  table fp64 [D][T][2], row 0 the ED frame:
+ * {radial, circumferential} Green-Lagrange strain 0.5 (L^2 - L0^2) / L0^2 in fp64 on (double)pixel * zoom (zoom_x for component 0),
+ * averaged over the points -- L the endo-epi distance of a point, and the distance from a point to the next one along its closed
+ * contour averaged over the two contours.  Rows are in the ED-first frame order; L0 = 0 gives NaN as in the script. */
+int cf_contour_strain_table(const float* pos, const float* ed_pts, long ed_stride, const int* counts, const int* counts_dev, int D, int T, int Pmax,
+                            double zoom_x, double zoom_y, double* table, void* stream);
 
 /* SwinCrossAttention (nnunet/lib/swin_cross_attention.py:13-112) after the projections: qk [B][2C][H][W] = the q and k maps of the
  * "rescaler" input, v [B][C][H][W] the value map of the "rescaled" input, bias_table [(2w-1)^2][heads] the learned relative position
