@@ -135,6 +135,8 @@ SIGNATURES = {
     "cf_cine_ssim_table": [P, P, P, I, I, I, I, I, I, DBL, DBL, DBL, P, P, P, P],
     "cf_contour_track_table": [P, P, P, P, I, I, I, I, I, I, P, P, P],
     "cf_contour_strain_table": [P, P, L, P, P, I, I, I, DBL, DBL, P, P],
+    "cf_edt": [P, I, I, I, I, DBL, DBL, DBL, P, P, P],
+    "cf_label_surface_edt": [P, P, I, I, I, I, P, I, DBL, DBL, DBL, I, P, P, L, P, P],
     "cf_window_attention": [P, P, P, P, I, I, I, I, I, I, I, P],
     "cf_frame_boxes": [P, I, P, I, I, I, P],
     "cf_sample_points_2d": [P, P, P, I, I, I, I, I, P],
@@ -168,6 +170,8 @@ def lib():
         fn.restype = ctypes.c_int
     h.cf_last_error.restype = ctypes.c_char_p
     h.cf_last_error.argtypes = []
+    h.cf_edt_workspace_bytes.restype = ctypes.c_long       # a size, not a status: declared `long` in the header
+    h.cf_edt_workspace_bytes.argtypes = [I, I, I]
     h.cf_version.restype = ctypes.c_int
     h.cf_version.argtypes = []
     _lib = h

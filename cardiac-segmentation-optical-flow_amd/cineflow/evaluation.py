@@ -4,9 +4,11 @@ aggregate_scores, aggregate_scores_for_experiment, evaluate_folder; same names, 
 The numbers come from cineflow.metrics.  All confusion-type metrics of a case come from ONE cf_label_confusion launch whose 16 x 16 histogram
 is sliced per label; tuple labels (joint regions), `rv_rejection`'s label 1 and volumes holding a label value the histogram cannot place
 take one ConfusionMatrix per label instead.  Files go through cineflow.nifti; a thread pool reads and inflates the next cases while the
-device works on the current one, and only this process opens the GPU.
+device works on the current one, and only this process opens the GPU.  The surface metrics search the two borders all-pairs
+(--surface pairs), or read HD, HD95 and ASSD of all histogram labels of a case from one exact distance-transform visit (--surface edt:
+cineflow.metrics.label_surface_edt_table, linear in the volume -- the route for 3-D organs); auto picks by the size of the borders.
 
-    python -m cineflow.evaluation -ref GT_FOLDER -pred PRED_FOLDER -l 1 2 3
+    python -m cineflow.evaluation -ref GT_FOLDER -pred PRED_FOLDER -l 1 2 3 [--surface auto|pairs|edt] [--surface_dice MM]
 """
 import collections
 import hashlib
@@ -28,6 +30,10 @@ from .nifti import read_nifti
 from .ops import _stream, _u8
 
 HIST_K = 16
+SURFACE_DICE = "Normalized Surface Dice"
+# the surface metrics a label_surface_edt_table entry answers, and the entry's key for each
+TABLE_COLUMNS = {"Hausdorff Distance": "hd", "Hausdorff Distance 95": "hd95", "Avg. Symmetric Surface Distance": "assd",
+                 "Avg. Surface Distance": "asd_test_to_ref"}
 
 # a volume that is already in memory: (file name it stands for, array [Z,Y,X], read_nifti's properties)
 Loaded = collections.namedtuple("Loaded", "path array props")
@@ -175,8 +181,29 @@ class Evaluator:
         self.confusion_matrix.set_reference(reference)
         return self.confusion_matrix
 
-    def evaluate(self, test=None, reference=None, advanced=False, **metric_kwargs):
-        """-> OrderedDict {label name: {metric: value}}; with advanced=True the surface metrics are added"""
+    def _surface_table(self, histogram, labels, surface, voxel_spacing):
+        """One label_surface_edt_table visit for the case's histogram labels -> {label: its entry}, or None when the route is `auto` and no
+        label's two borders hold more than metrics.EDT_AUTO_PAIRS pairs (the per-label search then scores the case exactly as before).
+        `auto` first asks the histogram: a label's border voxels are at most its voxels, so a case whose voxel products all stay under
+        the constant never pays for the visit."""
+        hist, test_t, ref_t, _ = histogram
+        labels = sorted(set(labels))
+        voxels = [(int(hist[c, :].sum()), int(hist[:, c].sum())) for c in labels]
+        if surface != "edt" and all(a * b <= metrics.EDT_AUTO_PAIRS for a, b in voxels):
+            return None
+        table = metrics.label_surface_edt_table(test_t, ref_t, labels, voxel_spacing, capacity=sum(a + b for a, b in voxels))
+        if surface != "edt" and all(e["n_test"] * e["n_ref"] <= metrics.EDT_AUTO_PAIRS for e in table.values()):
+            return None
+        return table
+
+    def evaluate(self, test=None, reference=None, advanced=False, surface=None, surface_dice_threshold=None, **metric_kwargs):
+        """-> OrderedDict {label name: {metric: value}}; with advanced=True the surface metrics are added.  surface: how their distances
+        are found -- "pairs" (the all-pairs search), "edt" (the exact distance transform: the histogram labels of the case in one
+        label_surface_edt_table visit, the other labels one by one), None / "auto" ("pairs" unless some label's borders hold more than
+        metrics.EDT_AUTO_PAIRS pairs).  surface_dice_threshold (mm): adds "Normalized Surface Dice" to every label."""
+        if surface not in (None, "auto", "pairs", "edt"):
+            raise ValueError("surface must be one of auto, pairs, edt, got %r" % (surface,))
+        surface = None if surface == "auto" else surface
         if test is not None:
             self.set_test(test)
         if reference is not None:
@@ -201,13 +228,39 @@ class Evaluator:
             routes.append((label, name, joint, cut_rv, not joint and not cut_rv and 0 <= int(label) < HIST_K))
         histogram = self._histogram() if any(r[4] for r in routes) else None
 
+        if surface is not None:
+            metric_kwargs["method"] = surface
+        if surface_dice_threshold is not None:
+            wanted.append(SURFACE_DICE)
+            funcs[SURFACE_DICE] = metrics.normalized_surface_dice_metric
+            metric_kwargs["threshold"] = float(surface_dice_threshold)
+        from_table = [m for m in wanted if funcs[m] is ALL_METRICS.get(m) and m in TABLE_COLUMNS or m == SURFACE_DICE]
+        table = None
+        if histogram is not None and from_table and surface != "pairs":
+            table = self._surface_table(histogram, [int(r[0]) for r in routes if r[4]], surface, metric_kwargs.get("voxel_spacing"))
+
         self.result = OrderedDict()
         for label, name, joint, cut_rv, sliced in routes:
-            cm = _SlicedMatrix(histogram[0], int(label), histogram[3], histogram[1], histogram[2]) if sliced and histogram is not None \
+            sliced = sliced and histogram is not None
+            cm = _SlicedMatrix(histogram[0], int(label), histogram[3], histogram[1], histogram[2]) if sliced \
                 else self._per_label_matrix(label, joint, cut_rv)
-            self.result[str(name)] = OrderedDict((m, funcs[m](confusion_matrix=cm, nan_for_nonexisting=self.nan_for_nonexisting, **metric_kwargs))
-                                                 for m in wanted)
+            entry = table[int(label)] if sliced and table is not None else None
+            scores = OrderedDict()
+            for m in wanted:
+                if entry is not None and m in from_table:
+                    scores[m] = self._from_table(m, entry, cm, metric_kwargs.get("threshold"))
+                else:
+                    scores[m] = funcs[m](confusion_matrix=cm, nan_for_nonexisting=self.nan_for_nonexisting, **metric_kwargs)
+            self.result[str(name)] = scores
         return self.result
+
+    def _from_table(self, metric, entry, cm, threshold):
+        """a surface metric of one label from its label_surface_edt_table entry, under _surface_metric's existence rule"""
+        if any(cm.get_existence()):
+            return float("NaN") if self.nan_for_nonexisting else 0
+        if metric == SURFACE_DICE:
+            return metrics.surface_dice_from_distances(entry["d_test_to_ref"], entry["d_ref_to_test"], threshold)
+        return entry[TABLE_COLUMNS[metric]]
 
     def to_dict(self):
         if self.result is None:
@@ -341,7 +394,8 @@ def aggregate_scores_for_experiment(score_file, labels=None, metrics=Evaluator.d
 
 def evaluate_folder(folder_with_gts, folder_with_predictions, labels, **metric_kwargs):
     """Scores every .nii.gz of folder_with_predictions against the file of the same name in folder_with_gts (both folders must hold the same
-    names) and writes folder_with_predictions/summary.json; surface metrics included, rv_rejection on, as in the fork (evaluator.py:486-487)."""
+    names) and writes folder_with_predictions/summary.json; surface metrics included, rv_rejection on, as in the fork (evaluator.py:486-487).
+    surface= and surface_dice_threshold= reach Evaluator.evaluate."""
     files_gt = subfiles(folder_with_gts, suffix=".nii.gz", join_=False)
     files_pred = subfiles(folder_with_predictions, suffix=".nii.gz", join_=False)
     assert set(files_gt) <= set(files_pred), "files missing in folder_with_predictions"
@@ -358,12 +412,18 @@ def build_parser():
     parser.add_argument("-ref", required=True, type=str, help="folder of the reference label files (.nii.gz)")
     parser.add_argument("-pred", required=True, type=str, help="folder of the predicted label files, named like the reference ones")
     parser.add_argument("-l", nargs="+", type=int, required=True, help="label values to score, e.g. -l 1 2 3 (0 is the background)")
+    parser.add_argument("--surface", choices=("auto", "pairs", "edt"), default="auto",
+                        help="how the surface metrics find their distances: pairs = all-pairs search (small objects), edt = exact distance "
+                             "transform, one device visit per case (3-D organs), auto = pairs unless an object is large (default)")
+    parser.add_argument("--surface_dice", type=float, default=None, metavar="MM",
+                        help="also report the Normalized Surface Dice at this tolerance in mm")
     return parser
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    return evaluate_folder(args.ref, args.pred, args.l)
+    extra = {} if args.surface_dice is None else {"surface_dice_threshold": args.surface_dice}
+    return evaluate_folder(args.ref, args.pred, args.l, surface=args.surface, **extra)
 
 
 nnunet_evaluate_folder = main

@@ -6,13 +6,17 @@ per-frame statistics of nnunet/compute_jacobian.py.  numpy arrays or device tens
 Counting, border extraction, nearest-border distances and reductions are HIP kernels (csrc/metrics.hip); the 95th percentile of
 hausdorff_distance_95 is taken by numpy on the downloaded distance vector (a few thousand values).
 cine_label_scores / cine_jacobian_table (csrc/score.hip) give the same figures for all frames, classes and slices of a patient in one
-device visit; cineflow.score writes the scripts' tables from them.
+device visit; cineflow.score writes the scripts' tables from them.  distance_transform_edt, surface_distances(method="edt"),
+label_surface_edt_table and normalized_surface_dice (csrc/edt.hip) are the route for 3-D label volumes: scipy's exact Euclidean distance
+transform on the device and medpy's surface distances read from it, all labels of a case in one visit, linear in the volume.
 """
+import ctypes
+
 import numpy as np
 import torch
 
 from . import ops
-from ._lib import check, lib
+from ._lib import CineflowError, check, lib
 from .ops import _f32, _stream, _u8
 
 
@@ -223,25 +227,136 @@ def _border(mask):
     return coords, int(count.item())
 
 
-def surface_distances(result, reference, voxelspacing=None, connectivity=1):
+# `auto` (method=None) leaves the all-pairs search for the transform when na x nb -- the border voxels of the two masks -- exceeds this.
+# profiles/edt_table.md: on two offset balls the transform won every repeat from na x nb = 6.6e6 on (2^23), but the suite's own masks reach
+# 4999 x 4999 on the default route (tests/test_gpu_metrics_kernels.py), and no input an existing test uses may change route: 2^25.
+EDT_AUTO_PAIRS = 1 << 25
+SURFACE_METHODS = (None, "pairs", "edt")
+
+
+def _no_cpu_tensor(a, name):
+    if torch.is_tensor(a) and not a.is_cuda:
+        raise TypeError("%s must be a CUDA/HIP tensor or a numpy array (cineflow has no CPU path)" % name)
+
+
+def _spacing3(spacing, nd):
+    sp = np.ones(nd) if spacing is None else np.asarray(spacing, dtype=np.float64) * np.ones(nd)
+    return [1.0] * (3 - nd) + [float(v) for v in sp]
+
+
+def _edt_workspace(D, H, W, device):
+    size = lib().cf_edt_workspace_bytes(D, H, W)
+    if size < 0:
+        check(int(size), "cf_edt_workspace_bytes")
+    return torch.empty(int(size), dtype=torch.uint8, device=device)
+
+
+def distance_transform_edt(input, sampling=None, return_distances=True, return_indices=False, distances=None, indices=None):
+    """scipy.ndimage.distance_transform_edt for 2-D and 3-D inputs: the distance of every element to the nearest element that is 0, with
+    `sampling` the spacing along each axis (a number or one per axis) -> fp64 device tensor of input's shape, scipy's bits whenever the
+    squared terms are exact in fp64 (cf_edt).  Only the distances are built: return_distances=False, return_indices, distances= and
+    indices= raise NotImplementedError.  An input without any zero raises (scipy's result there is meaningless)."""
+    for name, given in (("return_distances", return_distances is not True), ("return_indices", bool(return_indices)),
+                        ("distances", distances is not None), ("indices", indices is not None)):
+        if given:
+            raise NotImplementedError("distance_transform_edt: %s is not built (only the distance map is returned)" % name)
+    _no_cpu_tensor(input, "input")
+    m = _mask(input)
+    nd = m.dim()
+    if nd not in (2, 3):
+        raise NotImplementedError("distance_transform_edt is built for 2-D and 3-D inputs, got %d-D" % nd)
+    D, H, W = (1,) * (3 - nd) + tuple(m.shape)
+    sz, sy, sx = _spacing3(sampling, nd)
+    ws = _edt_workspace(D, H, W, m.device)
+    out = torch.empty(tuple(m.shape), dtype=torch.float64, device=m.device)
+    check(lib().cf_edt(_u8(m), D, H, W, nd, sz, sy, sx, ws.data_ptr(), out.data_ptr(), _stream()), "cf_edt")
+    if int(ws[24:28].view(torch.int32).item()):                  # the library never synchronises: "no zero anywhere" comes back as a status word
+        raise CineflowError("cf_edt failed (-1): the input holds no zero element, so no distance is defined")
+    return out
+
+
+def _label_surface_edt(t, r, labels, voxel_spacing, capacity=None, score_full=False):
+    """one cf_label_surface_edt call on uint8 device volumes -> (head row table [K, 8] and offsets [2 K + 1] on the host, dist on the device)"""
+    assert_shape(t, r)
+    nd = t.dim()
+    assert nd in (2, 3), "surface distances are built for 2-D and 3-D volumes"
+    D, H, W = (1,) * (3 - nd) + tuple(t.shape)
+    sz, sy, sx = _spacing3(voxel_spacing, nd)
+    labs = [int(l) for l in labels]
+    K = len(labs)
+    n = t.numel()
+    cap = max(1, 2 * n if capacity is None else min(2 * n, int(capacity)))
+    ws = _edt_workspace(D, H, W, t.device)
+    dist = torch.empty(cap, dtype=torch.float64, device=t.device)
+    head = torch.empty(10 * K + 2, dtype=torch.float64, device=t.device)
+    check(lib().cf_label_surface_edt(_u8(t), _u8(r), D, H, W, nd, (ctypes.c_int * K)(*labs), K, sz, sy, sx, int(bool(score_full)), ws.data_ptr(),
+                                     dist.data_ptr(), cap, head.data_ptr(), _stream()), "cf_label_surface_edt")
+    hd = head.cpu().numpy()
+    if hd[-1]:
+        raise CineflowError("cf_label_surface_edt: the distances did not fit the buffer of %d values" % cap)
+    return hd[2 * K + 1:-1].reshape(K, 8), hd[:2 * K + 1].astype(np.int64), dist
+
+
+def _surface_distances_edt(a, b, voxelspacing):
+    rows, offs, dist = _label_surface_edt(a, b, [1], voxelspacing, score_full=True)
+    if rows[0, 6] == 0:
+        raise RuntimeError("The first supplied array does not contain any binary object.")
+    if rows[0, 7] == 0:
+        raise RuntimeError("The second supplied array does not contain any binary object.")
+    return dist[offs[0]:offs[1]].clone()
+
+
+def surface_distances(result, reference, voxelspacing=None, connectivity=1, method=None):
     """medpy.metric.binary.__surface_distances: distance of every border voxel of `result` to the nearest border voxel of
-    `reference` -> fp64 device tensor (in no particular order)."""
+    `reference` -> fp64 device tensor.  method "pairs": the all-pairs search (values in no particular order); "edt": read from the exact
+    distance transform of reference's border (cf_label_surface_edt; values in raster order of result's border voxels, the same on every
+    run); None: "pairs" unless the two borders hold more than EDT_AUTO_PAIRS pairs."""
+    if method not in SURFACE_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (SURFACE_METHODS, method))
     if connectivity != 1:
         raise NotImplementedError("surface distances are built for connectivity 1 (the reference's only value)")
+    if method == "edt":
+        _no_cpu_tensor(result, "result")
+        _no_cpu_tensor(reference, "reference")
     a, b = _mask(result), _mask(reference)
     assert_shape(a, b)
+    if method == "edt":
+        return _surface_distances_edt(a, b, voxelspacing)
     nd = a.dim()
-    sp = np.ones(nd) if voxelspacing is None else np.asarray(voxelspacing, dtype=np.float64) * np.ones(nd)
-    sz, sy, sx = ([1.0] * (3 - nd) + [float(v) for v in sp])
+    sz, sy, sx = _spacing3(voxelspacing, nd)
     ca, na = _border(a)
     cb, nb = _border(b)
     if na == 0:
         raise RuntimeError("The first supplied array does not contain any binary object.")
     if nb == 0:
         raise RuntimeError("The second supplied array does not contain any binary object.")
+    if method is None and na * nb > EDT_AUTO_PAIRS:
+        return _surface_distances_edt(a, b, voxelspacing)
     dist = torch.empty(na, dtype=torch.float64, device=a.device)
     check(lib().cf_surface_min_dist(ca.data_ptr(), na, cb.data_ptr(), nb, sz, sy, sx, dist.data_ptr(), _stream()), "cf_surface_min_dist")
     return dist
+
+
+def surface_dice_from_distances(a_to_b, b_to_a, threshold):
+    """the arithmetic of nnunet/evaluation/surface_dice.py:46-56 on the two directed distance vectors (host arrays): the share of each
+    surface within `threshold` (<=) against the share beyond it (>), with the 1e-8 that keeps the quotient defined"""
+    a_to_b, b_to_a = np.asarray(a_to_b), np.asarray(b_to_a)
+    numel_a, numel_b = len(a_to_b), len(b_to_a)
+    tp_a = np.sum(a_to_b <= threshold) / numel_a
+    tp_b = np.sum(b_to_a <= threshold) / numel_b
+    fp = np.sum(a_to_b > threshold) / numel_a
+    fn = np.sum(b_to_a > threshold) / numel_b
+    return float((tp_a + tp_b) / (tp_a + tp_b + fp + fn + 1e-8))
+
+
+def normalized_surface_dice(a, b, threshold, spacing=None, connectivity=1, method=None):
+    """nnunet/evaluation/surface_dice.py:20-56 (not the official surface Dice, as the reference says itself): symmetric, threshold in mm"""
+    _no_cpu_tensor(a, "a")
+    _no_cpu_tensor(b, "b")
+    assert tuple(np.shape(a)) == tuple(np.shape(b)), "a and b must have the same shape. a.shape= %s, b.shape= %s" % (np.shape(a), np.shape(b))
+    a_to_b = surface_distances(a, b, spacing, connectivity, method)
+    b_to_a = surface_distances(b, a, spacing, connectivity, method)
+    return surface_dice_from_distances(a_to_b.cpu().numpy(), b_to_a.cpu().numpy(), threshold)
 
 
 def _max_sum(dist):
@@ -259,16 +374,19 @@ def _mean_distance(dist, reproducible):
     return _max_sum(dist)[1] / dist.numel()
 
 
-def _surface_metric(kind, test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity, reproducible=False):
+def _surface_metric(kind, test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity, reproducible=False, method=None,
+                    threshold=None):
     cm = _cm(test, reference, confusion_matrix)
     test_empty, test_full, reference_empty, reference_full = cm.get_existence()
     if test_empty or test_full or reference_empty or reference_full:
         return float("NaN") if nan_for_nonexisting else 0
     test, reference = cm.test, cm.reference
-    d1 = surface_distances(test, reference, voxel_spacing, connectivity)
+    d1 = surface_distances(test, reference, voxel_spacing, connectivity, method)
     if kind == "asd":
         return _mean_distance(d1, reproducible)
-    d2 = surface_distances(reference, test, voxel_spacing, connectivity)
+    d2 = surface_distances(reference, test, voxel_spacing, connectivity, method)
+    if kind == "nsd":
+        return surface_dice_from_distances(d1.cpu().numpy(), d2.cpu().numpy(), threshold)
     if kind == "hd":
         return max(_max_sum(d1)[0], _max_sum(d2)[0])
     if kind == "assd":
@@ -276,26 +394,34 @@ def _surface_metric(kind, test, reference, confusion_matrix, nan_for_nonexisting
     return float(np.percentile(np.hstack((d1.cpu().numpy(), d2.cpu().numpy())), 95))
 
 
-def hausdorff_distance(test=None, reference=None, confusion_matrix=None, nan_for_nonexisting=True, voxel_spacing=None, connectivity=1, **kwargs):
+def hausdorff_distance(test=None, reference=None, confusion_matrix=None, nan_for_nonexisting=True, voxel_spacing=None, connectivity=1, method=None,
+                       **kwargs):
     """metrics.py:323-338 (medpy.metric.hd)."""
-    return _surface_metric("hd", test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity)
+    return _surface_metric("hd", test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity, method=method)
 
 
-def hausdorff_distance_95(test=None, reference=None, confusion_matrix=None, nan_for_nonexisting=True, voxel_spacing=None, connectivity=1, **kwargs):
+def hausdorff_distance_95(test=None, reference=None, confusion_matrix=None, nan_for_nonexisting=True, voxel_spacing=None, connectivity=1, method=None,
+                          **kwargs):
     """metrics.py:341-356 (medpy.metric.hd95)."""
-    return _surface_metric("hd95", test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity)
+    return _surface_metric("hd95", test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity, method=method)
 
 
 def avg_surface_distance(test=None, reference=None, confusion_matrix=None, nan_for_nonexisting=True, voxel_spacing=None, connectivity=1,
-                         reproducible=False, **kwargs):
+                         reproducible=False, method=None, **kwargs):
     """metrics.py:359-374 (medpy.metric.asd)."""
-    return _surface_metric("asd", test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity, reproducible)
+    return _surface_metric("asd", test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity, reproducible, method)
 
 
 def avg_surface_distance_symmetric(test=None, reference=None, confusion_matrix=None, nan_for_nonexisting=True, voxel_spacing=None, connectivity=1,
-                                   reproducible=False, **kwargs):
+                                   reproducible=False, method=None, **kwargs):
     """metrics.py:377-392 (medpy.metric.assd)."""
-    return _surface_metric("assd", test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity, reproducible)
+    return _surface_metric("assd", test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity, reproducible, method)
+
+
+def normalized_surface_dice_metric(test=None, reference=None, confusion_matrix=None, nan_for_nonexisting=True, voxel_spacing=None, connectivity=1,
+                                   threshold=1.0, method=None, **kwargs):
+    """normalized_surface_dice under the existence rules of the other surface metrics (NaN where a mask is empty or fills the volume)"""
+    return _surface_metric("nsd", test, reference, confusion_matrix, nan_for_nonexisting, voxel_spacing, connectivity, method=method, threshold=threshold)
 
 
 ALL_METRICS = {
@@ -462,6 +588,41 @@ def cine_label_scores(test, reference, num_classes, voxel_spacing=None, reproduc
             out["asd_test_to_ref"][n, c], out["asd_ref_to_test"][n, c] = m1, m2
             out["assd"][n, c] = float(np.mean((m1, m2)))
             out["hd95"][n, c] = float(np.percentile(np.hstack((d1, d2)), 95))
+    return out
+
+
+def label_surface_edt_table(test, reference, labels, voxel_spacing=None, capacity=None):
+    """The surface metrics of every listed label of two 2-D or 3-D label volumes from ONE cf_label_surface_edt call: for label c the masks are
+    `test == c` and `reference == c`, the distances come from the exact distance transform of the other mask's border inside the joint
+    bounding box of the two borders, and nothing is searched over pairs.  Two reads: the offsets and the per-label table, then exactly
+    the distances.  `labels`: up to 16 values 0..255.  capacity: an upper bound of the number of distances when the caller knows a
+    better one than 2 x voxels (the voxels of the listed labels in both volumes, say).
+
+    Returns {label: dict} with d_test_to_ref / d_ref_to_test (fp64 numpy, raster order of the border voxels they belong to), n_test /
+    n_ref (border voxels), hd, hd95 (np.percentile of both vectors, 95), asd_test_to_ref, asd_ref_to_test (device sum / count: the
+    order is fixed, so the value is the same on every run) and assd.  A label that has no voxel, or fills the volume, in either input
+    gets empty vectors and NaN, the rule of hausdorff_distance and the others."""
+    _no_cpu_tensor(test, "test")
+    _no_cpu_tensor(reference, "reference")
+    labs = [int(l) for l in labels]
+    if not 1 <= len(labs) <= 16 or any(l < 0 or l > 255 for l in labs):
+        raise ValueError("labels must be 1..16 values in 0..255, got %r" % (labs,))
+    t, r = _labels_u8(test), _labels_u8(reference)
+    rows, offs, dist = _label_surface_edt(t, r, labs, voxel_spacing, capacity)
+    d = dist[:int(offs[-1])].cpu().numpy() if offs[-1] else np.zeros(0)
+    out = {}
+    nan = float("nan")
+    for k, c in enumerate(labs):
+        d1, d2 = d[offs[2 * k]:offs[2 * k + 1]], d[offs[2 * k + 1]:offs[2 * k + 2]]
+        n1, n2 = int(rows[k, 0]), int(rows[k, 1])
+        res = {"d_test_to_ref": d1, "d_ref_to_test": d2, "n_test": int(rows[k, 6]), "n_ref": int(rows[k, 7])}
+        if n1 and n2:
+            m1, m2 = float(rows[k, 4] / n1), float(rows[k, 5] / n2)
+            res.update(hd=max(float(rows[k, 2]), float(rows[k, 3])), hd95=float(np.percentile(np.hstack((d1, d2)), 95)),
+                       asd_test_to_ref=m1, asd_ref_to_test=m2, assd=float(np.mean((m1, m2))))
+        else:
+            res.update(hd=nan, hd95=nan, asd_test_to_ref=nan, asd_ref_to_test=nan, assd=nan)
+        out[c] = res
     return out
 
 

@@ -607,6 +607,33 @@ int cf_contour_track_table(const float* flow, const float* pts, const int* count
 int cf_contour_strain_table(const float* pos, const float* ed_pts, long ed_stride, const int* counts, const int* counts_dev, int D, int T, int Pmax,
                             double zoom_x, double zoom_y, double* table, void* stream);
 
+/* ---------------------------------------------------------------- exact distance transform and the evaluator's visit (csrc/edt.hip)
+ * scipy.ndimage.distance_transform_edt(mask, sampling = (sz, sy, sx)): out fp64 [D][H][W], every voxel's distance to the nearest voxel
+ * whose mask value is 0, defined as the minimum over those voxels of sqrt(fl(fl(fl((sz dz)^2) + fl((sy dy)^2)) + fl((sx dx)^2))) --
+ * cf_surface_min_dist's expression and order.  ndim 3, or 2 with D == 1; every extent <= 65534; 64-bit voxel indices.  Three separable
+ * passes that carry the nearest zero's integer offsets: O(N max(D, H, W)) at the worst, never a search over pairs.
+ * ws: cf_edt_workspace_bytes(D, H, W) bytes, 16-byte aligned, caller-owned (about 7 bytes per voxel: border flags 1, x offsets 2,
+ * (x, y) offsets 4, plus 8 bytes per 256 voxels and a 4 KiB header; cf_edt itself uses the last two arrays).  The query is host code and
+ * returns CF_ERR_ARG for a shape the calls refuse.
+ * Nothing synchronises, so a mask WITHOUT any zero voxel is reported on the device: the int at byte 24 of ws is 1 afterwards (0
+ * otherwise) and such voxels hold +inf; the caller that wants the error reads that word (cineflow.metrics.distance_transform_edt does). */
+long cf_edt_workspace_bytes(int D, int H, int W);
+int cf_edt(const uint8_t* mask, int D, int H, int W, int ndim, double sz, double sy, double sx, void* ws, double* out, void* stream);
+/* medpy's surface distances of `test == c` vs `reference == c` for K <= 16 listed label values c (host array `labels`), one label after
+ * another in one workspace (D H W < 2^31).  Border voxels by cf_surface_border's rule; for each border voxel the distance to the
+ * nearest border voxel of the OTHER volume, read from the transform of that border set -- confined to the joint bounding box of the
+ * label's two border sets, outside of which nothing is computed -- and only at the voxels where it is read.
+ *   dist  fp64 [capacity]: per label the test->ref distances, then the ref->test ones, each in raster (z, y, x) order of the voxels they
+ *         belong to.  Compaction is a prefix scan over 256-voxel blocks: no atomics, the same order and the same sums on every run.
+ *         The total never exceeds 2 D H W (a voxel carries one label per volume).
+ *   head  fp64 [2 K + 1 + 8 K + 1]: offsets [2 K + 1] (segment 2 k = test->ref of label k, 2 k + 1 = ref->test; segment s is
+ *         dist[offsets[s] .. offsets[s + 1])), then per label {count test->ref, count ref->test, max test->ref, max ref->test,
+ *         sum test->ref, sum ref->test, border voxels of test, border voxels of reference}, then 1.0 if some label did not fit capacity.
+ * A label without border voxels in either volume, or -- unless score_full -- filling either volume, or not fitting, gets two empty
+ * segments (counts 0); no launch touches memory for it beyond the flag pass. */
+int cf_label_surface_edt(const uint8_t* test, const uint8_t* reference, int D, int H, int W, int ndim, const int* labels, int K, double sz, double sy,
+                         double sx, int score_full, void* ws, double* dist, long capacity, double* head, void* stream);
+
 /* SwinCrossAttention (nnunet/lib/swin_cross_attention.py:13-112) after the projections: qk [B][2C][H][W] = the q and k maps of the
  * "rescaler" input, v [B][C][H][W] the value map of the "rescaled" input, bias_table [(2w-1)^2][heads] the learned relative position
  * bias; out [B][C][H][W] = softmax(q k^T / sqrt(C/heads) + bias + shift mask) v per window of w x w tokens (w <= 8 dividing H and W),
