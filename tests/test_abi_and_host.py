@@ -71,6 +71,49 @@ def test_argument_validation_needs_no_gpu():
     assert rc == -1
 
 
+def test_conv2d_argument_checks_need_no_gpu():
+    """cf_conv2d (csrc/conv.hip) refuses on the host, before any launch, what conv_igemm_f32_kernel is not built for: asked here with made-up
+    addresses.  Each call differs from an acceptable one (1 x 4 x 8 x 8 -> 6 channels, 3x3, stride 1, pad 1) in the one argument named."""
+    from cineflow import _lib
+    h = _lib.lib()
+    a = 4096
+    good = dict(x1=a, C1=4, x2=None, C2=0, wt=a, w_bstride=0, bias=None, res=None, out=a, out_ctotal=6, out_coff=0, B=1, H=8, W=8, Cout=6,
+                KH=3, KW=3, stride=1, pad_h=1, pad_w=1, act=0, alpha=1.0, stream=None)
+
+    def refused(message, **change):
+        args = dict(good, **change)
+        assert list(args) == list(good)
+        rc = h.cf_conv2d(*args.values())
+        err = h.cf_last_error()
+        assert rc == -1 and message in err, (change, rc, err)
+
+    refused(b"bad kernel", KH=16, pad_h=8)
+    refused(b"bad kernel", KW=16, pad_w=8)
+    refused(b"bad kernel", KH=0)
+    refused(b"bad kernel", stride=5)
+    refused(b"bad kernel", stride=0)
+    refused(b"bad kernel", pad_w=-1)
+    refused(b"output channel slice out of range", out_coff=1)              # [1, 7) of 6 channels
+    refused(b"output channel slice out of range", out_ctotal=5)
+    refused(b"output channel slice out of range", out_coff=-1, out_ctotal=8)
+    refused(b"empty output", H=2, pad_h=0)                                 # 2 rows under a 3-row kernel
+    refused(b"empty output", W=1, pad_w=0)
+    refused(b"bad channel split C1=4 C2=2", C2=2)                          # a second input of two channels and no pointer to it
+    refused(b"bad channel split C1=0 C2=0", C1=0)
+    refused(b"null pointer", x1=None)
+    refused(b"null pointer", wt=None)
+    refused(b"null pointer", out=None)
+    refused(b"bad shape", Cout=0)
+    refused(b"bad activation 6", act=6)
+    # per-sample weights: a 64-pixel wave tile must not straddle two samples
+    refused(b"per-sample weights need Ho*Wo % 64 == 0 (got 16)", w_bstride=4 * 9 * 6, stride=2)
+    refused(b"per-sample weights need Ho*Wo % 64 == 0 (got 36)", w_bstride=4 * 9 * 6, pad_h=0, pad_w=0)
+    # the transposed convolution's own checks
+    assert h.cf_conv_transpose2d_k2s2(a, a, None, a, 6, 1, 1, 4, 8, 8, 6, None) == -1 and b"output channel slice out of range" in h.cf_last_error()
+    assert h.cf_conv_transpose2d_k2s2(a, a, None, a, 6, 0, 1, 0, 8, 8, 6, None) == -1 and b"bad shape" in h.cf_last_error()
+    assert h.cf_conv_transpose2d_k2s2(a, None, None, a, 6, 0, 1, 4, 8, 8, 6, None) == -1 and b"null pointer" in h.cf_last_error()
+
+
 def test_corr_volume_route_probe_needs_no_gpu():
     """cf_corr_volume_route is host code: the dispatch of cf_corr_volume (0 generic, 1 persistent fp32, 2 f16 MFMA) on shape, alignment
     and the cf_corr_mfma_enable knob, asked here with made-up addresses"""
