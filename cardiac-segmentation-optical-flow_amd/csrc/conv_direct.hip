@@ -260,6 +260,8 @@ extern "C" int cf_conv2d_small_cin(const float* x, const float* weight, const fl
     CF_REQUIRE(B > 0 && B < 65536 && H > 0 && W > 0 && Cout > 0, "bad shape B=%d H=%d W=%d Cout=%d", B, H, W, Cout);
     CF_REQUIRE((K == 3 || K == 1) && (Cin == 1 || Cin == 2 || Cin == 6), "built for Cin 1, 2, 6 and 3x3 (pad 1) / 1x1 kernels, got Cin=%d K=%d", Cin, K);
     CF_REQUIRE(!gn_ws || (gn_groups > 0 && gn_groups <= 64 && Cout % gn_groups == 0), "bad GroupNorm statistics request (groups <= 64 dividing Cout)");
+    const int rows = K == 1 || Cin == 1 ? 32 : Cin == 2 ? 16 : 8;      // 4 * PY of the instantiation chosen below
+    CF_REQUIRE((H + rows - 1) / rows < 65536, "H=%d needs more than 65535 block rows", H);
     hipStream_t s = as_stream(stream);
     const int groups = gn_ws ? gn_groups : 0;
     if (gn_ws && hipMemsetAsync(gn_ws, 0, 2L * B * groups * sizeof(double), s) != hipSuccess) { set_error("cf_conv2d_small_cin: memset failed"); return CF_ERR_LAUNCH; }
@@ -282,6 +284,7 @@ extern "C" int cf_conv2d_small_cout(const float* x, const float* weight, const f
     CF_REQUIRE(B > 0 && B < 65536 && Cin > 0 && H > 0 && W > 0, "bad shape B=%d Cin=%d H=%d W=%d", B, Cin, H, W);
     CF_REQUIRE(Cout >= 1 && Cout <= 4, "built for 1..4 output channels, got %d", Cout);
     CF_REQUIRE((double)Cin * H * W * 4.0 < 2147483648.0, "one input sample must stay below 2 GiB (32-bit buffer offsets)");
+    CF_REQUIRE((H + 31) / 32 < 65536, "H=%d needs more than 65535 block rows", H);      // as cf_conv2d_small_cout_norm2_ok: refused here, not by the launch
     hipStream_t s = as_stream(stream);
     constexpr int PY = 8;
     dim3 grid((unsigned)((W + 63) / 64), (unsigned)((H + 4 * PY - 1) / (4 * PY)), (unsigned)B);

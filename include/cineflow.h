@@ -428,7 +428,8 @@ int cf_resize3d(const float* src, float* dst, int N, int X, int Y, int Z, int X2
 /* Stem convolutions (nn.Conv2d with 1, 2 or 6 input channels, 3x3 pad 1 or 1x1, stride 1, e.g. Generic_UNet's first conv,
  * nnunet/network_architecture/generic_UNet.py:70-86, and the encoders' first DoubleConv, nnunet/lib/utils.py:1175-1210) as a direct
  * fp32 kernel: weight fp32 [Cout][Cin][K][K] (the checkpoint layout), out dense [B][Cout][H][W].  gn_ws (may be NULL): device fp64
- * [B][gn_groups][2] = {sum, sum of squares} of the output per (sample, group), zeroed here; gn_groups <= 64 divides Cout. */
+ * [B][gn_groups][2] = {sum, sum of squares} of the output per (sample, group), zeroed here; gn_groups <= 64 divides Cout.  With a NULL
+ * gn_ws no statistics are formed and gn_groups is not read.  Each output is one fmaf chain: the bias (or +0), then ci, ky, kx. */
 int cf_conv2d_small_cin(const float* x, const float* weight, const float* bias, float* out, int B, int Cin, int H, int W, int Cout, int K,
                         double* gn_ws, int gn_groups, void* stream);
 /* Head convolutions (nn.Conv2d, 3x3 pad 1 stride 1, 1..4 OUTPUT channels: the flow head `final_conv` of Decoder2D,

@@ -13,6 +13,10 @@ conv_chain_reference / convT_chain_reference walk k = ci * KH * KW + kh * KW + k
 accumulator of +0, vectorised over every output element.  A tap that falls into the zero padding contributes fma(w, 0, acc) as in the
 kernel (which loads 0 there and multiplies): acc unchanged for finite w.  Subnormal products and sums are kept (gradual underflow): numpy
 does not flush, and neither may the kernel.
+
+direct_conv_reference is the same walk for the direct small-channel kernels (csrc/conv_direct.hip, csrc/conv_stem.hip), whose accumulator
+starts at the bias (`init`) instead of +0: fma(w, x, b) rounds once where fl32(fl32(w x) + b) rounds twice, and the two differ
+(test_fma_chain_cpu.py).  Held to those kernels, bit for bit, in test_gpu_direct_conv_chains.py.
 """
 import numpy as np
 import torch
@@ -71,13 +75,18 @@ def _double_rounding_triples():
 DOUBLE_ROUNDING_TRIPLES = _double_rounding_triples()
 
 
-def _chain(xp, w64, stride, Ho, Wo, order):
-    """xp float64 [B, Cin, Hp, Wp] (already zero padded), w64 float64 [Cout, Cin, KH, KW] -> (y32, y64, A) float arrays [B, Cout, Ho, Wo]"""
+def _chain(xp, w64, stride, Ho, Wo, order, init=None):
+    """xp float64 [B, Cin, Hp, Wp] (already zero padded), w64 float64 [Cout, Cin, KH, KW] -> (y32, y64, A) float arrays [B, Cout, Ho, Wo];
+    init: float32 [Cout], the value the accumulator starts from (None: +0) -- part of y64, its magnitude part of A"""
     B = xp.shape[0]
     Cout, Cin, KH, KW = w64.shape
     acc = np.zeros((B, Cout, Ho, Wo), dtype=F64)       # holds fp32 values
-    y64 = np.zeros_like(acc)
-    A = np.zeros_like(acc)
+    if init is not None:
+        init = np.asarray(init)
+        assert init.dtype == F32 and init.shape == (Cout,)
+        acc += init.astype(F64)[None, :, None, None]
+    y64 = acc.copy()
+    A = np.abs(acc)
     with np.errstate(invalid="ignore", over="ignore", under="ignore"):
         for k in (range(Cin * KH * KW) if order is None else order):
             ci, r = divmod(int(k), KH * KW)
@@ -90,10 +99,11 @@ def _chain(xp, w64, stride, Ho, Wo, order):
     return acc.astype(F32), y64, A
 
 
-def conv_chain_reference(x1, x2, w, stride, pad, order=None):
-    """conv2d of cat[x1, x2] (x2 may be None) with w [Cout, Cin, KH, KW], no bias: (y32, y64, A) as torch tensors [B, Cout, Ho, Wo] --
+def conv_chain_reference(x1, x2, w, stride, pad, order=None, init=None):
+    """conv2d of cat[x1, x2] (x2 may be None) with w [Cout, Cin, KH, KW]: (y32, y64, A) as torch tensors [B, Cout, Ho, Wo] --
     the fp32 fmaf chain in the kernel's k order (or in `order`, a permutation of range(K)), the fp64 sum of the exact products and
-    A = sum |w| |x|."""
+    A = sum |w| |x|.  init (float32 [Cout] or None for +0): the accumulator's first value, a bias the chain STARTS from (as the direct
+    kernels do) instead of one added to the finished sum; y64 includes it and A its magnitude."""
     x = _np(x1, F64) if x2 is None else np.concatenate([_np(x1, F64), _np(x2, F64)], 1)
     w64 = _np(w, F64)
     B, Cin, H, W = x.shape
@@ -104,7 +114,25 @@ def conv_chain_reference(x1, x2, w, stride, pad, order=None):
     assert Ho > 0 and Wo > 0
     xp = np.zeros((B, Cin, H + 2 * ph, W + 2 * pw), dtype=F64)
     xp[:, :, ph:ph + H, pw:pw + W] = x
-    return tuple(torch.from_numpy(np.ascontiguousarray(t)) for t in _chain(xp, w64, stride, Ho, Wo, order))
+    init = None if init is None else _np(init)
+    return tuple(torch.from_numpy(np.ascontiguousarray(t)) for t in _chain(xp, w64, stride, Ho, Wo, order, init))
+
+
+def direct_conv_reference(x, w, bias, res=None):
+    """the direct small-channel kernels (csrc/conv_direct.hip, csrc/conv_stem.hip): 3x3 pad 1 or 1x1 pad 0, stride 1, the chain over
+    ci, then ky, then kx from an accumulator that starts at the bias (float32 [Cout] or None); res (same shape as the output) is added
+    afterwards as one rounded fp32 addition, fl32(y32 + res), as conv3x3_small_cout_kernel does: (y32, y64, A), res in all three"""
+    K = w.shape[-1]
+    assert tuple(w.shape[2:]) in ((3, 3), (1, 1))
+    y32, y64, A = conv_chain_reference(x, None, w, 1, (K // 2, K // 2), init=bias)
+    if res is not None:
+        res = torch.from_numpy(_np(res, F32))
+        assert res.shape == y32.shape
+        with np.errstate(invalid="ignore", over="ignore"):
+            y32 = y32 + res                            # one fp32 addition per element
+        y64, A = y64 + res.double(), A + res.double().abs()
+    assert y32.dtype == torch.float32
+    return y32, y64, A
 
 
 def convT_chain_reference(x, w, order=None):

@@ -114,6 +114,83 @@ def test_conv2d_argument_checks_need_no_gpu():
     assert h.cf_conv_transpose2d_k2s2(a, None, None, a, 6, 0, 1, 4, 8, 8, 6, None) == -1 and b"null pointer" in h.cf_last_error()
 
 
+def test_direct_conv_argument_checks_need_no_gpu():
+    """the probes of the direct small-channel kernels (csrc/conv_direct.hip, csrc/conv_stem.hip) on both sides of each of their limits, and
+    the entry points' refusals -- a null or aliased pointer, a shape the probe declines -- which happen on the host before any launch: asked
+    here with made-up addresses.  The kernels themselves: tests/test_gpu_direct_conv_chains.py."""
+    from cineflow import _lib
+    h = _lib.lib()
+    ok2 = h.cf_conv2d_small_cout_norm2_ok                      # (B, Cin, H, W, Cout)
+    assert [ok2(2, 64, 33, 65, c) for c in (0, 1, 4, 5)] == [0, 1, 1, 0]
+    assert [ok2(b, 64, 33, 65, 2) for b in (0, 1, 65535, 65536)] == [0, 1, 1, 0]
+    assert [ok2(2, c, 33, 65, 2) for c in (0, 1)] == [0, 1]
+    assert [ok2(2, 64, 0, 65, 2), ok2(2, 64, 33, 0, 2)] == [0, 0]
+    assert [ok2(1, 1, 1, w, 1) for w in (2 ** 29 - 1, 2 ** 29)] == [1, 0]              # 4 Cin H W < 2 GiB: 32-bit byte offsets into one sample
+    assert [ok2(1, 64, 1024, w, 1) for w in (8191, 8192)] == [1, 0]
+    assert [ok2(1, 1, hh, 1, 1) for hh in (32 * 65535, 32 * 65535 + 1)] == [1, 0]      # grid.y
+    oks = h.cf_stem_block_ok                                   # (B, Cin, H, W, Cout, gn_groups)
+    assert [oks(2, c, 33, 65, 64, 8) for c in (0, 1, 2, 3, 6, 7)] == [0, 1, 0, 0, 1, 0]
+    assert [oks(2, 6, 33, 65, 64, g) for g in (-8, 0, 1, 64)] == [0, 0, 1, 1]
+    assert [oks(2, 6, 33, 65, 128, 64), oks(2, 6, 33, 65, 65, 65), oks(2, 6, 33, 65, 130, 65)] == [1, 0, 0]      # at most 64 groups
+    assert [oks(2, 6, 33, 65, 60, 8), oks(2, 6, 33, 65, 0, 1)] == [0, 0]               # groups divide Cout; Cout > 0
+    assert [oks(b, 1, 33, 65, 64, 8) for b in (0, 1, 65535, 65536)] == [0, 1, 1, 0]
+    assert [oks(1, 1, 1, w, 2, 1) for w in (2 ** 30 - 1, 2 ** 30)] == [1, 0]           # Cout H W < 2^31 elements in one output sample
+    assert [oks(1, 1, hh, 1, 1, 1) for hh in (8 * 65535, 8 * 65535 + 1)] == [1, 0]     # grid.y
+    a, b, c, d, e = 4096, 8192, 12288, 16384, 20480
+
+    def refused(message, rc):
+        err = h.cf_last_error()
+        assert rc == -1 and message in err, (rc, err)
+
+    # cf_conv2d_small_cin(x, weight, bias, out, B, Cin, H, W, Cout, K, gn_ws, gn_groups, stream)
+    for x, w, out in ((None, b, c), (a, None, c), (a, b, None), (a, b, a)):
+        refused(b"null or aliased pointer", h.cf_conv2d_small_cin(x, w, None, out, 1, 1, 8, 8, 6, 3, None, 0, None))
+    refused(b"built for Cin 1, 2, 6", h.cf_conv2d_small_cin(a, b, None, c, 1, 3, 8, 8, 6, 3, None, 0, None))
+    refused(b"built for Cin 1, 2, 6", h.cf_conv2d_small_cin(a, b, None, c, 1, 2, 8, 8, 6, 5, None, 0, None))
+    refused(b"bad shape", h.cf_conv2d_small_cin(a, b, None, c, 1, 1, 8, 8, 0, 3, None, 0, None))
+    for cout, groups in ((130, 65), (64, 0), (64, -8), (60, 8)):
+        refused(b"bad GroupNorm statistics request", h.cf_conv2d_small_cin(a, b, None, c, 1, 1, 8, 8, cout, 3, d, groups, None))
+    for cin, K, rows in ((1, 3, 32), (2, 3, 16), (6, 3, 8), (6, 1, 32)):               # grid.y of the instantiation that (Cin, K) selects
+        refused(b"block rows", h.cf_conv2d_small_cin(a, b, None, c, 1, cin, rows * 65535 + 1, 1, 6, K, None, 0, None))
+    # cf_conv2d_small_cout(x, weight, bias, res, out, B, Cin, H, W, Cout, stream)
+    for x, w, out in ((None, b, c), (a, None, c), (a, b, None), (a, b, a)):
+        refused(b"null or aliased pointer", h.cf_conv2d_small_cout(x, w, None, None, out, 1, 8, 8, 8, 2, None))
+    refused(b"built for 1..4 output channels, got 0", h.cf_conv2d_small_cout(a, b, None, None, c, 1, 8, 8, 8, 0, None))
+    refused(b"built for 1..4 output channels, got 5", h.cf_conv2d_small_cout(a, b, None, None, c, 1, 8, 8, 8, 5, None))
+    refused(b"below 2 GiB", h.cf_conv2d_small_cout(a, b, None, None, c, 1, 1, 1, 2 ** 29, 2, None))
+    refused(b"block rows", h.cf_conv2d_small_cout(a, b, None, None, c, 1, 1, 32 * 65535 + 1, 1, 2, None))
+    # cf_conv2d_small_cout_norm2(y2, coef2, r, coefr, weight, bias, out, B, Cin, H, W, Cout, stream)
+    good = [a, b, c, d, e, None, 24576]
+    for k in (0, 1, 2, 3, 4, 6):
+        refused(b"null or aliased pointer", h.cf_conv2d_small_cout_norm2(*[None if j == k else v for j, v in enumerate(good)], 1, 8, 8, 8, 2, None))
+    for k in (0, 2):                                                                   # out is y2, out is r
+        refused(b"null or aliased pointer", h.cf_conv2d_small_cout_norm2(*good[:6], good[k], 1, 8, 8, 8, 2, None))
+    refused(b"built for 1..4 output channels", h.cf_conv2d_small_cout_norm2(*good, 1, 8, 8, 8, 5, None))
+    refused(b"built for 1..4 output channels", h.cf_conv2d_small_cout_norm2(*good, 1, 1, 1, 2 ** 29, 2, None))
+    # cf_stem_block(x, w3, b3, w1, b1, y, r, B, Cin, H, W, Cout, ws_y, ws_r, gn_groups, stream) and cf_stem_block_y, the same without r
+    ptrs = dict(x=a, w3=b, b3=None, w1=c, b1=None, y=d, r=e)
+    shape, ws = (1, 6, 8, 8, 64), dict(ws_y=24576, ws_r=28672)
+
+    def stem(groups=8, shape=shape, with_r=True, **change):
+        p, s = dict(ptrs, **{k: v for k, v in change.items() if k in ptrs}), dict(ws, **{k: v for k, v in change.items() if k in ws})
+        if with_r:
+            return h.cf_stem_block(*p.values(), *shape, *s.values(), groups, None)
+        p.pop("r")
+        return h.cf_stem_block_y(*p.values(), *shape, *s.values(), groups, None)
+
+    for with_r in (True, False):
+        for name in ("x", "w3", "w1", "y", "ws_y", "ws_r") + (("r",) if with_r else ()):
+            refused(b"null pointer", stem(with_r=with_r, **{name: None}))
+        refused(b"aliased pointers", stem(with_r=with_r, y=a))
+        refused(b"aliased pointers", stem(with_r=with_r, ws_r=24576))
+        for groups in (65, 0, 60, -65):
+            refused(b"<= 64 statistics groups dividing Cout", stem(groups, with_r=with_r))
+        refused(b"built for Cin 1 or 6", stem(shape=(1, 2, 8, 8, 64), with_r=with_r))
+        refused(b"one output sample below 2^31 elements", stem(1, shape=(1, 1, 1, 2 ** 30, 2), with_r=with_r))
+    refused(b"aliased pointers", stem(r=a))
+    refused(b"aliased pointers", stem(r=d))
+
+
 def test_corr_volume_route_probe_needs_no_gpu():
     """cf_corr_volume_route is host code: the dispatch of cf_corr_volume (0 generic, 1 persistent fp32, 2 f16 MFMA) on shape, alignment
     and the cf_corr_mfma_enable knob, asked here with made-up addresses"""

@@ -1,5 +1,6 @@
 """tests/_fma_chain.py on the CPU: fma32 is libm's fmaf, a plain fp64 evaluation is not, the convolution chain obeys its deterministic bound,
-and the chain depends on its k order -- so a kernel with another order cannot equal it by accident."""
+and the chain depends on its k order -- so a kernel with another order cannot equal it by accident.  The chain that starts from a bias
+(direct_conv_reference, the direct small-channel kernels) is a scalar loop over fmaf too, and is not the chain from +0 plus the bias."""
 import ctypes
 import ctypes.util
 import math
@@ -9,7 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _fma_chain import DOUBLE_ROUNDING_TRIPLES, conv_chain_reference, convT_chain_reference, fma32, fma32_plain
+from _fma_chain import DOUBLE_ROUNDING_TRIPLES, conv_chain_reference, convT_chain_reference, direct_conv_reference, fma32, fma32_plain
 
 U = 2.0 ** -24                                         # unit roundoff of fp32
 
@@ -138,3 +139,63 @@ def test_chain_depends_on_its_k_order():
     sw = conv_chain_reference(x1, x2, w, stride, pad, order=swapped)[0]
     print("half-waves swapped: %d of %d elements differ" % (int((sw != y32).sum()), y32.numel()))
     assert int((sw != y32).sum()) >= 1
+
+
+# ---- the bias-initialised chain of the direct small-channel kernels (csrc/conv_direct.hip, csrc/conv_stem.hip)
+DIRECT_ROWS = [   # B, Cin, H, W, Cout, K, residual
+    (2, 1, 3, 4, 3, 3, False),
+    (1, 2, 4, 3, 2, 3, True),
+    (1, 6, 2, 5, 2, 1, False),
+    (1, 3, 1, 1, 2, 3, True),                          # one pixel: eight of nine taps are padding
+]
+
+
+def direct_operands(B, Cin, H, W, Cout, K, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, Cin, H, W, generator=g)
+    w = torch.randn(Cout, Cin, K, K, generator=g) / math.sqrt(Cin * K * K)
+    return x, w, torch.randn(Cout, generator=g), torch.randn(B, Cout, H, W, generator=g)
+
+
+@pytest.mark.parametrize("B,Cin,H,W,Cout,K,residual", DIRECT_ROWS)
+def test_direct_reference_is_a_scalar_fmaf_loop_from_the_bias(fmaf, B, Cin, H, W, Cout, K, residual):
+    """acc = bias[co]; for ci, ky, kx: acc = fmaf(w, x or the padding's 0, acc); then one fp32 addition of the residual -- libm's fmaf, one
+    output at a time, against direct_conv_reference, bit for bit"""
+    x, w, bias, res = direct_operands(B, Cin, H, W, Cout, K, 91)
+    y32, y64, A = direct_conv_reference(x, w, bias, res if residual else None)
+    xn, wn, bn, rn = x.numpy(), w.numpy(), bias.numpy(), res.numpy()
+    want = np.zeros((B, Cout, H, W), dtype=np.float32)
+    R = K // 2
+    for b in range(B):
+        for co in range(Cout):
+            for y in range(H):
+                for xx in range(W):
+                    acc = np.array([bn[co]], dtype=np.float32)
+                    for ci in range(Cin):
+                        for ky in range(K):
+                            for kx in range(K):
+                                yy, xc = y + ky - R, xx + kx - R
+                                v = xn[b, ci, yy, xc] if 0 <= yy < H and 0 <= xc < W else np.float32(0)
+                                acc = fmaf([wn[co, ci, ky, kx]], [v], acc)
+                    want[b, co, y, xx] = acc[0] + rn[b, co, y, xx] if residual else acc[0]
+    assert want.dtype == np.float32
+    assert same_bits(y32.numpy(), want).all()
+    true = F.conv2d(x.double(), w.double(), bias.double(), padding=R) + (res.double() if residual else 0.0)
+    assert float((y64 - true).abs().max()) <= 1e-13 * float(A.max())
+    assert bool((A >= bias.double().abs().view(1, -1, 1, 1)).all()), "|bias| is part of A"
+    # no bias is a chain from +0, the existing form
+    assert torch.equal(direct_conv_reference(x, w, None)[0], conv_chain_reference(x, None, w, 1, (R, R))[0])
+
+
+def test_chain_from_the_bias_is_not_the_chain_plus_the_bias():
+    """2 x 2 x 9 x 11 -> 6, 3x3: starting the accumulator at the bias and adding the bias to the finished sum differ (the first rounds
+    bias + w0 x0 once, the other w0 x0 and every later partial sum without the bias in it), so a kernel that does the other cannot
+    equal the reference by accident; both stay inside the deterministic bound"""
+    x, w, bias, _ = direct_operands(2, 2, 9, 11, 6, 3, 92)
+    y32, y64, A = direct_conv_reference(x, w, bias)
+    after = conv_chain_reference(x, None, w, 1, (1, 1))[0] + bias.view(1, -1, 1, 1)
+    assert after.dtype == torch.float32
+    differ = int((after != y32).sum())
+    print("\nbias first against bias last: %d of %d elements differ" % (differ, y32.numel()))
+    assert differ >= 1
+    assert float(((y32.double() - y64).abs() / (20 * U * A)).max()) <= 1.0 and float(((after.double() - y64).abs() / (20 * U * A)).max()) <= 1.0
