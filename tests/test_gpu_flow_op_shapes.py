@@ -43,8 +43,9 @@ Measured on the MI355X (pytest -s prints one line per row: worst figure, bar, ra
   second trips, warp family: warp 4.8e-7 (2.4e-7 past the first trip) at both sizes; memory_input 4.8e-7; labels 0 differing pixels of
       4,259,840 and of 1,125,000; both Jacobians and the 3-D warp identical to numpy / ATen (0)
   vecint, nsteps 2, at the 1e-5 bar: 3.2e-6 at 66600 x 8 x 8 (4,262,400 px), 2.4e-6 at 22000 x 8 x 6 (1,056,000 px); 3 x 21 x 30 and
-      3 x 20 x 32: <= 3.6e-6 for nsteps 0, 1, 2, 7.  At the full map width the 1e-5 of the 32- and 40-pixel fixtures does not hold for any
-      two fp32 implementations (see VECINT_BIG); those rows take four times the oracle's own fp32-against-fp64 error, measured in the row
+      3 x 20 x 32: <= 3.6e-6 for nsteps 0, 1, 2, 7.  At the full map width the 1e-5 of the 32- and 40-pixel fixtures does not hold between
+      two fp32 implementations that associate the tap sum differently, as the kernel and ATen do (see VECINT_BIG; against its own fp32 chain
+      the kernel is bit-equal there, nsteps 7 included: test_gpu_tap_chains.py); those rows take four times the oracle's own fp32-against-fp64 error, measured in the row
       on the CPU: oracle 1.69e-4 -> bar 6.8e-4, kernel 6.3e-5 at 65 x 256 x 256; oracle 1.64e-4 -> bar 6.6e-4, kernel 6.2e-5 at 17 x 250 x 250
   flat lookup 3.6e-7; convex upsample (C = 4) 5.7e-6; generic pyramid 32 x 64 1.7e-6; gru_blend 0.47 of its bound; tta_accumulate 2.7e-7;
       every copy, binary, crop / pad / flip, coords_grid, tile and argmax row 0; cf_count_out_of_range exact in all four launches
@@ -201,7 +202,8 @@ def memory_ref(x0, xt, cum):
 
 # ================================================================================================= rows 1 + 2: second grid trips, warp family
 BIG = {"v4": (65, 256, 256, 4 * TRIP1), "flat": (17, 250, 250, TRIP1)}      # frames, H, W, pixels of the first trip
-# vecint feeds one warp's output to the next as a displacement: two fp32 implementations whose first step differs by one ulp differ by one
+# vecint feeds one warp's output to the next as a displacement: two fp32 implementations whose first step differs by one ulp (the kernel's
+# chain and ATen's vectorised sampler associate differently; the kernel is bit-equal to its own chain, test_gpu_tap_chains.py) differ by one
 # ulp of (j + v) in the second step's sampling position -- 3.1e-5 px at j >= 128 -- times the field's slope, which is |v| itself where the
 # sample leaves the image (zero padding).  The 1e-5 of the 32- and 40-pixel golden fixtures therefore holds on maps of that size, not at 256
 # (module docstring: measured 5.7e-5 and 6.3e-5 there, and the same from the oracle against itself).  The second-trip rows of vecint reach
