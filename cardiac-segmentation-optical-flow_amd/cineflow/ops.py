@@ -270,6 +270,14 @@ def wino_form(B, C1, C2, H, W, cout, prenorm=False):
     return int(lib().cf_conv2d_wino_form(B, C1, C2, H, W, cout, 1 if prenorm else 0))
 
 
+def wino_mfma(B, C1, C2, H, W, cout, prenorm=0):
+    """the MFMA shape of the kernel cf_conv2d_wino runs this layer on at the current route level: 16 (the persistent kernel's 16x16x32 form),
+    32 (any other Winograd form) or 0 (not taken).  prenorm: 0 none, 1 deferred norm + LeakyReLU, 2 deferred norm + GELU"""
+    if not (WINO and CONV_MODE == "f16s"):
+        return 0
+    return int(lib().cf_conv2d_wino_mfma(B, C1, C2, H, W, cout, int(prenorm)))
+
+
 def pack_conv_weight_wino(w, c1=None):
     """torch conv weight [Cout,Cin,3,3] -> (packed fp16 tensor, scale exponent s) for cf_conv2d_wino.
 

@@ -101,6 +101,28 @@ __device__ __forceinline__ void wino_activate(f32x16 (&acc)[4][NTW], int act) {
 #undef CF_WINO_ACT_LOOP
 }
 
+// the same for the 16x16x32 form's accumulators: [output column of the pair][unit tile][unit block][channel block] of four registers
+__device__ __forceinline__ void wino_activate16(f32x4v (&acc)[4][2][2][2], int act) {
+#define CF_WINO_ACT_LOOP(A)                                                     \
+    _Pragma("unroll") for (int e = 0; e < 2; ++e)                               \
+    _Pragma("unroll") for (int nt = 0; nt < 2; ++nt)                            \
+    _Pragma("unroll") for (int ub = 0; ub < 2; ++ub)                            \
+    _Pragma("unroll") for (int cbk = 0; cbk < 2; ++cbk)                         \
+    _Pragma("unroll") for (int r = 0; r < 4; ++r) {                             \
+        acc[e][nt][ub][cbk][r] = act_apply(acc[e][nt][ub][cbk][r], A);          \
+        __builtin_amdgcn_sched_barrier(0);                                      \
+    }
+    switch (act) {
+        case CF_ACT_GELU: CF_WINO_ACT_LOOP(CF_ACT_GELU) break;
+        case CF_ACT_RELU: CF_WINO_ACT_LOOP(CF_ACT_RELU) break;
+        case CF_ACT_LRELU: CF_WINO_ACT_LOOP(CF_ACT_LRELU) break;
+        case CF_ACT_TANH: CF_WINO_ACT_LOOP(CF_ACT_TANH) break;
+        case CF_ACT_SIGMOID: CF_WINO_ACT_LOOP(CF_ACT_SIGMOID) break;
+        default: break;
+    }
+#undef CF_WINO_ACT_LOOP
+}
+
 template <int NTW, int PRE>
 __global__ void __launch_bounds__(256, NTW == 4 ? 1 : 2)
 conv_wino_kernel(const ConvParams p, const WinoGeom g, const _Float16* __restrict__ wpk) {
@@ -454,7 +476,7 @@ struct StageRegs {
     f32x4v cm, ca, cs;
 };
 
-template <int PRE>
+template <int PRE, int M16>
 __global__ void __launch_bounds__(512, 2)
 conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __restrict__ wpk) {
     constexpr int NTW = 2, REC = W_REC, CK = W_CK, NSTEP = W_NSTEP;
@@ -655,6 +677,206 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
         return;
     }
 
+    if constexpr (M16) {
+        // ================================================================================================ MFMA waves, 16x16x32 form
+        // The same three split products with v_mfma_f32_16x16x32_f16 (profiles/mfma_shape_f16.txt: the chip holds a 1.13-1.18x higher clock
+        // under this shape on data).  K = 32 is the two 16-channel chunks of one barrier pair: lane l = 16 kg + l15 takes k-group kg & 1
+        // (8 channels) of chunk gc + (kg >> 1).  The V records are the M operand (rows = units), the weights the N operand (columns =
+        // channels), so a lane's four accumulator registers are four adjacent units of one row for ONE channel: eight adjacent output
+        // columns = two dwordx4 stores, no lane swap, and bias / statistics are per lane instead of per register.
+        //   V operand: unit 16 ub + l15 of unit tile nt: the record's 16 bytes at (kg & 1) * 16 (hi; lo at + 32) in buffer (gc & 3) + (kg >> 1)
+        //   W operand: channel 16 cbk + l15: the 16 bytes of lane (kg & 1) * 32 + 16 cbk + l15 of the 32x32x16 fragment of chunk c + (kg >> 1)
+        //              (pack_conv_weight_wino's order [m-tile][chunk][step][hi|lo][lane = h * 32 + r][8], h = the k-group: nothing repacked)
+        //   D: acc[pos][nt][ub][cbk][r] = unit 16 ub + 4 kg + r, channel 16 cbk + l15
+        // 24 MFMAs of 16 clocks per step and pair of chunks against 2 x 6 x 32 before; 8 ds_read_b128 and 4 global dwordx4 per step and
+        // pair, as before.  The item's chunk count is even (host).
+        const int l15 = lane & 15, kg = lane >> 4;
+        int a_off[NTW][2];
+#pragma unroll
+        for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+            for (int ub = 0; ub < 2; ++ub) {
+                const int u = ub * 16 + l15;
+                a_off[nt][ub] = (nt * g.RT + u / g.UW) * g.ROWP + (u % g.UW) * REC + (kg & 1) * 16 + (kg >> 1) * buf_bytes;
+            }
+        const long mt_stride = (long)g.nchunk * (NSTEP * 2) * 64;             // f16x8 units per m-tile
+        const f16x8* const wbase = reinterpret_cast<const f16x8*>(wpk) + (kg >> 1) * (NSTEP * 2 * 64) + (kg & 1) * 32 + l15;
+        constexpr int R = 2;                                                   // weight ring: the next step's fragments load during this step
+        f16x8 wH[R][2] = {}, wL[R][2] = {};
+        auto load_w = [&](const f16x8* wc, int step, int slot) {
+#pragma unroll
+            for (int cbk = 0; cbk < 2; ++cbk) {
+                wH[slot][cbk] = wc[(step * 2) * 64 + cbk * 16];
+                wL[slot][cbk] = wc[(step * 2 + 1) * 64 + cbk * 16];
+            }
+        };
+        f16x8 vH[NTW][2] = {}, vL[NTW][2] = {};                               // the unit tile is the double buffer: nt = 1 loads while nt = 0 computes
+        auto load_v = [&](const unsigned char* xb, int step, int nt) {
+            const int toff = (step >> 2) * g.ROWP + (step & 3) * g.LINE;
+#pragma unroll
+            for (int ub = 0; ub < 2; ++ub) {
+                const unsigned char* rp = xb + a_off[nt][ub] + toff;
+                vH[nt][ub] = *reinterpret_cast<const f16x8*>(rp);
+                vL[nt][ub] = *reinterpret_cast<const f16x8*>(rp + CK * 2);
+            }
+        };
+        f32x4v acc[4][NTW][2][2];
+        int cb, b, y0, x0;
+        decode(0, cb, b, y0, x0);
+        const f16x8* wf = wbase + (long)(cb * 4 + wave) * mt_stride;
+        load_w(wf, 0, 0);
+        int cb_n = cb, b_n = b, y0_n = y0, x0_n = x0;
+        for (int i = 0; i < n_my; ++i) {
+            cb = cb_n; b = b_n; y0 = y0_n; x0 = x0_n;
+            const int mt = cb * 4 + wave;
+            wf = wbase + (long)mt * mt_stride;
+            if (i + 1 < n_my) decode(i + 1, cb_n, b_n, y0_n, x0_n);
+            const f16x8* wf_next = wbase + (long)(cb_n * 4 + wave) * mt_stride;
+#pragma unroll
+            for (int pos = 0; pos < 4; ++pos)
+#pragma unroll
+                for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+                    for (int ub = 0; ub < 2; ++ub)
+#pragma unroll
+                        for (int cbk = 0; cbk < 2; ++cbk) acc[pos][nt][ub][cbk] = f32x4v{0.f, 0.f, 0.f, 0.f};
+
+            for (int c = 0; c < g.nchunk; c += 2) {
+                const int gc = i * g.nchunk + c;                               // even: nchunk is
+                const f16x8* wc = wf + (long)c * NSTEP * 2 * 64;
+                const f16x8* wn = (c + 2 < g.nchunk) ? wc + 2 * NSTEP * 2 * 64 : wf_next;   // the next pair of the stream (the last one re-reads the item's first)
+                __syncthreads();                                               // chunks gc and gc + 1 are in LDS
+                const unsigned char* xb = lds + (gc & (PS_NBUF - 1)) * buf_bytes;
+                load_v(xb, 0, 0);
+#pragma unroll
+                for (int step = 0; step < NSTEP; ++step) {
+                    const int pos = step & 3, slot = step & 1;
+                    if (step + 1 < NSTEP) load_w(wc, step + 1, slot ^ 1);
+                    else load_w(wn, 0, slot ^ 1);
+                    load_v(xb, step, 1);
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int nt = 0; nt < NTW; ++nt) {
+                        // the products in the order of the 32x32x16 form (W lo x V hi, W hi x V lo, W hi x V hi), each over the four independent blocks
+#pragma unroll
+                        for (int q = 0; q < 3; ++q)
+#pragma unroll
+                            for (int ub = 0; ub < 2; ++ub)
+#pragma unroll
+                                for (int cbk = 0; cbk < 2; ++cbk)
+                                    acc[pos][nt][ub][cbk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(q == 1 ? vL[nt][ub] : vH[nt][ub], q == 0 ? wL[slot][cbk] : wH[slot][cbk],
+                                                                                                   acc[pos][nt][ub][cbk], 0, 0, 0);
+                        if (nt == 0) {
+                            if (step + 1 < NSTEP) load_v(xb, step + 1, 0);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
+                }
+            }
+
+            // ---- epilogue of item i: the meaning of conv_wino_ps_kernel's 32x32x16 epilogue in this lane layout
+#pragma unroll
+            for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+                for (int ub = 0; ub < 2; ++ub)
+#pragma unroll
+                    for (int cbk = 0; cbk < 2; ++cbk)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float m0 = acc[0][nt][ub][cbk][r], m1 = acc[1][nt][ub][cbk][r], m2 = acc[2][nt][ub][cbk][r], m3 = acc[3][nt][ub][cbk][r];
+                            acc[0][nt][ub][cbk][r] = (m0 + m1) + m2;
+                            acc[1][nt][ub][cbk][r] = (m1 - m2) - m3;
+                        }
+            bool co_ok[2];
+            unsigned ochan[2];
+            constexpr unsigned OOB_CH = 0x40000000u;
+#pragma unroll
+            for (int cbk = 0; cbk < 2; ++cbk) {
+                const int co = mt * 32 + cbk * 16 + l15;
+                co_ok[cbk] = co < p.Cout;
+                ochan[cbk] = co_ok[cbk] ? (unsigned)co * HW4 : OOB_CH;
+                const float bv = p.bias ? p.bias[co_ok[cbk] ? co : p.Cout - 1] : 0.f;
+#pragma unroll
+                for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+                    for (int ub = 0; ub < 2; ++ub)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            acc[0][nt][ub][cbk][r] = p.alpha * acc[0][nt][ub][cbk][r] + bv;
+                            acc[1][nt][ub][cbk][r] = p.alpha * acc[1][nt][ub][cbk][r] + bv;
+                        }
+            }
+            wino_activate16(acc, p.act);
+            const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(
+                p.out + ((long)b * p.out_ctotal + p.out_coff) * (long)HW, 0, (int)((long)(p.out_ctotal - p.out_coff) * HW * 4), 0x00020000);
+            float ssum[2] = {0.f, 0.f}, ssq[2] = {0.f, 0.f};
+#pragma unroll
+            for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+                for (int ub = 0; ub < 2; ++ub) {
+                    const int u = ub * 16 + 4 * kg;                            // the lane's four units: one row (UW is 8 or 16)
+                    const int oy = y0 + nt * g.RT + u / g.UW, ox = x0 + 2 * (u % g.UW);
+                    const unsigned o_off = (unsigned)(oy * p.W + ox) * 4u;
+#pragma unroll
+                    for (int cbk = 0; cbk < 2; ++cbk) {
+                        float v[8];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            v[2 * r] = acc[0][nt][ub][cbk][r];
+                            v[2 * r + 1] = acc[1][nt][ub][cbk][r];
+                        }
+                        if (p.res) {
+                            if (co_ok[cbk]) {
+                                const float* rp = p.res + ((long)b * p.Cout + (mt * 32 + cbk * 16 + l15)) * HW + (o_off >> 2);
+#pragma unroll
+                                for (int k = 0; k < 8; ++k) v[k] += rp[k];
+                            }
+                        }
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float m0 = co_ok[cbk] ? v[2 * r] : 0.f, m1 = co_ok[cbk] ? v[2 * r + 1] : 0.f;
+                            ssum[cbk] += m0 + m1;
+                            ssq[cbk] += m0 * m0 + m1 * m1;
+                        }
+                        u32x4 pk0, pk1;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) { pk0[k] = __builtin_bit_cast(unsigned, v[k]); pk1[k] = __builtin_bit_cast(unsigned, v[4 + k]); }
+                        __builtin_amdgcn_raw_buffer_store_b128(pk0, rs_out, o_off + ochan[cbk], 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b128(pk1, rs_out, o_off + 16u + ochan[cbk], 0, 0);
+                    }
+                }
+            if (p.gn_ws) {
+                // per-channel totals of the wave: over the registers (above) and the lane bits 4 and 5 (kg) in fp32, fp64 from there on, as in
+                // the 32x32x16 form.  Lanes with kg odd then carry channel block 1, so that lane bit 4 is bit 4 of the channel cl = 16 (kg & 1) + l15.
+#pragma unroll
+                for (int cbk = 0; cbk < 2; ++cbk) {
+                    ssum[cbk] += __shfl_xor(ssum[cbk], 16, 64);
+                    ssum[cbk] += __shfl_xor(ssum[cbk], 32, 64);
+                    ssq[cbk] += __shfl_xor(ssq[cbk], 16, 64);
+                    ssq[cbk] += __shfl_xor(ssq[cbk], 32, 64);
+                }
+                double s1 = (kg & 1) ? ssum[1] : ssum[0], s2 = (kg & 1) ? ssq[1] : ssq[0];
+                const int cpg = p.Cout / p.gn_groups;
+                const int cl = 16 * (kg & 1) + l15;
+                const bool pow2 = (cpg & (cpg - 1)) == 0;
+                int k = 0;
+                if (pow2 && cpg > 1) { s1 += __shfl_xor(s1, 1, 64); s2 += __shfl_xor(s2, 1, 64); k = 1; }
+                if (pow2 && cpg > 2) { s1 += __shfl_xor(s1, 2, 64); s2 += __shfl_xor(s2, 2, 64); k = 2; }
+                if (pow2 && cpg > 4) { s1 += __shfl_xor(s1, 4, 64); s2 += __shfl_xor(s2, 4, 64); k = 3; }
+                if (pow2 && cpg > 8) { s1 += __shfl_xor(s1, 8, 64); s2 += __shfl_xor(s2, 8, 64); k = 4; }
+                if (pow2 && cpg > 16) { s1 += __shfl_xor(s1, 16, 64); s2 += __shfl_xor(s2, 16, 64); k = 5; }
+                const int span = pow2 ? (1 << k) : 1;                        // channels whose total this lane now holds
+                const int co = mt * 32 + cl;
+                if (kg < 2 && (cl & (span - 1)) == 0 && co < p.Cout) {
+                    double* w = p.gn_ws + 2L * ((long)b * p.gn_groups + co / cpg);
+                    atomicAdd(w, s1);
+                    atomicAdd(w + 1, s2);
+                }
+            }
+        }
+        CF_CLOCK_END(g_clock_wino);
+        return;
+    } else {
     // =================================================================================================================== MFMA waves
     int b_off[NTW];
 #pragma unroll
@@ -851,18 +1073,20 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
     WINO_ADD(0, tm_wait); WINO_ADD(1, tm_comp); WINO_ADD(2, tm_epi); WINO_ADD(6, 1); WINO_ADD(7, N);
     WINO_ADD(8, tm_e1); WINO_ADD(9, tm_e2); WINO_ADD(10, tm_e3);
     CF_CLOCK_END(g_clock_wino);
+    }
 }
 
 // route level: 0 = off (every layer stays on the direct kernels), 1 = automatic (the persistent wave-specialised kernel where a layer has at
 // least two items per CU, else the one-tile-per-workgroup kernel with 2 unit tiles per wave), 2 / 4 = force the one-tile kernel with
 // NTW = 2 / 4 (NTW 4 runs only when forced), 8 = force the persistent kernel -- each where the geometry allows.  Initial value from CF_CONV_WINO (0 | 1 | 2 | 4 | 8);
-// cf_conv_wino_enable changes it at run time (tests, A/B runs).
+// cf_conv_wino_enable changes it at run time (tests, A/B runs).  16 = level 1's routing with the persistent kernel forced as at level 8 AND its
+// 16x16x32 MFMA form forced wherever that form applies (wino_mfma16); the other levels never change meaning.
 int g_wino_level = -1;
 int wino_level() {
     if (g_wino_level < 0) {
         const char* e = getenv("CF_CONV_WINO");
         int v = e ? atoi(e) : 1;
-        if (!(v == 0 || v == 1 || v == 2 || v == 4 || v == 8)) v = 1;
+        if (!(v == 0 || v == 1 || v == 2 || v == 4 || v == 8 || v == 16)) v = 1;
         g_wino_level = v;
     }
     return g_wino_level;
@@ -917,11 +1141,11 @@ int launch_wino(const ConvParams& p, const WinoGeom& g, const _Float16* wpk, hip
     return CF_OK;
 }
 
-template <int PRE>
+template <int PRE, int M16>
 int launch_wino_ps(const ConvParams& p, const WinoGeom& g, const _Float16* wpk, hipStream_t s) {
     const size_t lds_bytes = wino_ps_lds_bytes(g);
     if (lds_bytes > 160 * 1024) { set_error("conv_wino (persistent): LDS buffers too large"); return CF_ERR_ARG; }
-    auto kern = conv_wino_ps_kernel<PRE>;
+    auto kern = conv_wino_ps_kernel<PRE, M16>;
     static bool attr_set[64] = {};
     const int dev = current_device_slot();
     if (!attr_set[dev]) {
@@ -948,15 +1172,37 @@ int wino_pick_ntw(const ConvParams& p, WinoGeom& g) {
     const int lvl = wino_level();
     const long cblocks = (p.Cout + 127) / 128;
     // (PH * QW main + 2 PH edge lanes per staging wave: 60 of 64 in both geometries)
-    if ((lvl == 1 || lvl == 8) && wino_geometry(p, 2, g) && g.PH * (g.QW + 2) <= 64 && wino_ps_lds_bytes(g) <= 160 * 1024 &&
+    if ((lvl == 1 || lvl == 8 || lvl == 16) && wino_geometry(p, 2, g) && g.PH * (g.QW + 2) <= 64 && wino_ps_lds_bytes(g) <= 160 * 1024 &&
         (!p.in_norm || ((p.C1 & 3) == 0 && (reinterpret_cast<uintptr_t>(p.in_norm) & 15) == 0))) {
         const long nitems = (long)g.tiles_x * g.tiles_y * p.B * cblocks;
-        if (lvl == 8 || nitems >= 2L * wino_num_cus()) return 8;
+        if (lvl == 8 || lvl == 16 || nitems >= 2L * wino_num_cus()) return 8;
     }
     if (lvl == 8) return 0;
     // the one-tile kernel: NTW 2 (two workgroups per CU) unless level 4 forces NTW 4 -- level 1 never picks NTW 4
     const int ntw = wino_force_ntw() == 4 ? 4 : 2;
     return wino_geometry(p, ntw, g) ? ntw : 0;
+}
+
+// MFMA shape of the persistent kernel's matrix waves for a launch that wino_pick_ntw gave form 8: true = v_mfma_f32_16x16x32_f16.
+// The form needs an even number of 16-channel chunks per item (its K = 32 is a pair of chunks; an odd count would span two items).
+// Level 16 forces it where it applies.  Level 1 takes it per class of launch -- {plain, LeakyReLU-deferred, GELU-deferred} x {TW 32, TW 16}
+// -- and only where the layer table measured it faster (profiles/wino_mfma16_bench.md, tools/wino_ab.py on the bench's 13 layers, level 8
+// against level 16 in interleaved rounds): plain +5.4 ... +9.8 % (TW 32) and +7.3 % (TW 16), LeakyReLU-deferred +4.8 ... +5.5 % and +4.6 %,
+// GELU-deferred +1.4 ... +3.5 % at TW 32 (the staging waves pace those layers); the bench has no GELU-deferred layer at TW 16, so that
+// class is unmeasured and stays on the 32x32x16 form.
+constexpr bool WINO_M16_CLASS[3][2] = {
+    // TW 32, TW 16
+    {true, true},     // plain
+    {true, true},     // deferred norm + LeakyReLU
+    {true, false},    // deferred norm + GELU
+};
+bool wino_mfma16(const ConvParams& p, const WinoGeom& g) {
+    if ((g.nchunk & 1) != 0) return false;
+    const int lvl = wino_level();
+    if (lvl == 16) return true;
+    if (lvl != 1) return false;
+    const int cls = !p.in_norm ? 0 : (p.in_slope < 0.f ? 2 : 1);
+    return WINO_M16_CLASS[cls][g.TW == 32 ? 0 : 1];
 }
 
 }  // namespace
@@ -987,7 +1233,10 @@ int launch_conv_wino(const ConvParams& p, const _Float16* wpk, hipStream_t s) {
     if (!ntw) { set_error("conv_wino: layer shape not supported"); return CF_ERR_ARG; }
     if (p.gn_ws && !p.gn_prezeroed &&
         hipMemsetAsync(p.gn_ws, 0, sizeof(double) * 2 * (size_t)p.B * p.gn_groups, s) != hipSuccess) { set_error("conv_wino: memset failed"); return CF_ERR_LAUNCH; }
-    if (ntw == 8) return p.in_norm ? launch_wino_ps<1>(p, g, wpk, s) : launch_wino_ps<0>(p, g, wpk, s);
+    if (ntw == 8) {
+        if (wino_mfma16(p, g)) return p.in_norm ? launch_wino_ps<1, 1>(p, g, wpk, s) : launch_wino_ps<0, 1>(p, g, wpk, s);
+        return p.in_norm ? launch_wino_ps<1, 0>(p, g, wpk, s) : launch_wino_ps<0, 0>(p, g, wpk, s);
+    }
     if (p.in_norm) return ntw == 4 ? launch_wino<4, 1>(p, g, wpk, s) : launch_wino<2, 1>(p, g, wpk, s);
     return ntw == 4 ? launch_wino<4, 0>(p, g, wpk, s) : launch_wino<2, 0>(p, g, wpk, s);
 }
@@ -1018,7 +1267,7 @@ extern "C" int cf_debug_wino_phases(unsigned long long* out12) {
 
 extern "C" int cf_conv_wino_enable(int level) {
     const int prev = wino_level();
-    if (level == 0 || level == 1 || level == 2 || level == 4 || level == 8) g_wino_level = level;
+    if (level == 0 || level == 1 || level == 2 || level == 4 || level == 8 || level == 16) g_wino_level = level;
     return prev;
 }
 
@@ -1029,6 +1278,20 @@ extern "C" int cf_conv2d_wino_form(int B, int C1, int C2, int H, int W, int Cout
     wino_params(p, dummy, C1, C2 ? dummy : nullptr, C2, nullptr, nullptr, dummy, Cout, 0, B, H, W, Cout, CF_ACT_NONE, 1.f, nullptr, 0);
     if (prenorm) { p.in_norm = dummy; p.in_slope = 0.01f; }
     return conv_wino_form(p);
+}
+
+// MFMA shape the dispatch picks for the layer: 16 = the persistent kernel's 16x16x32 form, 32 = any other Winograd form, 0 = not a Winograd layer.
+// prenorm: 0 = none, 1 = deferred norm + LeakyReLU, 2 = deferred norm + GELU.
+extern "C" int cf_conv2d_wino_mfma(int B, int C1, int C2, int H, int W, int Cout, int prenorm) {
+    if (B <= 0 || C1 <= 0 || C2 < 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
+    ConvParams p;
+    float* dummy = reinterpret_cast<float*>(uintptr_t(256));      // never dereferenced
+    wino_params(p, dummy, C1, C2 ? dummy : nullptr, C2, nullptr, nullptr, dummy, Cout, 0, B, H, W, Cout, CF_ACT_NONE, 1.f, nullptr, 0);
+    if (prenorm) { p.in_norm = dummy; p.in_slope = prenorm == 2 ? -1.f : 0.01f; }
+    const int form = conv_wino_form(p);
+    if (!form) return 0;
+    WinoGeom g;
+    return (wino_pick_ntw(p, g) == 8 && wino_mfma16(p, g)) ? 16 : 32;
 }
 
 extern "C" int cf_conv2d_wino_ok(int B, int C1, int C2, int H, int W, int Cout, int prenorm) {

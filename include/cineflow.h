@@ -282,8 +282,14 @@ int cf_conv2d_wino_ok(int B, int C1, int C2, int H, int W, int Cout, int prenorm
 /* which kernel form the current route level sends the shape to (no launch): 0 = none, 2 / 4 = one tile per workgroup with 2 / 4 unit tiles
  * per wave, 8 = the persistent kernel.  Level 1 chooses between 8 and 2; the NTW 4 form runs only under the forced level 4. */
 int cf_conv2d_wino_form(int B, int C1, int C2, int H, int W, int Cout, int prenorm);
+/* MFMA shape of the kernel the current route level sends the shape to (no launch): 16 = the persistent kernel's v_mfma_f32_16x16x32_f16 form
+ * (an even number of 16-channel chunks per item; level 16 forces it, level 1 takes it per class of launch where it was measured faster),
+ * 32 = any other Winograd form, 0 = not a Winograd layer.  prenorm: 0 = none, 1 = deferred norm + LeakyReLU, 2 = deferred norm + GELU.
+ * cf_conv2d_wino_form answers 8 for the persistent kernel under either shape. */
+int cf_conv2d_wino_mfma(int B, int C1, int C2, int H, int W, int Cout, int prenorm);
 /* route level (tests, A/B runs): 0 = off, 1 = automatic (default: the persistent wave-specialised kernel where a layer has at least two items per
- * CU, else one tile per workgroup with 2 unit tiles per wave), 2 / 4 = force the one-tile kernel with 2 / 4 unit tiles per wave, 8 = force the persistent kernel -- each
+ * CU, else one tile per workgroup with 2 unit tiles per wave), 2 / 4 = force the one-tile kernel with 2 / 4 unit tiles per wave, 8 = force the persistent kernel (32x32x16 MFMAs),
+ * 16 = force the persistent kernel and its 16x16x32 MFMA form where that applies, level 1's routing otherwise -- each
  * where the geometry allows (initial value from CF_CONV_WINO).  Returns the previous level. */
 int cf_conv_wino_enable(int level);
 int cf_conv2d_wino(const float* x1, int C1, const float* x2, int C2, const void* wpk, const float* bias, const float* res, float* out,

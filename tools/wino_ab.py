@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """A/B of the row-Winograd kernel (conv_wino.hip) against the direct f16-split kernel (conv_f16s.hip) on the bench's >= 128-channel 3x3 layers,
 interleaved rounds in ONE process on random data (methodology rule 24): per case the median and the minimum over the rounds of
-  direct | wino, 2 unit tiles per wave (two workgroups per CU) | wino, 4 unit tiles per wave (one wave per SIMD)
+  direct | wino2: 2 unit tiles per wave (two workgroups per CU) | wino8: the persistent kernel, 32x32x16 MFMAs | wino16: the persistent
+  kernel with 16x16x32 MFMAs where that form applies (the line ends with the shape ops.wino_mfma names at level 16)
 in microseconds and in direct-form TFLOP/s, each with fused statistics (the form the networks run) and, for single-input cases, with the
 deferred normalisation.  Usage: python tools/wino_ab.py [rounds] [case indices...]"""
 import math
@@ -48,7 +49,7 @@ for (B, C1, C2, H, Cout, act, groups) in CASES:
         variants["direct"] = lambda: ops.conv2d_f16s(x1, wpd, wsd, None, Cout, 3, 3, 1, (1, 1), x2=x2, stats_groups=sg)
     else:
         variants["direct"] = lambda: ops.conv2d_f16s(x1, wpd, wsd, None, Cout, 3, 3, 1, (1, 1), stats_groups=sg)     # (+ an apply pass in the network)
-    for ntw in (2, 8):
+    for ntw in (2, 8, 16):
         lib().cf_conv_wino_enable(ntw)
         if ops.wino_ok(B, C1, C2, H, H, Cout, prenorm=pre):
             if pre:
@@ -63,6 +64,8 @@ for (B, C1, C2, H, Cout, act, groups) in CASES:
     for k in variants:
         med, mn = statistics.median(times[k]), min(times[k])
         line += " | %s %7.1f us (min %7.1f) %5.1f TF" % (k, med * 1e6, mn * 1e6, flops / med / 1e12)
+    lib().cf_conv_wino_enable(16)
+    line += " | mfma at 16: %d" % ops.wino_mfma(B, C1, C2, H, H, Cout, prenorm=(2 if act == "gelu" else 1) if pre else 0)
     print(line, flush=True)
     lib().cf_conv_wino_enable(1)
     del x1, x2
