@@ -23,6 +23,7 @@
 #include <hip/hip_fp16.h>
 
 #include "conv.h"
+#include "profile.h"
 
 namespace cf {
 namespace {
@@ -372,23 +373,10 @@ bool composition_is_faster(const C3Params& p, const C3Geom& g, int variant) {
 template <int WM, int NTW, int MAXT>
 int launch_variant(const C3Params& p, const C3Geom& g, const _Float16* wpk, hipStream_t s) {
     constexpr int NW = 4;
-    auto kern = conv3d_f16s_kernel<WM, NTW, MAXT, NW>;
-    static bool attr_set[64] = {};
-    const int dev = current_device_slot();
-    if (!attr_set[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set[dev] = true;
-    }
     size_t lds_bytes = (size_t)2 * g.NIMG * g.PH * g.PWR * 80;
     if (lds_bytes < (size_t)NW * 64 * sizeof(float)) lds_bytes = (size_t)NW * 64 * sizeof(float);     // the statistics combine
     dim3 grid((unsigned)(g.tiles_x * g.tiles_y * g.bgroups), (unsigned)((p.Cout + 32 * WM - 1) / (32 * WM)));
-    hipLaunchKernelGGL(kern, grid, dim3(64 * NW), lds_bytes, s, p, g, wpk);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string("conv3d_f16s launch failed: ") + hipGetErrorString(e));
-        return CF_ERR_LAUNCH;
-    }
-    return CF_OK;
+    return launch_lds<conv3d_f16s_kernel<WM, NTW, MAXT, NW>>("conv3d_f16s", -1, 0.0, grid, dim3(64 * NW), lds_bytes, s, p, g, wpk);      // not among the timed kernels
 }
 
 // one launch on a (sub-)batch; the statistics come from the fused epilogue when every workgroup stays inside one sample, else from norm.hip's pass

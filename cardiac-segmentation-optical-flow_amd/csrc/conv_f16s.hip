@@ -928,23 +928,11 @@ static int launch_f16s_shape(const ConvParams& p, const F16sPlan& pl, const _Flo
       if (pad > (long)lds_bytes) lds_bytes = (size_t)pad; }
     if (lds_bytes > 160 * 1024) { set_error("conv_f16s: LDS tile too large"); return CF_ERR_ARG; }
 #endif
-    auto kern = p.terms == 1 ? conv_f16s_kernel<KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL, 1> : conv_f16s_kernel<KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL, 3>;
-    static bool attr_set[64][2] = {};       // per device and variant
-    const int dev = current_device_slot();
-    if (!attr_set[dev][p.terms == 1]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set[dev][p.terms == 1] = true;
-    }
     const dim3 grid(pl.grid_x, pl.grid_y), block(64 * NW);
     const double flops = 2.0 * (double)p.B * p.Ho * p.Wo * p.Cout * (p.C1 + p.C2) * p.KH * p.KW;
-    hipEvent_t e0, e1;
-    if (profile_on() && profile_events(PK_CONV_F16S, flops, &e0, &e1))
-        hipExtLaunchKernelGGL(kern, grid, block, lds_bytes, s, e0, e1, 0, p, g, wpk);
-    else
-        hipLaunchKernelGGL(kern, grid, block, lds_bytes, s, p, g, wpk);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("conv_f16s launch failed: ") + hipGetErrorString(e)); return CF_ERR_LAUNCH; }
-    return CF_OK;
+    if (p.terms == 1)
+        return launch_lds<conv_f16s_kernel<KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL, 1>>("conv_f16s", PK_CONV_F16S, flops, grid, block, lds_bytes, s, p, g, wpk);
+    return launch_lds<conv_f16s_kernel<KH, KW, CK, WM, NTW, MAXT, NW, VEC, PRE, WL, 3>>("conv_f16s", PK_CONV_F16S, flops, grid, block, lds_bytes, s, p, g, wpk);
 }
 
 #define CF_F16S_ROW(...) launch_f16s_shape<__VA_ARGS__>,

@@ -597,25 +597,11 @@ static int launch_stream(const ConvParams& p, const StreamGeom& g, const _Float1
     constexpr int PH = st_tile_rows(WM) + 2;
     const size_t lds_bytes = (size_t)2 * PH * ST_PW * ST_REC + (size_t)2 * WM * 18 * 1024 + sizeof(float) * (2 * WM * 64 + WM * 32 + (PRE ? 2 * 2 * 64 * ST_NW : 0));
     if (lds_bytes > 160 * 1024) { set_error("conv_stream: LDS budget exceeded"); return CF_ERR_ARG; }
-    auto kern = conv_stream_kernel<WM, PRE>;
-    static bool attr_set[64] = {};       // per device: a second GPU driven by the same process needs the 160 KB opt-in too
-    const int dev = current_device_slot();
-    if (!attr_set[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set[dev] = true;
-    }
     // one persistent workgroup per CU (g.ntiles >= 1024), in whole groups of 8 (the kernel bands the tiles by blockIdx % 8 = XCD under
     // round-robin placement: speed only, any grid is correct)
     const unsigned nwg = (unsigned)device_cu_count();
     const double flops = 2.0 * (double)p.B * p.H * p.W * p.Cout * (p.C1 + p.C2) * 9.0;
-    hipEvent_t e0, e1;
-    if (profile_on() && profile_events(PK_CONV_STREAM, flops, &e0, &e1))
-        hipExtLaunchKernelGGL(kern, dim3(nwg), dim3(64 * ST_NW), lds_bytes, s, e0, e1, 0, p, g, wpk);
-    else
-        hipLaunchKernelGGL(kern, dim3(nwg), dim3(64 * ST_NW), lds_bytes, s, p, g, wpk);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("conv_stream launch failed: ") + hipGetErrorString(e)); return CF_ERR_LAUNCH; }
-    return CF_OK;
+    return launch_lds<conv_stream_kernel<WM, PRE>>("conv_stream", PK_CONV_STREAM, flops, dim3(nwg), dim3(64 * ST_NW), lds_bytes, s, p, g, wpk);
 }
 
 // The caller (conv_f16s.hip) has checked conv_stream_applicable(p) and zeroed p.gn_ws.

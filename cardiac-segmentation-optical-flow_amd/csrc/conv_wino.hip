@@ -27,6 +27,11 @@
 //   * weights: packed on the host in fragment order [m-tile][chunk][ky][position][hi|lo], loaded L2 -> registers two steps ahead.
 // Reference layers: DoubleConv / ConvBlocks (nnunet/lib/utils.py:1182-1215), ConvDropoutNormNonlin (generic_UNet.py:26-69), ConvGRUCell
 // (convGRU.py:57-66) at >= 128 output channels.
+//
+// The file, top to bottom: the activation switch both accumulator layouts share (wino_activate); conv_wino_kernel<NTW, PRE>, one tile per
+// workgroup; conv_wino_ps_kernel<PRE, M16>, persistent, with its staging waves and its MFMA waves in the 32x32x16 or the 16x16x32 form; the
+// host half -- WinoPlan / wino_plan name what one launch will be (argument gate, route level, form, MFMA shape, geometry, LDS, grid) as a pure
+// function of the ConvParams; the probes read that plan and launch_plan executes it.
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
 
@@ -79,48 +84,36 @@ __device__ __forceinline__ float from_lane_above(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(i, i, 0x101, 0xf, 0xf, false));
 }
 
-// activation over the accumulator registers: ONE workgroup-uniform switch with the element loops inside (with the switch inside the unrolled
-// element loop the epilogue was tens of KB of instructions, conv_f16s.hip)
-template <int NTW>
-__device__ __forceinline__ void wino_activate(f32x16 (&acc)[4][NTW], int act) {
-#define CF_WINO_ACT_LOOP(A)                                                     \
-    _Pragma("unroll") for (int e = 0; e < 2; ++e)                               \
-    _Pragma("unroll") for (int nt = 0; nt < NTW; ++nt)                          \
-    _Pragma("unroll") for (int r = 0; r < 16; ++r) {                            \
-        acc[e][nt][r] = act_apply(acc[e][nt][r], A);                            \
-        __builtin_amdgcn_sched_barrier(0); /* one element at a time: these cold paths must not set the kernel's register count */ \
-    }
-    switch (act) {
-        case CF_ACT_GELU: CF_WINO_ACT_LOOP(CF_ACT_GELU) break;
-        case CF_ACT_RELU: CF_WINO_ACT_LOOP(CF_ACT_RELU) break;
-        case CF_ACT_LRELU: CF_WINO_ACT_LOOP(CF_ACT_LRELU) break;
-        case CF_ACT_TANH: CF_WINO_ACT_LOOP(CF_ACT_TANH) break;
-        case CF_ACT_SIGMOID: CF_WINO_ACT_LOOP(CF_ACT_SIGMOID) break;
-        default: break;
-    }
-#undef CF_WINO_ACT_LOOP
+// Accumulators of every kernel form as a flat list of N vectors of type V per position: f32x16 [4][NTW] in the 32x32x16 forms, f32x4v [4][8]
+// in the 16x16x32 form, whose vector a16(nt, ub, cbk) is (unit tile, unit block, channel block).
+__device__ constexpr int a16(int nt, int ub, int cbk) { return nt * 4 + ub * 2 + cbk; }
+
+// activation over the accumulator registers (acc[0], acc[1]: the two output columns of a pair), for both layouts: ONE workgroup-uniform
+// switch with the element loops inside (with the switch inside the unrolled element loop the epilogue was tens of KB of instructions,
+// conv_f16s.hip)
+template <int ACT, class V, int N>
+__device__ __forceinline__ void wino_act_loop(V (&acc)[4][N]) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+#pragma unroll
+            for (int r = 0; r < (int)(sizeof(V) / sizeof(float)); ++r) {
+                acc[e][i][r] = act_apply(acc[e][i][r], ACT);
+                __builtin_amdgcn_sched_barrier(0);      // one element at a time: these cold paths must not set the kernel's register count
+            }
 }
 
-// the same for the 16x16x32 form's accumulators: [output column of the pair][unit tile][unit block][channel block] of four registers
-__device__ __forceinline__ void wino_activate16(f32x4v (&acc)[4][2][2][2], int act) {
-#define CF_WINO_ACT_LOOP(A)                                                     \
-    _Pragma("unroll") for (int e = 0; e < 2; ++e)                               \
-    _Pragma("unroll") for (int nt = 0; nt < 2; ++nt)                            \
-    _Pragma("unroll") for (int ub = 0; ub < 2; ++ub)                            \
-    _Pragma("unroll") for (int cbk = 0; cbk < 2; ++cbk)                         \
-    _Pragma("unroll") for (int r = 0; r < 4; ++r) {                             \
-        acc[e][nt][ub][cbk][r] = act_apply(acc[e][nt][ub][cbk][r], A);          \
-        __builtin_amdgcn_sched_barrier(0);                                      \
-    }
+template <class V, int N>
+__device__ __forceinline__ void wino_activate(V (&acc)[4][N], int act) {
     switch (act) {
-        case CF_ACT_GELU: CF_WINO_ACT_LOOP(CF_ACT_GELU) break;
-        case CF_ACT_RELU: CF_WINO_ACT_LOOP(CF_ACT_RELU) break;
-        case CF_ACT_LRELU: CF_WINO_ACT_LOOP(CF_ACT_LRELU) break;
-        case CF_ACT_TANH: CF_WINO_ACT_LOOP(CF_ACT_TANH) break;
-        case CF_ACT_SIGMOID: CF_WINO_ACT_LOOP(CF_ACT_SIGMOID) break;
+        case CF_ACT_GELU: wino_act_loop<CF_ACT_GELU>(acc); break;
+        case CF_ACT_RELU: wino_act_loop<CF_ACT_RELU>(acc); break;
+        case CF_ACT_LRELU: wino_act_loop<CF_ACT_LRELU>(acc); break;
+        case CF_ACT_TANH: wino_act_loop<CF_ACT_TANH>(acc); break;
+        case CF_ACT_SIGMOID: wino_act_loop<CF_ACT_SIGMOID>(acc); break;
         default: break;
     }
-#undef CF_WINO_ACT_LOOP
 }
 
 template <int NTW, int PRE>
@@ -373,7 +366,7 @@ conv_wino_kernel(const ConvParams p, const WinoGeom g, const _Float16* __restric
             acc[1][nt][r] = p.alpha * acc[1][nt][r] + bv;
         }
     }
-    wino_activate<NTW>(acc, p.act);      // workgroup-uniform; the ConvGRU gates (sigmoid / tanh) are the main users on this path
+    wino_activate(acc, p.act);      // workgroup-uniform; the ConvGRU gates (sigmoid / tanh) are the main users on this path
     constexpr unsigned OOB_CH = 0x40000000u;
     const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(
         p.out + ((long)b * p.out_ctotal + p.out_coff) * (long)HW, 0, (int)((long)(p.out_ctotal - p.out_coff) * HW * 4), 0x00020000);
@@ -687,7 +680,7 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
         //   V operand: unit 16 ub + l15 of unit tile nt: the record's 16 bytes at (kg & 1) * 16 (hi; lo at + 32) in buffer (gc & 3) + (kg >> 1)
         //   W operand: channel 16 cbk + l15: the 16 bytes of lane (kg & 1) * 32 + 16 cbk + l15 of the 32x32x16 fragment of chunk c + (kg >> 1)
         //              (pack_conv_weight_wino's order [m-tile][chunk][step][hi|lo][lane = h * 32 + r][8], h = the k-group: nothing repacked)
-        //   D: acc[pos][nt][ub][cbk][r] = unit 16 ub + 4 kg + r, channel 16 cbk + l15
+        //   D: acc[pos][a16(nt, ub, cbk)][r] = unit 16 ub + 4 kg + r, channel 16 cbk + l15
         // 24 MFMAs of 16 clocks per step and pair of chunks against 2 x 6 x 32 before; 8 ds_read_b128 and 4 global dwordx4 per step and
         // pair, as before.  The item's chunk count is even (host).
         const int l15 = lane & 15, kg = lane >> 4;
@@ -720,7 +713,7 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
                 vL[nt][ub] = *reinterpret_cast<const f16x8*>(rp + CK * 2);
             }
         };
-        f32x4v acc[4][NTW][2][2];
+        f32x4v acc[4][8];
         int cb, b, y0, x0;
         decode(0, cb, b, y0, x0);
         const f16x8* wf = wbase + (long)(cb * 4 + wave) * mt_stride;
@@ -739,7 +732,7 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
 #pragma unroll
                     for (int ub = 0; ub < 2; ++ub)
 #pragma unroll
-                        for (int cbk = 0; cbk < 2; ++cbk) acc[pos][nt][ub][cbk] = f32x4v{0.f, 0.f, 0.f, 0.f};
+                        for (int cbk = 0; cbk < 2; ++cbk) acc[pos][a16(nt, ub, cbk)] = f32x4v{0.f, 0.f, 0.f, 0.f};
 
             for (int c = 0; c < g.nchunk; c += 2) {
                 const int gc = i * g.nchunk + c;                               // even: nchunk is
@@ -764,8 +757,8 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
                             for (int ub = 0; ub < 2; ++ub)
 #pragma unroll
                                 for (int cbk = 0; cbk < 2; ++cbk)
-                                    acc[pos][nt][ub][cbk] = __builtin_amdgcn_mfma_f32_16x16x32_f16(q == 1 ? vL[nt][ub] : vH[nt][ub], q == 0 ? wL[slot][cbk] : wH[slot][cbk],
-                                                                                                   acc[pos][nt][ub][cbk], 0, 0, 0);
+                                    acc[pos][a16(nt, ub, cbk)] = __builtin_amdgcn_mfma_f32_16x16x32_f16(q == 1 ? vL[nt][ub] : vH[nt][ub], q == 0 ? wL[slot][cbk] : wH[slot][cbk],
+                                                                                                   acc[pos][a16(nt, ub, cbk)], 0, 0, 0);
                         if (nt == 0) {
                             if (step + 1 < NSTEP) load_v(xb, step + 1, 0);
                             __builtin_amdgcn_sched_barrier(0);
@@ -783,9 +776,9 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
                     for (int cbk = 0; cbk < 2; ++cbk)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            const float m0 = acc[0][nt][ub][cbk][r], m1 = acc[1][nt][ub][cbk][r], m2 = acc[2][nt][ub][cbk][r], m3 = acc[3][nt][ub][cbk][r];
-                            acc[0][nt][ub][cbk][r] = (m0 + m1) + m2;
-                            acc[1][nt][ub][cbk][r] = (m1 - m2) - m3;
+                            const float m0 = acc[0][a16(nt, ub, cbk)][r], m1 = acc[1][a16(nt, ub, cbk)][r], m2 = acc[2][a16(nt, ub, cbk)][r], m3 = acc[3][a16(nt, ub, cbk)][r];
+                            acc[0][a16(nt, ub, cbk)][r] = (m0 + m1) + m2;
+                            acc[1][a16(nt, ub, cbk)][r] = (m1 - m2) - m3;
                         }
             bool co_ok[2];
             unsigned ochan[2];
@@ -802,11 +795,11 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
                     for (int ub = 0; ub < 2; ++ub)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            acc[0][nt][ub][cbk][r] = p.alpha * acc[0][nt][ub][cbk][r] + bv;
-                            acc[1][nt][ub][cbk][r] = p.alpha * acc[1][nt][ub][cbk][r] + bv;
+                            acc[0][a16(nt, ub, cbk)][r] = p.alpha * acc[0][a16(nt, ub, cbk)][r] + bv;
+                            acc[1][a16(nt, ub, cbk)][r] = p.alpha * acc[1][a16(nt, ub, cbk)][r] + bv;
                         }
             }
-            wino_activate16(acc, p.act);
+            wino_activate(acc, p.act);
             const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(
                 p.out + ((long)b * p.out_ctotal + p.out_coff) * (long)HW, 0, (int)((long)(p.out_ctotal - p.out_coff) * HW * 4), 0x00020000);
             float ssum[2] = {0.f, 0.f}, ssq[2] = {0.f, 0.f};
@@ -822,8 +815,8 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
                         float v[8];
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            v[2 * r] = acc[0][nt][ub][cbk][r];
-                            v[2 * r + 1] = acc[1][nt][ub][cbk][r];
+                            v[2 * r] = acc[0][a16(nt, ub, cbk)][r];
+                            v[2 * r + 1] = acc[1][a16(nt, ub, cbk)][r];
                         }
                         if (p.res) {
                             if (co_ok[cbk]) {
@@ -989,7 +982,7 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
                 acc[1][nt][r] = p.alpha * acc[1][nt][r] + bv;
             }
         }
-        wino_activate<NTW>(acc, p.act);
+        wino_activate(acc, p.act);
         const unsigned long long te1 = WINO_T();
         constexpr unsigned OOB_CH = 0x40000000u;
         const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(
@@ -1080,7 +1073,7 @@ conv_wino_ps_kernel(const ConvParams p, const WinoGeom g, const _Float16* __rest
 // least two items per CU, else the one-tile-per-workgroup kernel with 2 unit tiles per wave), 2 / 4 = force the one-tile kernel with
 // NTW = 2 / 4 (NTW 4 runs only when forced), 8 = force the persistent kernel -- each where the geometry allows.  Initial value from CF_CONV_WINO (0 | 1 | 2 | 4 | 8);
 // cf_conv_wino_enable changes it at run time (tests, A/B runs).  16 = level 1's routing with the persistent kernel forced as at level 8 AND its
-// 16x16x32 MFMA form forced wherever that form applies (wino_mfma16); the other levels never change meaning.
+// 16x16x32 MFMA form forced wherever that form applies (wino_plan); the other levels never change meaning.  wino_plan is its one reader.
 int g_wino_level = -1;
 int wino_level() {
     if (g_wino_level < 0) {
@@ -1091,10 +1084,6 @@ int wino_level() {
     }
     return g_wino_level;
 }
-int wino_enabled() { return wino_level() != 0; }
-int wino_force_ntw() { const int v = wino_level(); return (v == 2 || v == 4) ? v : 0; }
-
-int wino_num_cus() { return device_cu_count(); }
 
 bool wino_geometry(const ConvParams& p, int ntw, WinoGeom& g) {
     g.TW = p.W >= 32 ? 32 : 16;
@@ -1114,132 +1103,109 @@ bool wino_geometry(const ConvParams& p, int ntw, WinoGeom& g) {
     return g.ntask <= 256 * (ntw == 4 ? 2 : 1);
 }
 
-size_t wino_lds_bytes(const WinoGeom& g, bool pre) { return (size_t)2 * g.PH * g.ROWP + (pre ? (size_t)3 * g.nchunk * W_CK * sizeof(float) : 0); }
-size_t wino_ps_lds_bytes(const WinoGeom& g) { return (size_t)PS_NBUF * g.PH * g.ROWP; }
-
-template <int NTW, int PRE>
-int launch_wino(const ConvParams& p, const WinoGeom& g, const _Float16* wpk, hipStream_t s) {
-    const size_t lds_bytes = wino_lds_bytes(g, PRE);
-    if (lds_bytes > 160 * 1024) { set_error("conv_wino: LDS tile too large"); return CF_ERR_ARG; }
-    auto kern = conv_wino_kernel<NTW, PRE>;
-    static bool attr_set[64] = {};
-    const int dev = current_device_slot();
-    if (!attr_set[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set[dev] = true;
-    }
-    dim3 grid((unsigned)(g.tiles_x * g.tiles_y * p.B), (unsigned)((p.Cout + 127) / 128));
-    dim3 block(256);
-    const double flops = 2.0 * (double)p.B * p.H * p.W * p.Cout * (p.C1 + p.C2) * 9.0;     // algorithmic (direct-form) flops
-    hipEvent_t e0, e1;
-    if (profile_on() && profile_events(PK_CONV_WINO, flops, &e0, &e1))
-        hipExtLaunchKernelGGL(kern, grid, block, lds_bytes, s, e0, e1, 0, p, g, wpk);
-    else
-        hipLaunchKernelGGL(kern, grid, block, lds_bytes, s, p, g, wpk);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("conv_wino launch failed: ") + hipGetErrorString(e)); return CF_ERR_LAUNCH; }
-    return CF_OK;
-}
-
-template <int PRE, int M16>
-int launch_wino_ps(const ConvParams& p, const WinoGeom& g, const _Float16* wpk, hipStream_t s) {
-    const size_t lds_bytes = wino_ps_lds_bytes(g);
-    if (lds_bytes > 160 * 1024) { set_error("conv_wino (persistent): LDS buffers too large"); return CF_ERR_ARG; }
-    auto kern = conv_wino_ps_kernel<PRE, M16>;
-    static bool attr_set[64] = {};
-    const int dev = current_device_slot();
-    if (!attr_set[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set[dev] = true;
-    }
-    const long nitems = (long)g.tiles_x * g.tiles_y * p.B * ((p.Cout + 127) / 128);
-    long nwg = wino_num_cus();                          // one workgroup per CU, a multiple of the 8 XCDs
-    if (nwg > ((nitems + 7) & ~7L)) nwg = (nitems + 7) & ~7L;
-    dim3 grid((unsigned)nwg), block(512);
-    const double flops = 2.0 * (double)p.B * p.H * p.W * p.Cout * (p.C1 + p.C2) * 9.0;
-    hipEvent_t e0, e1;
-    if (profile_on() && profile_events(PK_CONV_WINO, flops, &e0, &e1))
-        hipExtLaunchKernelGGL(kern, grid, block, lds_bytes, s, e0, e1, 0, p, g, wpk);
-    else
-        hipLaunchKernelGGL(kern, grid, block, lds_bytes, s, p, g, wpk);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("conv_wino (persistent) launch failed: ") + hipGetErrorString(e)); return CF_ERR_LAUNCH; }
-    return CF_OK;
-}
-
-// kernel shape for a layer: 0 = not a Winograd layer, 2 / 4 = one tile per workgroup with that many unit tiles per wave, 8 = persistent
-int wino_pick_ntw(const ConvParams& p, WinoGeom& g) {
-    const int lvl = wino_level();
-    const long cblocks = (p.Cout + 127) / 128;
-    // (PH * QW main + 2 PH edge lanes per staging wave: 60 of 64 in both geometries)
-    if ((lvl == 1 || lvl == 8 || lvl == 16) && wino_geometry(p, 2, g) && g.PH * (g.QW + 2) <= 64 && wino_ps_lds_bytes(g) <= 160 * 1024 &&
-        (!p.in_norm || ((p.C1 & 3) == 0 && (reinterpret_cast<uintptr_t>(p.in_norm) & 15) == 0))) {
-        const long nitems = (long)g.tiles_x * g.tiles_y * p.B * cblocks;
-        if (lvl == 8 || lvl == 16 || nitems >= 2L * wino_num_cus()) return 8;
-    }
-    if (lvl == 8) return 0;
-    // the one-tile kernel: NTW 2 (two workgroups per CU) unless level 4 forces NTW 4 -- level 1 never picks NTW 4
-    const int ntw = wino_force_ntw() == 4 ? 4 : 2;
-    return wino_geometry(p, ntw, g) ? ntw : 0;
-}
-
-// MFMA shape of the persistent kernel's matrix waves for a launch that wino_pick_ntw gave form 8: true = v_mfma_f32_16x16x32_f16.
-// The form needs an even number of 16-channel chunks per item (its K = 32 is a pair of chunks; an odd count would span two items).
-// Level 16 forces it where it applies.  Level 1 takes it per class of launch -- {plain, LeakyReLU-deferred, GELU-deferred} x {TW 32, TW 16}
-// -- and only where the layer table measured it faster (profiles/wino_mfma16_bench.md, tools/wino_ab.py on the bench's 13 layers, level 8
-// against level 16 in interleaved rounds): plain +5.4 ... +9.8 % (TW 32) and +7.3 % (TW 16), LeakyReLU-deferred +4.8 ... +5.5 % and +4.6 %,
-// GELU-deferred +1.4 ... +3.5 % at TW 32 (the staging waves pace those layers); the bench has no GELU-deferred layer at TW 16, so that
-// class is unmeasured and stays on the 32x32x16 form.
+// MFMA shape of the persistent kernel's matrix waves at level 1: true = v_mfma_f32_16x16x32_f16, per class of launch -- {plain,
+// LeakyReLU-deferred, GELU-deferred} x {TW 32, TW 16} -- and only where the layer table measured it faster (profiles/wino_mfma16_bench.md,
+// tools/wino_ab.py on the bench's 13 layers, level 8 against level 16 in interleaved rounds): plain +5.4 ... +9.8 % (TW 32) and +7.3 % (TW 16),
+// LeakyReLU-deferred +4.8 ... +5.5 % and +4.6 %, GELU-deferred +1.4 ... +3.5 % at TW 32 (the staging waves pace those layers); the bench has
+// no GELU-deferred layer at TW 16, so that class is unmeasured and stays on the 32x32x16 form.
 constexpr bool WINO_M16_CLASS[3][2] = {
     // TW 32, TW 16
     {true, true},     // plain
     {true, true},     // deferred norm + LeakyReLU
     {true, false},    // deferred norm + GELU
 };
-bool wino_mfma16(const ConvParams& p, const WinoGeom& g) {
-    if ((g.nchunk & 1) != 0) return false;
+
+// What one launch will be: a pure function of the ConvParams (pointers are read for their alignment, never dereferenced), of this thread's
+// product mode and of the route level.  The probes read it, launch_plan executes it: what a probe accepts, the launch runs.
+struct WinoPlan {
+    int form = 0;                // 0 = declined, 2 / 4 = one tile per workgroup with that many unit tiles per wave, 8 = persistent
+    bool m16 = false;            // form 8: the matrix waves run the 16x16x32 MFMA form
+    WinoGeom g = {};             // the kernel's geometry argument, complete
+    size_t lds_bytes = 0;        // dynamic LDS of the launch
+    dim3 grid, block;
+    const char* why = nullptr;   // form 0: the message for set_error
+};
+WinoPlan wino_declined(const char* why) { WinoPlan pl; pl.why = why; return pl; }
+
+WinoPlan wino_plan(const ConvParams& p) {
     const int lvl = wino_level();
-    if (lvl == 16) return true;
-    if (lvl != 1) return false;
-    const int cls = !p.in_norm ? 0 : (p.in_slope < 0.f ? 2 : 1);
-    return WINO_M16_CLASS[cls][g.TW == 32 ? 0 : 1];
+    // ---- the argument gate
+    if (lvl == 0) return wino_declined("conv_wino: switched off (route level 0)");
+    if (conv_terms() != 3) return wino_declined("conv_wino: the one-term product mode is built in conv_f16s only");
+    if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad_h != 1 || p.pad_w != 1 || p.w_bstride || p.scatter2x2)
+        return wino_declined("conv_wino: not a plain 3x3 / stride 1 / pad 1 convolution");
+    // Cout: whole 128-channel blocks, or a last block at least three quarters full (the U-Net's 480), as conv_f16s' 128-channel shapes
+    if (!(p.Cout % 128 == 0 || (p.Cout > 128 && p.Cout % 128 >= 96))) return wino_declined("conv_wino: Cout is neither whole 128-channel blocks nor ends in a block of >= 96");
+    if (p.W < 16 || (p.W & 15) != 0) return wino_declined("conv_wino: W is not a multiple of 16");
+    if (((reinterpret_cast<uintptr_t>(p.x1) | reinterpret_cast<uintptr_t>(p.x2)) & 15) != 0) return wino_declined("conv_wino: inputs are not 16-byte aligned");
+    const long HW = (long)p.H * p.W;
+    if ((long)p.C1 * HW * 4 >= (1L << 31) || (long)p.C2 * HW * 4 >= (1L << 31)) return wino_declined("conv_wino: one sample of an input reaches 2 GiB");
+    if ((long)p.out_ctotal * HW * 4 >= (1L << 30))          // 32-bit store offsets, two parking values (kernel epilogue)
+        return wino_declined("conv_wino: one sample of the output tensor reaches 1 GiB");
+    if (p.in_norm && (p.C2 != 0 || (reinterpret_cast<uintptr_t>(p.in_norm) & 3) != 0))
+        return wino_declined("conv_wino: a deferred normalisation needs a single input and an aligned coefficient table");
+    if (p.gn_ws && (p.gn_groups <= 0 || p.Cout % p.gn_groups != 0)) return wino_declined("conv_wino: bad GroupNorm statistics request");
+
+    WinoPlan pl;
+    const long cblocks = (p.Cout + 127) / 128;
+    // ---- the persistent form: levels 8 and 16 force it, level 1 takes it where the layer has at least two items per CU
+    // (PH * QW main + 2 PH edge lanes per staging wave: 60 of 64 in both geometries)
+    if ((lvl == 1 || lvl == 8 || lvl == 16) && wino_geometry(p, 2, pl.g) && pl.g.PH * (pl.g.QW + 2) <= 64 &&
+        (size_t)PS_NBUF * pl.g.PH * pl.g.ROWP <= LDS_LIMIT &&
+        (!p.in_norm || ((p.C1 & 3) == 0 && (reinterpret_cast<uintptr_t>(p.in_norm) & 15) == 0))) {
+        const long nitems = (long)pl.g.tiles_x * pl.g.tiles_y * p.B * cblocks;
+        const long ncu = device_cu_count();
+        if (lvl != 1 || nitems >= 2 * ncu) {
+            pl.form = 8;
+            // the 16x16x32 form needs an even number of 16-channel chunks per item (its K = 32 is a pair of chunks; an odd count would span
+            // two items); level 16 forces it where it applies, level 1 takes it per class of launch, level 8 never
+            const int cls = !p.in_norm ? 0 : (p.in_slope < 0.f ? 2 : 1);
+            pl.m16 = (pl.g.nchunk & 1) == 0 && (lvl == 16 || (lvl == 1 && WINO_M16_CLASS[cls][pl.g.TW == 32 ? 0 : 1]));
+            pl.lds_bytes = (size_t)PS_NBUF * pl.g.PH * pl.g.ROWP;
+            const long nwg = ncu < ((nitems + 7) & ~7L) ? ncu : ((nitems + 7) & ~7L);      // one workgroup per CU, a multiple of the 8 XCDs
+            pl.grid = dim3((unsigned)nwg);
+            pl.block = dim3(512);
+            return pl;
+        }
+    }
+    if (lvl == 8) return wino_declined("conv_wino: the forced persistent form does not take this geometry");
+    // ---- the one-tile form: NTW 2 (two workgroups per CU) unless level 4 forces NTW 4 -- level 1 never picks NTW 4
+    const int ntw = lvl == 4 ? 4 : 2;
+    if (!wino_geometry(p, ntw, pl.g)) return wino_declined("conv_wino: H or W is not a multiple of the tile");
+    // two V buffers and, behind them, the deferred norm's {mean, scale, shift} table of one sample
+    pl.lds_bytes = (size_t)2 * pl.g.PH * pl.g.ROWP + (p.in_norm ? (size_t)3 * pl.g.nchunk * W_CK * sizeof(float) : 0);
+    if (pl.lds_bytes > LDS_LIMIT) return wino_declined("conv_wino: the deferred norm's coefficient table does not fit the LDS beside the tile");
+    pl.form = ntw;
+    pl.grid = dim3((unsigned)(pl.g.tiles_x * pl.g.tiles_y * p.B), (unsigned)cblocks);
+    pl.block = dim3(256);
+    return pl;
+}
+
+template <auto KERNEL>
+int wino_run(const char* family, const ConvParams& p, const WinoPlan& pl, const _Float16* wpk, hipStream_t s) {
+    const double flops = 2.0 * (double)p.B * p.H * p.W * p.Cout * (p.C1 + p.C2) * 9.0;     // algorithmic (direct-form) flops
+    return launch_lds<KERNEL>(family, PK_CONV_WINO, flops, pl.grid, pl.block, pl.lds_bytes, s, p, pl.g, wpk);
+}
+
+int launch_plan(const ConvParams& p, const WinoPlan& pl, const _Float16* wpk, hipStream_t s) {
+    if (!pl.form) { set_error(pl.why); return CF_ERR_ARG; }
+    if (p.gn_ws && !p.gn_prezeroed &&
+        hipMemsetAsync(p.gn_ws, 0, sizeof(double) * 2 * (size_t)p.B * p.gn_groups, s) != hipSuccess) { set_error("conv_wino: memset failed"); return CF_ERR_LAUNCH; }
+    const bool pre = p.in_norm != nullptr;
+    if (pl.form == 8) {
+        const char* ps = "conv_wino (persistent)";
+        if (pl.m16) return pre ? wino_run<conv_wino_ps_kernel<1, 1>>(ps, p, pl, wpk, s) : wino_run<conv_wino_ps_kernel<0, 1>>(ps, p, pl, wpk, s);
+        return pre ? wino_run<conv_wino_ps_kernel<1, 0>>(ps, p, pl, wpk, s) : wino_run<conv_wino_ps_kernel<0, 0>>(ps, p, pl, wpk, s);
+    }
+    if (pl.form == 4) return pre ? wino_run<conv_wino_kernel<4, 1>>("conv_wino", p, pl, wpk, s) : wino_run<conv_wino_kernel<4, 0>>("conv_wino", p, pl, wpk, s);
+    return pre ? wino_run<conv_wino_kernel<2, 1>>("conv_wino", p, pl, wpk, s) : wino_run<conv_wino_kernel<2, 0>>("conv_wino", p, pl, wpk, s);
 }
 
 }  // namespace
 
-// Cout: whole 128-channel blocks, or a last block at least three quarters full (the U-Net's 480), as conv_f16s' 128-channel shapes
-// 0 = not a Winograd layer, else the kernel form wino_pick_ntw chooses (2 / 4 / 8)
-static int conv_wino_form(const ConvParams& p) {
-    if (!wino_enabled()) return 0;
-    if (conv_terms() != 3) return 0;       // the one-term ("mixed precision") product mode is built in conv_f16s.hip only
-    if (p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad_h != 1 || p.pad_w != 1 || p.w_bstride || p.scatter2x2) return 0;
-    if (!(p.Cout % 128 == 0 || (p.Cout > 128 && p.Cout % 128 >= 96))) return 0;
-    if (p.W < 16 || (p.W & 15) != 0) return 0;
-    if (((reinterpret_cast<uintptr_t>(p.x1) | reinterpret_cast<uintptr_t>(p.x2)) & 15) != 0) return 0;
-    const long HW = (long)p.H * p.W;
-    if ((long)p.C1 * HW * 4 >= (1L << 31) || (long)p.C2 * HW * 4 >= (1L << 31)) return 0;
-    if ((long)p.out_ctotal * HW * 4 >= (1L << 30)) return 0;          // 32-bit store offsets, two parking values (kernel epilogue)
-    if (p.in_norm && (p.C2 != 0 || (reinterpret_cast<uintptr_t>(p.in_norm) & 3) != 0)) return 0;
-    if (p.gn_ws && (p.gn_groups <= 0 || p.Cout % p.gn_groups != 0)) return 0;
-    WinoGeom g;
-    return wino_pick_ntw(p, g);
-}
+bool conv_wino_applicable(const ConvParams& p) { return wino_plan(p).form != 0; }
 
-bool conv_wino_applicable(const ConvParams& p) { return conv_wino_form(p) != 0; }
-
-int launch_conv_wino(const ConvParams& p, const _Float16* wpk, hipStream_t s) {
-    WinoGeom g;
-    const int ntw = wino_pick_ntw(p, g);
-    if (!ntw) { set_error("conv_wino: layer shape not supported"); return CF_ERR_ARG; }
-    if (p.gn_ws && !p.gn_prezeroed &&
-        hipMemsetAsync(p.gn_ws, 0, sizeof(double) * 2 * (size_t)p.B * p.gn_groups, s) != hipSuccess) { set_error("conv_wino: memset failed"); return CF_ERR_LAUNCH; }
-    if (ntw == 8) {
-        if (wino_mfma16(p, g)) return p.in_norm ? launch_wino_ps<1, 1>(p, g, wpk, s) : launch_wino_ps<0, 1>(p, g, wpk, s);
-        return p.in_norm ? launch_wino_ps<1, 0>(p, g, wpk, s) : launch_wino_ps<0, 0>(p, g, wpk, s);
-    }
-    if (p.in_norm) return ntw == 4 ? launch_wino<4, 1>(p, g, wpk, s) : launch_wino<2, 1>(p, g, wpk, s);
-    return ntw == 4 ? launch_wino<4, 0>(p, g, wpk, s) : launch_wino<2, 0>(p, g, wpk, s);
-}
+int launch_conv_wino(const ConvParams& p, const _Float16* wpk, hipStream_t s) { return launch_plan(p, wino_plan(p), wpk, s); }
 
 }  // namespace cf
 
@@ -1253,13 +1219,23 @@ static void wino_params(ConvParams& p, const float* x1, int C1, const float* x2,
     p.gn_ws = gn_ws; p.gn_groups = gn_groups < 0 ? -gn_groups : gn_groups; p.gn_prezeroed = gn_groups < 0;
 }
 
+// the plan of a shape query (no tensors: an aligned dummy address, never dereferenced).  prenorm: 0 = none, 1 = deferred norm + LeakyReLU,
+// 2 = deferred norm + GELU
+static WinoPlan wino_query(int B, int C1, int C2, int H, int W, int Cout, int prenorm) {
+    if (B <= 0 || C1 <= 0 || C2 < 0 || H <= 0 || W <= 0 || Cout <= 0) return WinoPlan();
+    ConvParams p;
+    float* dummy = reinterpret_cast<float*>(uintptr_t(256));
+    wino_params(p, dummy, C1, C2 ? dummy : nullptr, C2, nullptr, nullptr, dummy, Cout, 0, B, H, W, Cout, CF_ACT_NONE, 1.f, nullptr, 0);
+    if (prenorm) { p.in_norm = dummy; p.in_slope = prenorm == 2 ? -1.f : 0.01f; }
+    return wino_plan(p);
+}
+
 CF_CLOCK_READER(cf_debug_clock_wino, cf::g_clock_wino)
 #ifdef CF_CLOCK_STAMPS
 extern "C" int cf_debug_wino_phases(unsigned long long* out12) {
-    unsigned long long* out8 = out12;
-    unsigned long long z[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const unsigned long long z[12] = {};
     if (hipDeviceSynchronize() != hipSuccess) return CF_ERR_LAUNCH;
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(cf::g_wino_phase), sizeof(z)) != hipSuccess) return CF_ERR_LAUNCH;
+    if (hipMemcpyFromSymbol(out12, HIP_SYMBOL(cf::g_wino_phase), sizeof(z)) != hipSuccess) return CF_ERR_LAUNCH;
     if (hipMemcpyToSymbol(HIP_SYMBOL(cf::g_wino_phase), z, sizeof(z)) != hipSuccess) return CF_ERR_LAUNCH;
     return CF_OK;
 }
@@ -1271,32 +1247,16 @@ extern "C" int cf_conv_wino_enable(int level) {
     return prev;
 }
 
-extern "C" int cf_conv2d_wino_form(int B, int C1, int C2, int H, int W, int Cout, int prenorm) {
-    if (B <= 0 || C1 <= 0 || C2 < 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-    ConvParams p;
-    float* dummy = reinterpret_cast<float*>(uintptr_t(256));      // never dereferenced
-    wino_params(p, dummy, C1, C2 ? dummy : nullptr, C2, nullptr, nullptr, dummy, Cout, 0, B, H, W, Cout, CF_ACT_NONE, 1.f, nullptr, 0);
-    if (prenorm) { p.in_norm = dummy; p.in_slope = 0.01f; }
-    return conv_wino_form(p);
-}
+// the kernel form the dispatch picks for the layer: 0 = not a Winograd layer, 2 / 4 = one tile per workgroup, 8 = persistent
+extern "C" int cf_conv2d_wino_form(int B, int C1, int C2, int H, int W, int Cout, int prenorm) { return wino_query(B, C1, C2, H, W, Cout, prenorm).form; }
 
 // MFMA shape the dispatch picks for the layer: 16 = the persistent kernel's 16x16x32 form, 32 = any other Winograd form, 0 = not a Winograd layer.
-// prenorm: 0 = none, 1 = deferred norm + LeakyReLU, 2 = deferred norm + GELU.
 extern "C" int cf_conv2d_wino_mfma(int B, int C1, int C2, int H, int W, int Cout, int prenorm) {
-    if (B <= 0 || C1 <= 0 || C2 < 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-    ConvParams p;
-    float* dummy = reinterpret_cast<float*>(uintptr_t(256));      // never dereferenced
-    wino_params(p, dummy, C1, C2 ? dummy : nullptr, C2, nullptr, nullptr, dummy, Cout, 0, B, H, W, Cout, CF_ACT_NONE, 1.f, nullptr, 0);
-    if (prenorm) { p.in_norm = dummy; p.in_slope = prenorm == 2 ? -1.f : 0.01f; }
-    const int form = conv_wino_form(p);
-    if (!form) return 0;
-    WinoGeom g;
-    return (wino_pick_ntw(p, g) == 8 && wino_mfma16(p, g)) ? 16 : 32;
+    const WinoPlan pl = wino_query(B, C1, C2, H, W, Cout, prenorm);
+    return !pl.form ? 0 : (pl.m16 ? 16 : 32);
 }
 
-extern "C" int cf_conv2d_wino_ok(int B, int C1, int C2, int H, int W, int Cout, int prenorm) {
-    return cf_conv2d_wino_form(B, C1, C2, H, W, Cout, prenorm) != 0 ? 1 : 0;
-}
+extern "C" int cf_conv2d_wino_ok(int B, int C1, int C2, int H, int W, int Cout, int prenorm) { return wino_query(B, C1, C2, H, W, Cout, prenorm).form != 0 ? 1 : 0; }
 
 extern "C" int cf_conv2d_wino(const float* x1, int C1, const float* x2, int C2, const void* wpk, const float* bias, const float* res, float* out,
                               int out_ctotal, int out_coff, int B, int H, int W, int Cout, int act, float alpha, double* gn_ws, int gn_groups,
@@ -1310,9 +1270,10 @@ extern "C" int cf_conv2d_wino(const float* x1, int C1, const float* x2, int C2, 
     ConvParams p;
     wino_params(p, x1, C1, x2, C2, bias, res, out, out_ctotal, out_coff, B, H, W, Cout, act, alpha, gn_ws, gn_groups);
     CF_REQUIRE(!gn_ws || (p.gn_groups > 0 && Cout % p.gn_groups == 0 && out_coff == 0 && out_ctotal == Cout), "bad GroupNorm statistics request");
-    CF_REQUIRE(conv_wino_applicable(p), "layer shape outside the Winograd kernel (3x3 / stride 1 / pad 1, Cout in whole 128-channel blocks or a last block >= 96, "
-                                        "W %% 16 == 0, H a multiple of the tile rows, 16-byte aligned inputs; cf_conv2d_wino_ok answers per shape)");
-    return launch_conv_wino(p, reinterpret_cast<const _Float16*>(wpk), as_stream(stream));
+    const WinoPlan pl = wino_plan(p);
+    CF_REQUIRE(pl.form != 0, "layer shape outside the Winograd kernel (3x3 / stride 1 / pad 1, Cout in whole 128-channel blocks or a last block >= 96, "
+                             "W %% 16 == 0, H a multiple of the tile rows, 16-byte aligned inputs; cf_conv2d_wino_ok answers per shape): %s", pl.why);
+    return launch_plan(p, pl, reinterpret_cast<const _Float16*>(wpk), as_stream(stream));
 }
 
 extern "C" int cf_conv2d_wino_prenorm(const float* x, int C, const float* in_norm, float in_slope, const void* wpk, const float* bias, float* out,
@@ -1325,6 +1286,7 @@ extern "C" int cf_conv2d_wino_prenorm(const float* x, int C, const float* in_nor
     p.in_norm = in_norm;
     p.in_slope = in_slope;
     CF_REQUIRE(!gn_ws || (p.gn_groups > 0 && Cout % p.gn_groups == 0), "bad GroupNorm statistics request");
-    CF_REQUIRE(conv_wino_applicable(p), "layer shape outside the Winograd kernel (cf_conv2d_wino_ok answers per shape)");
-    return launch_conv_wino(p, reinterpret_cast<const _Float16*>(wpk), as_stream(stream));
+    const WinoPlan pl = wino_plan(p);
+    CF_REQUIRE(pl.form != 0, "layer shape outside the Winograd kernel (cf_conv2d_wino_ok answers per shape): %s", pl.why);
+    return launch_plan(p, pl, reinterpret_cast<const _Float16*>(wpk), as_stream(stream));
 }

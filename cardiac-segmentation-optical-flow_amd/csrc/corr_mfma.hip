@@ -298,13 +298,6 @@ template <int S>
 int launch_corr_mfma(const float* cur, const float* prev, float* out, int B, int C, int H, int W, hipStream_t s) {
     typedef CmGeom<S> G;
     const size_t lds_bytes = (size_t)G::LDS_BYTES;
-    auto kern = corr_volume_mfma_kernel<S>;
-    static bool attr_set[64] = {};
-    const int dev = current_device_slot();
-    if (!attr_set[dev]) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set[dev] = true;
-    }
     const int tiles_x = W / 64, tiles_y = (H / S) / 8;
     const long nt = (long)B * S * tiles_y * tiles_x;
     if (nt >= (1L << 31)) { set_error("corr_volume: too many tiles"); return CF_ERR_ARG; }
@@ -312,14 +305,8 @@ int launch_corr_mfma(const float* cur, const float* prev, float* out, int B, int
     const unsigned nwg = (unsigned)(nt >= ncu ? ncu : ((nt + 7) / 8) * 8);
     const double bytes = 4.0 * (double)B * H * W * (2.0 * C + 81.0);
     const int kid = S == 1 ? PK_CORRVOL_S1 : (S == 2 ? PK_CORRVOL_S2 : PK_CORRVOL_S4);
-    hipEvent_t e0, e1;
-    if (profile_on() && profile_events(kid, bytes, &e0, &e1))
-        hipExtLaunchKernelGGL(kern, dim3(nwg), dim3(CM_THREADS), lds_bytes, s, e0, e1, 0, cur, prev, out, B, C, H, W, tiles_x, tiles_y, (int)nt);
-    else
-        hipLaunchKernelGGL(kern, dim3(nwg), dim3(CM_THREADS), lds_bytes, s, cur, prev, out, B, C, H, W, tiles_x, tiles_y, (int)nt);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("corr_volume (MFMA) launch failed: ") + hipGetErrorString(e)); return CF_ERR_LAUNCH; }
-    return CF_OK;
+    return launch_lds<corr_volume_mfma_kernel<S>>("corr_volume (MFMA)", kid, bytes, dim3(nwg), dim3(CM_THREADS), lds_bytes, s, cur, prev, out, B, C, H, W, tiles_x,
+                                                  tiles_y, (int)nt);
 }
 
 }  // namespace

@@ -37,4 +37,27 @@ static inline void launch_profiled(int kid, double work, K kernel, dim3 grid, di
     }
 }
 
+// The same for a kernel with dynamic LDS, with what every such launcher repeated around it: the kernel's opt-in to the 160 KiB of LDS, once
+// per device (a second GPU driven by the same process needs it too), the timed (kid >= 0) or plain launch, and the launch error turned into
+// "<family> launch failed: ...".  KERNEL is a template argument so that every instantiation has its own opt-in table.  Returns CF_OK / CF_ERR_LAUNCH.
+constexpr size_t LDS_LIMIT = 160 * 1024;
+
+template <auto KERNEL, typename... Args>
+static inline int launch_lds(const char* family, int kid, double work, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, Args... args) {
+    static bool opted_in[64] = {};
+    const int dev = current_device_slot();
+    if (!opted_in[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
+        opted_in[dev] = true;
+    }
+    hipEvent_t e0, e1;
+    if (kid >= 0 && profile_on() && profile_events(kid, work, &e0, &e1))
+        hipExtLaunchKernelGGL(KERNEL, grid, block, lds_bytes, s, e0, e1, 0, args...);
+    else
+        hipLaunchKernelGGL(KERNEL, grid, block, lds_bytes, s, args...);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error(std::string(family) + " launch failed: " + hipGetErrorString(e)); return CF_ERR_LAUNCH; }
+    return CF_OK;
+}
+
 }  // namespace cf

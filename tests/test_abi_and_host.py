@@ -633,6 +633,159 @@ def test_wino_form_query_follows_the_route_level():
         h.cf_conv_wino_enable(prev)
 
 
+# (B, C1, C2, H, W, Cout): few items per CU unless B = 64
+_WINO_PLAN_SHAPES = (
+    (2, 128, 0, 16, 32, 128),
+    (2, 48, 0, 16, 32, 128),        # an odd number of 16-channel chunks: never the 16x16x32 form
+    (2, 20, 28, 16, 32, 128),       # a split input: no deferred norm
+    (2, 64, 0, 16, 32, 224),        # a last block of 96
+    (2, 64, 0, 16, 32, 200),        # a last block of 72: no form
+    (2, 64, 0, 16, 16, 128),        # W = 16: 16-column tiles
+    (2, 64, 0, 16, 48, 128),        # W = 48: no tile width divides it
+    (2, 64, 0, 12, 32, 128),        # H % 8 != 0: no NTW 4
+    (2, 64, 0, 12, 16, 128),        # 16-column tiles are 8 rows high
+    (2, 81, 0, 16, 32, 128),        # C % 4 != 0: the persistent form declines the deferred norm
+    (64, 64, 0, 64, 64, 256),       # enough items for the persistent form at level 1
+    (64, 48, 0, 64, 64, 256),
+    (64, 81, 0, 64, 64, 256),
+    (64, 64, 0, 64, 16, 256),       # GELU-deferred at 16-column tiles: the one class level 1 keeps on 32x32x16
+    (64, 20, 28, 64, 64, 224),
+)
+# route level -> per shape, per prenorm 0 | 1 | 2: (cf_conv2d_wino_form, cf_conv2d_wino_mfma), recorded from the build before wino_plan existed
+_WINO_PLAN_RECORDED = {
+    0: (((0, 0), (0, 0), (0, 0)),) * 15,
+    1: (
+        ((2, 32), (2, 32), (2, 32)),
+        ((2, 32), (2, 32), (2, 32)),
+        ((2, 32), (0, 0), (0, 0)),
+        ((2, 32), (2, 32), (2, 32)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((2, 32), (2, 32), (2, 32)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((2, 32), (2, 32), (2, 32)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((2, 32), (2, 32), (2, 32)),
+        ((8, 16), (8, 16), (8, 16)),
+        ((8, 32), (8, 32), (8, 32)),
+        ((8, 16), (2, 32), (2, 32)),
+        ((8, 16), (8, 16), (8, 32)),
+        ((8, 16), (0, 0), (0, 0)),
+    ),
+    2: (
+        ((2, 32), (2, 32), (2, 32)),
+        ((2, 32), (2, 32), (2, 32)),
+        ((2, 32), (0, 0), (0, 0)),
+        ((2, 32), (2, 32), (2, 32)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((2, 32), (2, 32), (2, 32)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((2, 32), (2, 32), (2, 32)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((2, 32), (2, 32), (2, 32)),
+        ((2, 32), (2, 32), (2, 32)),
+        ((2, 32), (2, 32), (2, 32)),
+        ((2, 32), (2, 32), (2, 32)),
+        ((2, 32), (2, 32), (2, 32)),
+        ((2, 32), (0, 0), (0, 0)),
+    ),
+    4: (
+        ((4, 32), (4, 32), (4, 32)),
+        ((4, 32), (4, 32), (4, 32)),
+        ((4, 32), (0, 0), (0, 0)),
+        ((4, 32), (4, 32), (4, 32)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((4, 32), (4, 32), (4, 32)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((4, 32), (4, 32), (4, 32)),
+        ((4, 32), (4, 32), (4, 32)),
+        ((4, 32), (4, 32), (4, 32)),
+        ((4, 32), (4, 32), (4, 32)),
+        ((4, 32), (4, 32), (4, 32)),
+        ((4, 32), (0, 0), (0, 0)),
+    ),
+    8: (
+        ((8, 32), (8, 32), (8, 32)),
+        ((8, 32), (8, 32), (8, 32)),
+        ((8, 32), (0, 0), (0, 0)),
+        ((8, 32), (8, 32), (8, 32)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((8, 32), (8, 32), (8, 32)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((8, 32), (8, 32), (8, 32)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((8, 32), (0, 0), (0, 0)),
+        ((8, 32), (8, 32), (8, 32)),
+        ((8, 32), (8, 32), (8, 32)),
+        ((8, 32), (0, 0), (0, 0)),
+        ((8, 32), (8, 32), (8, 32)),
+        ((8, 32), (0, 0), (0, 0)),
+    ),
+    16: (
+        ((8, 16), (8, 16), (8, 16)),
+        ((8, 32), (8, 32), (8, 32)),
+        ((8, 16), (0, 0), (0, 0)),
+        ((8, 16), (8, 16), (8, 16)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((8, 16), (8, 16), (8, 16)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((8, 16), (8, 16), (8, 16)),
+        ((0, 0), (0, 0), (0, 0)),
+        ((8, 16), (2, 32), (2, 32)),
+        ((8, 16), (8, 16), (8, 16)),
+        ((8, 32), (8, 32), (8, 32)),
+        ((8, 16), (2, 32), (2, 32)),
+        ((8, 16), (8, 16), (8, 16)),
+        ((8, 16), (0, 0), (0, 0)),
+    ),
+}
+
+
+def test_wino_probes_read_one_plan():
+    """cf_conv2d_wino_ok, cf_conv2d_wino_form and cf_conv2d_wino_mfma read the one plan a launch executes (wino_plan, host code, no launch):
+    ok is `form != 0`, the MFMA shape is 0 exactly where the form is, 16 only on the persistent form, and over shapes x route levels x
+    deferred-norm classes both equal what the dispatch answered before the plan existed."""
+    from cineflow import _lib, ops
+    h = _lib.lib()
+    prev = h.cf_conv_wino_enable(1)
+    try:
+        for level in (0, 1, 2, 4, 8, 16):
+            h.cf_conv_wino_enable(level)
+            for shape, recorded in zip(_WINO_PLAN_SHAPES, _WINO_PLAN_RECORDED[level]):
+                for pre in (0, 1, 2):
+                    form, mfma = ops.wino_form(*shape, prenorm=pre != 0), ops.wino_mfma(*shape, prenorm=pre)
+                    what = (level, shape, pre)
+                    assert ops.wino_ok(*shape, prenorm=pre != 0) == (form != 0), what
+                    assert (mfma == 0) == (form == 0) and mfma in (0, 16, 32) and (mfma != 16 or form == 8), what
+                    assert (form, mfma) == recorded[pre], what
+    finally:
+        h.cf_conv_wino_enable(prev)
+
+
+def test_wino_plan_declines_a_norm_table_past_the_lds():
+    """The one-tile form keeps the deferred norm's {mean, scale, shift} table of 3 * (C / 16) * 16 floats in LDS behind its two V buffers
+    (2 * 6 patch rows * 5120 bytes at 32-column tiles, NTW 2).  C is the smallest multiple of 16 at which the sum passes 160 KiB: the probes
+    accepted that shape (form 2) and the launch then failed with "LDS tile too large"; the plan declines it, and keeps the shape one chunk
+    below.  The persistent form has no table and still takes both when forced."""
+    from cineflow import _lib, ops
+    C = next(c for c in range(16, 1 << 16, 16) if 2 * 6 * 5120 + 3 * (c // 16) * 16 * 4 > 160 * 1024)
+    assert C == 8544
+    h = _lib.lib()
+    prev = h.cf_conv_wino_enable(1)
+    try:
+        for level in (1, 2):
+            h.cf_conv_wino_enable(level)
+            assert ops.wino_form(1, C, 0, 4, 32, 128, prenorm=True) == 0 and not ops.wino_ok(1, C, 0, 4, 32, 128, prenorm=True), level
+            assert ops.wino_mfma(1, C, 0, 4, 32, 128, prenorm=1) == 0, level
+            assert ops.wino_form(1, C - 16, 0, 4, 32, 128, prenorm=True) == 2, level
+            assert ops.wino_form(1, C, 0, 4, 32, 128) == 2, level                  # no deferred norm, no table
+        h.cf_conv_wino_enable(8)
+        assert ops.wino_form(1, C, 0, 4, 32, 128, prenorm=True) == 8
+    finally:
+        h.cf_conv_wino_enable(prev)
+
+
 class _FakeTensor:
     """what the route decisions read of a tensor: its shape, its element count and an aligned address"""
 

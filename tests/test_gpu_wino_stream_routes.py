@@ -1,13 +1,13 @@
-"""Every instantiation of the row-Winograd kernels (csrc/conv_wino.hip: conv_wino_kernel<NTW = 2|4, PRE = 0|1>, conv_wino_ps_kernel<PRE = 0|1>)
+"""Every instantiation of the row-Winograd kernels (csrc/conv_wino.hip: conv_wino_kernel<NTW = 2|4, PRE = 0|1>, conv_wino_ps_kernel<PRE = 0|1, M16 = 0|1>)
 and of the persistent pipelined kernel (csrc/conv_stream.hip: conv_stream_kernel<WM = 1|2, PRE = 0|1>) against a split-exact fp64 reference,
 per output element, at the geometry edges of each form.  No row skips: a row names the forms that must take it, forces each with
 cf_conv_wino_enable(2 | 4 | 8) / cf_conv_stream_enable(2) and asserts the routing (ops.wino_ok and ops.wino_form; the launch counters of cf_profile_read
 tell which family took a launch, a rocprofv3 kernel trace read by tools/kernel_coverage.py tells which instantiation).
 
-Which form takes which map (wino_geometry / wino_pick_ntw).  W must be 16 or a multiple of 32.  W >= 32: tiles of 32 columns x TH rows with
+Which form takes which map (wino_geometry / wino_plan, the one plan the probes read and the launch executes).  W must be 16 or a multiple of 32.  W >= 32: tiles of 32 columns x TH rows with
 TH = 4 (NTW 2 and the persistent kernel) or 8 (NTW 4); W == 16: 16 columns x TH = 8 (NTW 2, persistent) or 16 (NTW 4).  H must be a multiple
 of TH; the staging-task and LDS budgets hold for all of these.  Level 1 (as shipped) takes the persistent kernel from 2 x CUs items (tiles x
-samples x 128-channel blocks), else NTW 2: wino_pick_ntw never chooses NTW 4 by itself, so conv_wino_kernel<4, *> runs only under the
+samples x 128-channel blocks), else NTW 2: wino_plan never chooses NTW 4 by itself, so conv_wino_kernel<4, *> runs only under the
 forced level 4 (CF_CONV_WINO=4 / cf_conv_wino_enable(4)) -- a kernel that is built and tested here but that no shipped route reaches.
 ops.wino_form (cf_conv2d_wino_form) returns the form the dispatch picks; every row asserts it.  The persistent kernel declines a deferred
 normalisation with C % 4 != 0.
@@ -134,7 +134,7 @@ def ps_samples(B, H, W, Cout, ncu):
 
 
 def auto_form(B, H, W, Cout, ncu):
-    """what wino_pick_ntw does at route level 1 for a plain layer: the persistent kernel from two items per CU, else NTW 2 (never NTW 4)"""
+    """what wino_plan does at route level 1 for a plain layer: the persistent kernel from two items per CU, else NTW 2 (never NTW 4)"""
     TW, TH = wino_tile(2, W)
     if W % TW or H % TH:
         return 0
@@ -142,7 +142,7 @@ def auto_form(B, H, W, Cout, ncu):
 
 
 # ------------------------------------------------------------------------------------------------------------------ Winograd, plain
-# forms: the route levels that must take the row (2 / 4: conv_wino_kernel<NTW, 0>, 8: conv_wino_ps_kernel<0>); every other level must decline
+# forms: the route levels that must take the row (2 / 4: conv_wino_kernel<NTW, 0>, 8: conv_wino_ps_kernel<0, 0>); every other level must decline
 # it (test_wino_forms_decline_what_their_geometry_forbids).  groups: fused statistics groups.  All five activations (the ConvGRU gates'
 # sigmoid at Cout = 512 among them), alpha, residual and the sentinel-fenced slice run on every row.
 WRow = namedtuple("WRow", "name forms B C1 C2 H W Cout groups")
@@ -319,7 +319,7 @@ def test_conv_wino_route_as_shipped(dev, row):
 
 
 # ------------------------------------------------------------------------------------------------------------------ Winograd, PRE
-# deferred normalisation: conv_wino_kernel<NTW, 1>, conv_wino_ps_kernel<1>.  gn: groups of the GroupNorm + GELU pass (8 where C % 8 == 0).
+# deferred normalisation: conv_wino_kernel<NTW, 1>, conv_wino_ps_kernel<1, 0>.  gn: groups of the GroupNorm + GELU pass (8 where C % 8 == 0).
 PreRow = namedtuple("PreRow", "name forms B C H W Cout gn")
 WINO_PRE_ROWS = [
     PreRow("c128", (2, 4, 8), 3, 128, 16, 32, 128, 8),
