@@ -913,6 +913,18 @@ static F16sPlan f16s_plan(const ConvParams& p) {
         t.MAXT = 3;
         if (f16s_cout_wide(p.Cout)) t.WM = 4; else t.NTW = 1;
     }
+    // An output map one or two columns wide (up to three for 1x5) gets a tile of up to 128 rows, whose patch -- (TH - 1) * stride + KH rows
+    // of TW + 2 (1x5: TW + 4) columns -- is past the scalar staging budget of every shape (f16s_finish would decline it): such a tile
+    // takes fewer rows until its patch fits.  The lanes past TH * TW idle, as they do on any map smaller than the tile.  Wider tiles
+    // never get here, so no plan that was taken before changes.
+    if (spatial && g.NIMG == 1) {
+        const int nstage = 64 * t.NW, th0 = g.TH;
+        while (g.TH > 1 && (g.PH * g.PW * (CK / 8) + nstage - 1) / nstage > t.MAXT) {
+            --g.TH;
+            g.PH = (g.TH - 1) * p.stride + p.KH;
+        }
+        if (g.TH != th0) g.tiles_y = (p.Ho + g.TH - 1) / g.TH;
+    }
     if (const char* why = f16s_staging(p, t, g)) return f16s_declined(why);
     return f16s_finish(p, t, g);
 }

@@ -46,6 +46,16 @@ ROWS = [
     Row((5, 1, 32, 4, 2, 4, 8, 0, 0, 0), 2, 72, 12, 40, 128, (5, 1), 1, True, 1),    # misaligned input
 ]
 
+# Maps one to three columns wide and taller than the scalar staging budget holds in one tile: f16s_plan gives the tile fewer rows (83 of a
+# 130x1 map at 3x3 / stride 1: two tiles along y, the second part-filled).  Shapes the table above has already; the tile geometry is new.
+NARROW_ROWS = [
+    Row((3, 3, 16, 2, 2, 2, 4, 0, 0, 0), 2, 40, 130, 1, 48, (3, 3), 1, False, 1),    # 130x1: (128 + 2) x 3 records x 2 tasks > 2 x 256
+    Row((3, 3, 16, 1, 1, 2, 4, 0, 0, 0), 2, 40, 70, 2, 20, (3, 3), 1, False, 1),     # 70x2: 64-row tiles, (64 + 2) x 4 x 2 > 512
+    Row((3, 3, 16, 2, 1, 3, 4, 0, 0, 0), 2, 40, 135, 2, 64, (3, 3), 2, False, 1),    # stride 2, 68x1 outputs: (2 x 63 + 3) x 3 x 2 > 3 x 256
+    Row((3, 3, 16, 1, 1, 5, 4, 0, 0, 0), 2, 40, 270, 1, 20, (3, 3), 2, False, 1),    # stride 2, Cout <= 32, 135x1 outputs
+    Row((1, 5, 32, 2, 2, 4, 4, 0, 0, 0), 2, 40, 50, 3, 48, (1, 5), 1, False, 1),     # 1x5 on 50x3: 42 x (3 + 4) x 4 > 4 x 256
+]
+
 # deferred input normalisation (cf_conv2d_f16s_prenorm): 3x3, stride 1, vector staging, one sample per workgroup
 PreRow = namedtuple("PreRow", "tup B C H W Cout")
 PRE_ROWS = [
@@ -67,4 +77,4 @@ CONVT_ROWS = [
 
 
 def row_id(r):
-    return "<%s>" % ",".join(map(str, r.tup)) + ("_view" if getattr(r, "view", False) else "")
+    return "<%s>" % ",".join(map(str, r.tup)) + ("_view" if getattr(r, "view", False) else "") + ("_%dx%d" % (r.H, r.W) if r in NARROW_ROWS else "")

@@ -45,6 +45,8 @@ ROWS = [
                                                                     # two valid depth taps per plane; statistics when a workgroup spans samples
     Row(10, 2, 40, 0, 1, 6, 12, 48, (3, 3, 3), (1, 1, 1), False),    # D = 1: centre tap only
     Row(11, 2, 40, 0, 5, 12, 20, 48, (3, 3, 3), (1, 1, 1), True),    # row 1, input one float into a NaN-fenced buffer
+    Row(12, 2, 40, 0, 5, 12, 20, 48, (3, 3, 3), (2, 1, 1), False),   # depth stride 2 at in-plane stride 1 (BasicResidualBlock3D), odd D
+    Row(13, 2, 40, 0, 4, 12, 20, 48, (3, 3, 3), (2, 1, 1), False),   # the same, even D: the last output plane loses its far tap
 ]
 
 

@@ -42,6 +42,9 @@ fraction of A (>= 216 products per output here): an output that collects a few f
 bar is 2^-13 A (A of the two-pass operands), a quarter of the 2^-11 A that separates the one-term mode from the true operands; the
 measured ratio is printed.
 
+NARROW_ROWS run shapes of the table again on maps one to three columns wide and taller than one tile's staging budget, where f16s_plan
+gives the tile fewer rows: the part-filled tiles and the second tile along y are what those rows add.
+
 Large rows compare only a few samples against the CPU reference: the first, the last and the two on either side of the first
 multi-image workgroup boundary.
 """
@@ -51,7 +54,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _conv_f16s_rows import CONVT_ROWS, PAD, PRE_ROWS, ROWS, row_id
+from _conv_f16s_rows import CONVT_ROWS, NARROW_ROWS, PAD, PRE_ROWS, ROWS, row_id
 from _split_exact import (ACTS, SPLIT_BAR, TORCH_ACT, check_stats, device_input, randn, ratio, samples_of, split_reference, split_w,
                           split_x)
 
@@ -61,7 +64,7 @@ ONE_TERM_BAR = 3 * 2.0 ** -11
 PRE_ONE_TERM_BAR = 2.0 ** -13
 
 
-@pytest.mark.parametrize("row", ROWS, ids=row_id)
+@pytest.mark.parametrize("row", ROWS + NARROW_ROWS, ids=row_id)
 def test_conv_f16s_route(dev, row):
     from cineflow import ops
     B, C, H, W, Cout, (kh, kw), stride = row.B, row.C, row.H, row.W, row.Cout, row.k, row.stride

@@ -160,3 +160,10 @@ def test_conv3d_probe_answers_on_the_host():
         assert not ops.conv3d_f16s_ok(1, 32, 0, 20, 256, 224, 32, (3, 3, 3), (1, 1, 1))
     assert ops.conv3d_f16s_ok(1, 32, 0, 20, 256, 224, 32, (3, 3, 3), (1, 1, 1))
     assert not ops.conv3d_f16s_ok(1, 32, 0, 20, 256, 224, 32, (3, 3, 3), (1, 2, 1))  # unequal in-plane strides
+    # the shapes the probe leaves to the composition (composition_is_faster (a), (b), (c); no geometry), each next to the nearest shape it
+    # takes: the layer table of test_gpu_conv3d_layer_routes.py runs the declined side of these same tuples
+    from _conv3d_layer_refs import PROBE_PAIRS
+    assert len(PROBE_PAIRS) >= 8
+    for what, declined, taken in PROBE_PAIRS:
+        assert h.cf_conv3d_f16s_ok(*declined) == 0, (what, declined)
+        assert h.cf_conv3d_f16s_ok(*taken) == 1, (what, taken)

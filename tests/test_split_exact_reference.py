@@ -1,12 +1,15 @@
 """CPU checks of the row-Winograd split-exact reference (tests/_split_exact.py) that the GPU table test_gpu_wino_stream_routes.py holds
 conv_wino.hip to: the reference itself against an fp64 convolution, the host packing against the reference's operands, and the proof that
-the GPU bar can fail.  No GPU and no built library: pack_conv_weight_wino runs on CPU tensors."""
+the GPU bar can fail; then the same for the composed Conv3d / ConvTranspose layer references (tests/_conv3d_layer_refs.py) that
+test_gpu_conv3d_layer_routes.py holds the layers to.  No GPU and no built library: the host packers run on CPU tensors."""
 import math
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+from _conv3d_layer_refs import (LAYER_ROWS, T_ROWS, composed_reference, host_scales, layer_operands, layer_reference, lrow_id, shifted,
+                                t_host_scales, t_operands, t_reference, t_swaps, trow_id)
 from _split_exact import SPLIT_BAR, randn, ratio, wino_scale, wino_split_reference, wino_split_u, wino_unpack
 
 # B, C1, C2, H, W, Cout: 16-wide maps, two inputs with a split that is not a chunk multiple, a channel tail, three tile columns, one row
@@ -88,3 +91,105 @@ def test_pack_conv_weight_wino_holds_the_reference_operands(Cout, C1, C2):
     U = torch.einsum("pk,ocyk->ocyp", G, w.double()) * 2.0 ** s
     assert bool(((uh + ul - U).abs() <= 2.0 ** -21 * U.abs() + 2.0 ** -25).all())
     assert 512.0 <= float(U.abs().max()) < 1024.0
+
+
+# ---- the composed Conv3d layer reference ------------------------------------------------------------------------------------------------------
+# C, Cout, D, H, W, kernel, stride: every stride pair of the layer table, odd and even depth, no depth taps, one plane
+COMPOSED_SHAPES = [
+    (40, 48, 5, 12, 20, (3, 3, 3), (1, 1, 1)),
+    (40, 48, 5, 13, 11, (3, 3, 3), (2, 2, 2)),
+    (40, 48, 4, 12, 20, (3, 3, 3), (2, 2, 2)),
+    (24, 40, 4, 12, 20, (3, 3, 3), (1, 2, 2)),
+    (24, 40, 5, 12, 20, (3, 3, 3), (2, 1, 1)),
+    (24, 40, 3, 12, 20, (1, 3, 3), (1, 2, 2)),
+    (24, 40, 1, 6, 12, (3, 3, 3), (1, 1, 1)),
+    (24, 40, 5, 9, 7, (3, 1, 1), (1, 1, 1)),
+]
+
+
+def _grid(t, bits):
+    return torch.round(t * 2.0 ** bits) / 2.0 ** bits
+
+
+@pytest.mark.parametrize("shape", COMPOSED_SHAPES, ids=lambda s: "x".join(str(v) for v in s[:5]) + "_k%d%d_s%d%d" % (s[5][0], s[5][1], s[6][0], s[6][1]))
+def test_composed_reference_is_the_3d_reference_when_the_scales_agree(shape):
+    """With one scale exponent for every tap the per-tap sum is the 3-D split_reference of test_gpu_conv3d_routes.py term for term, summed
+    in another order.  On operands from a coarse grid (x in multiples of 2^-10 below 8, w in multiples of 2^-12: every product a multiple
+    of 2^-11 after the 2^s scaling, every partial sum below 2^25, 36 bits) float64 holds every partial sum exactly, so the order cannot
+    matter and the two must agree to the last bit -- y3, y1, A, d3 and z3; the grid still leaves both lo halves non-zero.  On randn
+    operands the orders differ by fp64 rounding alone: 2^-40 A, where the GPU bar is 2^-18 A."""
+    from cineflow import ops
+    from test_gpu_conv3d_routes import split_reference as reference_3d
+    C, Cout, D, H, W, k, st = shape
+    pad = tuple(v // 2 for v in k)
+    conv = lambda a, m: F.conv3d(a, m, stride=st, padding=pad)
+    seed = 31 * sum(shape[:5]) + k[0] + st[0]
+    x = randn(2, C, D, H, W, seed=seed)
+    w = randn(Cout, C, *k, seed=seed + 1) / math.sqrt(C * k[0] * k[1] * k[2])
+    b = randn(Cout, seed=seed + 2)
+    for exact in (True, False):
+        if exact:
+            x, w, b = _grid(x.clamp(-7.5, 7.5), 10), _grid(w, 12), _grid(b, 10)
+        s = ops._scaled_split(w.reshape(Cout, C, -1), 16, 2)[2]
+        want = reference_3d(x, w, b, s, conv)
+        got = composed_reference(x, w, b, (s,) * k[0], st)
+        assert set(got) == set(want)
+        if exact:
+            xh = x.half().float()
+            assert bool(((x - xh) != 0).any()) and bool(((x - xh).half().float() == x - xh).all())
+        for key in want:
+            assert got[key].shape == want[key].shape
+            if exact:
+                assert torch.equal(got[key], want[key]), key
+            else:
+                assert ratio(got[key], want[key], want["A"]) <= 2.0 ** -40, key
+    # two different exponents: the taps' sums carry their own 2^-s (the scaled operands differ, the values do not, outside fp16's subnormals)
+    s2 = (s, s - 2, s)[:k[0]] if k[0] == 3 else (s - 2,)
+    other = composed_reference(x, w, b, s2, st)
+    assert ratio(other["y3"], want["y3"], want["A"]) <= 2.0 ** -20 and ratio(other["true"], want["true"], want["A"]) == 0.0
+
+
+@pytest.mark.parametrize("row", LAYER_ROWS, ids=lrow_id)
+def test_layer_bar_can_fail(row):
+    """what the GPU rows assert of the device output, on the reference alone and on the very inputs of each row: the one-term result, the
+    result without the last input channel, without depth tap 0 (kd = 3 and D > 1) and the result one plane off along depth each miss the
+    2^-18 A bar against y3 somewhere.  A condition on the inputs: a row that does not meet it gets another seed or weight scale."""
+    x, w, b = layer_operands(row)
+    r = layer_reference(row, host_scales(row, w))
+    bar = SPLIT_BAR * r["A"]
+    assert bool((r["A"] > 0).all()) and ratio(r["y3"], r["true"], r["A"]) <= 2.0 ** -20
+    assert ratio(r["y1"], r["y3"], bar) > 1.0
+    assert ratio(r["y3"] - r["d3"], r["y3"], bar) > 1.0
+    if row.k[0] == 3:
+        if row.D > 1:
+            assert ratio(r["y3"] - r["z3"], r["y3"], bar) > 1.0
+        else:
+            assert float(r["z3"].abs().max()) == 0.0
+    if r["y3"].shape[2] > 1:
+        assert ratio(shifted(r["y3"]), r["y3"], bar) > 1.0
+    # the last channel's contribution is exactly what zeroing that channel removes
+    if row.n in (4, 6, 10):
+        x0 = x.clone()
+        x0[:, -1] = 0
+        r0 = composed_reference(x0, w, b, host_scales(row, w), row.stride)
+        assert ratio(r["y3"] - r["d3"], r0["y3"], r["A"]) <= 2.0 ** -40
+
+
+@pytest.mark.parametrize("row", T_ROWS, ids=trow_id)
+def test_transposed_layer_bar_can_fail(row):
+    """the same for the transposed rows: one term, a dropped last input channel, and the two interleaved positions (depth taps of a
+    (2,2,2) kernel, sub-rows / sub-columns of an anisotropic 2-D one) exchanged"""
+    x, w, b = t_operands(row)
+    r = t_reference(row, t_host_scales(row, w))
+    want = (F.conv_transpose3d if row.dims == 3 else F.conv_transpose2d)(x.double(), w.double(), None if b is None else b.double(), stride=row.k)
+    assert float((r["true"] - want).abs().max()) <= 1e-12
+    bar = SPLIT_BAR * r["A"]
+    assert bool((r["A"] > 0).all()) and ratio(r["y3"], r["true"], r["A"]) <= 2.0 ** -20
+    assert ratio(r["y1"], r["y3"], bar) > 1.0
+    assert ratio(r["y3"] - r["d3"], r["y3"], bar) > 1.0
+    if row.dims == 3:
+        assert ratio(shifted(r["y3"]), r["y3"], bar) > 1.0
+    swaps = t_swaps(row, r["y3"])
+    assert bool(swaps) == (row.k[0] == 2 or row.dims == 2)
+    for name, y in swaps.items():
+        assert ratio(y, r["y3"], bar) > 1.0, name
