@@ -80,6 +80,7 @@ SIGNATURES = {
     "cf_crop2d": [P, P, I, I, I, I, I, I, I, P],
     "cf_pad2d": [P, P, I, I, I, I, I, I, I, P],
     "cf_tta_accumulate": [P, P, I, I, I, I, I, I, F, P],
+    "cf_tta_accumulate_window": [P, P, P, I, I, I, I, I, I, I, F, P],
     "cf_flip2d": [P, P, I, I, I, I, I, P],
     "cf_tile_accumulate": [P, P, P, P, I, I, I, I, I, I, I, P],
     "cf_tile_finalize": [P, P, P, P, I, I, I, P],
@@ -140,6 +141,7 @@ SIGNATURES = {
     "cf_label_surface_edt": [P, P, I, I, I, I, P, I, DBL, DBL, DBL, I, P, P, L, P, P],
     "cf_window_attention": [P, P, P, P, I, I, I, I, I, I, I, P],
     "cf_frame_boxes": [P, I, P, I, I, I, P],
+    "cf_crop_windows": [P, P, P, I, I, I, I, I, P],
     "cf_sample_points_2d": [P, P, P, I, I, I, I, I, P],
     "cf_profile_enable": [I],
     "cf_profile_reset": [],

@@ -68,6 +68,19 @@ def _gaussian_on(device, patch_size):
 
 
 # ------------------------------------------------------------------------------------------------ TTA + tiles
+def flip_variants(mirror_axes=(0, 1), do_mirroring=True):
+    """the (flip_h, flip_w) pairs of neural_network.py:596-615, in its order"""
+    variants = [(0, 0)]
+    if do_mirroring:
+        if 1 in mirror_axes:
+            variants.append((0, 1))
+        if 0 in mirror_axes:
+            variants.append((1, 0))
+        if 0 in mirror_axes and 1 in mirror_axes:
+            variants.append((1, 1))
+    return variants
+
+
 def mirror_and_predict_2d(net, x, mirror_axes=(0, 1), do_mirroring=True, mult=None, acc=None, weight=None):
     """SegmentationNetwork._internal_maybe_mirror_and_pred_2D, neural_network.py:573-621 (upstream 4-argument
     semantics).  x [B,C,X,Y] on the GPU; returns the TTA-averaged softmax [B,K,X,Y] (times `mult` [X,Y]).
@@ -79,15 +92,7 @@ def mirror_and_predict_2d(net, x, mirror_axes=(0, 1), do_mirroring=True, mult=No
         acc = torch.zeros((B, net.num_classes, X, Y), dtype=torch.float32, device=x.device)
     n = 2 ** len(mirror_axes) if do_mirroring else 1
     w = 1.0 / n if weight is None else weight
-    variants = [(0, 0)]
-    if do_mirroring:
-        if 1 in mirror_axes:
-            variants.append((0, 1))
-        if 0 in mirror_axes:
-            variants.append((1, 0))
-        if 0 in mirror_axes and 1 in mirror_axes:
-            variants.append((1, 1))
-    for fh, fw in variants:
+    for fh, fw in flip_variants(mirror_axes, do_mirroring):
         xin = x if (fh, fw) == (0, 0) else ops.flip2d(x, fh, fw)
         ops.tta_accumulate(net(xin), acc, fh, fw, w)
     if mult is not None:
@@ -101,6 +106,18 @@ def ensemble_predict_2d(nets, x, mirror_axes=(0, 1), do_mirroring=True, mult=Non
     predict.py:952-960 / :1074-1082 intend), accumulated in one buffer (`acc` [B,K,X,Y], zero-filled, or a fresh one) through
     cf_tta_accumulate with weight 1 / (flips * folds), then times `mult`.  One network: mirror_and_predict_2d, operation for operation."""
     nets = list(nets) if isinstance(nets, (list, tuple)) else [nets]
+    if hasattr(nets[0], "accumulate_tta_batch"):
+        # MTLmodel segmenters (cineflow.mtl): each fold crops, predicts and un-crops on the device; the windows come from the first fold's
+        # Processor once per batch and serve every fold
+        if acc is None:
+            acc = torch.zeros((x.shape[0], nets[0].num_classes) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+        flips = len(flip_variants(mirror_axes, do_mirroring))
+        windows = None
+        for net in nets:
+            windows = net.accumulate_tta_batch(x, acc, 1.0 / (flips * len(nets)), mirror_axes, do_mirroring, windows=windows)
+        if mult is not None:
+            ops.mul(acc, mult, out=acc)
+        return acc
     if len(nets) == 1 and acc is None:
         return mirror_and_predict_2d(nets[0], x, mirror_axes, do_mirroring, mult)
     B, _, X, Y = x.shape
@@ -292,10 +309,10 @@ class Processor:
         # a constant frame has std 0: monai's NormalizeIntensity then divides by 1 (-> all zeros), the kernel's 0 * inf is NaN.  Every
         # z-scored frame that is not finite is such a frame: it becomes zeros, which is also what keeps the all-zero frame out of the batch
         const = ~torch.isfinite(flat.view(T, -1)[:, 0])
-        x[const | ~nonempty] = 0
+        x.masked_fill_((const | ~nonempty).view(T, 1, 1, 1), 0.0)                 # (a mask on the device: nothing is read back)
         logits = self.cropping_network(x)["pred"]
         lab = ops.argmax_channels(logits.contiguous())                            # softmax is monotone: argmax of the logits
-        lab[~nonempty] = 0
+        lab.masked_fill_(~nonempty.view(T, 1, 1), 0)
         return lab
 
     # -- processor.py:140-160

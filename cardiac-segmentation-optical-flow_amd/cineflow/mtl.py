@@ -285,6 +285,7 @@ class MTLmodel(Module):
         in_dims, out_encoder_dims, conv_depth = list(in_dims), list(out_encoder_dims), list(conv_depth)
         self.num_classes, self.image_size = num_classes, image_size
         self._processor = processor
+        self.normalize = False                              # accumulate_tta_batch's default: plans['seg_net']['normalize'] of a model folder
         self.d_model = out_encoder_dims[-1] * 2
         self.encoder = Encoder(conv_depth, in_dims, out_encoder_dims)
         dec_depth = [x // 2 for x in conv_depth[::-1]] if asymmetric_unet else conv_depth[::-1]
@@ -321,13 +322,63 @@ class MTLmodel(Module):
                 pads.append(p)
             x = torch.cat(crops, dim=0)
         if normalize:
-            x = x.contiguous().clone()
-            flat = x.view(x.shape[0], 1, -1)
-            ops.group_norm(flat, None, None, 1, eps=0.0, out=flat)
-        net = type("_", (), {"num_classes": self.num_classes, "__call__": lambda s, t: self(t)["pred"]})()
-        out = mirror_and_predict_2d(net, x.contiguous(), mirror_axes, do_mirroring, None)
+            x = _zscore_samples_(x.contiguous().clone())
+        out = mirror_and_predict_2d(_LogitsOf(self), x.contiguous(), mirror_axes, do_mirroring, None)
         if pads is not None:
             out = torch.stack([proc.uncrop_no_registration(out[b].contiguous(), pads[b]) for b in range(out.shape[0])], dim=0)
         if mult is not None:
             ops.mul(out, mult, out=out)
         return out
+
+    # -- the same wrapper for a whole device batch (the tiles of the cine-batched sliding window), nothing read back to the host
+    def crop_windows_of(self, x):
+        """x [B,1,H,W] on the device -> (windows int32 [B,4], jobs int32 [B,3]) on the device: ONE Processor.discretize call on the whole
+        batch (T as the batch: per-sample z-score, all-zero samples skipped -- what MTL_model.py:870-872 does sample by sample), then
+        cf_crop_windows = get_mean_centroid of each sample on its own + adjust_cropping_window."""
+        proc = self._processor
+        return ops.crop_windows(proc.discretize(x), proc.crop_size, proc.image_size)
+
+    def accumulate_tta_batch(self, x, acc, weight, mirror_axes=(0, 1), do_mirroring=True, normalize=None, windows=None):
+        """acc [B,K,H,W] += weight * (every flip's softmax of x [B,1,H,W]); `acc` and `weight` as in inference.mirror_and_predict_2d.
+        With a Processor: crop_windows_of (or the caller's `windows`, which the folds of an ensemble share: the cropper is one fixed
+        network, nnMTLTrainerV2.py:598-604), one cf_tile_gather for the crops, the per-sample z-score when `normalize` (None: the model's
+        own `normalize` attribute), one network call per flip at B, and cf_tta_accumulate_window per flip straight into each sample's window
+        of acc -- zero outside it when acc started as zeros (uncrop_no_registration's F.pad).  Without a Processor it is
+        inference.mirror_and_predict_2d.  Returns the (windows, jobs) pair used, or None."""
+        from .inference import flip_variants, mirror_and_predict_2d
+        normalize = self.normalize if normalize is None else normalize
+        x = x.contiguous()
+        if self._processor is None:
+            if normalize:
+                x = _zscore_samples_(x.clone())
+            mirror_and_predict_2d(_LogitsOf(self), x, mirror_axes, do_mirroring, None, acc=acc, weight=weight)
+            return None
+        c = self._processor.crop_size
+        windows = self.crop_windows_of(x) if windows is None else windows
+        crops = ops.tile_gather(x, windows[1], c, c)                           # a fresh buffer: normalised in place
+        if normalize:
+            _zscore_samples_(crops)
+        for fh, fw in flip_variants(mirror_axes, do_mirroring):
+            xin = crops if (fh, fw) == (0, 0) else ops.flip2d(crops, fh, fw)
+            ops.tta_accumulate_window(self(xin)["pred"], windows[0], acc, fh, fw, weight)
+        return windows
+
+
+class _LogitsOf:
+    """MTLmodel behind the interface of inference.mirror_and_predict_2d: net(x) = logits, net.num_classes"""
+
+    def __init__(self, model):
+        self.model, self.num_classes = model, model.num_classes
+
+    def __call__(self, x):
+        return self.model(x)["pred"]
+
+
+def _zscore_samples_(x):
+    """NormalizeIntensity per sample of x [B,1,h,w], in place (cf_group_norm: one group, eps 0, population std).  A constant sample has
+    std 0: monai then subtracts the mean alone (zeros) where the kernel's 0 * inf is NaN -- such a sample becomes zeros, as in
+    Processor.discretize, by a mask on the device."""
+    flat = x.view(x.shape[0], 1, -1)
+    ops.group_norm(flat, None, None, 1, eps=0.0, out=flat)
+    x.masked_fill_(~torch.isfinite(flat[:, 0, 0]).view(-1, 1, 1, 1), 0.0)
+    return x

@@ -908,6 +908,20 @@ def tta_accumulate(logits, acc, flip_h, flip_w, weight):
     return acc
 
 
+def tta_accumulate_window(logits, windows, acc, flip_h, flip_w, weight):
+    """logits [B,K,c,c] of one flip variant, windows: device int32 [B,4] (crop_windows), acc [B,K,H,W]: acc[b][:, window b] += weight *
+    flip(softmax(logits[b])); nothing outside the windows is touched (bits of tta_accumulate into a crop-sized buffer + pad2d inside)."""
+    B, K, c, c2 = logits.shape
+    if not isinstance(windows, torch.Tensor) or not windows.is_cuda or windows.dtype != torch.int32 or not windows.is_contiguous() \
+            or tuple(windows.shape) != (B, 4):
+        raise TypeError("windows must be a contiguous CUDA int32 tensor [B,4]")
+    assert c == c2 and acc.dim() == 4 and acc.shape[:2] == (B, K), (logits.shape, acc.shape)
+    H, W = acc.shape[2:]
+    check(lib().cf_tta_accumulate_window(_f32(logits), windows.data_ptr(), _f32(acc), B, K, c, H, W, int(flip_h), int(flip_w), float(weight),
+                                         _stream()), "cf_tta_accumulate_window")
+    return acc
+
+
 def flip2d(src, flip_h, flip_w):
     H, W = src.shape[-2:]
     N = src.numel() // (H * W)
@@ -1008,6 +1022,18 @@ def frame_boxes(x):
     boxes = torch.empty((N, 4), dtype=torch.int32, device=x.device)
     check(lib().cf_frame_boxes(x.data_ptr(), int(x.dtype == torch.float32), boxes.data_ptr(), N, H, W, _stream()), "cf_frame_boxes")
     return boxes
+
+
+def crop_windows(labels, crop, image):
+    """labels uint8 [N,H,W] on the device -> (windows int32 [N,4] = (x_low, x_high, y_low, y_high), jobs int32 [N,3] = (n, y_low, x_low)):
+    Processor.get_mean_centroid of each map on its own + adjust_cropping_window, on the device; `jobs` is tile_gather's job table."""
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        raise TypeError("labels must be a contiguous CUDA uint8 tensor [N,H,W]")
+    N, H, W = labels.shape
+    windows = torch.empty((N, 4), dtype=torch.int32, device=labels.device)
+    jobs = torch.empty((N, 3), dtype=torch.int32, device=labels.device)
+    check(lib().cf_crop_windows(labels.data_ptr(), windows.data_ptr(), jobs.data_ptr(), N, H, W, int(crop), int(image), _stream()), "cf_crop_windows")
+    return windows, jobs
 
 
 def sample_points(field, pts):

@@ -27,7 +27,11 @@ A folder of nnUNetTrainerV2_ResencUNet (or its _DA3 variant) -- recognised by nu
 trainer's name -- gets seg_net.arch = 'resenc': the residual-encoder U-Net (FabiansUNet3D).  The decoder tensors the reference registers
 twice are checked for equality and kept once.  Its BatchNorm variants (_BN trainers, running statistics in the checkpoint) are refused.
 
-Command line:  python -m cineflow.reference_models -s SEG [-w FLOW] -o OUT [--crop_weights F --crop_config Y] [-f FOLDS] [-chk NAME]
+A folder of nnMTLTrainerV2 -- recognised by its trainer's name -- is imported with `--seg_config` (the trainer's YAML) and without `-w` as a
+seg_net.arch = 'mtl' folder: the fork's own MTLmodel segmenter, behind the 2-class MTLmodel cropper when the YAML sets `cropper: true`
+(`--crop_weights`, `--crop_config` are then required).
+
+Command line:  python -m cineflow.reference_models -s SEG [-w FLOW] -o OUT [--seg_config Y] [--crop_weights F --crop_config Y] [-f FOLDS] [-chk NAME]
 """
 import argparse
 import os
@@ -352,7 +356,7 @@ def _trainer_info(fold_dir, checkpoint_name):
 
 
 def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, crop_weights=None, crop_config=None, folds=None,
-                                  checkpoint_name="model_final_checkpoint", crop_size=None, image_size=None, window_size=None):
+                                  checkpoint_name="model_final_checkpoint", crop_size=None, image_size=None, window_size=None, seg_config=None):
     """seg_folder: output folder of a 2-D nnU-Net trainer (plans.pkl, fold_X/); flow_weight_folder: the `-w` folder of run_training.py
     (config.yaml, <task>/fold_X/) or its <task> folder; crop_weights / crop_config: optionally the MTLmodel cropper's checkpoint and its
     YAML (nnMTLTrainerV2FlowSuccessive.py:482-484, adversarial_acdc.yaml).  Writes `out_folder` in the plans.json format (save_model_folder):
@@ -368,11 +372,19 @@ def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, cr
     from . import config as C
     if not os.path.isfile(join(seg_folder, "plans.pkl")):
         raise FileNotFoundError("%s has no plans.pkl (not the output folder of an nnU-Net trainer)" % seg_folder)
+    first = _checkpoint_folds(seg_folder, checkpoint_name)
+    info = _trainer_info(first[sorted(first)[0]], checkpoint_name) if first else None
+    if _MTL_TRAINER in str((info or {}).get("name") or ""):
+        if flow_weight_folder is not None:
+            raise ValueError("%s was written by %s (an MTLmodel segmenter) and cannot be paired with a flow folder (-w %s): MTLmodel next to "
+                             "the flow network is not built.  Import it on its own (no -w)." % (seg_folder, info["name"], flow_weight_folder))
+        return _import_mtl_folder(seg_folder, out_folder, seg_config, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size,
+                                  window_size)
+    if seg_config is not None:
+        raise ValueError("seg_config is the YAML of an %s folder; %s was written by %r" % (_MTL_TRAINER, seg_folder, (info or {}).get("name")))
     if flow_weight_folder is None:
         return _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size,
                                          window_size)
-    first = _checkpoint_folds(seg_folder, checkpoint_name)
-    info = _trainer_info(first[sorted(first)[0]], checkpoint_name) if first else None
     if _stage_is_3d(load_reference_pickle(join(seg_folder, "plans.pkl")), info["init"][5] if info and len(info.get("init") or ()) > 5 else None):
         raise ValueError("%s is a 3-D segmentation folder (3-entry patch_size) and cannot be paired with a flow folder (-w %s): the flow path "
                          "is 2-D.  Import it on its own (no -w)." % (seg_folder, flow_weight_folder))
@@ -540,6 +552,93 @@ def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config,
     return plans
 
 
+_MTL_TRAINER = "nnMTLTrainerV2"
+
+
+def mtl_window_size(image_size):
+    """nnMTLTrainerV2.py:121, value for value (None: the rule knows no window for that image size)"""
+    return {224: 7, 288: 9, 384: 8, 192: 8}.get(int(image_size))
+
+
+def mtl_crop_size(task):
+    """the crop size of nnMTLTrainerV2.py:110-117 from the task folder's name (31 / 35 -> 128, else 192); the image and window sizes of
+    those lines are overwritten at :120-121 and play no part"""
+    return 128 if any(x in task for x in ("31", "35")) else 192
+
+
+def _import_mtl_folder(seg_folder, out_folder, seg_config, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size, window_size):
+    """A folder of nnMTLTrainerV2 (the trainer's name in `.model.pkl`) -> a seg_net.arch = 'mtl' folder.  seg_config: the trainer's YAML
+    (seg_model.yaml; the copy nnMTLTrainerV2.py:488 writes as config.yaml into its log folder).  image_size = config['patch_size'][0];
+    window_size by the rule of :121; with config['cropper'] the crop size by the task rule of :110-117, and the cropper's checkpoint and
+    YAML are required (the trainer reads them from its working directory, :107, :601).  crop_size / image_size / window_size override the
+    rules.  Every tensor of every fold and of the cropper is checked against the networks the new plans build before anything is written."""
+    from . import config as C
+    seg_folds = _checkpoint_folds(seg_folder, checkpoint_name)
+    if folds is None or folds == "None":
+        if not seg_folds:
+            raise ValueError("the segmentation folder %s holds no fold_X/%s.model" % (seg_folder, checkpoint_name))
+        folds = sorted(seg_folds)
+    folds = [int(f) for f in ([folds] if isinstance(folds, (int, str)) else folds)]
+    for f in folds:
+        if f not in seg_folds:
+            raise FileNotFoundError("fold_%d/%s.model is missing from the segmentation folder %s" % (f, checkpoint_name, seg_folder))
+    info = _trainer_info(seg_folds[folds[0]], checkpoint_name)
+    init = tuple(info.get("init") or ())
+    if seg_config is None:
+        raise ValueError("%s was written by %s: pass seg_config (--seg_config) -- the YAML the trainer was configured with, which it copies "
+                         "as config.yaml into its log folder (nnMTLTrainerV2.py:488)" % (seg_folder, info["name"]))
+    if len(init) > 9 and init[9]:
+        raise NotImplementedError("%s: the trainer was built with binary = True, which is outside what the build implements" % seg_folder)
+    cfg = C.read_config(seg_config, False, False)
+    if cfg.get("unlabeled"):
+        raise NotImplementedError("%s: unlabeled = true (ModelWrap(net1, net2)) is outside what the build implements" % seg_config)
+    stage = init[5] if len(init) > 5 else None
+    plans = plans_from_reference(load_reference_pickle(join(seg_folder, "plans.pkl")), stage)
+    im = int(image_size or cfg["patch_size"][0])
+    win = window_size or mtl_window_size(im)
+    if win is None:
+        raise ValueError("nnMTLTrainerV2.py:121 has no window_size for image_size %d (224 -> 7, 288 -> 9, 384 / 192 -> 8): pass window_size" % im)
+    plans.update(image_size=im, patch_size=[im, im])
+    plans["seg_net"] = {"arch": "mtl", "config": cfg, "window_size": int(win), "normalize": False}
+    cropper = bool(cfg.get("cropper"))
+    if cropper:
+        if crop_weights is None or crop_config is None:
+            raise ValueError("%s sets cropper: true: crop_weights and crop_config (--crop_weights, --crop_config) are required -- the "
+                             "2-class MTLmodel's checkpoint and its YAML (adversarial_acdc.yaml), which the trainer reads from its working "
+                             "directory (nnMTLTrainerV2.py:107, :601)" % seg_config)
+        task = os.path.basename(str(init[3]).rstrip("/\\")) if len(init) > 3 and init[3] else ""
+        plans["crop_size"] = int(crop_size or mtl_crop_size(task))
+        plans["cropping_net"] = {"type": "mtl", "config": C.read_config(crop_config, False, False), "window_size": int(win)}
+    elif crop_weights is not None or crop_config is not None or crop_size is not None:
+        raise ValueError("%s sets cropper: false: crop_weights / crop_config / crop_size make no sense without the cropping network" % seg_config)
+    trainer = CineTrainer(plans, torch.device("cpu"))                           # the networks' key / shape lists, no device work
+    crop_sd = None
+    if cropper:
+        shapes = trainer.crop_net.state_shapes()
+        crop_sd = load_reference_checkpoint(crop_weights, shapes)["state_dict"]
+        check_state_dict(crop_sd, shapes, "cropping network %s" % crop_weights)
+        crop_sd = {k: v for k, v in crop_sd.items() if not k.endswith(_DERIVED_BUFFERS)}
+    params = {}
+    for f in folds:                                                             # every tensor of every fold is checked before anything is written
+        path = join(seg_folds[f], checkpoint_name + ".model")
+        shapes = trainer.seg_net.state_shapes()
+        sd = load_reference_checkpoint(path, shapes)["state_dict"]
+        check_state_dict(sd, shapes, "segmentation network %s" % path)
+        params[f] = {k: v for k, v in sd.items() if not k.endswith(_DERIVED_BUFFERS)}
+    os.makedirs(out_folder, exist_ok=True)
+    shutil.copy(seg_config, join(out_folder, "seg_config.yaml"))
+    plans["seg_net"]["config"] = "seg_config.yaml"
+    if cropper:
+        shutil.copy(crop_config, join(out_folder, "cropping_config.yaml"))
+        plans["cropping_net"]["config"] = "cropping_config.yaml"
+    for f in folds:
+        save_model_folder(out_folder, trainer.seg_net, None, plans, fold=f, checkpoint_name=checkpoint_name, seg_sd=params[f], flow_sd=None,
+                          crop_sd=crop_sd)
+    if os.path.isfile(join(seg_folder, "postprocessing.json")):
+        shutil.copy(join(seg_folder, "postprocessing.json"), join(out_folder, "postprocessing.json"))
+    return plans
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description="Write a cineflow model folder (plans.json + fold_X/<chk>.model) from the folders the "
                                                  "reference's trainers wrote; predict_from_folder / cineflow.predict -m take it unchanged.")
@@ -550,6 +649,8 @@ def main(argv=None):
     parser.add_argument("-o", "--output_folder", required=True)
     parser.add_argument("--crop_weights", default=None, help="the MTLmodel cropper's model_final_checkpoint.model")
     parser.add_argument("--crop_config", default=None, help="the cropper's YAML (adversarial_acdc.yaml)")
+    parser.add_argument("--seg_config", default=None, help="for a folder of nnMTLTrainerV2: the trainer's YAML (seg_model.yaml / the config.yaml "
+                                                           "it wrote into its log folder); the folder is then imported as an MTLmodel segmenter, without -w")
     parser.add_argument("-f", "--folds", nargs="+", default="None")
     parser.add_argument("-chk", default="model_final_checkpoint", required=False)
     parser.add_argument("--crop_size", type=int, default=None)
@@ -557,8 +658,11 @@ def main(argv=None):
     parser.add_argument("--window_size", type=int, default=None)
     a = parser.parse_args(argv)
     plans = import_reference_model_folder(a.seg_folder, a.flow_weight_folder, a.output_folder, a.crop_weights, a.crop_config,
-                                          None if a.folds == "None" else a.folds, a.chk, a.crop_size, a.image_size, a.window_size)
-    if "flow_net" not in plans:
+                                          None if a.folds == "None" else a.folds, a.chk, a.crop_size, a.image_size, a.window_size, a.seg_config)
+    if plans["seg_net"].get("arch") == "mtl":
+        print("wrote %s (MTLmodel segmenter, image %d, crop %s, window %d, %d classes)" % (a.output_folder, plans["image_size"], plans.get("crop_size"),
+                                                                                        plans["seg_net"]["window_size"], plans["num_classes"]))
+    elif "flow_net" not in plans:
         print("wrote %s (segmentation only, patch %s, %d classes)" % (a.output_folder, plans["patch_size"], plans["num_classes"]))
     else:
         print("wrote %s (crop %d, image %d, %d classes)" % (a.output_folder, plans["crop_size"], plans["image_size"], plans["num_classes"]))

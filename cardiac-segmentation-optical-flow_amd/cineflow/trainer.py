@@ -112,7 +112,11 @@ class CineTrainer:
     preprocess_patient appends the previous stage's labels as one-hot channels.  3-D segmentation-only models alone.
     plans['seg_net']['arch'] = 'resenc' (with num_blocks_encoder / num_blocks_decoder, and a pool_op_kernel_sizes list that starts with the
     first stage's stride [1, 1, 1]) makes the network the residual-encoder U-Net of nnUNetTrainerV2_ResencUNet (FabiansUNet3D): 3-D
-    segmentation-only models alone, never a cascade stage."""
+    segmentation-only models alone, never a cascade stage.
+    plans['seg_net'] = {'arch': 'mtl', 'config': <seg_model.yaml values or file name>, 'window_size': 7, 'normalize': false} makes the network
+    the fork's own MTLmodel (nnMTLTrainerV2): 2-D segmentation-only models alone, patch_size = [image_size, image_size]; built at
+    crop_size behind the Processor when the plans hold a cropping_net, at image_size without one (nnMTLTrainerV2.py:598-610); every
+    fold's segmenter shares the one Processor, and tile batches go through MTLmodel.accumulate_tta_batch (inference.ensemble_predict_2d)."""
 
     def __init__(self, plans, device, model_folder=None):
         self.plans = plans
@@ -123,9 +127,11 @@ class CineTrainer:
         fk = plans.get("flow_net")
         self.seg_dim = int((plans.get("seg_net") or {}).get("dim", 2))
         arch = (plans.get("seg_net") or {}).get("arch")
-        if arch is not None:
+        if arch == "mtl":
+            _check_mtl_plans(plans, self.seg_dim, fk)
+        elif arch is not None:
             if arch != "resenc":
-                raise ValueError("seg_net.arch must be 'resenc' (the residual-encoder U-Net) or absent (Generic_UNet), got %r" % (arch,))
+                raise ValueError("seg_net.arch must be 'resenc' (the residual-encoder U-Net), 'mtl' (MTLmodel) or absent (Generic_UNet), got %r" % (arch,))
             if self.seg_dim != 3:
                 raise ValueError("plans.json holds seg_net.arch == 'resenc' with seg_net.dim == %d: the residual-encoder U-Net is built in 3-D "
                                  "only (the reference's 2-D branch cannot be built either)" % self.seg_dim)
@@ -153,7 +159,9 @@ class CineTrainer:
         self.seg_arch = arch
         self.model_folder = model_folder
         # (a segmentation-only model has no heart-centred crop: no Processor)
-        self.processor = Processor(crop_size=plans["crop_size"], image_size=plans["patch_size"][0]) if (fk or "crop_size" in plans) else None
+        # (an MTLmodel segmenter crops only with a cropping network: nnMTLTrainerV2.py:598-606 builds no Processor without one)
+        has_crop = (fk or "crop_size" in plans) and not (arch == "mtl" and not plans.get("cropping_net"))
+        self.processor = Processor(crop_size=plans["crop_size"], image_size=plans["patch_size"][0]) if has_crop else None
         # mixed_precision of load_model_and_checkpoint_files / predict_from_folder (the reference's default True): with CF_SEG_MIXED_PRECISION=1
         # the segmentation U-Net runs its convolutions in the one-term fp16 product mode (ops.conv_terms(1)), like the reference's autocast on
         # that path (neural_network.py:140-146); the flow network never does (SegFlowGaussian.py:2905-2909).  Default: flag accepted, f32-class.
@@ -187,6 +195,14 @@ class CineTrainer:
 
     def _new_seg_net(self):
         sk = self.plans["seg_net"]
+        if self.seg_arch == "mtl":      # nnMTLTrainerV2.py:608-610: MTLmodel at the crop size behind a Processor, at the image size without one
+            from . import config as C
+            cfg = _config_values(sk["config"], self.model_folder, lambda f: C.read_config(f, False, False))
+            size = self.plans["crop_size"] if self.processor is not None else self.plans["image_size"]
+            net = C.build_2d_model(cfg, conv_layer=None, norm=None, log_function=None, image_size=size, window_size=sk["window_size"],
+                                   middle=False, num_classes=self.num_classes, processor=self.processor)
+            net.normalize = bool(sk.get("normalize", False))
+            return net
         if self.seg_arch == "resenc":   # nnUNetTrainerV2_ResencUNet: FabiansUNet with conv_op = nn.Conv3d, at most 320 filters
             return FabiansUNet3D(self.plans["num_modalities"], sk["base_num_features"], sk["num_blocks_encoder"], sk["pool_op_kernel_sizes"],
                                  sk["conv_kernel_sizes"], self.num_classes, sk["num_blocks_decoder"])
@@ -267,7 +283,7 @@ class CineTrainer:
             if self.seg_dim == 3:
                 seg, prob = self._predict_volume_3d(data, step_size, do_mirroring, mirror_axes, use_gaussian, pad_border_mode, pad_kwargs)
                 return seg.cpu().numpy(), prob.cpu().numpy()
-            if len(self.seg_nets) == 1:
+            if len(self.seg_nets) == 1 and self.seg_arch != "mtl":
                 return predict_3D_2Dconv_tiled(self.seg_net, data, self.patch_size, step_size=step_size, do_mirroring=do_mirroring,
                                                mirror_axes=mirror_axes, use_gaussian=use_gaussian, pad_border_mode=pad_border_mode,
                                                pad_kwargs=pad_kwargs)
@@ -452,6 +468,28 @@ class CineTrainer:
             torch.cuda.synchronize()
             DEVICE_SPLIT["finish_s"] = DEVICE_SPLIT.get("finish_s", 0.0) + time.perf_counter() - t2
         return res
+
+
+def _check_mtl_plans(plans, seg_dim, flow_net):
+    """plans['seg_net']['arch'] == 'mtl' (the segmenter nnMTLTrainerV2 trains): what the plans must not hold next to it"""
+    sk = plans["seg_net"]
+    if seg_dim != 2:
+        raise ValueError("plans.json holds seg_net.arch == 'mtl' with seg_net.dim == %d: MTLmodel is a 2-D network" % seg_dim)
+    if flow_net:
+        raise ValueError("plans.json holds both seg_net.arch == 'mtl' and flow_net: MTLmodel next to the flow network is not built (an "
+                         "MTLmodel folder is segmentation-only)")
+    if sk.get("prev_stage_classes") is not None:
+        raise ValueError("plans.json holds both seg_net.arch == 'mtl' and seg_net.prev_stage_classes: the reference has no cascade trainer "
+                         "for MTLmodel")
+    if "image_size" not in plans or list(plans["patch_size"]) != [plans["image_size"], plans["image_size"]]:
+        raise ValueError("seg_net.arch == 'mtl' needs patch_size == [image_size, image_size] (nnMTLTrainerV2 predicts on the whole "
+                         "image_size square), got patch_size %r and image_size %r" % (plans["patch_size"], plans.get("image_size")))
+    if plans.get("cropping_net") and "crop_size" not in plans:
+        raise ValueError("plans.json holds seg_net.arch == 'mtl' and cropping_net without crop_size: the segmenter runs on the crop_size "
+                         "window the cropping network centres")
+    for key in ("config", "window_size"):
+        if key not in sk:
+            raise ValueError("seg_net.arch == 'mtl' needs seg_net.%s" % key)
 
 
 def _check_prev_stage(prev_stage_classes, given, model_folder):

@@ -401,7 +401,11 @@ conv_f16s_kernel(const ConvParams p, const F16sGeom g, const _Float16* __restric
         }
     } else {
     // packed weights: fragment (mt, chunk, tap, ks, part) = 64 lanes x 8 halves
-    const f16x8* wfrag = reinterpret_cast<const f16x8*>(wpk) + (long)mt * g.nchunk * (KHW * KS * 2) * 64 + lane;
+    // A 1x5 / 5x1 layer of <= 32 output channels runs the two-m-tile shape (f16s_plan has no one-tile 1x5 shape) on weights that
+    // pack_conv_weight_f16s packs as ONE m-tile: the second tile's waves, whose every store the epilogue drops (co >= Cout), take the first
+    // tile's fragments -- their own would lie behind the end of the buffer (a read of nchunk * 20 KiB of whatever follows it, or of nothing).
+    const int mtw = (KHW == 5 && p.Cout <= 32) ? 0 : mt;
+    const f16x8* wfrag = reinterpret_cast<const f16x8*>(wpk) + (long)mtw * g.nchunk * (KHW * KS * 2) * 64 + lane;
 
     // A-fragment register ring, prefetched D steps ahead (NSTEP % R == 0 keeps the slots static).
     constexpr int R = (NSTEP % 3 == 0) ? 3 : 2;

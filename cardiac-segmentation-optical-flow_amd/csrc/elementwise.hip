@@ -108,6 +108,31 @@ __global__ void __launch_bounds__(256) tta_accumulate_kernel(const float* __rest
     }
 }
 
+// tta_accumulate_kernel with a per-sample placement: logits [B,K,c,c] of the crops, acc [B,K,H,W]; sample b's window starts at column
+// windows[b][0], row windows[b][2] (the crop_indices of cf_crop_windows).  The same softmax expression and the same `+= weight * p` as
+// tta_accumulate_kernel: inside the window acc carries the bits of that kernel on a crop-sized buffer followed by pad2d_kernel; outside it
+// nothing is read or written.  A window that leaves the map (the table is device data the host never sees) is skipped.
+__global__ void __launch_bounds__(256) tta_accumulate_window_kernel(const float* __restrict__ logits, const int* __restrict__ windows,
+                                                                   float* __restrict__ acc, int K, int c, int H, int W, int fh, int fw,
+                                                                   float weight, long total) {
+    const long cc = (long)c * c, HW = (long)H * W;
+    GRID_STRIDE(i, total) {  // i over (b, y, x) of the crop
+        int p = (int)(i % cc);
+        long b = i / cc;
+        int y = p / c, x = p - y * c;
+        const int x0 = windows[b * 4], y0 = windows[b * 4 + 2];
+        if (x0 < 0 || y0 < 0 || x0 > W - c || y0 > H - c) continue;
+        int ys = fh ? c - 1 - y : y, xs = fw ? c - 1 - x : x;
+        const float* lp = logits + b * K * cc + (long)ys * c + xs;
+        float mx = -INFINITY;
+        for (int k = 0; k < K; ++k) mx = fmaxf(mx, lp[k * cc]);
+        float sum = 0.f;
+        for (int k = 0; k < K; ++k) sum += expf(lp[k * cc] - mx);
+        float* ap = acc + b * K * HW + (long)(y0 + y) * W + x0 + x;
+        for (int k = 0; k < K; ++k) ap[k * HW] += weight * (expf(lp[k * cc] - mx) / sum);
+    }
+}
+
 __global__ void __launch_bounds__(256) flip2d_kernel(const float* __restrict__ src, float* __restrict__ dst, int H, int W, int fh,
                                                     int fw, long total) {
     const long HW = (long)H * W;
@@ -390,6 +415,14 @@ extern "C" int cf_tta_accumulate(const float* logits, float* acc, int B, int K, 
     LAUNCH_FLAT(tta_accumulate_kernel, total, logits, acc, K, H, W, flip_h, flip_w, weight, total);
 }
 
+extern "C" int cf_tta_accumulate_window(const float* logits, const int* windows, float* acc, int B, int K, int crop, int H, int W, int flip_h,
+                                        int flip_w, float weight, void* stream) {
+    CF_REQUIRE(logits && windows && acc, "null pointer");
+    CF_REQUIRE(B > 0 && K > 0 && K <= 64 && crop > 0 && crop <= H && crop <= W, "bad shape B=%d K=%d crop=%d H=%d W=%d", B, K, crop, H, W);
+    long total = (long)B * crop * crop;
+    LAUNCH_FLAT(tta_accumulate_window_kernel, total, logits, windows, acc, K, crop, H, W, flip_h, flip_w, weight, total);
+}
+
 extern "C" int cf_flip2d(const float* src, float* dst, int N, int H, int W, int flip_h, int flip_w, void* stream) {
     CF_REQUIRE(src && dst && src != dst, "null or aliased pointer");
     CF_REQUIRE(N > 0 && H > 0 && W > 0, "bad shape");
@@ -515,6 +548,60 @@ __global__ void __launch_bounds__(256) frame_boxes_kernel(const T* __restrict__ 
     if (threadIdx.x < 4) boxes[blockIdx.x * 4 + threadIdx.x] = red[2] < 0 ? -1 : red[threadIdx.x];
 }
 
+// Processor.get_mean_centroid for ONE frame followed by Processor.adjust_cropping_window (processor.py:140-160, :109-132), per sample and
+// in integers: the box of the non-zero labels as frame_boxes_kernel finds it, centre x1 + (x2 - x1) / 2 (the reference's fp32 value has a
+// fraction of 0 or .5 and .int() truncates it: the integer division), an empty map takes (H / 2, W / 2) in that order, then the clamps.
+// One block per sample, a grid-stride loop over the samples.  WORDS: the map is read four labels per load (W % 4 == 0, 4-byte aligned base).
+// windows[n] = {x_low, x_high, y_low, y_high} (crop_indices);  jobs[n] = {n, y_low, x_low}: a cf_tile_gather job (rows first).
+template <bool WORDS>
+__global__ void __launch_bounds__(256) crop_windows_kernel(const uint8_t* __restrict__ lab, int* __restrict__ windows, int* __restrict__ jobs,
+                                                          int N, int H, int W, int crop, int image) {
+    __shared__ int red[4];   // x1, y1 (min), x2, y2 (max)
+    for (int n = blockIdx.x; n < N; n += gridDim.x) {
+        if (threadIdx.x < 4) red[threadIdx.x] = threadIdx.x < 2 ? INT_MAX : -1;
+        __syncthreads();
+        const uint8_t* f = lab + (long)n * H * W;
+        int x1 = INT_MAX, y1 = INT_MAX, x2 = -1, y2 = -1;
+        if constexpr (WORDS) {
+            const uint32_t* f4 = reinterpret_cast<const uint32_t*>(f);
+            for (int i = threadIdx.x; i < H * W / 4; i += blockDim.x) {
+                const uint32_t v = f4[i];
+                if (v) {
+                    const int yy = (i * 4) / W, xx = i * 4 - yy * W;      // W % 4 == 0: the four labels lie in one row
+                    x1 = min(x1, xx + ((__ffs((int)v) - 1) >> 3)); x2 = max(x2, xx + ((31 - __clz((int)v)) >> 3));
+                    y1 = min(y1, yy); y2 = max(y2, yy);
+                }
+            }
+        } else {
+            for (int i = threadIdx.x; i < H * W; i += blockDim.x) {
+                if (f[i]) {
+                    const int yy = i / W, xx = i - yy * W;
+                    x1 = min(x1, xx); y1 = min(y1, yy); x2 = max(x2, xx); y2 = max(y2, yy);
+                }
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            x1 = min(x1, __shfl_xor(x1, o, 64)); y1 = min(y1, __shfl_xor(y1, o, 64));
+            x2 = max(x2, __shfl_xor(x2, o, 64)); y2 = max(y2, __shfl_xor(y2, o, 64));
+        }
+        if ((threadIdx.x & 63) == 0) { atomicMin(&red[0], x1); atomicMin(&red[1], y1); atomicMax(&red[2], x2); atomicMax(&red[3], y2); }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int cx = red[2] < 0 ? H / 2 : red[0] + (red[2] - red[0]) / 2;
+            const int cy = red[2] < 0 ? W / 2 : red[1] + (red[3] - red[1]) / 2;
+            const int half = crop / 2;
+            int x_low = max(0, cx - half), x_high = min(image, cx + half), y_low = max(0, cy - half), y_high = min(image, cy + half);
+            if (x_low == 0) x_high = crop;
+            if (x_high == image) x_low = image - crop;
+            if (y_low == 0) y_high = crop;
+            if (y_high == image) y_low = image - crop;
+            windows[n * 4 + 0] = x_low; windows[n * 4 + 1] = x_high; windows[n * 4 + 2] = y_low; windows[n * 4 + 3] = y_high;
+            jobs[n * 3 + 0] = n; jobs[n * 3 + 1] = y_low; jobs[n * 3 + 2] = x_low;
+        }
+        __syncthreads();     // red is reset by the next trip
+    }
+}
+
 // out[b, c, p] = bilinear sample of field[b, c] at the point whose grid_sample coordinates are (gx, gy) = the normalised
 // (pts[b,0,p], pts[b,1,p]): 2 * (v / (size - 1) - 0.5) with size = W for channel 0 and H for channel 1 (the reference's shape[~i]),
 // align_corners = True, zeros outside -- every intermediate rounded as PyTorch rounds it.
@@ -542,6 +629,21 @@ extern "C" int cf_frame_boxes(const void* x, int is_float, int* boxes, int N, in
     CF_REQUIRE(N > 0 && H > 0 && W > 0 && (long)H * W < (1L << 31), "bad shape N=%d H=%d W=%d", N, H, W);
     if (is_float) hipLaunchKernelGGL(cf::frame_boxes_kernel<float>, dim3((unsigned)N), dim3(256), 0, cf::as_stream(stream), (const float*)x, boxes, H, W);
     else hipLaunchKernelGGL(cf::frame_boxes_kernel<uint8_t>, dim3((unsigned)N), dim3(256), 0, cf::as_stream(stream), (const uint8_t*)x, boxes, H, W);
+    CF_CHECK_LAUNCH();
+    return CF_OK;
+}
+
+extern "C" int cf_crop_windows(const uint8_t* labels, int* windows, int* jobs, int N, int H, int W, int crop, int image, void* stream) {
+    CF_REQUIRE(labels && windows && jobs, "null pointer");
+    CF_REQUIRE(N > 0 && H > 0 && W > 0 && (long)H * W < (1L << 31) && N <= (1 << 28), "bad shape N=%d H=%d W=%d", N, H, W);
+    CF_REQUIRE(crop > 0 && crop % 2 == 0 && crop <= image && image <= H && image <= W,
+               "bad window crop=%d image=%d on a %dx%d map: crop must be even (Processor.crop_and_pad cuts 2 * (crop / 2) pixels) and crop <= image <= H, W",
+               crop, image, H, W);
+    const unsigned grid = (unsigned)(N < 4096 ? N : 4096);
+    if (W % 4 == 0 && (reinterpret_cast<uintptr_t>(labels) & 3) == 0)
+        hipLaunchKernelGGL(cf::crop_windows_kernel<true>, dim3(grid), dim3(256), 0, cf::as_stream(stream), labels, windows, jobs, N, H, W, crop, image);
+    else
+        hipLaunchKernelGGL(cf::crop_windows_kernel<false>, dim3(grid), dim3(256), 0, cf::as_stream(stream), labels, windows, jobs, N, H, W, crop, image);
     CF_CHECK_LAUNCH();
     return CF_OK;
 }

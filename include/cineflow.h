@@ -353,6 +353,14 @@ int cf_pad2d(const float* src, float* dst, int N, int h, int w, int y0, int x0, 
  * logits [B,K,H,W] are the network output on the (possibly flipped) input; flips undo the mirroring. */
 int cf_tta_accumulate(const float* logits, float* acc, int B, int K, int H, int W, int flip_h, int flip_w, float weight,
                       void* stream);
+/* cf_tta_accumulate with a per-sample placement (MTL_model.py:905-936: flip-averaged softmax of the crops, then uncrop_no_registration's
+ * F.pad): logits [B,K,crop,crop] of one flip variant, acc [B,K,H,W]; windows: DEVICE int32 [B,4] = cf_crop_windows' crop_indices, sample b
+ * lands at rows windows[b][2].., columns windows[b][0]...  acc[b][:, window] += weight * flip(softmax_K(logits[b])); nothing outside the
+ * window is read or written, so a zero-filled acc stays zero there (the pad).  Inside the window the value carries the bits of
+ * cf_tta_accumulate into a [B,K,crop,crop] buffer followed by cf_pad2d (same softmax, same order of additions over successive calls).
+ * A window that leaves the map is skipped. */
+int cf_tta_accumulate_window(const float* logits, const int* windows, float* acc, int B, int K, int crop, int H, int W, int flip_h,
+                             int flip_w, float weight, void* stream);
 int cf_flip2d(const float* src, float* dst, int N, int H, int W, int flip_h, int flip_w, void* stream);
 /* :711-731: agg[:, lx:lx+ph, ly:ly+pw] += pred * g ; cnt[...] += g   (g nullable = ones). pred [K,ph,pw]. */
 int cf_tile_accumulate(const float* pred, const float* gauss, float* agg, float* cnt, int K, int X, int Y, int lx,
@@ -651,6 +659,12 @@ int cf_window_attention(const float* qk, const float* v, const float* bias_table
 /* Processor.get_mean_centroid's masks_to_boxes (training/network_training/processor.py:140-160): per frame n of x [N][H][W]
  * (uint8, or float32 when is_float) boxes[n] = {x1, y1, x2, y2} of the non-zero pixels, or {-1,-1,-1,-1} for an all-zero frame. */
 int cf_frame_boxes(const void* x, int is_float, int* boxes, int N, int H, int W, void* stream);
+/* Processor.get_mean_centroid for one frame + Processor.adjust_cropping_window (processor.py:140-160, :109-132) per sample, integer for
+ * integer, nothing read back: labels uint8 [N][H][W]; the centre of the non-zero labels' box is (x1 + (x2 - x1) / 2, y1 + (y2 - y1) / 2)
+ * truncated, an all-zero map takes (H / 2, W / 2) in that order; the window of `crop` (even) pixels around it is clamped into
+ * [0, image), crop <= image <= H, W.  Two DEVICE outputs: windows int32 [N][4] = {x_low, x_high, y_low, y_high} (crop_indices; x is the
+ * column) and jobs int32 [N][3] = {n, y_low, x_low}, the job table cf_tile_gather takes (rows first), so the gather cuts the crops. */
+int cf_crop_windows(const uint8_t* labels, int* windows, int* jobs, int N, int H, int W, int crop, int image, void* stream);
 /* SpatialTransformerContour.forward(new_locs, original) (network_architecture/integration.py:5-34) as get_strain.py calls it:
  * out[b,c,p] = bilinear sample (align_corners, zeros outside) of field [B][C][H][W] at the contour point (pts[b,0,p], pts[b,1,p]) --
  * channel 0 is normalised by W - 1 and used as grid x, channel 1 by H - 1 as grid y (the reference's shape[~i]). */
