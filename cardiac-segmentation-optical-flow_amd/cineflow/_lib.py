@@ -52,6 +52,9 @@ SIGNATURES = {
     "cf_group_norm_apply": [P, P, P, P, P, I, I, I, I, F, I, I, P, P],
     "cf_group_norm_coef": [P, P, P, I, I, I, I, F, P, P],
     "cf_norm_head_1x1": [P, P, F, P, P, P, I, I, I, I, P],
+    "cf_batch_norm_coef": [P, P, P, P, F, I, I, P, P],
+    "cf_coef_apply_ok": [I, I, L],
+    "cf_coef_apply": [P, P, I, F, P, I, I, I, P],
     "cf_conv2d_f16s_prenorm_ok": [I, I, I, I, I],
     "cf_conv_stream_enable": [I],
     "cf_conv2d_f16s_route": [I] * 16 + [P],

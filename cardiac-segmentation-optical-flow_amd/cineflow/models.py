@@ -10,7 +10,7 @@ import torch
 
 from . import ops
 from .convroute import PackedConv
-from .nn import (Module, RawMap, conv_norm, Conv2d, ConvTranspose2d, GroupNorm, Conv3d, ConvTranspose3d, InstanceNorm3d, ResidualLayer3D, ConvBlocks2DGroupLegacy, Encoder2D, Decoder2D, CrossAttentionLayer,
+from .nn import (Module, RawMap, Nonlin, LRELU, make_norm, conv_norm, Conv2d, ConvTranspose2d, GroupNorm, Conv3d, ConvTranspose3d, InstanceNorm3d, ResidualLayer3D, ConvBlocks2DGroupLegacy, Encoder2D, Decoder2D, CrossAttentionLayer,
                  TransformerFlowEncoderSuccessiveNoEmb, ConvGRUCell, SpatialTransformer, VecInt)
 
 
@@ -440,46 +440,72 @@ class ModelWrap(Module):
 
 
 # ------------------------------------------------------------------------------------------------ Generic_UNet (2D)
-class ConvDropoutNormNonlin(Module):
-    """nnunet/network_architecture/generic_UNet.py:26-69: conv3x3 -> InstanceNorm(affine) -> LeakyReLU(0.01)."""
+BLOCK_ORDERS = ("conv_norm_nonlin", "conv_nonlin_norm")
 
-    def __init__(self, cin, cout, stride=1):
+
+class ConvDropoutNormNonlin(Module):
+    """nnunet/network_architecture/generic_UNet.py:26-69: conv3x3 -> InstanceNorm(affine) -> LeakyReLU(0.01) as nnUNetTrainerV2 builds it.
+    The trainer variants choose the norm (nn.make_norm: 'in', 'gn', 'bn', 'none' -- always under the key `instnorm`), the activation
+    (nn.Nonlin) and the order: 'conv_nonlin_norm' is ConvDropoutNonlinNorm (:72-77), whose statistics are those of the ACTIVATED map, so
+    it runs unfused -- convolution, activation pass, norm pass."""
+    THREE_D = False
+
+    def __init__(self, cin, cout, stride=1, norm="in", norm_groups=8, nonlin=LRELU, order="conv_norm_nonlin"):
         super().__init__()
         self.conv = Conv2d(cin, cout, 3, stride=stride, padding=1, bias=True)
-        self.instnorm = GroupNorm(cout, cout)
+        self.instnorm = make_norm(norm, cout, norm_groups, self.THREE_D)
+        self.nonlin, self.order = nonlin, order
 
     def forward(self, x, x2=None):
-        return conv_norm(self.conv, self.instnorm, x, x2=x2, act="lrelu")
+        if self.order == "conv_nonlin_norm":
+            y = self.nonlin.act_pass(self.conv(x, x2=x2))
+            return RawMap(y, None, self.instnorm).norm_act(None)
+        g = self.instnorm.groups
+        y = self.conv(x, x2=x2, stats_groups=g)
+        return RawMap(*(y if g else (y, None)), self.instnorm).norm_act(self.nonlin)
 
 
 class StackedConvLayers(Module):
     """generic_UNet.py:79-144."""
+    BLOCK = ConvDropoutNormNonlin
 
-    def __init__(self, cin, cout, num_convs, first_stride=None):
+    def __init__(self, cin, cout, num_convs, first_stride=None, **block):
         super().__init__()
         self.input_channels, self.output_channels = cin, cout
-        self.blocks = [ConvDropoutNormNonlin(cin, cout, first_stride if first_stride is not None else 1)] + \
-                      [ConvDropoutNormNonlin(cout, cout) for _ in range(num_convs - 1)]
+        self.blocks = [self.BLOCK(cin, cout, first_stride if first_stride is not None else 1, **block)] + \
+                      [self.BLOCK(cout, cout, **block) for _ in range(num_convs - 1)]
 
     def forward(self, x, x2=None, pending=None, defer_last=None):
-        """A block whose output feeds only the next convolution leaves its InstanceNorm + LeakyReLU to that convolution (applied while the
+        """A block whose output feeds only the next convolution leaves its norm + activation to that convolution (applied while the
         tile is staged, ops.conv2d_f16s_prenorm): one 8-byte-per-element pass less per pair.
         pending = the nn.RawMap (raw conv output, its statistics, its norm module) handed over by the PREVIOUS stack (x is then ignored);
         defer_last = the convolution that will consume this stack's output alone: when it qualifies, the last block's norm is handed on
-        as the returned `pending` instead of being applied.  Returns x, or (x, pending) when defer_last is given."""
+        as the returned `pending` instead of being applied.  Returns x, or (x, pending) when defer_last is given.
+        What can be deferred: a norm with a table at hand (RawMap.ready: InstanceNorm / GroupNorm with fused statistics, BatchNorm) under an
+        activation the staging code has (Nonlin.stage_slope: LeakyReLU of any slope, ReLU as slope 0, GELU; the 1x1 head has no GELU).
+        Mish, no norm at all and the conv_nonlin_norm order defer nowhere."""
+        nl = self.blocks[0].nonlin
+        slope = nl.stage_slope
+        if self.blocks[0].order == "conv_nonlin_norm":
+            assert pending is None
+            for i, b in enumerate(self.blocks):
+                x = b(x, x2=x2 if i == 0 else None)
+            return (x, None) if defer_last is not None else x
         for i, b in enumerate(self.blocks):
             last = i == len(self.blocks) - 1
+            g = b.instnorm.groups
             if pending is not None:
-                y = b.conv.prenorm(pending.raw, pending.coef(), 0.01, stats_groups=b.instnorm.groups)
+                y = b.conv.prenorm(pending.raw, pending.coef(), slope, stats_groups=g)
             else:
-                y = b.conv(x, x2=x2 if i == 0 else None, stats_groups=b.instnorm.groups)
-            pending = RawMap(*y, b.instnorm)
+                y = b.conv(x, x2=x2 if i == 0 else None, stats_groups=g)
+            pending = RawMap(*(y if g else (y, None)), b.instnorm)
             nxt = defer_last if last else self.blocks[i + 1].conv
-            if nxt is not None and pending.ws is not None and nxt.ks == (3, 3) and nxt.prenorm_ok(pending.raw):
+            if nxt is not None and slope is not None and pending.ready and nxt.ks == (3, 3) and nxt.prenorm_ok(pending.raw):
                 continue
-            if last and nxt is not None and pending.ws is not None and nxt.ks == (1, 1) and nxt.stride == 1 and ops.norm_head_ok(pending.raw, nxt.cout):
+            if (last and nxt is not None and slope is not None and slope >= 0.0 and pending.ready and nxt.ks == (1, 1) and nxt.stride == 1
+                    and ops.norm_head_ok(pending.raw, nxt.cout)):
                 continue                             # a 1x1 head takes the norm + LeakyReLU itself (ops.norm_head_1x1)
-            x, pending = pending.apply("lrelu"), None
+            x, pending = pending.norm_act(nl), None
         return (x, pending) if defer_last is not None else x
 
     def first_conv(self):
@@ -493,31 +519,46 @@ class Generic_UNet(Module):
 
     MAX_FILTERS_2D = 480
 
-    def __init__(self, input_channels, base_num_features, num_classes, num_pool, num_conv_per_stage=2, pool_op_kernel_sizes=None):
+    @staticmethod
+    def block_kwargs(norm="in", norm_groups=8, nonlin="lrelu", nonlin_slope=0.01, block_order="conv_norm_nonlin"):
+        """the trainer variants' choices (plans.json seg_net keys of the same names) -> the keyword arguments of every conv block"""
+        if norm not in ("in", "gn", "bn", "none"):
+            raise ValueError("seg_net.norm must be 'in', 'gn', 'bn' or 'none', got %r" % (norm,))
+        if nonlin not in ("lrelu", "relu", "gelu", "mish"):
+            raise ValueError("seg_net.nonlin must be 'lrelu', 'relu', 'gelu' or 'mish', got %r" % (nonlin,))
+        if block_order not in BLOCK_ORDERS:
+            raise ValueError("seg_net.block_order must be one of %s, got %r" % (BLOCK_ORDERS, block_order))
+        return dict(norm=norm, norm_groups=int(norm_groups), nonlin=Nonlin(nonlin, float(nonlin_slope)), order=block_order)
+
+    def __init__(self, input_channels, base_num_features, num_classes, num_pool, num_conv_per_stage=2, pool_op_kernel_sizes=None,
+                 seg_output_bias=False, **variant):
         """pool_op_kernel_sizes: the plans' per-stage pooling kernels (generic_UNet.py:247-248; strided first convolutions :283-285,
-        transposed convolutions :343-344), e.g. [[2,2]]*5 + [[2,1]] for the ACDC 2-D patch (256, 224); default (2, 2) everywhere."""
+        transposed convolutions :343-344), e.g. [[2,2]]*5 + [[2,1]] for the ACDC 2-D patch (256, 224); default (2, 2) everywhere.
+        variant: block_kwargs' arguments (norm, norm_groups, nonlin, nonlin_slope, block_order); seg_output_bias: seg_output_use_bias."""
         super().__init__()
         self.num_classes = num_classes
         self.input_channels = input_channels
+        blk = self.block_kwargs(**variant)
+        self.nonlin = blk["nonlin"]
         pool = [tuple(int(v) for v in p_) for p_ in (pool_op_kernel_sizes or [(2, 2)] * num_pool)]
         assert len(pool) == num_pool and all(p_ in ((2, 2), (2, 1), (1, 2)) for p_ in pool), "pooling kernels (2,2), (2,1) or (1,2), one per stage"
         self.pool_op_kernel_sizes = pool
         ctx, loc, tu, seg = [], [], [], []
         out_f, in_f = base_num_features, input_channels
         for d in range(num_pool):
-            ctx.append(StackedConvLayers(in_f, out_f, num_conv_per_stage, pool[d - 1] if d != 0 else None))
+            ctx.append(StackedConvLayers(in_f, out_f, num_conv_per_stage, pool[d - 1] if d != 0 else None, **blk))
             in_f = out_f
             out_f = min(int(np.round(out_f * 2)), self.MAX_FILTERS_2D)
         final = out_f
-        ctx.append({0: StackedConvLayers(in_f, out_f, num_conv_per_stage - 1, pool[-1]), 1: StackedConvLayers(out_f, final, 1)})
+        ctx.append({0: StackedConvLayers(in_f, out_f, num_conv_per_stage - 1, pool[-1], **blk), 1: StackedConvLayers(out_f, final, 1, **blk)})
         skip_ch = [c.output_channels for c in ctx[:-1]]
         for u in range(num_pool):
             from_down = final
             from_skip = skip_ch[-(1 + u)]
             final = from_skip
             tu.append(ConvTranspose2d(from_down, from_skip, bias=False, kernel_size=pool[-(u + 1)]))
-            loc.append({0: StackedConvLayers(from_skip * 2, from_skip, num_conv_per_stage - 1), 1: StackedConvLayers(from_skip, final, 1)})
-            seg.append(Conv2d(final, num_classes, 1, bias=False))
+            loc.append({0: StackedConvLayers(from_skip * 2, from_skip, num_conv_per_stage - 1, **blk), 1: StackedConvLayers(from_skip, final, 1, **blk)})
+            seg.append(Conv2d(final, num_classes, 1, bias=bool(seg_output_bias)))
         self.conv_blocks_localization = loc
         self.conv_blocks_context = ctx
         self.tu = tu
@@ -555,33 +596,33 @@ class Generic_UNet(Module):
                 # the last stack hands its norm to the 1x1 head: one pass over the raw map instead of apply + 1x1 convolution
                 x, pend = blk[1](x, pending=pend, defer_last=head)
                 if pend is not None:
-                    return ops.norm_head_1x1(pend.raw, pend.coef(), 0.01, head._p["weight"], head._p.get("bias"))
+                    return ops.norm_head_1x1(pend.raw, pend.coef(), self.nonlin.stage_slope, head._p["weight"], head._p.get("bias"))
             else:
                 x = blk[1](x, pending=pend)
         return head(x)
 
 
 # ------------------------------------------------------------------------------------------------ Generic_UNet (3D)
-class ConvDropoutNormNonlin3D(Module):
-    """generic_UNet.py:26-69 with conv_op = nn.Conv3d: conv -> InstanceNorm3d(affine) -> LeakyReLU(0.01)."""
+class ConvDropoutNormNonlin3D(ConvDropoutNormNonlin):
+    """generic_UNet.py:26-69 with conv_op = nn.Conv3d: conv -> InstanceNorm3d(affine) -> LeakyReLU(0.01), and the trainer variants'
+    choices as in 2-D."""
+    THREE_D = True
 
-    def __init__(self, cin, cout, kernel=(3, 3, 3), stride=(1, 1, 1)):
-        super().__init__()
+    def __init__(self, cin, cout, kernel=(3, 3, 3), stride=(1, 1, 1), norm="in", norm_groups=8, nonlin=LRELU, order="conv_norm_nonlin"):
+        Module.__init__(self)
         self.conv = Conv3d(cin, cout, kernel, stride, bias=True)
-        self.instnorm = InstanceNorm3d(cout)
-
-    def forward(self, x, x2=None):
-        return conv_norm(self.conv, self.instnorm, x, x2=x2, act="lrelu")
+        self.instnorm = make_norm(norm, cout, norm_groups, True)
+        self.nonlin, self.order = nonlin, order
 
 
 class StackedConvLayers3D(Module):
     """generic_UNet.py:79-144."""
 
-    def __init__(self, cin, cout, num_convs, kernel, first_stride=None):
+    def __init__(self, cin, cout, num_convs, kernel, first_stride=None, **block):
         super().__init__()
         self.input_channels, self.output_channels = cin, cout
-        self.blocks = [ConvDropoutNormNonlin3D(cin, cout, kernel, first_stride if first_stride is not None else (1, 1, 1))] + \
-                      [ConvDropoutNormNonlin3D(cout, cout, kernel) for _ in range(num_convs - 1)]
+        self.blocks = [ConvDropoutNormNonlin3D(cin, cout, kernel, first_stride if first_stride is not None else (1, 1, 1), **block)] + \
+                      [ConvDropoutNormNonlin3D(cout, cout, kernel, **block) for _ in range(num_convs - 1)]
 
     def forward(self, x, x2=None, pending=None, defer_last=None):
         for i, b in enumerate(self.blocks):
@@ -601,31 +642,33 @@ class Generic_UNet3D(Generic_UNet):
     MAX_NUM_FILTERS_3D = 320
 
     def __init__(self, input_channels, base_num_features, num_classes, num_pool, num_conv_per_stage=2, pool_op_kernel_sizes=None,
-                 conv_kernel_sizes=None):
+                 conv_kernel_sizes=None, seg_output_bias=False, **variant):
         Module.__init__(self)
         self.num_classes = num_classes
         self.input_channels = input_channels
+        blk = self.block_kwargs(**variant)
+        self.nonlin = blk["nonlin"]
         pool = [tuple(p) for p in (pool_op_kernel_sizes or [(2, 2, 2)] * num_pool)]
         kern = [tuple(k) for k in (conv_kernel_sizes or [(3, 3, 3)] * (num_pool + 1))]
         self.pool_op_kernel_sizes, self.conv_kernel_sizes = pool, kern
         ctx, loc, tu, seg = [], [], [], []
         out_f, in_f = base_num_features, input_channels
         for d in range(num_pool):
-            ctx.append(StackedConvLayers3D(in_f, out_f, num_conv_per_stage, kern[d], pool[d - 1] if d != 0 else None))
+            ctx.append(StackedConvLayers3D(in_f, out_f, num_conv_per_stage, kern[d], pool[d - 1] if d != 0 else None, **blk))
             in_f = out_f
             out_f = min(int(np.round(out_f * 2)), self.MAX_NUM_FILTERS_3D)
         final = out_f
-        ctx.append({0: StackedConvLayers3D(in_f, out_f, num_conv_per_stage - 1, kern[num_pool], pool[-1]),
-                    1: StackedConvLayers3D(out_f, final, 1, kern[num_pool])})
+        ctx.append({0: StackedConvLayers3D(in_f, out_f, num_conv_per_stage - 1, kern[num_pool], pool[-1], **blk),
+                    1: StackedConvLayers3D(out_f, final, 1, kern[num_pool], **blk)})
         skip_ch = [c.output_channels for c in ctx[:-1]]
         for u in range(num_pool):
             from_down = final
             from_skip = skip_ch[-(1 + u)]
             final = from_skip
             tu.append(ConvTranspose3d(from_down, from_skip, pool[-(u + 1)], bias=False))
-            loc.append({0: StackedConvLayers3D(from_skip * 2, from_skip, num_conv_per_stage - 1, kern[-(u + 1)]),
-                        1: StackedConvLayers3D(from_skip, final, 1, kern[-(u + 1)])})
-            seg.append(Conv3d(final, num_classes, (1, 1, 1), bias=False))
+            loc.append({0: StackedConvLayers3D(from_skip * 2, from_skip, num_conv_per_stage - 1, kern[-(u + 1)], **blk),
+                        1: StackedConvLayers3D(from_skip, final, 1, kern[-(u + 1)], **blk)})
+            seg.append(Conv3d(final, num_classes, (1, 1, 1), bias=bool(seg_output_bias)))
         self.conv_blocks_localization = loc
         self.conv_blocks_context = ctx
         self.tu = tu

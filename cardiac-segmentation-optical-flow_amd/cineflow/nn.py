@@ -207,18 +207,105 @@ class InstanceNorm3d(GroupNorm):
         super().__init__(channels, channels, eps)
 
 
+class BatchNorm(Module):
+    """nn.BatchNorm2d / nn.BatchNorm3d(C, affine=True) in eval mode (nnUNetTrainerV2_BN): the [B, 3, C] table comes from the running
+    statistics (ops.batch_norm_coef), one call per batch size, kept until the next load.  `groups` is None: the producing convolution is
+    asked for no statistics.  `num_batches_tracked` is a derived buffer and never loaded."""
+    groups = None
+
+    def __init__(self, channels, eps=1e-5):
+        super().__init__()
+        self.eps = eps
+        for k in ("weight", "bias", "running_mean", "running_var"):
+            self._param(k, (channels,))
+        self._tables = {}
+
+    def _prepare(self):
+        self._tables = {}
+
+    def table(self, B):
+        if B not in self._tables:
+            p = self._p
+            self._tables[B] = ops.batch_norm_coef(p["running_mean"], p["running_var"], p["weight"], p["bias"], B, self.eps)
+        return self._tables[B]
+
+
+class NoNorm(Module):
+    """helperModules.Identity in the norm slot (nnUNetTrainerV2_NoNormalization): no parameters, no table -- the activation alone is applied"""
+    groups = None
+
+    def table(self, B):
+        return None
+
+
+def make_norm(kind, channels, groups=8, three_d=False):
+    """the norm module of a Generic_UNet block: 'in' InstanceNorm(affine), 'gn' MyGroupNorm(groups), 'bn' BatchNorm (eval), 'none' Identity"""
+    if kind == "in":
+        return InstanceNorm3d(channels) if three_d else GroupNorm(channels, channels)
+    if kind == "gn":
+        return GroupNorm(groups, channels)
+    if kind == "bn":
+        return BatchNorm(channels)
+    if kind == "none":
+        return NoNorm()
+    raise ValueError("norm must be 'in', 'gn', 'bn' or 'none', got %r" % (kind,))
+
+
+class Nonlin(NamedTuple):
+    """the activation of a Generic_UNet: kind 'lrelu' (with slope), 'relu', 'gelu' (erf form) or 'mish'"""
+    kind: str = "lrelu"
+    slope: float = 0.01
+
+    @property
+    def stage_slope(self):
+        """what a consumer that normalises while staging takes for it (csrc/conv.h in_slope: v > 0 ? v : v * slope, negative: GELU);
+        None: not deferrable (Mish)"""
+        return {"lrelu": float(self.slope), "relu": 0.0, "gelu": -1.0}.get(self.kind)
+
+    @property
+    def fused(self):
+        """its name among the fixed activations of the GroupNorm apply pass (LeakyReLU there is 0.01), or None: the pass is ops.coef_apply"""
+        if self.kind == "lrelu":
+            return "lrelu" if self.slope == 0.01 else None
+        return self.kind if self.kind in ("relu", "gelu") else None
+
+    def act_pass(self, x):
+        """the activation alone, in place"""
+        return ops.coef_apply(x, None, self.kind, self.slope, out=x)
+
+
+LRELU = Nonlin()
+
+
 class RawMap(NamedTuple):
     """a normalisation that has not run yet: a convolution's raw output, its statistics from the convolution's epilogue (None: not fused)
-    and the norm module.  Whoever holds it applies the norm -- as a pass (`apply`) or while staging the map (`coef`)."""
+    and the norm module.  Whoever holds it applies the norm -- as a pass (`apply`, `norm_act`) or while staging the map (`coef`)."""
     raw: torch.Tensor
     ws: torch.Tensor
-    norm: GroupNorm
+    norm: Module
+
+    @property
+    def ready(self):
+        """can a consumer have the table without another pass over the map?  GroupNorm: the statistics came fused; BatchNorm: always;
+        no norm: never (there is no table)"""
+        return self.ws is not None if isinstance(self.norm, GroupNorm) else isinstance(self.norm, BatchNorm)
 
     def coef(self):
-        """the [B, 3, C] table {mean, rstd * gamma, beta} a consumer that normalises while staging reads"""
+        """the [B, 3, C] table {mean, rstd * gamma, beta} a consumer that normalises while staging reads (None: no norm)"""
         B, C = self.raw.shape[:2]
         n = self.norm
-        return ops.group_norm_coef(self.ws, n._p["weight"], n._p["bias"], n.groups, B, C, self.raw.numel() // (B * C), n.eps)
+        if not isinstance(n, GroupNorm):
+            return n.table(B)
+        ws = self.ws if self.ws is not None else ops.group_norm_stats(self.raw, n.groups)
+        return ops.group_norm_coef(ws, n._p["weight"], n._p["bias"], n.groups, B, C, self.raw.numel() // (B * C), n.eps)
+
+    def norm_act(self, nonlin=None):
+        """nonlin(norm(raw)) as one pass, in place (nonlin None: the norm alone): the GroupNorm apply pass where its fixed activations cover
+        `nonlin`, else ops.coef_apply on the table -- BatchNorm, no norm, LeakyReLU with another slope, Mish"""
+        if isinstance(self.norm, GroupNorm) and (nonlin is None or nonlin.fused):
+            return self.apply(None if nonlin is None else nonlin.fused)
+        kind, slope = (None, 0.0) if nonlin is None else nonlin
+        return ops.coef_apply(self.raw, self.coef(), kind, slope, out=self.raw)
 
     def apply(self, act=None, res=None, res_mode=None, inplace=True):
         """act(norm(raw)) with the residual inside the pass; a residual that is itself a RawMap gets its norm in the same pass"""

@@ -16,6 +16,7 @@ import torch
 from ._lib import lib, check
 
 ACT = {None: 0, "none": 0, "gelu": 1, "relu": 2, "lrelu": 3, "tanh": 4, "sigmoid": 5}
+ACT_COEF = dict(ACT, mish=6)      # cf_coef_apply's codes: the fused epilogues' plus Mish
 RES = {None: 0, "none": 0, "before_act": 1, "after_act": 2}
 OP = {"add": 0, "sub": 1, "mul": 2}
 
@@ -628,6 +629,33 @@ def group_norm_coef(ws, gamma, beta, groups, B, C, HW, eps=1e-5):
     coef = torch.empty((B, 3, C), dtype=torch.float32, device=ws.device)
     check(lib().cf_group_norm_coef(ws.data_ptr(), _opt(gamma), _opt(beta), B, C, HW, groups, float(eps), _f32(coef), _stream()), "cf_group_norm_coef")
     return coef
+
+
+def batch_norm_coef(running_mean, running_var, gamma, beta, B, eps=1e-5):
+    """BatchNorm in eval mode as a table: float [B,3,C] = {running_mean, gamma / sqrt(running_var + eps), beta}, group_norm_coef's layout"""
+    C = running_mean.numel()
+    coef = torch.empty((B, 3, C), dtype=torch.float32, device=running_mean.device)
+    check(lib().cf_batch_norm_coef(_f32(running_mean), _f32(running_var), _opt(gamma), _opt(beta), float(eps), B, C, _f32(coef), _stream()),
+          "cf_batch_norm_coef")
+    return coef
+
+
+def coef_apply_ok(B, C, HW):
+    """does cf_coef_apply's index arithmetic hold [B, C, HW]?"""
+    return lib().cf_coef_apply_ok(int(B), int(C), int(HW)) == 1
+
+
+def coef_apply(x, coef=None, act=None, slope=0.01, out=None):
+    """out = act((x - mean) * scale + shift) with coef [B,3,C] = {mean, scale, shift} (group_norm_coef / batch_norm_coef); coef None: the
+    activation alone.  act: an ACT_COEF name ('mish' included); 'lrelu' takes `slope`.  x [B,C,...] (an NCDHW tensor as its rows);
+    out may be x or a tensor of x's shape -- contiguous, but at any 4-byte address (a view into a larger buffer)."""
+    B, C = x.shape[0], x.shape[1]
+    HW = x.numel() // (B * C)
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and (coef is None or tuple(coef.shape) == (B, 3, C))
+    check(lib().cf_coef_apply(_f32(x), _opt(coef), ACT_COEF[act], float(slope), _f32(out), B, C, HW, _stream()), "cf_coef_apply")
+    return out
 
 
 def norm_head_ok(x, K):

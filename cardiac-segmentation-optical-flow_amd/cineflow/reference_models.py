@@ -31,7 +31,7 @@ A folder of nnMTLTrainerV2 -- recognised by its trainer's name -- is imported wi
 seg_net.arch = 'mtl' folder: the fork's own MTLmodel segmenter, behind the 2-class MTLmodel cropper when the YAML sets `cropper: true`
 (`--crop_weights`, `--crop_config` are then required).
 
-Command line:  python -m cineflow.reference_models -s SEG [-w FLOW] -o OUT [--seg_config Y] [--crop_weights F --crop_config Y] [-f FOLDS] [-chk NAME]
+Command line:  python -m cineflow.reference_models -s SEG [-w FLOW] -o OUT [--seg_config Y] [--crop_weights F --crop_config Y] [-f FOLDS] [-chk NAME] [--seg_variant NAME]
 """
 import argparse
 import os
@@ -356,7 +356,8 @@ def _trainer_info(fold_dir, checkpoint_name):
 
 
 def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, crop_weights=None, crop_config=None, folds=None,
-                                  checkpoint_name="model_final_checkpoint", crop_size=None, image_size=None, window_size=None, seg_config=None):
+                                  checkpoint_name="model_final_checkpoint", crop_size=None, image_size=None, window_size=None, seg_config=None,
+                                  seg_variant=None):
     """seg_folder: output folder of a 2-D nnU-Net trainer (plans.pkl, fold_X/); flow_weight_folder: the `-w` folder of run_training.py
     (config.yaml, <task>/fold_X/) or its <task> folder; crop_weights / crop_config: optionally the MTLmodel cropper's checkpoint and its
     YAML (nnMTLTrainerV2FlowSuccessive.py:482-484, adversarial_acdc.yaml).  Writes `out_folder` in the plans.json format (save_model_folder):
@@ -375,6 +376,8 @@ def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, cr
     first = _checkpoint_folds(seg_folder, checkpoint_name)
     info = _trainer_info(first[sorted(first)[0]], checkpoint_name) if first else None
     if _MTL_TRAINER in str((info or {}).get("name") or ""):
+        if seg_variant is not None:
+            raise ValueError("seg_variant %r names a Generic_UNet trainer variant; %s was written by %s" % (seg_variant, seg_folder, info["name"]))
         if flow_weight_folder is not None:
             raise ValueError("%s was written by %s (an MTLmodel segmenter) and cannot be paired with a flow folder (-w %s): MTLmodel next to "
                              "the flow network is not built.  Import it on its own (no -w)." % (seg_folder, info["name"], flow_weight_folder))
@@ -384,7 +387,7 @@ def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, cr
         raise ValueError("seg_config is the YAML of an %s folder; %s was written by %r" % (_MTL_TRAINER, seg_folder, (info or {}).get("name")))
     if flow_weight_folder is None:
         return _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size,
-                                         window_size)
+                                         window_size, seg_variant)
     if _stage_is_3d(load_reference_pickle(join(seg_folder, "plans.pkl")), info["init"][5] if info and len(info.get("init") or ()) > 5 else None):
         raise ValueError("%s is a 3-D segmentation folder (3-entry patch_size) and cannot be paired with a flow folder (-w %s): the flow path "
                          "is 2-D.  Import it on its own (no -w)." % (seg_folder, flow_weight_folder))
@@ -405,6 +408,9 @@ def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, cr
     flow_info = _trainer_info(flow_folds[folds[0]], checkpoint_name)
     stage = seg_info["init"][5] if seg_info and len(seg_info.get("init") or ()) > 5 else None
     plans = plans_from_reference(load_reference_pickle(join(seg_folder, "plans.pkl")), stage)
+    row = seg_variant_row((seg_info or {}).get("name"), seg_variant)
+    if row:                     # CineTrainer refuses the keys next to flow_net: a trainer variant's folder is imported on its own
+        _apply_seg_variant(plans, row)
     flow_cfg = C.with_defaults(C.read_config_video(config_path), prediction=False)
     successive = "no_error" in flow_cfg and "d_model" not in flow_cfg          # config.build_flow_net's dispatch
     task = os.path.basename(str(flow_info["init"][3]).rstrip("/\\")) if flow_info and len(flow_info.get("init") or ()) > 3 else os.path.basename(task_dir)
@@ -499,7 +505,101 @@ def _drop_resenc_aliases(sd, path):
     return out
 
 
-def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size, window_size):
+# ------------------------------------------------------------------------------------------------ trainer variants
+# nnunet/training/network_training/nnUNet_variants/architectural_variants/: the class name `.model.pkl` holds -> what the trainer's
+# initialize_network changes in Generic_UNet, as plans['seg_net'] keys (trainer.SEG_VARIANT_KEYS).  An empty row: nothing changes at
+# inference.  Two private entries: 'base_num_features' (the trainer overwrites the plans' width after reading them) and 'all_conv_3x3'
+# (it overwrites every conv_kernel_sizes entry with 3).  The ResencUNet trainers have their own route (seg_net.arch = 'resenc').
+SEG_VARIANTS = {
+    "nnUNetTrainerV2_ReLU": {"nonlin": "relu"},
+    "nnUNetTrainerV2_GeLU": {"nonlin": "gelu"},                                # its GeLU module is torch.nn.functional.gelu: the erf form, CF_ACT_GELU
+    "nnUNetTrainerV2_Mish": {"nonlin": "mish"},
+    "nnUNetTrainerV2_LReLU_slope_2en1": {"nonlin": "lrelu", "nonlin_slope": 0.2},
+    "nnUNetTrainerV2_GN": {"norm": "gn", "norm_groups": 8},                    # MyGroupNorm(num_groups=8) under the instnorm keys
+    "nnUNetTrainerV2_BN": {"norm": "bn"},
+    "nnUNetTrainerV2_NoNormalization": {"norm": "none"},
+    "nnUNetTrainerV2_NoNormalization_lr1en3": {"norm": "none"},
+    "nnUNetTrainerV2_ReLU_convReLUIN": {"nonlin": "relu", "block_order": "conv_nonlin_norm"},
+    "nnUNetTrainerV2_lReLU_convReLUIN": {"block_order": "conv_nonlin_norm"},   # the class in nnUNetTrainerV2_lReLU_convlReLUIN.py
+    "nnUNetTrainerV2_lReLU_convlReLUIN": {"block_order": "conv_nonlin_norm"},  # ... and that file's name
+    "nnUNetTrainerV2_ReLU_biasInSegOutput": {"nonlin": "relu", "seg_output_bias": True},
+    "nnUNetTrainerV2_lReLU_biasInSegOutput": {"seg_output_bias": True},
+    "nnUNetTrainerV2_3ConvPerStage": {"conv_per_stage": 3, "base_num_features": 24},
+    "nnUNetTrainerV2_3ConvPerStageSameFilters": {"conv_per_stage": 3},         # the class in nnUNetTrainerV2_3ConvPerStage_samefilters.py
+    "nnUNetTrainerV2_3ConvPerStage_samefilters": {"conv_per_stage": 3},
+    "nnUNetTrainerV2_allConv3x3": {"all_conv_3x3": True},
+    "nnUNetTrainerV2_noDeepSupervision": {},                                   # the heads below full resolution exist and are never evaluated
+    "nnUNetTrainerV2_softDeepSupervision": {},
+    "nnUNetTrainerV2_ResencUNet": None, "nnUNetTrainerV2_ResencUNet_DA3": None, "nnUNetTrainerV2_ResencUNet_DA3_BN": None,
+}
+_FRN = "nnUNetTrainerV2_FRN"
+
+
+def seg_variant_row(name, forced=None):
+    """The table row of a trainer's class name (forced: --seg_variant, a row chosen for a user's own subclass), or None: a name the table
+    does not know or a ResencUNet trainer -- the import goes on as it did.  nnUNetTrainerV2_FRN is refused by name."""
+    key = forced if forced is not None else str(name or "")
+    if key == _FRN:
+        raise NotImplementedError("%s: its 3-D network normalises with FRN3D (feature response normalisation with a learned threshold, "
+                                  "custom_modules/feature_response_normalization.py), which the build does not implement, and its 2-D "
+                                  "branch is BatchNorm2d(eps 1e-6) under an identity activation, which is not built either" % _FRN)
+    if forced is not None and SEG_VARIANTS.get(forced) is None:
+        raise ValueError("seg_variant %r is no row of the trainer-variant table (%s)" % (forced, ", ".join(k for k, v in SEG_VARIANTS.items() if v is not None)))
+    return SEG_VARIANTS.get(key)
+
+
+def _apply_seg_variant(plans, row):
+    """the row's keys into plans['seg_net'] (the translated plans); the two private entries change base_num_features / conv_kernel_sizes"""
+    sk = plans["seg_net"]
+    for k, v in row.items():
+        if k == "all_conv_3x3":
+            if "conv_kernel_sizes" in sk:
+                sk["conv_kernel_sizes"] = [[3] * len(ks) for ks in sk["conv_kernel_sizes"]]
+        else:
+            sk[k] = v
+
+
+def check_seg_variant(sd, row, trainer, path):
+    """The table row and the checkpoint must agree before check_state_dict's shape report can mislead: a ValueError that names the trainer
+    and the first offending key.  row = {} for a stock trainer (or an unknown name): then the checkpoint must hold a stock network's norms."""
+    what = "%s: trainer %s" % (path, trainer or "(unnamed)")
+    norm = row.get("norm", "in")
+    stats = sorted(k for k in sd if k.endswith((".running_mean", ".running_var")))
+    norms = sorted(k for k in sd if ".instnorm." in k and not k.endswith(_DERIVED_BUFFERS))
+    if norm == "bn":
+        for k in sorted(k for k in sd if k.endswith(".instnorm.weight")):
+            for leaf in ("running_mean", "running_var"):
+                twin = k[:-len("weight")] + leaf
+                if twin not in sd:
+                    raise ValueError("%s builds BatchNorm (seg_net.norm = 'bn'), but the checkpoint lacks %s" % (what, twin))
+        if not stats:
+            raise ValueError("%s builds BatchNorm (seg_net.norm = 'bn'), but the checkpoint holds no running statistics (first norm tensor: %s)"
+                             % (what, norms[0] if norms else "none"))
+    elif stats:
+        raise ValueError("%s builds seg_net.norm = %r, but the checkpoint holds BatchNorm running statistics: %s (a _BN trainer's folder? "
+                         "--seg_variant nnUNetTrainerV2_BN)" % (what, norm, stats[0]))
+    if norm == "none" and norms:
+        raise ValueError("%s builds no normalisation (seg_net.norm = 'none'), but the checkpoint holds %s" % (what, norms[0]))
+    biases = sorted(k for k in sd if re.fullmatch(r"seg_outputs\.\d+\.bias", k))
+    heads = sorted(k for k in sd if re.fullmatch(r"seg_outputs\.\d+\.weight", k))
+    if row.get("seg_output_bias", False):
+        for k in heads:
+            if k[:-len("weight")] + "bias" not in sd:
+                raise ValueError("%s builds segmentation heads with a bias (seg_net.seg_output_bias), but the checkpoint lacks %s"
+                                 % (what, k[:-len("weight")] + "bias"))
+    elif biases:
+        raise ValueError("%s builds bias-free segmentation heads, but the checkpoint holds %s" % (what, biases[0]))
+    cps = row.get("conv_per_stage", 2)
+    blocks = sorted({int(m.group(1)) for m in (re.match(r"conv_blocks_context\.0\.blocks\.(\d+)\.", k) for k in sd) if m})
+    if blocks and len(blocks) != cps:
+        raise ValueError("%s builds %d convolutions per stage (seg_net.conv_per_stage), but the checkpoint's first stage has %d: "
+                         "conv_blocks_context.0.blocks.%d" % (what, cps, len(blocks), min(len(blocks), cps)))
+    if "base_num_features" in row and _FIRST_CONV in sd and int(sd[_FIRST_CONV].shape[0]) != row["base_num_features"]:
+        raise ValueError("%s sets base_num_features = %d, but %s has %d output channels"
+                         % (what, row["base_num_features"], _FIRST_CONV, int(sd[_FIRST_CONV].shape[0])))
+
+
+def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size, window_size, seg_variant=None):
     """import_reference_model_folder without a flow folder: every check of the segmentation side, nothing of the flow side"""
     given = {k: v for k, v in dict(crop_weights=crop_weights, crop_config=crop_config, crop_size=crop_size, image_size=image_size,
                                    window_size=window_size).items() if v is not None}
@@ -534,6 +634,11 @@ def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config,
         # a `3d_cascade_fullres` folder (nnUNetTrainerCascadeFullRes.py:87-88: num_input_channels += num_classes - 1, background excluded):
         # the previous stage's foreground labels come in as one-hot channels (predict.py:176, classes = range(1, num_classes))
         plans["seg_net"]["prev_stage_classes"] = list(range(1, plans["num_classes"]))
+    row = None if resenc else seg_variant_row(name, seg_variant)
+    if resenc and seg_variant is not None:
+        raise ValueError("seg_variant %r: %s is a residual-encoder folder, which has no trainer variants here" % (seg_variant, seg_folder))
+    if row:
+        _apply_seg_variant(plans, row)
     trainer = CineTrainer(plans, torch.device("cpu"))                           # the network's key / shape list, no device work
     params = {}
     for f in folds:                                                             # every tensor of every fold is checked before anything is written
@@ -542,6 +647,8 @@ def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config,
         sd = load_reference_checkpoint(path, shapes)["state_dict"]
         if resenc:
             sd = _drop_resenc_aliases(sd, path)
+        else:
+            check_seg_variant(sd, row or {}, seg_variant or name, path)
         check_state_dict(sd, shapes, "segmentation network %s" % path)
         params[f] = {k: v for k, v in sd.items() if not k.endswith(_DERIVED_BUFFERS)}
     os.makedirs(out_folder, exist_ok=True)
@@ -651,6 +758,9 @@ def main(argv=None):
     parser.add_argument("--crop_config", default=None, help="the cropper's YAML (adversarial_acdc.yaml)")
     parser.add_argument("--seg_config", default=None, help="for a folder of nnMTLTrainerV2: the trainer's YAML (seg_model.yaml / the config.yaml "
                                                            "it wrote into its log folder); the folder is then imported as an MTLmodel segmenter, without -w")
+    parser.add_argument("--seg_variant", default=None, metavar="NAME",
+                        help="build the segmentation network as this trainer variant does (a class name of nnUNet_variants/architectural_variants, "
+                             "e.g. nnUNetTrainerV2_BN), whatever name the folder's .model.pkl holds: for a subclass of one's own")
     parser.add_argument("-f", "--folds", nargs="+", default="None")
     parser.add_argument("-chk", default="model_final_checkpoint", required=False)
     parser.add_argument("--crop_size", type=int, default=None)
@@ -658,7 +768,7 @@ def main(argv=None):
     parser.add_argument("--window_size", type=int, default=None)
     a = parser.parse_args(argv)
     plans = import_reference_model_folder(a.seg_folder, a.flow_weight_folder, a.output_folder, a.crop_weights, a.crop_config,
-                                          None if a.folds == "None" else a.folds, a.chk, a.crop_size, a.image_size, a.window_size, a.seg_config)
+                                          None if a.folds == "None" else a.folds, a.chk, a.crop_size, a.image_size, a.window_size, a.seg_config, a.seg_variant)
     if plans["seg_net"].get("arch") == "mtl":
         print("wrote %s (MTLmodel segmenter, image %d, crop %s, window %d, %d classes)" % (a.output_folder, plans["image_size"], plans.get("crop_size"),
                                                                                         plans["seg_net"]["window_size"], plans["num_classes"]))

@@ -116,7 +116,11 @@ class CineTrainer:
     plans['seg_net'] = {'arch': 'mtl', 'config': <seg_model.yaml values or file name>, 'window_size': 7, 'normalize': false} makes the network
     the fork's own MTLmodel (nnMTLTrainerV2): 2-D segmentation-only models alone, patch_size = [image_size, image_size]; built at
     crop_size behind the Processor when the plans hold a cropping_net, at image_size without one (nnMTLTrainerV2.py:598-610); every
-    fold's segmenter shares the one Processor, and tile batches go through MTLmodel.accumulate_tta_batch (inference.ensemble_predict_2d)."""
+    fold's segmenter shares the one Processor, and tile batches go through MTLmodel.accumulate_tta_batch (inference.ensemble_predict_2d).
+    With 'arch' absent, plans['seg_net'] may hold the choices of nnU-Net's architectural trainer variants (SEG_VARIANT_KEYS: norm,
+    norm_groups, nonlin, nonlin_slope, conv_per_stage, block_order, seg_output_bias; cascade stages included): Generic_UNet / Generic_UNet3D
+    are then built as that trainer built them, in every fold of load_ensemble.  Without them the network is the stock one; next to 'arch'
+    or 'flow_net', or with an unknown value, each is refused."""
 
     def __init__(self, plans, device, model_folder=None):
         self.plans = plans
@@ -141,6 +145,7 @@ class CineTrainer:
             if (plans.get("seg_net") or {}).get("prev_stage_classes") is not None:
                 raise ValueError("plans.json holds both seg_net.arch == 'resenc' and seg_net.prev_stage_classes: the reference has no cascade "
                                  "trainer for the residual-encoder U-Net")
+        self.seg_variant = _seg_variant_kwargs(plans.get("seg_net") or {}, arch, fk)
         if self.seg_dim == 3:
             if fk:
                 raise ValueError("plans.json holds both seg_net.dim == 3 and flow_net: the flow path is 2-D (a 3-D segmentation folder is segmentation-only)")
@@ -208,9 +213,10 @@ class CineTrainer:
                                  sk["conv_kernel_sizes"], self.num_classes, sk["num_blocks_decoder"])
         if self.seg_dim == 3:           # a `3d_fullres` stage: Generic_UNet with conv_op = nn.Conv3d, at most MAX_NUM_FILTERS_3D = 320 filters
             return Generic_UNet3D(self.plans["num_modalities"] + len(self.prev_stage_classes or ()), sk["base_num_features"], self.num_classes, sk["num_pool"],
-                                  pool_op_kernel_sizes=sk.get("pool_op_kernel_sizes"), conv_kernel_sizes=sk.get("conv_kernel_sizes"))
+                                  pool_op_kernel_sizes=sk.get("pool_op_kernel_sizes"), conv_kernel_sizes=sk.get("conv_kernel_sizes"), **self.seg_variant)
         return Generic_UNet(self.plans["num_modalities"], sk["base_num_features"], self.num_classes, sk["num_pool"],
-                            pool_op_kernel_sizes=sk.get("pool_op_kernel_sizes"))     # the plans' per-stage pooling (plans_per_stage[...]['pool_op_kernel_sizes'])
+                            pool_op_kernel_sizes=sk.get("pool_op_kernel_sizes"),     # the plans' per-stage pooling (plans_per_stage[...]['pool_op_kernel_sizes'])
+                            **self.seg_variant)
 
     # -- network_trainer.py:418 load_checkpoint_ram(params, train)
     def load_checkpoint_ram(self, params, train=False):
@@ -468,6 +474,56 @@ class CineTrainer:
             torch.cuda.synchronize()
             DEVICE_SPLIT["finish_s"] = DEVICE_SPLIT.get("finish_s", 0.0) + time.perf_counter() - t2
         return res
+
+
+# the trainer variants' choices in plans['seg_net'] (nnUNet_variants/architectural_variants): key -> (allowed values or None, default)
+SEG_VARIANT_KEYS = {
+    "norm": (("in", "gn", "bn", "none"), "in"),
+    "norm_groups": (None, 8),
+    "nonlin": (("lrelu", "relu", "gelu", "mish"), "lrelu"),
+    "nonlin_slope": (None, 0.01),
+    "conv_per_stage": (None, 2),
+    "block_order": (("conv_norm_nonlin", "conv_nonlin_norm"), "conv_norm_nonlin"),
+    "seg_output_bias": ((True, False), False),
+}
+
+
+def _seg_variant_kwargs(sk, arch, flow_net):
+    """plans['seg_net'] -> the keyword arguments Generic_UNet / Generic_UNet3D take for a trainer variant ({} for a folder without the
+    keys: exactly the stock network).  The keys belong to Generic_UNet alone: next to seg_net.arch or flow_net each is refused, like an
+    unknown value, with a ValueError naming both keys."""
+    given = [k for k in SEG_VARIANT_KEYS if k in sk]
+    for k in given:
+        if arch is not None:
+            raise ValueError("plans.json holds both seg_net.%s and seg_net.arch == %r: the trainer variants' keys belong to Generic_UNet "
+                             "(seg_net.arch absent)" % (k, arch))
+        if flow_net:
+            raise ValueError("plans.json holds both seg_net.%s and flow_net: the segmentation network next to the flow network is the stock "
+                             "Generic_UNet (a trainer variant's folder is segmentation-only)" % k)
+        allowed, v = SEG_VARIANT_KEYS[k][0], sk[k]
+        if allowed is not None and (v not in allowed or (isinstance(v, bool) != isinstance(allowed[0], bool))):
+            raise ValueError("seg_net.%s must be one of %s, got %r" % (k, ", ".join(repr(a) for a in allowed), v))
+    def num(k, lo, integer):
+        v = sk[k]
+        if isinstance(v, bool) or not isinstance(v, (int,) if integer else (int, float)) or not v >= lo:
+            raise ValueError("seg_net.%s must be %s >= %s, got %r" % (k, "an integer" if integer else "a number", lo, v))
+        return v
+    kw = {}
+    if "norm" in sk:
+        kw["norm"] = sk["norm"]
+    if "norm_groups" in sk:
+        kw["norm_groups"] = num("norm_groups", 1, True)          # read with norm == 'gn'
+    if "nonlin" in sk:
+        kw["nonlin"] = sk["nonlin"]
+    if "nonlin_slope" in sk:
+        kw["nonlin_slope"] = float(num("nonlin_slope", 0.0, False))          # read with nonlin == 'lrelu'
+    if "conv_per_stage" in sk:
+        kw["num_conv_per_stage"] = num("conv_per_stage", 2, True)
+    if "block_order" in sk:
+        kw["block_order"] = sk["block_order"]
+    if "seg_output_bias" in sk:
+        kw["seg_output_bias"] = sk["seg_output_bias"]
+    return kw
 
 
 def _check_mtl_plans(plans, seg_dim, flow_net):

@@ -35,6 +35,7 @@ extern "C" {
 #define CF_ACT_LRELU 3   /* LeakyReLU(0.01), generic_UNet.py:38          */
 #define CF_ACT_TANH 4
 #define CF_ACT_SIGMOID 5
+#define CF_ACT_MISH 6    /* x tanh(softplus(x)); cf_coef_apply only       */
 
 /* residual placement for cf_group_norm */
 #define CF_RES_NONE 0
@@ -243,6 +244,21 @@ int cf_group_norm_coef(const double* ws, const float* gamma, const float* beta, 
  * in channel order; w is the [K][C] weight, bias may be NULL. */
 int cf_norm_head_1x1(const float* x, const float* coef, float slope, const float* w, const float* bias, float* out, int B, int C, int HW,
                      int K, void* stream);
+/* Normalisations whose table is not made of statistics of the map, and the apply pass that takes a table (csrc/norm_coef.hip): what
+ * nnU-Net's trainer variants need beside InstanceNorm + LeakyReLU(0.01).
+ * cf_batch_norm_coef: BatchNorm in eval mode -> coef float [B][3][C] = {running_mean, gamma / sqrt(running_var + eps), beta}, the same
+ * rows for every sample: layout and meaning of cf_group_norm_coef's output, so every consumer of that table takes this one.  gamma / beta
+ * may be NULL (1 / 0).
+ * cf_coef_apply: out = act((x - mean) * scale + shift) on x [B][C][HW] with mean / scale / shift from coef [B][3][C]; coef == NULL applies
+ * the activation alone.  act is a CF_ACT_* code (CF_ACT_MISH included); CF_ACT_LRELU uses `slope` (>= 0) instead of the fixed 0.01 of the
+ * fused epilogues, every other code ignores it.  out may be x.  x and out need 4-byte alignment only: rows are read and written in 16-byte
+ * pieces between a scalar head and tail wherever x and out agree modulo 16, one value at a time otherwise; HW is arbitrary.  An NCDHW
+ * tensor is passed as its [B][C][D*H*W] rows.  cf_coef_apply_ok (host code, no launch) returns 1 when the index arithmetic holds the
+ * shape (HW <= 2^30, B * C * HW <= 2^40), and the call fails with CF_ERR_ARG otherwise. */
+int cf_batch_norm_coef(const float* running_mean, const float* running_var, const float* gamma, const float* beta, float eps, int B, int C,
+                       float* coef, void* stream);
+int cf_coef_apply_ok(int B, int C, long HW);
+int cf_coef_apply(const float* x, const float* coef, int act, float slope, float* out, int B, int C, int HW, void* stream);
 /* Tuning / A-B knob without a reference counterpart: the short-K layers on large maps (3x3, stride 1, 32 or 64 output channels, >= 1024 tiles of
  * 16 / 8 rows x 32 pixels) run on a persistent software-pipelined kernel (csrc/conv_stream.hip) that sums the taps of a chunk in (kx, ky)
  * instead of (ky, kx) order: outputs equal the one-tile-per-workgroup kernel's to fp32 summation-order noise (<= 4e-6 of the output scale).
