@@ -93,6 +93,9 @@ SIGNATURES = {
     "cf_flip3d": [P, P, I, I, I, I, I, I, I, P],
     "cf_tile_accumulate_3d": [P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     "cf_argmax_channels": [P, P, I, I, I, P],
+    "cf_tta_accumulate_nonlin": [P, P, I, I, I, I, I, I, F, I, P],
+    "cf_tta_accumulate_3d_nonlin": [P, P, I, I, I, I, I, I, I, I, F, I, P],
+    "cf_region_labels": [P, P, I, I, L, P, P],
     "cf_resize3d": [P, P, I, I, I, I, I, I, I, I, I, I, P],
     "cf_cc_init": [P, P, L, P, I, P],
     "cf_cc_sweep": [P, I, I, I, P, P],

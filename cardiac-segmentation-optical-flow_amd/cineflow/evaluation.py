@@ -9,11 +9,20 @@ device works on the current one, and only this process opens the GPU.  The surfa
 cineflow.metrics.label_surface_edt_table, linear in the volume -- the route for 3-D organs); auto picks by the size of the borders.
 
     python -m cineflow.evaluation -ref GT_FOLDER -pred PRED_FOLDER -l 1 2 3 [--surface auto|pairs|edt] [--surface_dice MM]
+
+Region-based evaluation (nnunet/evaluation/region_based_evaluation.py: get_brats_regions, get_KiTS_regions, create_region_from_mask,
+evaluate_case, evaluate_regions; same names and summary.csv layout), restated: a region is a set of label values, each case is read once,
+its K x K label confusion is counted by one cf_label_confusion launch, and every region's |P n G|, |P| and |G| are sums of its cells.
+Dice = 2 |P n G| / (|P| + |G|), NaN when both are empty -- the value medpy's metric.dc gives; medpy and SimpleITK are not used, so parity
+of summary.csv with the reference's file is by this restatement, not pinned against a run of it.
+
+    python -m cineflow.evaluation --regions brats|kits|JSON -ref GT_FOLDER -pred PRED_FOLDER
 """
 import collections
 import hashlib
 import inspect
 import json
+import warnings
 from collections import OrderedDict
 from concurrent.futures import ThreadPoolExecutor
 from datetime import datetime
@@ -405,13 +414,124 @@ def evaluate_folder(folder_with_gts, folder_with_predictions, labels, **metric_k
                             rv_rejection=True, **metric_kwargs)
 
 
+# ------------------------------------------------------------------------------------------------ region-based evaluation
+def get_brats_regions():
+    """the BraTS regions on the labels 1, 2, 3 of the nnU-Net conversion (not the original BraTS convention)"""
+    return {"whole tumor": (1, 2, 3), "tumor core": (2, 3), "enhancing tumor": (3,)}
+
+
+def get_KiTS_regions():
+    return {"kidney incl tumor": (1, 2), "tumor": (2,)}
+
+
+def create_region_from_mask(mask, join_labels):
+    """uint8 mask of the voxels of `mask` that hold one of `join_labels`"""
+    return np.isin(np.asarray(mask), list(join_labels)).astype(np.uint8)
+
+
+def _region_dice(hist, region):
+    """hist[test label, reference label] -> Dice of the region (the union of its label values); NaN when it is empty in both"""
+    idx = sorted(set(int(c) for c in region))
+    n_pred, n_gt = int(hist[idx, :].sum()), int(hist[:, idx].sum())
+    if n_pred == 0 and n_gt == 0:
+        return float("nan")
+    return 2.0 * int(hist[np.ix_(idx, idx)].sum()) / float(n_pred + n_gt)
+
+
+def _label_histogram(pred, gt, what):
+    """[K,K] counts of (pred label, gt label) with K = 1 + the largest label: cf_label_confusion on the device where both volumes hold
+    labels below HIST_K (every nnU-Net label set in practice), numpy's bincount otherwise"""
+    pred, gt = np.asarray(pred), np.asarray(gt)
+    if pred.shape != gt.shape:
+        raise ValueError("%s: prediction %s and ground truth %s differ in shape" % (what, pred.shape, gt.shape))
+    ev = Evaluator(pred, gt, labels=[])
+    got = ev._histogram()
+    if got is not None:
+        return got[0]
+    if pred.min() < 0 or gt.min() < 0 or np.any(pred != np.round(pred)) or np.any(gt != np.round(gt)):
+        raise ValueError("%s: label volumes must hold non-negative integers" % what)
+    p, g = pred.astype(np.int64).ravel(), gt.astype(np.int64).ravel()
+    K = int(max(p.max(), g.max())) + 1
+    return np.bincount(p * K + g, minlength=K * K).reshape(K, K)
+
+
+def _score_regions(pred, gt, regions, what="case"):
+    hist = _label_histogram(pred, gt, what)
+    K = hist.shape[0]
+    out = []
+    for r in regions:
+        inside = [c for c in r if 0 <= int(c) < K]                   # a label value beyond the histogram occurs in neither volume
+        out.append(_region_dice(hist, inside) if inside else float("nan"))
+    return out
+
+
+def evaluate_case(file_pred, file_gt, regions):
+    """Dice of every region (a list of label tuples) between two label files, NaN for a region empty in both; each file is read once"""
+    return _score_regions(load_volume(file_pred).array, load_volume(file_gt).array, regions, file_pred)
+
+
+def evaluate_regions(folder_predicted, folder_gt, regions, processes=8):
+    """Scores every .nii.gz of folder_predicted against the file of the same name in folder_gt, region by region (regions: an ordered
+    {name: labels}), and writes folder_predicted/summary.csv: one row per case, then mean, median (both ignoring NaN) and the two with NaN
+    counted as 1, every number as "%02.4f".  A prediction without ground truth is an error, ground truth without a prediction a warning.
+    processes: reader threads (files are read and inflated ahead of the device); only this process opens the GPU.
+    Returns {region name: [Dice per case]}."""
+    names = list(regions.keys())
+    files_pred = subfiles(folder_predicted, suffix=".nii.gz", join_=False)
+    files_gt = subfiles(folder_gt, suffix=".nii.gz", join_=False)
+    assert all(f in files_gt for f in files_pred), "Some files in folder_predicted have not ground truth in folder_gt"
+    if any(f not in files_pred for f in files_gt):
+        print("WARNING! Some files in folder_gt were not predicted (not present in folder_predicted)!")
+    files_pred.sort()
+    region_labels = [tuple(v) for v in regions.values()]
+    with ThreadPoolExecutor(max_workers=max(1, int(processes))) as pool:
+        loads = [(pool.submit(load_volume, join(folder_predicted, f)), pool.submit(load_volume, join(folder_gt, f))) for f in files_pred]
+        res = [_score_regions(p.result().array, g.result().array, region_labels, f) for f, (p, g) in zip(files_pred, loads)]
+    scores = {r: [case[k] for case in res] for k, r in enumerate(names)}
+    as_one = {r: np.where(np.isnan(v), 1.0, v) for r, v in ((r, np.asarray(scores[r], dtype=np.float64)) for r in names)}
+
+    def row(title, values):
+        return title + "".join(",%02.4f" % v for v in values) + "\n"
+
+    with open(join(folder_predicted, "summary.csv"), "w") as f, warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)               # a region that is NaN in every case: nanmean of nothing is NaN
+        f.write("casename" + "".join(",%s" % r for r in names) + "\n")
+        for name, case in zip(files_pred, res):
+            f.write(row(name[:-7], case))
+        f.write(row("mean", [np.nanmean(scores[r]) for r in names]))
+        f.write(row("median", [np.nanmedian(scores[r]) for r in names]))
+        f.write(row("mean (nan is 1)", [np.mean(as_one[r]) for r in names]))
+        f.write(row("median (nan is 1)", [np.median(as_one[r]) for r in names]))
+    return scores
+
+
+REGION_SETS = {"brats": get_brats_regions, "kits": get_KiTS_regions}
+
+
+def parse_regions(spec):
+    """--regions: 'brats', 'kits' or a JSON object {region name: [label values]} -> ordered {name: tuple of labels}"""
+    if spec in REGION_SETS:
+        return REGION_SETS[spec]()
+    try:
+        regions = json.loads(spec)
+    except ValueError as e:
+        raise ValueError("--regions %r is neither brats, kits nor a JSON object {region name: [labels]}: %s" % (spec, e))
+    if not isinstance(regions, dict) or not regions or any(not isinstance(v, list) or not v for v in regions.values()):
+        raise ValueError("--regions %r must be a non-empty JSON object {region name: non-empty list of labels}" % (spec,))
+    return OrderedDict((str(k), tuple(int(c) for c in v)) for k, v in regions.items())
+
+
 def build_parser():
     import argparse
     parser = argparse.ArgumentParser(description="Scores the label files of -pred against those of -ref and writes PRED/summary.json: the "
                                                  "scores of every case under 'all', their means over the cases under 'mean'.")
     parser.add_argument("-ref", required=True, type=str, help="folder of the reference label files (.nii.gz)")
     parser.add_argument("-pred", required=True, type=str, help="folder of the predicted label files, named like the reference ones")
-    parser.add_argument("-l", nargs="+", type=int, required=True, help="label values to score, e.g. -l 1 2 3 (0 is the background)")
+    parser.add_argument("-l", nargs="+", type=int, default=None,
+                        help="label values to score, e.g. -l 1 2 3 (0 is the background); required unless --regions is given")
+    parser.add_argument("--regions", default=None, metavar="brats|kits|JSON",
+                        help="region-based evaluation instead (-l is not read): Dice per region into PRED/summary.csv; brats, kits, or a JSON "
+                             "object {region name: [labels]}")
     parser.add_argument("--surface", choices=("auto", "pairs", "edt"), default="auto",
                         help="how the surface metrics find their distances: pairs = all-pairs search (small objects), edt = exact distance "
                              "transform, one device visit per case (3-D organs), auto = pairs unless an object is large (default)")
@@ -421,7 +541,12 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.regions is not None:
+        return evaluate_regions(args.pred, args.ref, parse_regions(args.regions))
+    if args.l is None:
+        parser.error("the following arguments are required: -l (or --regions)")
     extra = {} if args.surface_dice is None else {"surface_dice_threshold": args.surface_dice}
     return evaluate_folder(args.ref, args.pred, args.l, surface=args.surface, **extra)
 

@@ -26,6 +26,20 @@ def get_lowres_axis(new_spacing):
     return np.where(max(new_spacing) / np.array(new_spacing) == 1)[0]
 
 
+def probabilities_as_stored(probs, region_class_order=None):
+    """The fp16 array a `-z` run stores.  Softmax models: numpy's round-to-nearest, as the reference stores it.  Region models paint a label
+    where p > 0.5, and fp16 has no value between 0.5 and 0.5 + 2^-11: round-to-nearest turns every p in (0.5, 0.5 + 2^-12] into 0.5, which
+    is no longer `> 0.5`, so the stored member would contradict the label file written from the same probabilities (on a seeded 3-D case 21
+    of 5376 voxels).  Those values alone are rounded UP to the next fp16 instead (0.5 + 2^-11: one unit in the last place instead of a
+    half); nothing at or below 0.5 can round above it, 0.5 being an fp16 value.  So `stored > 0.5` exactly where `p > 0.5`, and
+    cineflow.ensemble_predictions on a folder and its copy writes the folder's own label files."""
+    stored = probs.astype(np.float16)
+    if region_class_order is not None:
+        half = np.float16(0.5)
+        stored[(probs > 0.5) & (stored <= half)] = np.nextafter(half, np.float16(1))
+    return stored
+
+
 def save_segmentation_nifti_from_softmax(segmentation_softmax, out_fname, properties_dict, order=1, region_class_order=None,
                                          seg_postprogess_fn=None, seg_postprocess_args=None, resampled_npz_fname=None,
                                          non_postprocessed_fname=None, force_separate_z=None, interpolation_order_z=0, verbose=True,
@@ -82,7 +96,9 @@ def save_segmentation_nifti_from_softmax(segmentation_softmax, out_fname, proper
             print("no resampling necessary")
         seg_old_spacing = segmentation_softmax
     if resampled_npz_fname is not None:
-        np.savez_compressed(resampled_npz_fname, softmax=seg_old_spacing.astype(np.float16))
+        np.savez_compressed(resampled_npz_fname, softmax=probabilities_as_stored(seg_old_spacing, region_class_order))
+        if region_class_order is not None:                                       # segmentation_export.py:141-142: an ensemble member says so itself
+            properties_dict["regions_class_order"] = region_class_order
         if properties_pkl:
             with open(resampled_npz_fname[:-4] + ".pkl", "wb") as f:
                 pickle.dump(properties_dict, f)

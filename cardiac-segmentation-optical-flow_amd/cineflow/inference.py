@@ -81,6 +81,21 @@ def flip_variants(mirror_axes=(0, 1), do_mirroring=True):
     return variants
 
 
+def inference_nonlin(net):
+    """the network's inference_apply_nonlin: "softmax" (also for networks without the attribute) or "sigmoid" (region heads)"""
+    nonlin = getattr(net, "inference_apply_nonlin", "softmax")
+    if nonlin not in ops.NONLIN_CODES:
+        raise ValueError("inference_apply_nonlin must be 'softmax' or 'sigmoid', got %r" % (nonlin,))
+    return nonlin
+
+
+def _labels(prob, argmax_seg, regions_class_order):
+    """the label map of merged probabilities [N,K,...]: the merge's arg-max, or with a regions_class_order the region rule on `prob`"""
+    if regions_class_order is None:
+        return argmax_seg
+    return ops.region_labels(prob.contiguous(), regions_class_order)
+
+
 def mirror_and_predict_2d(net, x, mirror_axes=(0, 1), do_mirroring=True, mult=None, acc=None, weight=None):
     """SegmentationNetwork._internal_maybe_mirror_and_pred_2D, neural_network.py:573-621 (upstream 4-argument
     semantics).  x [B,C,X,Y] on the GPU; returns the TTA-averaged softmax [B,K,X,Y] (times `mult` [X,Y]).
@@ -92,9 +107,10 @@ def mirror_and_predict_2d(net, x, mirror_axes=(0, 1), do_mirroring=True, mult=No
         acc = torch.zeros((B, net.num_classes, X, Y), dtype=torch.float32, device=x.device)
     n = 2 ** len(mirror_axes) if do_mirroring else 1
     w = 1.0 / n if weight is None else weight
+    nonlin = inference_nonlin(net)
     for fh, fw in flip_variants(mirror_axes, do_mirroring):
         xin = x if (fh, fw) == (0, 0) else ops.flip2d(x, fh, fw)
-        ops.tta_accumulate(net(xin), acc, fh, fw, w)
+        ops.tta_accumulate(net(xin), acc, fh, fw, w, nonlin)
     if mult is not None:
         assert not shared, "a shared accumulator is weighted by its owner"
         ops.mul(acc, mult, out=acc)
@@ -137,8 +153,9 @@ TILE_JOBS_PER_LAUNCH = int(os.environ.get("CF_TILE_JOBS", "64"))
 
 
 def _predict_cine_tiled_device(nets, volumes, patch_size, step_size, do_mirroring, mirror_axes, use_gaussian, pad_border_mode, pad_kwargs,
-                               max_batch):
-    """predict_cine_2Dconv_tiled up to the host copies: per volume (seg uint8 [Z,X,Y], softmax [K,Z,X,Y]) as device tensors."""
+                               max_batch, regions_class_order=None):
+    """predict_cine_2Dconv_tiled up to the host copies: per volume (seg uint8 [Z,X,Y], softmax [K,Z,X,Y]) as device tensors.
+    regions_class_order: the labels are the region rule on the merged probabilities (ops.region_labels) instead of the merge's arg-max."""
     nets = list(nets) if isinstance(nets, (list, tuple)) else [nets]
     patch_size = tuple(int(v) for v in patch_size)
     max_batch = int(max_batch or TILE_JOBS_PER_LAUNCH)
@@ -171,6 +188,7 @@ def _predict_cine_tiled_device(nets, volumes, patch_size, step_size, do_mirrorin
             batch = ops.tile_gather(vol, jobs[j0:j1], patch_size[0], patch_size[1])
             ensemble_predict_2d(nets, batch, mirror_axes, do_mirroring, gauss, acc=pred[j0:j1])
         seg, prob = ops.tile_merge(pred, gauss, Xp, Yp, steps[0], steps[1])                                 # [N,Xp,Yp], [N,K,Xp,Yp]
+        seg = _labels(prob, seg, regions_class_order)
         del pred
         n0 = 0
         for i in idx:
@@ -181,7 +199,7 @@ def _predict_cine_tiled_device(nets, volumes, patch_size, step_size, do_mirrorin
 
 
 def predict_cine_2Dconv_tiled(nets, volumes, patch_size, step_size=0.5, do_mirroring=True, mirror_axes=(0, 1), use_gaussian=True,
-                              pad_border_mode="constant", pad_kwargs=None, max_batch=None):
+                              pad_border_mode="constant", pad_kwargs=None, max_batch=None, regions_class_order=None):
     """SegmentationNetwork._internal_predict_3D_2Dconv_tiled (neural_network.py:814-857) for MANY volumes and an ensemble of networks.
     volumes: list of numpy [C,Z_i,X_i,Y_i] (all frames of a patient, or of several patients); nets: one network or a list (the folds).
     Returns per volume (seg [Z,X,Y] uint8, softmax [K,Z,X,Y] fp32): the mean over the networks of predict_3D_2Dconv_tiled's softmax.
@@ -189,14 +207,15 @@ def predict_cine_2Dconv_tiled(nets, volumes, patch_size, step_size=0.5, do_mirro
     Every volume is padded as predict_3D_2Dconv_tiled pads it (pad_nd_image, the same step lists); volumes with one padded in-plane shape
     are stacked on the slice axis and share one job table.  Per chunk of `max_batch` jobs (default TILE_JOBS_PER_LAUNCH): cf_tile_gather
     cuts the tiles, every network's flips accumulate into the chunk's rows of the prediction buffer; one cf_tile_merge per group weights,
-    normalises and arg-maxes all slices (bit-identical to the per-tile cf_tile_accumulate + per-slice cf_tile_finalize sequence)."""
+    normalises and arg-maxes all slices (bit-identical to the per-tile cf_tile_accumulate + per-slice cf_tile_finalize sequence).
+    regions_class_order (region-based networks, inference_apply_nonlin == "sigmoid"): seg is the region rule on the merged probabilities."""
     res = _predict_cine_tiled_device(nets, volumes, patch_size, step_size, do_mirroring, mirror_axes, use_gaussian, pad_border_mode,
-                                     pad_kwargs, max_batch)
+                                     pad_kwargs, max_batch, regions_class_order)
     return [(s.cpu().numpy(), p.cpu().numpy()) for s, p in res]
 
 
 def predict_3D_2Dconv_tiled(net, x, patch_size, step_size=0.5, do_mirroring=True, mirror_axes=(0, 1), use_gaussian=True,
-                            pad_border_mode="constant", pad_kwargs=None, max_batch=64, return_device=False):
+                            pad_border_mode="constant", pad_kwargs=None, max_batch=64, return_device=False, regions_class_order=None):
     """SegmentationNetwork._internal_predict_3D_2Dconv_tiled (neural_network.py:814-857) over
     _internal_predict_2D_2Dconv_tiled (:623-769).  x: numpy [C,Z,X,Y] -> (seg [Z,X,Y] uint8, softmax [K,Z,X,Y] fp32).
     All Z slices and all tiles are batched through the network (the reference loops tile by tile)."""
@@ -227,7 +246,8 @@ def predict_3D_2Dconv_tiled(net, x, patch_size, step_size=0.5, do_mirroring=True
         s, p = ops.tile_finalize(agg[z], cnt[z])
         segs.append(s)
         probs.append(p)
-    seg = torch.stack(segs, 0)[:, slicer[2], slicer[3]]
+    seg = torch.stack(segs, 0) if regions_class_order is None else ops.region_labels(torch.stack(probs, 0), regions_class_order)   # (:749-751)
+    seg = seg[:, slicer[2], slicer[3]]
     prob = torch.stack(probs, 1)[:, :, slicer[2], slicer[3]]
     if return_device:
         return seg, prob
@@ -246,16 +266,17 @@ def mirror_and_predict_3d(net, x, mirror_axes=(0, 1, 2), do_mirroring=True, mult
             f = (bool(m & 4), bool(m & 2), bool(m & 1))
             if all((not f[a]) or (a in mirror_axes) for a in range(3)):
                 variants.append(tuple(int(v) for v in f))
+    nonlin = inference_nonlin(net)
     for f in variants:
         xin = x if f == (0, 0, 0) else ops.flip3d(x, *f)
-        ops.tta_accumulate_3d(net(xin), acc, f[0], f[1], f[2], 1.0 / n)
+        ops.tta_accumulate_3d(net(xin), acc, f[0], f[1], f[2], 1.0 / n, nonlin)
     if mult is not None:
         ops.mul(acc, mult, out=acc)
     return acc
 
 
 def predict_3D_3Dconv_tiled(net, x, patch_size, step_size=0.5, do_mirroring=True, mirror_axes=(0, 1, 2), use_gaussian=True,
-                            pad_border_mode="constant", pad_kwargs=None, return_device=False):
+                            pad_border_mode="constant", pad_kwargs=None, return_device=False, regions_class_order=None):
     """SegmentationNetwork._internal_predict_3D_3Dconv_tiled (neural_network.py:292-430).  x: numpy [C,X,Y,Z] ->
     (seg [X,Y,Z] uint8, softmax [K,X,Y,Z] fp32).  Volume, aggregation buffers and Gaussian stay on the GPU; one 3-D patch
     per network call as in the reference."""
@@ -277,6 +298,7 @@ def predict_3D_3Dconv_tiled(net, x, patch_size, step_size=0.5, do_mirroring=True
         pred = mirror_and_predict_3d(net, tile, mirror_axes, do_mirroring, gauss)
         ops.tile_accumulate_3d(pred[0], gauss, agg, cnt, lx, ly, lz)
     seg, prob = ops.tile_finalize(agg.view(K, Xp, Yp * Zp), cnt.view(K, Xp, Yp * Zp))
+    seg = _labels(prob[None], seg[None], regions_class_order)[0]                          # (neural_network.py:414-418 with an order)
     seg = seg.view(Xp, Yp, Zp)[slicer[1], slicer[2], slicer[3]]
     prob = prob.view(K, Xp, Yp, Zp)[:, slicer[1], slicer[2], slicer[3]]
     if return_device:

@@ -518,6 +518,9 @@ class Generic_UNet(Module):
     full-resolution logits (deep supervision off at inference)."""
 
     MAX_FILTERS_2D = 480
+    # the reference's network attribute of the same name (a callable there): "softmax" over the classes, or "sigmoid" per channel for a
+    # region-based head (nnUNetTrainerV2BraTSRegions*).  Read by the TTA accumulation (cineflow.inference), never by forward: logits leave raw.
+    inference_apply_nonlin = "softmax"
 
     @staticmethod
     def block_kwargs(norm="in", norm_groups=8, nonlin="lrelu", nonlin_slope=0.01, block_order="conv_norm_nonlin"):
@@ -759,6 +762,8 @@ class FabiansUNet3D(Module):
     """generic_modular_residual_UNet.py:305-337 as nnUNetTrainerV2_ResencUNet.py:25-45 builds it: residual encoder, plain conv decoder,
     conv_op = nn.Conv3d, InstanceNorm3d(affine), LeakyReLU(0.01), features doubling per stage up to max_features = 320.  Same state_dict
     keys as the reference.  forward: [B,C,D,H,W] -> full-resolution logits [B,K,D,H,W] (deep supervision off at inference)."""
+
+    inference_apply_nonlin = "softmax"      # as Generic_UNet.inference_apply_nonlin
 
     def __init__(self, input_channels, base_num_features, num_blocks_per_stage_encoder, pool_op_kernel_sizes, conv_kernel_sizes, num_classes,
                  num_blocks_per_stage_decoder, max_features=320):

@@ -928,11 +928,25 @@ def pad2d(src, y0, x0, H, W):
     return dst
 
 
-def tta_accumulate(logits, acc, flip_h, flip_w, weight):
+NONLIN_CODES = {"softmax": 0, "sigmoid": 1}     # CF_NONLIN_* of include/cineflow.h
+
+
+def _nonlin_code(nonlin):
+    if nonlin not in NONLIN_CODES:
+        raise ValueError("nonlin must be 'softmax' or 'sigmoid', got %r" % (nonlin,))
+    return NONLIN_CODES[nonlin]
+
+
+def tta_accumulate(logits, acc, flip_h, flip_w, weight, nonlin="softmax"):
+    """acc += weight * flip(nonlin(logits)); nonlin "softmax" over K (the default, cf_tta_accumulate) or "sigmoid" per channel (region heads)."""
     B, K, H, W = logits.shape
     assert acc.shape == logits.shape
-    check(lib().cf_tta_accumulate(_f32(logits), _f32(acc), B, K, H, W, int(flip_h), int(flip_w), float(weight), _stream()),
-          "cf_tta_accumulate")
+    if nonlin == "softmax":
+        check(lib().cf_tta_accumulate(_f32(logits), _f32(acc), B, K, H, W, int(flip_h), int(flip_w), float(weight), _stream()),
+              "cf_tta_accumulate")
+    else:
+        check(lib().cf_tta_accumulate_nonlin(_f32(logits), _f32(acc), B, K, H, W, int(flip_h), int(flip_w), float(weight), _nonlin_code(nonlin),
+                                             _stream()), "cf_tta_accumulate_nonlin")
     return acc
 
 
@@ -1001,11 +1015,15 @@ def tile_merge(pred, gauss, X, Y, lx, ly):
     return seg, probs
 
 
-def tta_accumulate_3d(logits, acc, flip_d, flip_h, flip_w, weight):
+def tta_accumulate_3d(logits, acc, flip_d, flip_h, flip_w, weight, nonlin="softmax"):
     B, K, D, H, W = logits.shape
     assert acc.shape == logits.shape
-    check(lib().cf_tta_accumulate_3d(_f32(logits), _f32(acc), B, K, D, H, W, int(flip_d), int(flip_h), int(flip_w), float(weight),
-                                     _stream()), "cf_tta_accumulate_3d")
+    if nonlin == "softmax":
+        check(lib().cf_tta_accumulate_3d(_f32(logits), _f32(acc), B, K, D, H, W, int(flip_d), int(flip_h), int(flip_w), float(weight),
+                                         _stream()), "cf_tta_accumulate_3d")
+    else:
+        check(lib().cf_tta_accumulate_3d_nonlin(_f32(logits), _f32(acc), B, K, D, H, W, int(flip_d), int(flip_h), int(flip_w), float(weight),
+                                                _nonlin_code(nonlin), _stream()), "cf_tta_accumulate_3d_nonlin")
     return acc
 
 
@@ -1029,6 +1047,27 @@ def argmax_channels(x):
     HW = x.numel() // (B * K)
     out = torch.empty((B,) + tuple(x.shape[2:]), dtype=torch.uint8, device=x.device)
     check(lib().cf_argmax_channels(_f32(x), _u8(out), B, K, HW, _stream()), "cf_argmax_channels")
+    return out
+
+
+def check_regions_class_order(order, K, who="regions_class_order"):
+    """the K label values of a region head as a list of ints in 0..255"""
+    order = [int(c) for c in order]
+    if len(order) != K or any(c < 0 or c > 255 for c in order):
+        raise ValueError("%s must hold one label in 0..255 per region channel (%d), got %r" % (who, K, order))
+    return order
+
+
+def region_labels(probs, regions_class_order):
+    """probs [B,K,...] fp32 (one sigmoid channel per region) -> uint8 [B,...]: 0, overwritten by regions_class_order[i] where probs[:, i] > 0.5,
+    i = 0..K-1 in that order (neural_network.py:749-751; the rule ensemble_merge applies to a mean)."""
+    import ctypes
+    B, K = probs.shape[0], probs.shape[1]
+    order = check_regions_class_order(regions_class_order, K)
+    HW = probs.numel() // max(B * K, 1)
+    out = torch.empty((B,) + tuple(probs.shape[2:]), dtype=torch.uint8, device=probs.device)
+    corder = (ctypes.c_uint8 * K)(*order)
+    check(lib().cf_region_labels(_f32(probs), _u8(out), B, K, HW, ctypes.cast(corder, ctypes.c_void_p), _stream()), "cf_region_labels")
     return out
 
 

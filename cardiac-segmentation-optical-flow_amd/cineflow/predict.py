@@ -164,7 +164,10 @@ def _submit_export(pool, trainer, export_kw, seg, softmax, npz, **kwargs):
         kwargs["resampled_npz_fname"] = npz
     if softmax is not None:
         kwargs["segmentation_softmax"] = _to_file_axes(softmax, trainer.plans)
-    else:
+        # a region-based model: the labels of the (possibly resampled) probabilities follow the region rule, and the .pkl next to the npz
+        # records the order (segmentation_export.py:141-150); None for every other model
+        kwargs["region_class_order"] = getattr(trainer, "regions_class_order", None)
+    else:                                        # (a region-based model's device labels are region labels already)
         kwargs.update(segmentation_softmax=None, seg_precomputed=_to_file_axes(seg, trainer.plans))
     return pool.apply_async(_timed_export, (trainer.device,), dict(export_kw, verbose=False, **kwargs))
 

@@ -32,6 +32,7 @@ seg_net.arch = 'mtl' folder: the fork's own MTLmodel segmenter, behind the 2-cla
 (`--crop_weights`, `--crop_config` are then required).
 
 Command line:  python -m cineflow.reference_models -s SEG [-w FLOW] -o OUT [--seg_config Y] [--crop_weights F --crop_config Y] [-f FOLDS] [-chk NAME] [--seg_variant NAME]
+               [--seg_regions NAME_OR_JSON] [--seg_regions_class_order L [L ...]]
 """
 import argparse
 import os
@@ -357,7 +358,7 @@ def _trainer_info(fold_dir, checkpoint_name):
 
 def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, crop_weights=None, crop_config=None, folds=None,
                                   checkpoint_name="model_final_checkpoint", crop_size=None, image_size=None, window_size=None, seg_config=None,
-                                  seg_variant=None):
+                                  seg_variant=None, seg_regions=None, seg_regions_class_order=None):
     """seg_folder: output folder of a 2-D nnU-Net trainer (plans.pkl, fold_X/); flow_weight_folder: the `-w` folder of run_training.py
     (config.yaml, <task>/fold_X/) or its <task> folder; crop_weights / crop_config: optionally the MTLmodel cropper's checkpoint and its
     YAML (nnMTLTrainerV2FlowSuccessive.py:482-484, adversarial_acdc.yaml).  Writes `out_folder` in the plans.json format (save_model_folder):
@@ -369,6 +370,9 @@ def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, cr
     patches (SegFlowGaussian.py:366), which become plans['patch_size']; the segmentation stage's own patch stays in plans_per_stage.
     flow_weight_folder=None imports the segmentation folder on its own (a segmentation-only model folder: the stage's patch size stays
     plans['patch_size'], no 'flow_net' / 'crop_size'; a cropper or crop_size / image_size / window_size make no sense then and are refused).
+    A folder of a region trainer (REGION_TRAINERS, or seg_regions / seg_regions_class_order for a subclass of one's own: seg_regions_spec)
+    gets seg_net.regions / seg_net.regions_class_order and num_classes = len(regions); it is segmentation-only, 2-D or 3-D Generic_UNet
+    or the residual-encoder U-Net.
     Returns the plans written."""
     from . import config as C
     if not os.path.isfile(join(seg_folder, "plans.pkl")):
@@ -378,6 +382,9 @@ def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, cr
     if _MTL_TRAINER in str((info or {}).get("name") or ""):
         if seg_variant is not None:
             raise ValueError("seg_variant %r names a Generic_UNet trainer variant; %s was written by %s" % (seg_variant, seg_folder, info["name"]))
+        if seg_regions is not None or seg_regions_class_order is not None:
+            raise ValueError("seg_regions / seg_regions_class_order next to a folder of %s: seg_net.regions and seg_net.arch == 'mtl' do not go "
+                             "together (MTLmodel has no region-based trainer)" % info["name"])
         if flow_weight_folder is not None:
             raise ValueError("%s was written by %s (an MTLmodel segmenter) and cannot be paired with a flow folder (-w %s): MTLmodel next to "
                              "the flow network is not built.  Import it on its own (no -w)." % (seg_folder, info["name"], flow_weight_folder))
@@ -387,7 +394,11 @@ def import_reference_model_folder(seg_folder, flow_weight_folder, out_folder, cr
         raise ValueError("seg_config is the YAML of an %s folder; %s was written by %r" % (_MTL_TRAINER, seg_folder, (info or {}).get("name")))
     if flow_weight_folder is None:
         return _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size,
-                                         window_size, seg_variant)
+                                         window_size, seg_variant, seg_regions, seg_regions_class_order)
+    if seg_regions_spec((info or {}).get("name"), seg_regions, seg_regions_class_order)[0] is not None:
+        raise ValueError("%s is a region-based folder (trainer %r, seg_regions %r: seg_net.regions) and cannot be paired with a flow folder "
+                         "(-w %s, flow_net): label propagation one-hot encodes exclusive labels.  Import it on its own (no -w)."
+                         % (seg_folder, (info or {}).get("name"), seg_regions, flow_weight_folder))
     if _stage_is_3d(load_reference_pickle(join(seg_folder, "plans.pkl")), info["init"][5] if info and len(info.get("init") or ()) > 5 else None):
         raise ValueError("%s is a 3-D segmentation folder (3-entry patch_size) and cannot be paired with a flow folder (-w %s): the flow path "
                          "is 2-D.  Import it on its own (no -w)." % (seg_folder, flow_weight_folder))
@@ -531,7 +542,71 @@ SEG_VARIANTS = {
     "nnUNetTrainerV2_noDeepSupervision": {},                                   # the heads below full resolution exist and are never evaluated
     "nnUNetTrainerV2_softDeepSupervision": {},
     "nnUNetTrainerV2_ResencUNet": None, "nnUNetTrainerV2_ResencUNet_DA3": None, "nnUNetTrainerV2_ResencUNet_DA3_BN": None,
+    # competitions_with_custom_Trainers: two BatchNorm softmax trainers (the first is no region trainer despite its name)
+    "nnUNetTrainerV2BraTSRegions_BN": {"norm": "bn"},
+    "nnUNetTrainerV2_MMS": {"norm": "bn"},
 }
+
+# Region-based training (competitions_with_custom_Trainers/BraTS2020): one sigmoid channel per region, num_classes = len(regions), labels
+# painted in regions_class_order.  The two region sets are those of nnunet/evaluation/region_based_evaluation.py with the class orders the
+# trainers set; a trainer's class name -> (region set, its SEG_VARIANTS-style row).
+REGION_SETS = {
+    "brats": ({"whole tumor": [1, 2, 3], "tumor core": [2, 3], "enhancing tumor": [3]}, [1, 2, 3]),
+    "kits": ({"kidney incl tumor": [1, 2], "tumor": [2]}, [1, 2]),
+}
+_BR = "nnUNetTrainerV2BraTSRegions"
+REGION_TRAINERS = {
+    _BR: ("brats", {}), _BR + "_Dice": ("brats", {}), _BR + "_DDP": ("brats", {}),
+    _BR + "_DA3": ("brats", {}), _BR + "_DA3_BD": ("brats", {}),
+    _BR + "_DA3_BN": ("brats", {"norm": "bn"}), _BR + "_DA3_BN_BD": ("brats", {"norm": "bn"}),
+    _BR + "_DA4_BN": ("brats", {"norm": "bn"}), _BR + "_DA4_BN_BD": ("brats", {"norm": "bn"}),
+}
+
+
+def seg_regions_spec(name, seg_regions=None, seg_regions_class_order=None):
+    """(regions {name: [labels]}, regions_class_order) of a folder, or (None, None).  name: the trainer's class name (a REGION_TRAINERS row
+    gives its set); seg_regions: --seg_regions, a REGION_SETS name or a JSON object / mapping {region: [labels]}, for a subclass of one's own
+    (it replaces the trainer's set); seg_regions_class_order: --seg_regions_class_order (default: the named set's own order)."""
+    regions = order = None
+    if str(name or "") in REGION_TRAINERS:
+        regions, order = REGION_SETS[REGION_TRAINERS[str(name)][0]]
+    if seg_regions is not None:
+        if isinstance(seg_regions, str) and seg_regions in REGION_SETS:
+            regions, order = REGION_SETS[seg_regions]
+        else:
+            import json
+            try:
+                regions = json.loads(seg_regions) if isinstance(seg_regions, str) else dict(seg_regions)
+            except (TypeError, ValueError) as e:
+                raise ValueError("seg_regions %r is neither a region set (%s) nor a JSON object {region name: [labels]}: %s"
+                                 % (seg_regions, ", ".join(sorted(REGION_SETS)), e))
+            if not isinstance(regions, dict):
+                raise ValueError("seg_regions %r is neither a region set (%s) nor a JSON object {region name: [labels]}"
+                                 % (seg_regions, ", ".join(sorted(REGION_SETS))))
+            order = None
+    if seg_regions_class_order is not None:
+        if regions is None:
+            raise ValueError("seg_regions_class_order %r without regions: pass seg_regions (--seg_regions) too" % (seg_regions_class_order,))
+        order = [int(c) for c in seg_regions_class_order]
+    if regions is None:
+        return None, None
+    if order is None:
+        raise ValueError("seg_regions given as a mapping needs seg_regions_class_order (--seg_regions_class_order): one label per region")
+    return {str(k): [int(c) for c in v] for k, v in regions.items()}, [int(c) for c in order]
+
+
+def check_region_head(sd, regions, trainer, path):
+    """A region-based network has one output channel per region: the full-resolution head of the checkpoint must agree before
+    check_state_dict's shape report can mislead (a softmax folder's head has num_classes + 1 channels)."""
+    heads = sorted((int(m.group(1)), k) for k, m in ((k, re.fullmatch(r"seg_outputs\.(\d+)\.weight", k)) for k in sd) if m)
+    key = heads[-1][1] if heads else ("decoder.segmentation_output.weight" if "decoder.segmentation_output.weight" in sd else None)
+    if key is None:
+        raise KeyError("%s: trainer %s: the checkpoint holds no segmentation head (seg_outputs.N.weight / decoder.segmentation_output.weight)"
+                       % (path, trainer or "(unnamed)"))
+    if int(sd[key].shape[0]) != len(regions):
+        raise ValueError("%s: trainer %s: the segmentation head %s has %d output channels, but there are %d regions (%s): a region-based "
+                         "network has one sigmoid channel per region (seg_regions / --seg_regions names another set)"
+                         % (path, trainer or "(unnamed)", key, int(sd[key].shape[0]), len(regions), ", ".join(regions)))
 _FRN = "nnUNetTrainerV2_FRN"
 
 
@@ -599,7 +674,8 @@ def check_seg_variant(sd, row, trainer, path):
                          % (what, row["base_num_features"], _FIRST_CONV, int(sd[_FIRST_CONV].shape[0])))
 
 
-def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size, window_size, seg_variant=None):
+def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config, folds, checkpoint_name, crop_size, image_size, window_size, seg_variant=None,
+                              seg_regions=None, seg_regions_class_order=None):
     """import_reference_model_folder without a flow folder: every check of the segmentation side, nothing of the flow side"""
     given = {k: v for k, v in dict(crop_weights=crop_weights, crop_config=crop_config, crop_size=crop_size, image_size=image_size,
                                    window_size=window_size).items() if v is not None}
@@ -635,10 +711,18 @@ def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config,
         # the previous stage's foreground labels come in as one-hot channels (predict.py:176, classes = range(1, num_classes))
         plans["seg_net"]["prev_stage_classes"] = list(range(1, plans["num_classes"]))
     row = None if resenc else seg_variant_row(name, seg_variant)
+    if row is None and not resenc and seg_variant is None and name in REGION_TRAINERS:
+        row = REGION_TRAINERS[name][1]                                          # the _BN region trainers build BatchNorm
     if resenc and seg_variant is not None:
         raise ValueError("seg_variant %r: %s is a residual-encoder folder, which has no trainer variants here" % (seg_variant, seg_folder))
     if row:
         _apply_seg_variant(plans, row)
+    regions, order = seg_regions_spec(name, seg_regions, seg_regions_class_order)
+    if regions is not None:                                                     # process_plans: self.num_classes = len(self.regions), no background
+        plans["num_classes"] = len(regions)
+        plans["seg_net"]["regions"], plans["seg_net"]["regions_class_order"] = regions, order
+        first_path = join(seg_folds[folds[0]], checkpoint_name + ".model")
+        check_region_head(load_reference_checkpoint(first_path)["state_dict"], regions, seg_variant or name, first_path)
     trainer = CineTrainer(plans, torch.device("cpu"))                           # the network's key / shape list, no device work
     params = {}
     for f in folds:                                                             # every tensor of every fold is checked before anything is written
@@ -649,6 +733,8 @@ def _import_segmentation_only(seg_folder, out_folder, crop_weights, crop_config,
             sd = _drop_resenc_aliases(sd, path)
         else:
             check_seg_variant(sd, row or {}, seg_variant or name, path)
+        if regions is not None:
+            check_region_head(sd, regions, seg_variant or name, path)
         check_state_dict(sd, shapes, "segmentation network %s" % path)
         params[f] = {k: v for k, v in sd.items() if not k.endswith(_DERIVED_BUFFERS)}
     os.makedirs(out_folder, exist_ok=True)
@@ -761,6 +847,12 @@ def main(argv=None):
     parser.add_argument("--seg_variant", default=None, metavar="NAME",
                         help="build the segmentation network as this trainer variant does (a class name of nnUNet_variants/architectural_variants, "
                              "e.g. nnUNetTrainerV2_BN), whatever name the folder's .model.pkl holds: for a subclass of one's own")
+    parser.add_argument("--seg_regions", default=None, metavar="NAME_OR_JSON",
+                        help="the folder is region-based (one sigmoid channel per region): 'brats' or 'kits' (the region sets of "
+                             "region_based_evaluation.py) or a JSON object {region name: [labels]} in channel order; for a subclass of one's own -- "
+                             "the nnUNetTrainerV2BraTSRegions* trainers are recognised by name")
+    parser.add_argument("--seg_regions_class_order", nargs="+", type=int, default=None, metavar="L",
+                        help="the label each region paints, in channel order (a later region overwrites an earlier one); default: the named set's own")
     parser.add_argument("-f", "--folds", nargs="+", default="None")
     parser.add_argument("-chk", default="model_final_checkpoint", required=False)
     parser.add_argument("--crop_size", type=int, default=None)
@@ -768,7 +860,8 @@ def main(argv=None):
     parser.add_argument("--window_size", type=int, default=None)
     a = parser.parse_args(argv)
     plans = import_reference_model_folder(a.seg_folder, a.flow_weight_folder, a.output_folder, a.crop_weights, a.crop_config,
-                                          None if a.folds == "None" else a.folds, a.chk, a.crop_size, a.image_size, a.window_size, a.seg_config, a.seg_variant)
+                                          None if a.folds == "None" else a.folds, a.chk, a.crop_size, a.image_size, a.window_size, a.seg_config, a.seg_variant,
+                                          a.seg_regions, a.seg_regions_class_order)
     if plans["seg_net"].get("arch") == "mtl":
         print("wrote %s (MTLmodel segmenter, image %d, crop %s, window %d, %d classes)" % (a.output_folder, plans["image_size"], plans.get("crop_size"),
                                                                                         plans["seg_net"]["window_size"], plans["num_classes"]))

@@ -131,6 +131,7 @@ class CineTrainer:
         fk = plans.get("flow_net")
         self.seg_dim = int((plans.get("seg_net") or {}).get("dim", 2))
         arch = (plans.get("seg_net") or {}).get("arch")
+        self.regions, self.regions_class_order = _check_regions(plans, arch, fk)      # both None unless the folder is region-based
         if arch == "mtl":
             _check_mtl_plans(plans, self.seg_dim, fk)
         elif arch is not None:
@@ -199,6 +200,12 @@ class CineTrainer:
             self.flow_net = SegFlowGaussian(**kw)
 
     def _new_seg_net(self):
+        net = self._build_seg_net()
+        if self.regions is not None:        # nnUNetTrainerV2BraTSRegions.initialize_network: self.network.inference_apply_nonlin = nn.Sigmoid()
+            net.inference_apply_nonlin = "sigmoid"
+        return net
+
+    def _build_seg_net(self):
         sk = self.plans["seg_net"]
         if self.seg_arch == "mtl":      # nnMTLTrainerV2.py:608-610: MTLmodel at the crop size behind a Processor, at the image size without one
             from . import config as C
@@ -292,25 +299,28 @@ class CineTrainer:
             if len(self.seg_nets) == 1 and self.seg_arch != "mtl":
                 return predict_3D_2Dconv_tiled(self.seg_net, data, self.patch_size, step_size=step_size, do_mirroring=do_mirroring,
                                                mirror_axes=mirror_axes, use_gaussian=use_gaussian, pad_border_mode=pad_border_mode,
-                                               pad_kwargs=pad_kwargs)
+                                               pad_kwargs=pad_kwargs, regions_class_order=self.regions_class_order)
             return predict_cine_2Dconv_tiled(self.seg_nets, [data], self.patch_size, step_size=step_size, do_mirroring=do_mirroring,
                                              mirror_axes=mirror_axes, use_gaussian=use_gaussian, pad_border_mode=pad_border_mode,
-                                             pad_kwargs=pad_kwargs)[0]
+                                             pad_kwargs=pad_kwargs, regions_class_order=self.regions_class_order)[0]
 
     def _predict_volume_3d(self, data, step_size, do_mirroring, mirror_axes, use_gaussian, pad_border_mode, pad_kwargs):
         """One volume [C,Z,Y,X] through predict_3D_3Dconv_tiled, one fold at a time, everything on the device: (seg uint8, softmax).  Several
         folds: the softmax is the fold mean -- each fold's sliding-window softmax added in fold order, each with weight 1 / folds as in the
-        2-D ensemble -- and the labels are its arg-max; one fold: predict_3D_3Dconv_tiled's own labels."""
+        2-D ensemble -- and the labels are its arg-max; one fold: predict_3D_3Dconv_tiled's own labels.  A region-based folder: the
+        labels are the region rule (regions_class_order) on the same probabilities, one fold or the fold mean."""
         acc = seg = None
         n = len(self.seg_nets)
         for net in self.seg_nets:
             seg, prob = predict_3D_3Dconv_tiled(net, data, self.patch_size, step_size, do_mirroring, mirror_axes, use_gaussian, pad_border_mode,
-                                                pad_kwargs, return_device=True)
+                                                pad_kwargs, return_device=True, regions_class_order=self.regions_class_order)
             if n == 1:
                 return seg, prob
             prob = prob.contiguous().mul_(1.0 / n)
             acc = prob if acc is None else ops.add(acc, prob, out=acc)
         K, Z, Y, X = acc.shape
+        if self.regions_class_order is not None:
+            return ops.region_labels(acc[None], self.regions_class_order)[0], acc
         return ops.argmax_channels(acc.view(1, K, Z * Y, X)).view(Z, Y, X), acc
 
     def predict_volumes_seg(self, volumes, do_mirroring=True, mirror_axes=None, step_size=0.5, use_gaussian=True, pad_border_mode="constant",
@@ -324,7 +334,7 @@ class CineTrainer:
                 res = [self._predict_volume_3d(v, step_size, do_mirroring, mirror_axes, use_gaussian, pad_border_mode, pad_kwargs) for v in volumes]
             else:
                 res = _predict_cine_tiled_device(self.seg_nets, volumes, self.patch_size, step_size, do_mirroring, mirror_axes, use_gaussian,
-                                                 pad_border_mode, pad_kwargs, None)
+                                                 pad_border_mode, pad_kwargs, None, self.regions_class_order)
         dev_out = []
         for s_, p_ in res:
             dev_out.append(s_.contiguous())
@@ -524,6 +534,43 @@ def _seg_variant_kwargs(sk, arch, flow_net):
     if "seg_output_bias" in sk:
         kw["seg_output_bias"] = sk["seg_output_bias"]
     return kw
+
+
+def _check_regions(plans, arch, flow_net):
+    """plans['seg_net']['regions'] / ['regions_class_order'] (region-based training, nnUNetTrainerV2BraTSRegions*: one sigmoid channel per
+    region, labels painted in regions_class_order) -> (regions as an ordered {name: [labels]}, [label per region]), or (None, None) for a
+    folder without either key.  Everything the two keys must not stand next to is refused here, before a network is built."""
+    sk = plans.get("seg_net") or {}
+    has_r, has_o = sk.get("regions") is not None, sk.get("regions_class_order") is not None
+    if not has_r and not has_o:
+        return None, None
+    if has_r != has_o:
+        raise ValueError("plans.json holds seg_net.%s without seg_net.%s: a region-based folder needs both seg_net.regions and "
+                         "seg_net.regions_class_order" % (("regions", "regions_class_order") if has_r else ("regions_class_order", "regions")))
+    if flow_net:
+        raise ValueError("plans.json holds both seg_net.regions and flow_net: label propagation one-hot encodes exclusive labels (a "
+                         "region-based folder is segmentation-only)")
+    if arch == "mtl":
+        raise ValueError("plans.json holds both seg_net.regions and seg_net.arch == 'mtl': MTLmodel has no region-based trainer")
+    if sk.get("prev_stage_classes") is not None:
+        raise ValueError("plans.json holds both seg_net.regions and seg_net.prev_stage_classes: a cascade stage takes and gives exclusive labels")
+    regions, order = sk["regions"], sk["regions_class_order"]
+    is_label = lambda c: isinstance(c, int) and not isinstance(c, bool) and 0 <= c <= 255     # noqa: E731
+    if not isinstance(regions, dict) or not regions:
+        raise ValueError("seg_net.regions must be a non-empty mapping from region name to a list of label values, got %r" % (regions,))
+    for name, labels in regions.items():
+        if not isinstance(labels, (list, tuple)) or not labels:
+            raise ValueError("seg_net.regions[%r] is an empty region: every region is a non-empty list of label values, got %r" % (name, labels))
+        if not all(is_label(c) for c in labels):
+            raise ValueError("seg_net.regions[%r] holds a label outside 0..255: %r" % (name, labels))
+    if not isinstance(order, (list, tuple)) or not all(is_label(c) for c in order):
+        raise ValueError("seg_net.regions_class_order must be a list of label values in 0..255, got %r" % (order,))
+    if len(order) != len(regions):
+        raise ValueError("seg_net.regions_class_order has %d entries and seg_net.regions has %d: one label per region" % (len(order), len(regions)))
+    if plans["num_classes"] != len(regions):
+        raise ValueError("plans.json holds num_classes == %r next to %d seg_net.regions: a region-based network has one sigmoid channel per "
+                         "region and no background channel, so num_classes must equal len(seg_net.regions)" % (plans["num_classes"], len(regions)))
+    return {str(k): [int(c) for c in v] for k, v in regions.items()}, [int(c) for c in order]
 
 
 def _check_mtl_plans(plans, seg_dim, flow_net):

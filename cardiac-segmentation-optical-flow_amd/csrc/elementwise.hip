@@ -179,6 +179,41 @@ __global__ void __launch_bounds__(256) tta_accumulate_3d_kernel(const float* __r
     }
 }
 
+// The sigmoid form of the two accumulate kernels above (region-based heads, inference_apply_nonlin = nn.Sigmoid()): every channel on its
+// own, acc[n,z,y,x] += weight * sigmoid(logits[n, zf, yf, xf]) with n = b * K + k.  No max / sum pass: one read of the logits, one
+// read-modify-write of acc.  V = 4: one thread owns 4 consecutive x of a row (W % 4 == 0, no flip along x, both pointers 16-byte aligned:
+// every row then starts on a 16-byte boundary); V = 1: one value.  A 2-D map is D = 1.  exp overflows to +inf for logits below about -88.7 and
+// 1 / (1 + inf) is 0; it underflows to 0 above, and 1 / (1 + 0) is 1: saturated logits give exactly 0 and 1, never NaN.
+__device__ __forceinline__ float sigmoid_f32(float v) { return 1.f / (1.f + expf(-v)); }
+
+template <int V>
+__global__ void __launch_bounds__(256) tta_accumulate_sigmoid_kernel(const float* __restrict__ logits, float* __restrict__ acc, int D, int H,
+                                                                    int W, int fd, int fh, int fw, float weight, long total) {
+    const int Wv = W / V;
+    GRID_STRIDE(i, total) {  // i over (n, z, y, x / V)
+        const int x = (int)(i % Wv) * V;
+        long r = i / Wv;
+        const int y = (int)(r % H);
+        r /= H;
+        const int z = (int)(r % D);
+        const long n = r / D;
+        const int zs = fd ? D - 1 - z : z, ys = fh ? H - 1 - y : y;
+        const float* lp = logits + ((n * D + zs) * H + ys) * (long)W;
+        float* ap = acc + ((n * D + z) * H + y) * (long)W + x;
+        if constexpr (V == 4) {
+            const float4 l = *reinterpret_cast<const float4*>(lp + x);
+            float4 a = *reinterpret_cast<const float4*>(ap);
+            a.x += weight * sigmoid_f32(l.x);
+            a.y += weight * sigmoid_f32(l.y);
+            a.z += weight * sigmoid_f32(l.z);
+            a.w += weight * sigmoid_f32(l.w);
+            *reinterpret_cast<float4*>(ap) = a;
+        } else {
+            ap[0] += weight * sigmoid_f32(lp[fw ? W - 1 - x : x]);
+        }
+    }
+}
+
 __global__ void __launch_bounds__(256) flip3d_kernel(const float* __restrict__ src, float* __restrict__ dst, int D, int H, int W, int fd,
                                                     int fh, int fw, long total) {
     const long HW = (long)H * W, V = (long)D * HW;
@@ -502,6 +537,44 @@ extern "C" int cf_tta_accumulate_3d(const float* logits, float* acc, int B, int 
     CF_REQUIRE(B > 0 && K > 0 && D > 0 && H > 0 && W > 0, "bad shape");
     long total = (long)B * D * H * W;
     LAUNCH_FLAT(tta_accumulate_3d_kernel, total, logits, acc, K, D, H, W, flip_d, flip_h, flip_w, weight, total);
+}
+
+// the sigmoid accumulate of [N = B * K] maps of (D, H, W); a 2-D call is D = 1
+static int launch_tta_sigmoid(const char* who, const float* logits, float* acc, long N, int D, int H, int W, int fd, int fh, int fw, float weight,
+                              void* stream) {
+    const long n = N * D * H * W;
+    if (W % 4 == 0 && !fw && aligned16(logits) && aligned16(acc)) {
+        const long total = n / 4;
+        hipLaunchKernelGGL(tta_accumulate_sigmoid_kernel<4>, dim3(flat_grid(total, 256)), dim3(256), 0, as_stream(stream), logits, acc, D, H, W, fd,
+                           fh, fw, weight, total);
+    } else {
+        hipLaunchKernelGGL(tta_accumulate_sigmoid_kernel<1>, dim3(flat_grid(n, 256)), dim3(256), 0, as_stream(stream), logits, acc, D, H, W, fd, fh,
+                           fw, weight, n);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error(std::string(who) + ": launch failed: " + hipGetErrorString(e));
+        return CF_ERR_LAUNCH;
+    }
+    return CF_OK;
+}
+
+extern "C" int cf_tta_accumulate_nonlin(const float* logits, float* acc, int B, int K, int H, int W, int flip_h, int flip_w, float weight,
+                                        int nonlin, void* stream) {
+    CF_REQUIRE(nonlin == CF_NONLIN_SOFTMAX || nonlin == CF_NONLIN_SIGMOID, "nonlin = %d is neither CF_NONLIN_SOFTMAX nor CF_NONLIN_SIGMOID", nonlin);
+    if (nonlin == CF_NONLIN_SOFTMAX) return cf_tta_accumulate(logits, acc, B, K, H, W, flip_h, flip_w, weight, stream);   // the same kernel
+    CF_REQUIRE(logits && acc, "null pointer");
+    CF_REQUIRE(B > 0 && K > 0 && K <= 64 && H > 0 && W > 0, "bad shape");
+    return launch_tta_sigmoid(__func__, logits, acc, (long)B * K, 1, H, W, 0, flip_h, flip_w, weight, stream);
+}
+
+extern "C" int cf_tta_accumulate_3d_nonlin(const float* logits, float* acc, int B, int K, int D, int H, int W, int flip_d, int flip_h, int flip_w,
+                                           float weight, int nonlin, void* stream) {
+    CF_REQUIRE(nonlin == CF_NONLIN_SOFTMAX || nonlin == CF_NONLIN_SIGMOID, "nonlin = %d is neither CF_NONLIN_SOFTMAX nor CF_NONLIN_SIGMOID", nonlin);
+    if (nonlin == CF_NONLIN_SOFTMAX) return cf_tta_accumulate_3d(logits, acc, B, K, D, H, W, flip_d, flip_h, flip_w, weight, stream);
+    CF_REQUIRE(logits && acc, "null pointer");
+    CF_REQUIRE(B > 0 && K > 0 && D > 0 && H > 0 && W > 0, "bad shape");
+    return launch_tta_sigmoid(__func__, logits, acc, (long)B * K, D, H, W, flip_d, flip_h, flip_w, weight, stream);
 }
 
 extern "C" int cf_flip3d(const float* src, float* dst, int N, int D, int H, int W, int flip_d, int flip_h, int flip_w, void* stream) {

@@ -177,9 +177,57 @@ static void launch_ensemble(unsigned blocks, hipStream_t s, const EnsembleMember
                            static_cast<T*>(mean), ord);
 }
 
+// The label step above on its own, for probabilities that are already on the device (the sliding window's merged sigmoid maps):
+// probs [B,K,HW] fp32 -> seg [B,HW]: label = 0, then for i = 0..K-1 label = order[i] where probs[i] > 0.5f (neural_network.py:749-751,
+// segmentation_export.py:148-150).  V = 4: four voxels per thread, one 16-byte load per region and one 4-byte store (HW % 4 == 0, probs
+// 16-byte and seg 4-byte aligned); V = 1: one voxel.
+template <int V>
+__global__ void __launch_bounds__(256) region_labels_kernel(const float* __restrict__ probs, uint8_t* __restrict__ seg, int K, long HW, long total,
+                                                            EnsembleOrder order) {
+    const long HWv = HW / V;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {   // i over (b, p / V)
+        const long b = i / HWv, p = (i - b * HWv) * V;
+        const float* q = probs + b * K * HW + p;
+        int label[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) label[v] = 0;
+        for (int k = 0; k < K; ++k) {
+            const int c_k = order.v[k];
+            if constexpr (V == 4) {
+                const float4 m = *reinterpret_cast<const float4*>(q + k * HW);
+                label[0] = m.x > 0.5f ? c_k : label[0];
+                label[1] = m.y > 0.5f ? c_k : label[1];
+                label[2] = m.z > 0.5f ? c_k : label[2];
+                label[3] = m.w > 0.5f ? c_k : label[3];
+            } else {
+                label[0] = q[k * HW] > 0.5f ? c_k : label[0];
+            }
+        }
+        uint8_t* d = seg + b * HW + p;
+        if constexpr (V == 4) *reinterpret_cast<uchar4*>(d) = make_uchar4((uint8_t)label[0], (uint8_t)label[1], (uint8_t)label[2], (uint8_t)label[3]);
+        else d[0] = (uint8_t)label[0];
+    }
+}
+
 }  // namespace cf
 
 using namespace cf;
+
+extern "C" int cf_region_labels(const float* probs, uint8_t* seg, int B, int K, long HW, const uint8_t* order, void* stream) {
+    CF_REQUIRE(probs && seg && order, "null pointer");
+    CF_REQUIRE(K >= 1 && K <= ENSEMBLE_MAX_CLASSES, "K = %d is outside 1..%d", K, ENSEMBLE_MAX_CLASSES);
+    CF_REQUIRE(B > 0 && HW > 0, "bad shape B=%d HW=%ld", B, HW);
+    EnsembleOrder ord = {};
+    for (int k = 0; k < K; ++k) ord.v[k] = order[k];                // HOST array of the regions' label values
+    const bool vec = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(probs) & 15) == 0 && (reinterpret_cast<uintptr_t>(seg) & 3) == 0;
+    const long total = vec ? (long)B * (HW / 4) : (long)B * HW;
+    if (vec)
+        hipLaunchKernelGGL(region_labels_kernel<4>, dim3(flat_grid(total, 256)), dim3(256), 0, as_stream(stream), probs, seg, K, HW, total, ord);
+    else
+        hipLaunchKernelGGL(region_labels_kernel<1>, dim3(flat_grid(total, 256)), dim3(256), 0, as_stream(stream), probs, seg, K, HW, total, ord);
+    CF_CHECK_LAUNCH();
+    return CF_OK;
+}
 
 extern "C" int cf_ensemble_merge(const void* const* members, int n_members, int dtype, int K, int Z, int Y, int X, uint8_t* seg, int Zf, int Yf,
                                  int Xf, int z0, int y0, int x0, void* mean, const uint8_t* order, void* stream) {

@@ -408,6 +408,21 @@ int cf_tile_accumulate_3d(const float* pred, const float* gauss, float* agg, flo
                           int lz, int px, int py, int pz, void* stream);
 /* argmax over K of [B,K,HW] -> uint8 [B,HW] */
 int cf_argmax_channels(const float* x, uint8_t* out, int B, int K, int HW, void* stream);
+/* Region-based heads (nnUNetTrainerV2BraTSRegions*: inference_apply_nonlin = nn.Sigmoid(), one channel per region).
+ * cf_tta_accumulate[_3d] with the nonlinearity as an argument.  CF_NONLIN_SOFTMAX launches the kernel of cf_tta_accumulate[_3d] itself (the
+ * same bits); CF_NONLIN_SIGMOID: acc[b,k,p] += weight * (1 / (1 + exp(-logits[b,k,flip(p)]))), every channel on its own, one thread per value
+ * (per 4 values of a row with 16-byte accesses when W % 4 == 0, flip_w == 0 and both pointers are 16-byte aligned).  Logits of +-100 give
+ * exactly 1 and 0.  Any other nonlin is CF_ERR_ARG. */
+#define CF_NONLIN_SOFTMAX 0
+#define CF_NONLIN_SIGMOID 1
+int cf_tta_accumulate_nonlin(const float* logits, float* acc, int B, int K, int H, int W, int flip_h, int flip_w, float weight, int nonlin,
+                             void* stream);
+int cf_tta_accumulate_3d_nonlin(const float* logits, float* acc, int B, int K, int D, int H, int W, int flip_d, int flip_h, int flip_w,
+                                float weight, int nonlin, void* stream);
+/* The region label rule (neural_network.py:749-751, segmentation_export.py:148-150; cf_ensemble_merge applies the same): probs [B,K,HW]
+ * fp32 -> seg uint8 [B,HW], label = 0, then for i = 0..K-1: label = order[i] where probs[b,i,p] > 0.5f, a later region overwriting an earlier
+ * one.  order: HOST array of K label values (regions_class_order), passed to the kernel by value; 1 <= K <= 255. */
+int cf_region_labels(const float* probs, uint8_t* seg, int B, int K, long HW, const uint8_t* order, void* stream);
 
 /* ---------------------------------------------------------------- export post-processing
  * remove_all_but_the_largest_connected_component, nnunet/postprocessing/connected_components.py:51-107, on the device.
