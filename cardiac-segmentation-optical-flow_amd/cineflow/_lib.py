@@ -128,6 +128,7 @@ SIGNATURES = {
     "cf_seg_outside_mask": [P, P, I, L, F, P],
     "cf_prev_stage_onehot": [P, I, I, I, P, I, I, I, P, I, P],
     "cf_ensemble_merge": [P, I, I, I, I, I, I, P, I, I, I, I, I, I, P, P, P],
+    "cf_ensemble_pairs": [P, I, I, I, I, I, I, P, I, P, P, I, I, I, I, I, I, P, P, P],
     "cf_confusion_counts": [P, P, L, P, P],
     "cf_label_confusion": [P, P, L, I, P, P],
     "cf_surface_border": [P, I, I, I, I, P, P, P],

@@ -46,6 +46,9 @@ TABLE_COLUMNS = {"Hausdorff Distance": "hd", "Hausdorff Distance 95": "hd95", "A
 
 # a volume that is already in memory: (file name it stands for, array [Z,Y,X], read_nifti's properties)
 Loaded = collections.namedtuple("Loaded", "path array props")
+# a test volume whose label confusion against its reference is already counted (cineflow.ops.ensemble_pairs counts it while it writes the
+# labels): (file name it stands for, hist [16,16] of counts[test label, reference label], voxels).  Neither file is read.
+Counted = collections.namedtuple("Counted", "path hist n")
 
 
 def load_volume(path):
@@ -205,14 +208,18 @@ class Evaluator:
             return None
         return table
 
-    def evaluate(self, test=None, reference=None, advanced=False, surface=None, surface_dice_threshold=None, **metric_kwargs):
+    def evaluate(self, test=None, reference=None, advanced=False, surface=None, surface_dice_threshold=None, histogram=None, **metric_kwargs):
         """-> OrderedDict {label name: {metric: value}}; with advanced=True the surface metrics are added.  surface: how their distances
         are found -- "pairs" (the all-pairs search), "edt" (the exact distance transform: the histogram labels of the case in one
         label_surface_edt_table visit, the other labels one by one), None / "auto" ("pairs" unless some label's borders hold more than
-        metrics.EDT_AUTO_PAIRS pairs).  surface_dice_threshold (mm): adds "Normalized Surface Dice" to every label."""
+        metrics.EDT_AUTO_PAIRS pairs).  surface_dice_threshold (mm): adds "Normalized Surface Dice" to every label.
+        histogram: (hist [16,16] of counts[test label, reference label], voxels) of the case, counted already -- the volumes are then not
+        needed and nothing is launched; it answers plain labels below 16 and the confusion-type metrics only (anything else is refused)."""
         if surface not in (None, "auto", "pairs", "edt"):
             raise ValueError("surface must be one of auto, pairs, edt, got %r" % (surface,))
         surface = None if surface == "auto" else surface
+        if histogram is not None:
+            return self._evaluate_counted(histogram, advanced, surface_dice_threshold, metric_kwargs)
         if test is not None:
             self.set_test(test)
         if reference is not None:
@@ -261,6 +268,31 @@ class Evaluator:
                 else:
                     scores[m] = funcs[m](confusion_matrix=cm, nan_for_nonexisting=self.nan_for_nonexisting, **metric_kwargs)
             self.result[str(name)] = scores
+        return self.result
+
+    def _evaluate_counted(self, histogram, advanced, surface_dice_threshold, metric_kwargs):
+        """evaluate() from a ready histogram: the same _SlicedMatrix per label and the same metric functions, no volume and no launch"""
+        hist, n = np.asarray(histogram[0]), int(histogram[1])
+        if hist.shape != (HIST_K, HIST_K):
+            raise ValueError("histogram must be [%d,%d] counts[test label, reference label], got %s" % (HIST_K, HIST_K, hist.shape))
+        if advanced or surface_dice_threshold is not None:
+            raise ValueError("a ready histogram answers the confusion-type metrics only: surface metrics need the volumes")
+        if self.labels is None:
+            raise ValueError("a ready histogram needs the labels to score")
+        named = isinstance(self.labels, dict)
+        items = list(self.labels.items()) if named else [(l, l) for l in self.labels]
+        for label, _ in items:
+            if hasattr(label, "__iter__") or not 0 <= int(label) < HIST_K or (bool(self.rv_rejection) and not named and label == 1):
+                raise ValueError("label %r is not answered by the histogram (joint region, rv_rejection's label 1, or a value >= %d)"
+                                 % (label, HIST_K))
+        self.metrics.sort()
+        funcs = self._metric_functions(list(self.metrics))
+        metric_kwargs.setdefault("reproducible", True)
+        self.result = OrderedDict()
+        for label, name in items:
+            cm = _SlicedMatrix(hist, int(label), n, None, None)
+            self.result[str(name)] = OrderedDict((m, funcs[m](confusion_matrix=cm, nan_for_nonexisting=self.nan_for_nonexisting, **metric_kwargs))
+                                                 for m in self.metrics)
         return self.result
 
     def _from_table(self, metric, entry, cm, threshold):
@@ -317,17 +349,20 @@ class NiftiEvaluator(Evaluator):
 
 
 def _name(x):
-    return x.path if isinstance(x, Loaded) else x
+    return x.path if isinstance(x, (Loaded, Counted)) else x
 
 
 def run_evaluation(args):
     """one case: (test, reference, evaluator, metric_kwargs, metadata, binary) -> its scores plus file names and metadata"""
     test, ref, evaluator, metric_kwargs, metadata, binary = args
-    evaluator.set_test(test)
-    evaluator.set_reference(ref, binary)
-    if evaluator.labels is None:
-        evaluator.construct_labels()
-    scores = evaluator.evaluate(**metric_kwargs)
+    if isinstance(test, Counted):                                  # scored from its ready histogram: neither file is read
+        scores = Evaluator.evaluate(evaluator, histogram=(test.hist, test.n), **metric_kwargs)
+    else:
+        evaluator.set_test(test)
+        evaluator.set_reference(ref, binary)
+        if evaluator.labels is None:
+            evaluator.construct_labels()
+        scores = evaluator.evaluate(**metric_kwargs)
     for key, source in (("test", test), ("reference", ref)):
         if isinstance(_name(source), str):
             scores[key] = _name(source)
@@ -346,7 +381,7 @@ def _summary(name, description, task, author, results):
 def aggregate_scores(test_ref_pairs, evaluator=NiftiEvaluator, labels=None, nanmean=True, json_output_file=None, json_name="",
                      json_description="", json_author="Fabian", json_task="", num_threads=2, metadata_list=None, rv_rejection=False,
                      nb_threads=1, binary=False, **metric_kwargs):
-    """Scores every (test, reference) pair -- file names or `Loaded` volumes -- and returns {"all": [scores of each case], "mean": {label:
+    """Scores every (test, reference) pair -- file names, `Loaded` volumes, or a `Counted` test with its reference's file name -- and returns {"all": [scores of each case], "mean": {label:
     {metric: mean over the cases}}} (nanmean: NaN cases do not count); with json_output_file the summary.json is written.  labels: a list of
     ints or a dict int -> name.  num_threads / nb_threads: reader threads (the larger of the two); the device work stays in this process."""
     if isinstance(evaluator, type):
@@ -362,7 +397,10 @@ def aggregate_scores(test_ref_pairs, evaluator=NiftiEvaluator, labels=None, nanm
     per_case = []
     with ThreadPoolExecutor(readers) as pool:
         def start(i):
-            return [pool.submit(load_volume, f) if prefetch and isinstance(f, str) else f for f in (tests[i], refs[i])] if i < count else None
+            if i >= count:
+                return None
+            counted = isinstance(tests[i], Counted)               # its reference is not read either
+            return [pool.submit(load_volume, f) if prefetch and not counted and isinstance(f, str) else f for f in (tests[i], refs[i])]
 
         ahead = collections.deque(start(i) for i in range(min(readers, count)))
         for i in range(count):

@@ -1200,6 +1200,73 @@ def ensemble_merge(members, full_shape=None, bbox_lo=(0, 0, 0), want_mean=False,
     return seg, mean
 
 
+ENSEMBLE_PAIRS_MAX_MEMBERS = 8
+ENSEMBLE_PAIRS_MAX = 28
+ENSEMBLE_PAIRS_HIST_K = 16
+
+
+def ensemble_pairs(members, pairs, gt, bbox_lo=(0, 0, 0), regions_class_order=None, out=None):
+    """Every listed two-member ensemble of `members` against one ground truth, one kernel (cf_ensemble_pairs): members, a list of 2..8
+    softmax volumes [K,Z,Y,X] of one shape, all float16 or all float32; pairs, a list of 1..28 (i, j) with i != j; gt, uint8 [Zf,Yf,Xf]
+    -> (seg uint8 [P,Zf,Yf,Xf], hist int64 [P, 16 * 16 + 1]).  seg[p] is ensemble_merge([members[i], members[j]], gt.shape, bbox_lo,
+    regions_class_order=...)[0] byte for byte and hist[p] is cf_label_confusion(seg[p], gt) at K = 16 count for count (hist[p, t * 16 + r];
+    the last bin counts the voxels with a label >= 16 in either volume).  Each member is read once.  out: (seg, hist) tensors to write into
+    (every element of both is written)."""
+    import ctypes
+    members = list(members)
+    if not 2 <= len(members) <= ENSEMBLE_PAIRS_MAX_MEMBERS:
+        raise ValueError("ensemble_pairs: %d members (2..%d are supported)" % (len(members), ENSEMBLE_PAIRS_MAX_MEMBERS))
+    for i, m in enumerate(members):
+        if not isinstance(m, torch.Tensor) or not m.is_cuda:
+            raise TypeError("ensemble_pairs: member %d must be a CUDA/HIP tensor (cineflow has no CPU path)" % i)
+    first = members[0]
+    if first.dtype not in (torch.float16, torch.float32) or first.dim() != 4:
+        raise ValueError("ensemble_pairs: members must be [K,Z,Y,X] float16 or float32, member 0 is %s %s" % (tuple(first.shape), first.dtype))
+    for i, m in enumerate(members):
+        if m.dtype != first.dtype or m.shape != first.shape or m.device != first.device:
+            raise ValueError("ensemble_pairs: member %d is %s %s on %s, member 0 is %s %s on %s"
+                             % (i, tuple(m.shape), m.dtype, m.device, tuple(first.shape), first.dtype, first.device))
+        if not m.is_contiguous():
+            raise ValueError("ensemble_pairs: member %d must be contiguous" % i)
+    K, Z, Y, X = first.shape
+    if not 1 <= K <= 255:
+        raise ValueError("ensemble_pairs: %d classes (1..255 are supported)" % K)
+    pairs = [(int(i), int(j)) for i, j in pairs]
+    if not 1 <= len(pairs) <= ENSEMBLE_PAIRS_MAX:
+        raise ValueError("ensemble_pairs: %d pairs (1..%d are supported)" % (len(pairs), ENSEMBLE_PAIRS_MAX))
+    for i, j in pairs:
+        if i == j or not (0 <= i < len(members) and 0 <= j < len(members)):
+            raise ValueError("ensemble_pairs: pair (%d, %d) does not name two of the %d members" % (i, j, len(members)))
+    if not isinstance(gt, torch.Tensor) or gt.dtype != torch.uint8 or gt.dim() != 3 or gt.device != first.device or not gt.is_contiguous():
+        raise ValueError("ensemble_pairs: gt must be a contiguous uint8 [Zf,Yf,Xf] tensor on the members' device")
+    Zf, Yf, Xf = gt.shape
+    bbox_lo = tuple(int(v) for v in bbox_lo)
+    if len(bbox_lo) != 3 or any(lo < 0 or lo + n > f for lo, n, f in zip(bbox_lo, (Z, Y, X), (Zf, Yf, Xf))):
+        raise ValueError("ensemble_pairs: members of size %s at %s do not fit into %s" % ((Z, Y, X), bbox_lo, (Zf, Yf, Xf)))
+    order = None
+    if regions_class_order is not None:
+        regions_class_order = [int(c) for c in regions_class_order]
+        if len(regions_class_order) != K or any(c < 0 or c > 255 for c in regions_class_order):
+            raise ValueError("ensemble_pairs: regions_class_order must hold one label in 0..255 per class (%d), got %r" % (K, regions_class_order))
+        order = ctypes.cast((ctypes.c_uint8 * K)(*regions_class_order), ctypes.c_void_p)
+    P = len(pairs)
+    bins = ENSEMBLE_PAIRS_HIST_K * ENSEMBLE_PAIRS_HIST_K + 1
+    if out is None:
+        seg = torch.empty((P, Zf, Yf, Xf), dtype=torch.uint8, device=first.device)
+        hist = torch.empty((P, bins), dtype=torch.int64, device=first.device)
+    else:
+        seg, hist = out
+        for t, shape, dtype, what in ((seg, (P, Zf, Yf, Xf), torch.uint8, "seg"), (hist, (P, bins), torch.int64, "hist")):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or t.device != first.device or not t.is_contiguous():
+                raise ValueError("ensemble_pairs: out %s must be a contiguous %s %s tensor on the members' device" % (what, shape, dtype))
+    ptrs = (ctypes.c_void_p * len(members))(*[m.data_ptr() for m in members])
+    flat = (ctypes.c_int * (2 * P))(*[v for ij in pairs for v in ij])
+    check(lib().cf_ensemble_pairs(ctypes.cast(ptrs, ctypes.c_void_p), len(members), int(first.dtype == torch.float32), K, Z, Y, X,
+                                  ctypes.cast(flat, ctypes.c_void_p), P, _u8(gt, "gt"), _u8(seg, "seg"), Zf, Yf, Xf, bbox_lo[0], bbox_lo[1],
+                                  bbox_lo[2], order, hist.data_ptr(), _stream()), "cf_ensemble_pairs")
+    return seg, hist
+
+
 def resample_data_or_seg(data, new_shape, is_seg, axis=None, order=3, do_separate_z=False, order_z=0):
     """nnunet/preprocessing/preprocessing.py:111-200 on the device for the orders the export uses (0 and 1).  data: numpy or
     device tensor (c, x, y, z); returns the same kind.  Segmentations of order 0 are nearest-neighbour in every axis; data is

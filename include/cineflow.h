@@ -563,6 +563,16 @@ int cf_prev_stage_onehot(const uint8_t* seg, int X, int Y, int Z, float* dst, in
  * mean[i] > 0.5 mapped through order[i], else 0 (csrc/ensemble.hip). */
 int cf_ensemble_merge(const void* const* members, int n_members, int dtype, int K, int Z, int Y, int X, uint8_t* seg, int Zf, int Yf, int Xf,
                       int z0, int y0, int x0, void* mean, const uint8_t* order, void* stream);
+/* Every two-member ensemble of n_members (2..8) saved softmax volumes against one ground truth, in one launch (model selection:
+ * nnunet/evaluation/model_selection/ensemble.py merge + aggregate_scores' confusion counts).  members, dtype, K, the crop and `order` as in
+ * cf_ensemble_merge.  pairs: HOST array of n_pairs (1..28) index pairs (i, j), i != j, both below n_members.  gt: device uint8
+ * [Zf][Yf][Xf].  seg: device uint8 [n_pairs][Zf][Yf][Xf], written everywhere: seg[p] is what cf_ensemble_merge writes for the members
+ * (i, j) of pair p.  hist: device u64 [n_pairs][16 * 16 + 1]: hist[p] is what cf_label_confusion(seg[p], gt, ., 16, .) gives, the
+ * overflow bin for voxels with a label >= 16 included.  This call zeroes hist (on `stream`, before the launch); the caller need not.
+ * Each member value is loaded once per class and serves every pair that holds it (csrc/ensemble.hip). */
+int cf_ensemble_pairs(const void* const* members, int n_members, int dtype, int K, int Z, int Y, int X, const int* pairs, int n_pairs,
+                      const uint8_t* gt, uint8_t* seg, int Zf, int Yf, int Xf, int z0, int y0, int x0, const uint8_t* order,
+                      unsigned long long* hist, void* stream);
 
 /* ---------------------------------------------------------------- downstream metrics (consumers of the output layout)
  * ConfusionMatrix.compute, nnunet/evaluation/metrics.py:65-82: counts3 (device u64 [3]) = {TP, FP, FN} of test != 0 vs
