@@ -27,6 +27,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+from .folder_io import load_softmax as _load_softmax, read_ahead, softmax_case_geometry   # (the private name: the one its tests patch)
 from .nifti import write_nifti
 from .safe_pickle import load_plain_pickle
 
@@ -51,10 +52,6 @@ def find_cases(folders):
     return sorted(cases)
 
 
-def _load_softmax(path):
-    return np.load(path, allow_pickle=False)["softmax"]
-
-
 def _regions_class_order(props, files):
     """ensemble_predictions.py:33-45."""
     reg_class_orders = [p["regions_class_order"] if "regions_class_order" in p.keys() else None for p in props]
@@ -76,19 +73,7 @@ def _check_case(softmax, props, files):
     dtypes = [s.dtype for s in softmax]
     if dtypes[0] not in (np.float16, np.float32) or any(d != dtypes[0] for d in dtypes):
         raise ValueError("%s: the members' softmax must be all float16 or all float32, got %s" % (files[0], [str(d) for d in dtypes]))
-    first = props[0]
-    crop = shapes[0][1:]
-    after = tuple(int(v) for v in first["size_after_cropping"])
-    if crop != after:
-        raise ValueError("%s: softmax of size %s, size_after_cropping is %s (nothing is resampled when merging)" % (files[0], crop, after))
-    bbox = first.get("crop_bbox")
-    if bbox is None:
-        full, lo = crop, (0, 0, 0)
-    else:
-        full = tuple(int(v) for v in first["original_size_of_raw_data"])
-        lo = tuple(int(b[0]) for b in bbox)
-        if len(full) != 3 or any(a < 0 or a + n > f for a, n, f in zip(lo, crop, full)):
-            raise ValueError("%s: the crop %s at %s overhangs original_size_of_raw_data %s" % (files[0], crop, lo, full))
+    full, lo = softmax_case_geometry(shapes[0], props[0], files[0])
     if regions_class_order is not None and len(regions_class_order) != shapes[0][0]:
         raise ValueError("%s: regions_class_order %s does not name the %d channels of the softmax" % (files[0], regions_class_order, shapes[0][0]))
     return full, lo, regions_class_order
@@ -159,14 +144,10 @@ def merge(folders, output_folder, threads, override=True, postprocessing_file=No
             out_files.append(out_file)
 
     with ThreadPoolExecutor(max(1, int(threads))) as pool:
-        def read(i):
-            return [pool.submit(_load_softmax, f) for f in files[i]]
-
         writes = []
-        loading = read(0) if files else None
-        for i, out_file in enumerate(out_files):
-            softmax = [f.result() for f in loading]
-            loading = read(i + 1) if i + 1 < len(files) else None       # the next case inflates while the device and the writers work
+        cases = read_ahead(files, _load_softmax, depth=1, pool=pool)     # the next case inflates while the device and the writers work
+        for i, (_, softmax) in enumerate(cases):
+            out_file = out_files[i]
             props = [load_plain_pickle(f) for f in property_files[i]]
             seg, mean = _merge_loaded(softmax, props, files[i], store_npz)
             os.makedirs(os.path.dirname(out_file), exist_ok=True)

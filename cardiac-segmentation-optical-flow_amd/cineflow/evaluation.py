@@ -24,19 +24,15 @@ import inspect
 import json
 import warnings
 from collections import OrderedDict
-from concurrent.futures import ThreadPoolExecutor
 from datetime import datetime
 from os.path import join
 
 import numpy as np
-import torch
 
 from . import metrics
-from ._lib import check, lib
-from .export import subfiles
-from .metrics import ALL_METRICS, ConfusionMatrix
-from .nifti import read_nifti
-from .ops import _stream, _u8
+from ._lib import lib                                              # noqa: F401  (every launch is metrics'; call counters patch the name here too)
+from .folder_io import Loaded, load_volume, read_ahead, save_json, subfiles
+from .metrics import ALL_METRICS, ConfusionMatrix, label_volume_u8
 
 HIST_K = 16
 SURFACE_DICE = "Normalized Surface Dice"
@@ -44,38 +40,9 @@ SURFACE_DICE = "Normalized Surface Dice"
 TABLE_COLUMNS = {"Hausdorff Distance": "hd", "Hausdorff Distance 95": "hd95", "Avg. Symmetric Surface Distance": "assd",
                  "Avg. Surface Distance": "asd_test_to_ref"}
 
-# a volume that is already in memory: (file name it stands for, array [Z,Y,X], read_nifti's properties)
-Loaded = collections.namedtuple("Loaded", "path array props")
 # a test volume whose label confusion against its reference is already counted (cineflow.ops.ensemble_pairs counts it while it writes the
 # labels): (file name it stands for, hist [16,16] of counts[test label, reference label], voxels).  Neither file is read.
 Counted = collections.namedtuple("Counted", "path hist n")
-
-
-def load_volume(path):
-    array, props = read_nifti(path)
-    return Loaded(path, array, props)
-
-
-def save_json(obj, file, indent=4, sort_keys=True):
-    with open(file, "w") as f:
-        json.dump(obj, f, sort_keys=sort_keys, indent=indent)
-
-
-def label_volume_u8(a, what="label volume"):
-    """numpy array or tensor holding the integers 0..255 (in any integer or float dtype) -> contiguous uint8 device tensor"""
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if torch.is_tensor(a):
-        a = a.cpu().numpy() if a.dtype != torch.uint8 else a
-    if torch.is_tensor(a):
-        return a.to(dev).contiguous()
-    a = np.asarray(a)
-    if a.dtype != np.uint8:
-        as_u8 = a.astype(np.uint8) if a.size and a.min() >= 0 and a.max() <= 255 else None
-        if as_u8 is None or not np.array_equal(as_u8, a):
-            raise ValueError("%s: the values must be the integers 0..255 (dtype %s, range %s..%s)"
-                             % (what, a.dtype, a.min() if a.size else "-", a.max() if a.size else "-"))
-        a = as_u8
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
 
 class _SlicedMatrix(ConfusionMatrix):
@@ -175,11 +142,8 @@ class Evaluator:
             test_t, ref_t = label_volume_u8(self.test, "test"), label_volume_u8(self.reference, "reference")
         except ValueError:
             return None
-        metrics.assert_shape(test_t, ref_t)
-        hist = torch.empty(HIST_K * HIST_K + 1, dtype=torch.int64, device=test_t.device)
-        check(lib().cf_label_confusion(_u8(test_t), _u8(ref_t), test_t.numel(), HIST_K, hist.data_ptr(), _stream()), "cf_label_confusion")
-        h = hist.cpu().numpy()
-        return None if h[-1] else (h[:-1].reshape(HIST_K, HIST_K), test_t, ref_t, test_t.numel())
+        hist, overflow = metrics.label_histogram(test_t, ref_t, HIST_K)
+        return None if overflow else (hist, test_t, ref_t, test_t.numel())
 
     def _per_label_matrix(self, label, joint, cut_rv):
         """the per-label route: one ConfusionMatrix on masks (a joint region is the union of its labels, evaluator.py:204-210; rv_rejection
@@ -394,19 +358,11 @@ def aggregate_scores(test_ref_pairs, evaluator=NiftiEvaluator, labels=None, nanm
 
     readers = max(1, min(16, max(int(nb_threads or 1), int(num_threads or 1))))
     prefetch = isinstance(evaluator, NiftiEvaluator)
-    per_case = []
-    with ThreadPoolExecutor(readers) as pool:
-        def start(i):
-            if i >= count:
-                return None
-            counted = isinstance(tests[i], Counted)               # its reference is not read either
-            return [pool.submit(load_volume, f) if prefetch and not counted and isinstance(f, str) else f for f in (tests[i], refs[i])]
-
-        ahead = collections.deque(start(i) for i in range(min(readers, count)))
-        for i in range(count):
-            pair = [f.result() if hasattr(f, "result") else f for f in ahead.popleft()]
-            ahead.append(start(i + readers))
-            per_case.append(run_evaluation((pair[0], pair[1], evaluator, metric_kwargs, metadata_list[i], binary)))
+    # read ahead of case i: both files, or nothing for a Counted test (its reference is not read either); Loaded entries pass through
+    groups = [(tests[i], refs[i]) if prefetch and not isinstance(tests[i], Counted) else () for i in range(count)]
+    cases = read_ahead(groups, lambda f: load_volume(f) if isinstance(f, str) else f, depth=readers, readers=readers)
+    per_case = [run_evaluation((*(pair or (tests[i], refs[i])), evaluator, metric_kwargs, metadata_list[i], binary))
+                for i, (_, pair) in enumerate(cases)]
 
     mean_of = np.nanmean if nanmean else np.mean
     collected = OrderedDict()
@@ -522,9 +478,9 @@ def evaluate_regions(folder_predicted, folder_gt, regions, processes=8):
         print("WARNING! Some files in folder_gt were not predicted (not present in folder_predicted)!")
     files_pred.sort()
     region_labels = [tuple(v) for v in regions.values()]
-    with ThreadPoolExecutor(max_workers=max(1, int(processes))) as pool:
-        loads = [(pool.submit(load_volume, join(folder_predicted, f)), pool.submit(load_volume, join(folder_gt, f))) for f in files_pred]
-        res = [_score_regions(p.result().array, g.result().array, region_labels, f) for f, (p, g) in zip(files_pred, loads)]
+    processes = max(1, int(processes))
+    cases = read_ahead([(join(folder_predicted, f), join(folder_gt, f)) for f in files_pred], load_volume, depth=processes, readers=processes)
+    res = [_score_regions(p.array, g.array, region_labels, f) for (_, (p, g)), f in zip(cases, files_pred)]
     scores = {r: [case[k] for case in res] for k, r in enumerate(names)}
     as_one = {r: np.where(np.isnan(v), 1.0, v) for r, v in ((r, np.asarray(scores[r], dtype=np.float64)) for r in names)}
 

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .folder_io import subfiles                                    # noqa: F401  (the old import path)
 from .nifti import read_nifti, write_nifti
 
 join = os.path.join
@@ -159,10 +160,3 @@ def load_remove_save(input_file, output_file, for_which_classes, minimum_valid_o
     t, largest_removed, kept_size = ops.remove_all_but_the_largest_connected_component(t, fw, volume_per_voxel, mv)
     write_nifti(output_file, t.cpu().numpy(), props["itk_spacing"], props["itk_origin"], props["itk_direction"])
     return largest_removed, kept_size
-
-
-def subfiles(folder, suffix=None, join_=True, sort=True):
-    res = [f for f in os.listdir(folder) if os.path.isfile(join(folder, f)) and (suffix is None or f.endswith(suffix))]
-    if sort:
-        res.sort()
-    return [join(folder, f) for f in res] if join_ else res

@@ -435,19 +435,47 @@ ALL_METRICS = {
 }
 
 
-def label_confusion(test, reference, num_classes):
-    """All classes of nnunet/compute_metrics.py:96-106 in one pass: K x K int64 matrix M[t, r] = #voxels with test label t and
-    reference label r (labels must be < num_classes <= 16); per-class Dice = 2 M[c,c] / (M[c,:].sum() + M[:,c].sum())."""
-    t = (test if torch.is_tensor(test) else torch.from_numpy(np.ascontiguousarray(test))).to(_dev()).to(torch.uint8).contiguous()
-    r = (reference if torch.is_tensor(reference) else torch.from_numpy(np.ascontiguousarray(reference))).to(_dev()).to(torch.uint8).contiguous()
+def label_volume_u8(a, what="label volume"):
+    """numpy array or tensor holding the integers 0..255 (in any integer or float dtype) -> contiguous uint8 device tensor; anything else
+    is refused (_cast_labels_u8 is the cast that does not look)"""
+    if torch.is_tensor(a):
+        a = a.cpu().numpy() if a.dtype != torch.uint8 else a
+    if torch.is_tensor(a):
+        return a.to(_dev()).contiguous()
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        as_u8 = a.astype(np.uint8) if a.size and a.min() >= 0 and a.max() <= 255 else None
+        if as_u8 is None or not np.array_equal(as_u8, a):
+            raise ValueError("%s: the values must be the integers 0..255 (dtype %s, range %s..%s)"
+                             % (what, a.dtype, a.min() if a.size else "-", a.max() if a.size else "-"))
+        a = as_u8
+    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
+
+
+def _cast_labels_u8(a):
+    """label volume -> contiguous uint8 device tensor by a plain cast, no value check (label_volume_u8 is the one that refuses)"""
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.to(_dev()).to(torch.uint8).contiguous()
+
+
+def label_histogram(t, r, K):
+    """One cf_label_confusion launch on two uint8 device tensors of one shape -> (hist [K,K] int64 numpy of counts[t label, r label], the
+    number of voxels with a label >= K in either volume, which are in no cell)"""
     assert_shape(t, r)
-    K = int(num_classes)
     hist = torch.empty(K * K + 1, dtype=torch.int64, device=t.device)
     check(lib().cf_label_confusion(_u8(t), _u8(r), t.numel(), K, hist.data_ptr(), _stream()), "cf_label_confusion")
     h = hist.cpu().numpy()
-    if h[-1]:
-        raise ValueError("label_confusion: %d voxels carry a label >= num_classes=%d" % (int(h[-1]), K))
-    return h[:-1].reshape(K, K)
+    return h[:-1].reshape(K, K), int(h[-1])
+
+
+def label_confusion(test, reference, num_classes):
+    """All classes of nnunet/compute_metrics.py:96-106 in one pass: K x K int64 matrix M[t, r] = #voxels with test label t and
+    reference label r (labels must be < num_classes <= 16); per-class Dice = 2 M[c,c] / (M[c,:].sum() + M[:,c].sum())."""
+    K = int(num_classes)
+    hist, overflow = label_histogram(_cast_labels_u8(test), _cast_labels_u8(reference), K)
+    if overflow:
+        raise ValueError("label_confusion: %d voxels carry a label >= num_classes=%d" % (overflow, K))
+    return hist
 
 
 # ------------------------------------------------------------------------------------------------ compute_jacobian.py
@@ -516,11 +544,6 @@ def gradient_means(slice_flow):
 
 
 # ------------------------------------------------------------------------------------------------ one visit per patient
-def _labels_u8(a):
-    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
-    return t.to(_dev()).to(torch.uint8).contiguous()
-
-
 def label_surface_table(test, reference, num_classes, voxel_spacing=None):
     """All frames and classes of a patient in two library calls (cf_label_surface_count, cf_label_surface_table) and three reads.
 
@@ -531,7 +554,7 @@ def label_surface_table(test, reference, num_classes, voxel_spacing=None):
     1 ref->test -- are dist[offsets[n, c, side, 0]:offsets[n, c, side, 1]], in compaction order.  Where one side of a pair has no border the
     other side's distances are not computed (NaN).  The distance search is brute force: cine-sized objects, not hundreds of thousands of
     border voxels."""
-    t, r = _labels_u8(test), _labels_u8(reference)
+    t, r = _cast_labels_u8(test), _cast_labels_u8(reference)
     assert_shape(t, r)
     assert t.dim() in (3, 4), "label stacks are [N, H, W] or [N, D, H, W]"
     nd = t.dim() - 1
@@ -607,7 +630,7 @@ def label_surface_edt_table(test, reference, labels, voxel_spacing=None, capacit
     labs = [int(l) for l in labels]
     if not 1 <= len(labs) <= 16 or any(l < 0 or l > 255 for l in labs):
         raise ValueError("labels must be 1..16 values in 0..255, got %r" % (labs,))
-    t, r = _labels_u8(test), _labels_u8(reference)
+    t, r = _cast_labels_u8(test), _cast_labels_u8(reference)
     rows, offs, dist = _label_surface_edt(t, r, labs, voxel_spacing, capacity)
     d = dist[:int(offs[-1])].cpu().numpy() if offs[-1] else np.zeros(0)
     out = {}

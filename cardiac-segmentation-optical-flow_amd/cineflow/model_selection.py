@@ -40,10 +40,11 @@ from os.path import isdir, isfile, join
 
 import numpy as np
 
-from .evaluation import Counted, HIST_K, aggregate_scores, evaluate_folder, label_volume_u8, load_volume, save_json
-from .export import subfiles
+from .evaluation import Counted, HIST_K, aggregate_scores, evaluate_folder
+from .folder_io import load_json, load_softmax, load_volume, save_json, softmax_case_geometry, subfiles
+from .metrics import label_volume_u8
 from .nifti import write_nifti
-from .postprocessing import collect_cv_niftis, consolidate_folds, determine_postprocessing, load_json
+from .postprocessing import collect_cv_niftis, consolidate_folds, determine_postprocessing
 from .reference_models import load_reference_pickle
 from .safe_pickle import load_plain_pickle
 
@@ -108,26 +109,6 @@ def _validation_cases(folder1, folder2, validation_folder, folds):
     return cases
 
 
-def _load_softmax(path):
-    return np.load(path, allow_pickle=False)["softmax"]
-
-
-def _case_geometry(softmax, props, what):
-    """-> (full shape, crop origin) of the label volume of a case, refused on the host when the .pkl and the softmax disagree"""
-    crop = tuple(softmax.shape[1:])
-    after = tuple(int(v) for v in props["size_after_cropping"])
-    if softmax.ndim != 4 or crop != after:
-        raise ValueError("%s: softmax of shape %s, size_after_cropping is %s (nothing is resampled when ensembling)" % (what, softmax.shape, after))
-    bbox = props.get("crop_bbox")
-    if bbox is None:
-        return crop, (0, 0, 0)
-    full = tuple(int(v) for v in props["original_size_of_raw_data"])
-    lo = tuple(int(b[0]) for b in bbox)
-    if len(full) != 3 or any(a < 0 or a + n > f for a, n, f in zip(lo, crop, full)):
-        raise ValueError("%s: the crop %s at %s overhangs original_size_of_raw_data %s" % (what, crop, lo, full))
-    return full, lo
-
-
 def _visit_case(folders, wanted, fold, case, validation_folder, gt_file, regions_from_pkl):
     """One validation case, one launch: wanted = [(a, b)] indices into `folders` -> {(a, b): (labels uint8 [Zf,Yf,Xf] numpy, hist [257]
     numpy, props of member a)}.  Pairs are grouped by what the launch shares: the first member's geometry and region order."""
@@ -136,7 +117,7 @@ def _visit_case(folders, wanted, fold, case, validation_folder, gt_file, regions
     used = sorted(set(i for ab in wanted for i in ab))
     assert len(used) >= 2, "a pair needs two members"
     val = {i: join(folders[i], "fold_%d" % fold, validation_folder) for i in used}
-    softmax = {i: _load_softmax(join(val[i], case + ".npz")) for i in used}           # each model's .npz is inflated once
+    softmax = {i: load_softmax(join(val[i], case + ".npz")) for i in used}           # each model's .npz is inflated once
     props = {i: load_plain_pickle(join(val[i], case + ".pkl")) for i in set(a for a, _ in wanted)}
     shapes = {softmax[i].shape for i in used}
     if len(shapes) != 1:
@@ -152,7 +133,7 @@ def _visit_case(folders, wanted, fold, case, validation_folder, gt_file, regions
     slot = {i: n for n, i in enumerate(used)}
     groups = OrderedDict()
     for a, b in wanted:
-        full, lo = _case_geometry(softmax[a], props[a], join(val[a], case))
+        full, lo = softmax_case_geometry(softmax[a].shape, props[a], join(val[a], case))
         order = props[a].get("regions_class_order") if regions_from_pkl else None
         groups.setdefault((full, lo, None if order is None else tuple(order)), []).append((a, b))
     out = {}

@@ -1148,6 +1148,35 @@ def prev_stage_onehot(seg, classes, out):
 ENSEMBLE_MAX_MEMBERS = 16
 
 
+def _check_members(who, members, lo, hi):
+    """lo..hi contiguous CUDA tensors [K,Z,Y,X] of one shape, dtype (float16 / float32) and device, K in 1..255 -> the first"""
+    if not lo <= len(members) <= hi:
+        raise ValueError("%s: %d members (%d..%d are supported)" % (who, len(members), lo, hi))
+    for i, m in enumerate(members):
+        if not isinstance(m, torch.Tensor) or not m.is_cuda:
+            raise TypeError("%s: member %d must be a CUDA/HIP tensor (cineflow has no CPU path)" % (who, i))
+    first = members[0]
+    if first.dtype not in (torch.float16, torch.float32) or first.dim() != 4:
+        raise ValueError("%s: members must be [K,Z,Y,X] float16 or float32, member 0 is %s %s" % (who, tuple(first.shape), first.dtype))
+    for i, m in enumerate(members):
+        if m.dtype != first.dtype or m.shape != first.shape or m.device != first.device:
+            raise ValueError("%s: member %d is %s %s on %s, member 0 is %s %s on %s"
+                             % (who, i, tuple(m.shape), m.dtype, m.device, tuple(first.shape), first.dtype, first.device))
+        if not m.is_contiguous():
+            raise ValueError("%s: member %d must be contiguous" % (who, i))
+    if not 1 <= first.shape[0] <= 255:
+        raise ValueError("%s: %d classes (1..255 are supported)" % (who, first.shape[0]))
+    return first
+
+
+def _check_placement(who, size, bbox_lo, full_shape):
+    """the crop of `size` at bbox_lo must lie inside full_shape; returns bbox_lo as ints"""
+    bbox_lo = tuple(int(v) for v in bbox_lo)
+    if len(full_shape) != 3 or len(bbox_lo) != 3 or any(lo < 0 or lo + n > f for lo, n, f in zip(bbox_lo, size, full_shape)):
+        raise ValueError("%s: members of size %s at %s do not fit into %s" % (who, tuple(size), bbox_lo, tuple(full_shape)))
+    return bbox_lo
+
+
 def _ensemble_merge_into(members, seg, bbox_lo, mean, regions_class_order):
     """cf_ensemble_merge on checked arguments: members [K,Z,Y,X] float16 / float32 -> labels into `seg` (uint8 [Zf,Yf,Xf], contiguous, every
     voxel written) and, when `mean` is a tensor like a member, the mean into it."""
@@ -1169,31 +1198,11 @@ def ensemble_merge(members, full_shape=None, bbox_lo=(0, 0, 0), want_mean=False,
     np.mean(np.vstack([m[None] for m in members]), 0) bit for bit; seg is its argmax(0) -- or, with a regions_class_order, 0 overwritten by
     regions_class_order[i] where mean[i] > 0.5, in that order -- placed at bbox_lo inside zeros of full_shape (default: the members' own)."""
     members = list(members)
-    if not 1 <= len(members) <= ENSEMBLE_MAX_MEMBERS:
-        raise ValueError("ensemble_merge: %d members (1..%d are supported)" % (len(members), ENSEMBLE_MAX_MEMBERS))
-    for i, m in enumerate(members):
-        if not isinstance(m, torch.Tensor) or not m.is_cuda:
-            raise TypeError("ensemble_merge: member %d must be a CUDA/HIP tensor (cineflow has no CPU path)" % i)
-    first = members[0]
-    if first.dtype not in (torch.float16, torch.float32) or first.dim() != 4:
-        raise ValueError("ensemble_merge: members must be [K,Z,Y,X] float16 or float32, member 0 is %s %s" % (tuple(first.shape), first.dtype))
-    for i, m in enumerate(members):
-        if m.dtype != first.dtype or m.shape != first.shape or m.device != first.device:
-            raise ValueError("ensemble_merge: member %d is %s %s on %s, member 0 is %s %s on %s"
-                             % (i, tuple(m.shape), m.dtype, m.device, tuple(first.shape), first.dtype, first.device))
-        if not m.is_contiguous():
-            raise ValueError("ensemble_merge: member %d must be contiguous" % i)
-    K = first.shape[0]
-    if not 1 <= K <= 255:
-        raise ValueError("ensemble_merge: %d classes (1..255 are supported)" % K)
+    first = _check_members("ensemble_merge", members, 1, ENSEMBLE_MAX_MEMBERS)
     full_shape = tuple(int(v) for v in (first.shape[1:] if full_shape is None else full_shape))
-    bbox_lo = tuple(int(v) for v in bbox_lo)
-    if len(full_shape) != 3 or len(bbox_lo) != 3 or any(lo < 0 or lo + n > f for lo, n, f in zip(bbox_lo, first.shape[1:], full_shape)):
-        raise ValueError("ensemble_merge: members of size %s at %s do not fit into %s" % (tuple(first.shape[1:]), bbox_lo, full_shape))
+    bbox_lo = _check_placement("ensemble_merge", first.shape[1:], bbox_lo, full_shape)
     if regions_class_order is not None:
-        regions_class_order = [int(c) for c in regions_class_order]
-        if len(regions_class_order) != K or any(c < 0 or c > 255 for c in regions_class_order):
-            raise ValueError("ensemble_merge: regions_class_order must hold one label in 0..255 per class (%d), got %r" % (K, regions_class_order))
+        regions_class_order = check_regions_class_order(regions_class_order, first.shape[0], "ensemble_merge: regions_class_order")
     seg = torch.empty(full_shape, dtype=torch.uint8, device=first.device)
     mean = torch.empty_like(first) if want_mean else None
     _ensemble_merge_into(members, seg, bbox_lo, mean, regions_class_order)
@@ -1214,23 +1223,8 @@ def ensemble_pairs(members, pairs, gt, bbox_lo=(0, 0, 0), regions_class_order=No
     (every element of both is written)."""
     import ctypes
     members = list(members)
-    if not 2 <= len(members) <= ENSEMBLE_PAIRS_MAX_MEMBERS:
-        raise ValueError("ensemble_pairs: %d members (2..%d are supported)" % (len(members), ENSEMBLE_PAIRS_MAX_MEMBERS))
-    for i, m in enumerate(members):
-        if not isinstance(m, torch.Tensor) or not m.is_cuda:
-            raise TypeError("ensemble_pairs: member %d must be a CUDA/HIP tensor (cineflow has no CPU path)" % i)
-    first = members[0]
-    if first.dtype not in (torch.float16, torch.float32) or first.dim() != 4:
-        raise ValueError("ensemble_pairs: members must be [K,Z,Y,X] float16 or float32, member 0 is %s %s" % (tuple(first.shape), first.dtype))
-    for i, m in enumerate(members):
-        if m.dtype != first.dtype or m.shape != first.shape or m.device != first.device:
-            raise ValueError("ensemble_pairs: member %d is %s %s on %s, member 0 is %s %s on %s"
-                             % (i, tuple(m.shape), m.dtype, m.device, tuple(first.shape), first.dtype, first.device))
-        if not m.is_contiguous():
-            raise ValueError("ensemble_pairs: member %d must be contiguous" % i)
+    first = _check_members("ensemble_pairs", members, 2, ENSEMBLE_PAIRS_MAX_MEMBERS)
     K, Z, Y, X = first.shape
-    if not 1 <= K <= 255:
-        raise ValueError("ensemble_pairs: %d classes (1..255 are supported)" % K)
     pairs = [(int(i), int(j)) for i, j in pairs]
     if not 1 <= len(pairs) <= ENSEMBLE_PAIRS_MAX:
         raise ValueError("ensemble_pairs: %d pairs (1..%d are supported)" % (len(pairs), ENSEMBLE_PAIRS_MAX))
@@ -1240,14 +1234,10 @@ def ensemble_pairs(members, pairs, gt, bbox_lo=(0, 0, 0), regions_class_order=No
     if not isinstance(gt, torch.Tensor) or gt.dtype != torch.uint8 or gt.dim() != 3 or gt.device != first.device or not gt.is_contiguous():
         raise ValueError("ensemble_pairs: gt must be a contiguous uint8 [Zf,Yf,Xf] tensor on the members' device")
     Zf, Yf, Xf = gt.shape
-    bbox_lo = tuple(int(v) for v in bbox_lo)
-    if len(bbox_lo) != 3 or any(lo < 0 or lo + n > f for lo, n, f in zip(bbox_lo, (Z, Y, X), (Zf, Yf, Xf))):
-        raise ValueError("ensemble_pairs: members of size %s at %s do not fit into %s" % ((Z, Y, X), bbox_lo, (Zf, Yf, Xf)))
+    bbox_lo = _check_placement("ensemble_pairs", (Z, Y, X), bbox_lo, (Zf, Yf, Xf))
     order = None
     if regions_class_order is not None:
-        regions_class_order = [int(c) for c in regions_class_order]
-        if len(regions_class_order) != K or any(c < 0 or c > 255 for c in regions_class_order):
-            raise ValueError("ensemble_pairs: regions_class_order must hold one label in 0..255 per class (%d), got %r" % (K, regions_class_order))
+        regions_class_order = check_regions_class_order(regions_class_order, K, "ensemble_pairs: regions_class_order")
         order = ctypes.cast((ctypes.c_uint8 * K)(*regions_class_order), ctypes.c_void_p)
     P = len(pairs)
     bins = ENSEMBLE_PAIRS_HIST_K * ENSEMBLE_PAIRS_HIST_K + 1

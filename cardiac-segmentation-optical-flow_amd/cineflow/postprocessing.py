@@ -16,7 +16,6 @@ several hundred CT-sized volumes does not fit and has to be split.
 
     python -m cineflow.postprocessing -f EXPERIMENT_FOLDER          # consolidate_folds
 """
-import json
 import os
 import shutil
 import time
@@ -27,9 +26,10 @@ import numpy as np
 import torch
 
 from . import metrics, ops
-from .evaluation import Loaded, aggregate_scores, label_volume_u8, load_volume, save_json
-from .export import load_remove_save, subfiles
-from .metrics import ConfusionMatrix
+from .evaluation import aggregate_scores
+from .export import load_remove_save
+from .folder_io import Loaded, load_json, load_volume, save_json, subfiles
+from .metrics import ConfusionMatrix, label_volume_u8
 from .nifti import write_nifti
 
 default_num_threads = 1          # nnunet/configuration.py:4
@@ -43,11 +43,6 @@ def _timed_load(path):
     v = load_volume(path)
     LAST_TIMING["read_s"] = LAST_TIMING.get("read_s", 0.0) + time.perf_counter() - t0       # (float add under the GIL)
     return v
-
-
-def load_json(file):
-    with open(file) as f:
-        return json.load(f)
 
 
 class _Case:

@@ -35,15 +35,14 @@ jacobian_tables, ssim_tables, contour_tables, strain_tables).
 """
 import collections
 import csv
-import json
 import os
 import warnings
 import zipfile
 import zlib
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+from .folder_io import read_ahead, save_json
 from .nifti import read_nifti
 
 join = os.path.join
@@ -443,11 +442,6 @@ def strain_tables(per_patient):
     return {"all": collections.OrderedDict((p, [dict(e) for e in entries]) for p, entries in per_patient.items()), "mean": mean}
 
 
-def save_json(obj, file):
-    with open(file, "w") as f:
-        json.dump(obj, f, sort_keys=True, indent=4)
-
-
 def write_csv(file, columns, rows):
     with open(file, "w", newline="") as f:
         writer = csv.DictWriter(f, fieldnames=list(columns))
@@ -516,13 +510,8 @@ def _read_contour_case(case):
 
 def _prefetched(patients, read):
     """yields (patient, cases, [read(case)]) in order; the files of the next patient are read while the caller works on this one"""
-    with ThreadPoolExecutor(READERS) as pool:
-        submit = lambda i: [pool.submit(read, c) for c in patients[i][1]] if i < len(patients) else None          # noqa: E731
-        ahead = submit(0)
-        for i, (patient, cases) in enumerate(patients):
-            loaded = [f.result() for f in ahead]
-            ahead = submit(i + 1)
-            yield patient, cases, loaded
+    for (_, loaded), (patient, cases) in zip(read_ahead([cases for _, cases in patients], read, depth=1, readers=READERS), patients):
+        yield patient, cases, loaded
 
 
 # ------------------------------------------------------------------------------------------------ drivers

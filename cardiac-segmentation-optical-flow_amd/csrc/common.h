@@ -15,15 +15,16 @@ namespace cf {
 
 void set_error(const std::string& s);
 
-#define CF_REQUIRE(cond, ...)                                   \
+#define CF_REQUIRE_AS(who, cond, ...)                           \
     do {                                                        \
         if (!(cond)) {                                          \
             char _b[512];                                       \
             snprintf(_b, sizeof(_b), __VA_ARGS__);              \
-            cf::set_error(std::string(__func__) + ": " + _b);   \
+            cf::set_error(std::string(who) + ": " + _b);        \
             return CF_ERR_ARG;                                  \
         }                                                       \
     } while (0)
+#define CF_REQUIRE(cond, ...) CF_REQUIRE_AS(__func__, cond, __VA_ARGS__)   // _AS: for code that entry points share, under the entry's name
 
 #define CF_CHECK_LAUNCH()                                                                  \
     do {                                                                                   \

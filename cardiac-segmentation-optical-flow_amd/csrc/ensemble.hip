@@ -381,12 +381,51 @@ __global__ void __launch_bounds__(256) region_labels_kernel(const float* __restr
 
 using namespace cf;
 
+static EnsembleOrder order_of(const uint8_t* order, int K) {        // HOST array of the regions' label values; all 0 without one
+    EnsembleOrder ord = {};
+    if (order)
+        for (int k = 0; k < K; ++k) ord.v[k] = order[k];
+    return ord;
+}
+
+// What cf_ensemble_merge and cf_ensemble_pairs share ahead of their launch, under the entry's name `who` (the prefix of cf_last_error()).
+// Two steps, with the entry's own checks in between, so that the first check to fail is the one it always was.
+struct EnsembleCall {
+    EnsembleMembers mem;
+    EnsembleOrder ord;
+    long units;                                                     // 8-voxel chunks of the output
+
+    int check(const char* who, const void* const* members, int n_members, int dtype, int K, int Z, int Y, int X, int Zf, int Yf, int Xf, int z0,
+              int y0, int x0, const uint8_t* order) {
+        CF_REQUIRE_AS(who, dtype == 0 || dtype == 1, "dtype = %d is neither 0 (fp16) nor 1 (fp32)", dtype);
+        CF_REQUIRE_AS(who, K >= 1 && K <= ENSEMBLE_MAX_CLASSES, "K = %d is outside 1..%d", K, ENSEMBLE_MAX_CLASSES);
+        CF_REQUIRE_AS(who, Z > 0 && Y > 0 && X > 0 && Zf > 0 && Yf > 0 && Xf > 0, "bad shape (%d, %d, %d) in (%d, %d, %d)", Z, Y, X, Zf, Yf, Xf);
+        CF_REQUIRE_AS(who, z0 >= 0 && y0 >= 0 && x0 >= 0 && (long)z0 + Z <= Zf && (long)y0 + Y <= Yf && (long)x0 + X <= Xf,
+                      "the crop (%d, %d, %d) at (%d, %d, %d) overhangs the volume (%d, %d, %d)", Z, Y, X, z0, y0, x0, Zf, Yf, Xf);
+        const uintptr_t emask = dtype == 0 ? 1 : 3;
+        mem = {};
+        for (int n = 0; n < n_members; ++n) {                       // HOST array of device pointers
+            CF_REQUIRE_AS(who, members[n], "member %d is a null pointer", n);
+            CF_REQUIRE_AS(who, (reinterpret_cast<uintptr_t>(members[n]) & emask) == 0, "member %d is not aligned to its element size", n);
+            mem.p[n] = members[n];
+        }
+        ord = order_of(order, K);
+        units = (long)Zf * Yf * ((x0 + 7) / 8 + (X + 7) / 8 + (Xf - x0 - X + 7) / 8);
+        return CF_OK;
+    }
+    int grid(const char* who, unsigned* blocks) const {
+        CF_REQUIRE_AS(who, units < (1L << 31) - 1, "output of %ld 8-voxel chunks is too large", units);
+        const long cap = (long)device_cu_count() * 8;               // grid-stride: 8 blocks of 4 waves per compute unit
+        *blocks = (unsigned)std::min((units + 255) / 256, cap);
+        return CF_OK;
+    }
+};
+
 extern "C" int cf_region_labels(const float* probs, uint8_t* seg, int B, int K, long HW, const uint8_t* order, void* stream) {
     CF_REQUIRE(probs && seg && order, "null pointer");
     CF_REQUIRE(K >= 1 && K <= ENSEMBLE_MAX_CLASSES, "K = %d is outside 1..%d", K, ENSEMBLE_MAX_CLASSES);
     CF_REQUIRE(B > 0 && HW > 0, "bad shape B=%d HW=%ld", B, HW);
-    EnsembleOrder ord = {};
-    for (int k = 0; k < K; ++k) ord.v[k] = order[k];                // HOST array of the regions' label values
+    const EnsembleOrder ord = order_of(order, K);
     const bool vec = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(probs) & 15) == 0 && (reinterpret_cast<uintptr_t>(seg) & 3) == 0;
     const long total = vec ? (long)B * (HW / 4) : (long)B * HW;
     if (vec)
@@ -401,32 +440,15 @@ extern "C" int cf_ensemble_merge(const void* const* members, int n_members, int 
                                  int Xf, int z0, int y0, int x0, void* mean, const uint8_t* order, void* stream) {
     CF_REQUIRE(n_members >= 1 && n_members <= ENSEMBLE_MAX_MEMBERS, "n_members = %d is outside 1..%d", n_members, ENSEMBLE_MAX_MEMBERS);
     CF_REQUIRE(members && seg, "null pointer");
-    CF_REQUIRE(dtype == 0 || dtype == 1, "dtype = %d is neither 0 (fp16) nor 1 (fp32)", dtype);
-    CF_REQUIRE(K >= 1 && K <= ENSEMBLE_MAX_CLASSES, "K = %d is outside 1..%d", K, ENSEMBLE_MAX_CLASSES);
-    CF_REQUIRE(Z > 0 && Y > 0 && X > 0 && Zf > 0 && Yf > 0 && Xf > 0, "bad shape (%d, %d, %d) in (%d, %d, %d)", Z, Y, X, Zf, Yf, Xf);
-    CF_REQUIRE(z0 >= 0 && y0 >= 0 && x0 >= 0 && (long)z0 + Z <= Zf && (long)y0 + Y <= Yf && (long)x0 + X <= Xf,
-               "the crop (%d, %d, %d) at (%d, %d, %d) overhangs the volume (%d, %d, %d)", Z, Y, X, z0, y0, x0, Zf, Yf, Xf);
-    const uintptr_t emask = dtype == 0 ? 1 : 3;
-    EnsembleMembers mem = {};
-    for (int n = 0; n < n_members; ++n) {                           // HOST array of device pointers
-        CF_REQUIRE(members[n], "member %d is a null pointer", n);
-        CF_REQUIRE((reinterpret_cast<uintptr_t>(members[n]) & emask) == 0, "member %d is not aligned to its element size", n);
-        mem.p[n] = members[n];
-    }
-    CF_REQUIRE((reinterpret_cast<uintptr_t>(mean) & emask) == 0, "mean is not aligned to its element size");
-    EnsembleOrder ord = {};
-    if (order)
-        for (int k = 0; k < K; ++k) ord.v[k] = order[k];            // HOST array of the regions' label values
-    const long per_row = (x0 + 7) / 8 + (X + 7) / 8 + (Xf - x0 - X + 7) / 8;
-    const long units = (long)Zf * Yf * per_row;
-    CF_REQUIRE(units < (1L << 31) - 1, "output of %ld 8-voxel chunks is too large", units);
-    long blocks = (units + 255) / 256;
-    const long cap = (long)device_cu_count() * 8;                   // grid-stride: 8 blocks of 4 waves per compute unit
-    if (blocks > cap) blocks = cap;
+    EnsembleCall c;
+    unsigned blocks;
+    if (int e = c.check(__func__, members, n_members, dtype, K, Z, Y, X, Zf, Yf, Xf, z0, y0, x0, order)) return e;
+    CF_REQUIRE((reinterpret_cast<uintptr_t>(mean) & (dtype == 0 ? 1 : 3)) == 0, "mean is not aligned to its element size");
+    if (int e = c.grid(__func__, &blocks)) return e;
     if (dtype == 0)
-        launch_ensemble<__half>((unsigned)blocks, as_stream(stream), mem, n_members, K, Z, Y, X, seg, Zf, Yf, Xf, z0, y0, x0, mean, ord, order != nullptr);
+        launch_ensemble<__half>(blocks, as_stream(stream), c.mem, n_members, K, Z, Y, X, seg, Zf, Yf, Xf, z0, y0, x0, mean, c.ord, order != nullptr);
     else
-        launch_ensemble<float>((unsigned)blocks, as_stream(stream), mem, n_members, K, Z, Y, X, seg, Zf, Yf, Xf, z0, y0, x0, mean, ord, order != nullptr);
+        launch_ensemble<float>(blocks, as_stream(stream), c.mem, n_members, K, Z, Y, X, seg, Zf, Yf, Xf, z0, y0, x0, mean, c.ord, order != nullptr);
     CF_CHECK_LAUNCH();
     return CF_OK;
 }
@@ -450,18 +472,9 @@ extern "C" int cf_ensemble_pairs(const void* const* members, int n_members, int 
     CF_REQUIRE(n_members >= 2 && n_members <= PAIRS_MAX_MEMBERS, "n_members = %d is outside 2..%d", n_members, PAIRS_MAX_MEMBERS);
     CF_REQUIRE(n_pairs >= 1 && n_pairs <= PAIRS_MAX, "n_pairs = %d is outside 1..%d", n_pairs, PAIRS_MAX);
     CF_REQUIRE(members && pairs && gt && seg && hist, "null pointer");
-    CF_REQUIRE(dtype == 0 || dtype == 1, "dtype = %d is neither 0 (fp16) nor 1 (fp32)", dtype);
-    CF_REQUIRE(K >= 1 && K <= ENSEMBLE_MAX_CLASSES, "K = %d is outside 1..%d", K, ENSEMBLE_MAX_CLASSES);
-    CF_REQUIRE(Z > 0 && Y > 0 && X > 0 && Zf > 0 && Yf > 0 && Xf > 0, "bad shape (%d, %d, %d) in (%d, %d, %d)", Z, Y, X, Zf, Yf, Xf);
-    CF_REQUIRE(z0 >= 0 && y0 >= 0 && x0 >= 0 && (long)z0 + Z <= Zf && (long)y0 + Y <= Yf && (long)x0 + X <= Xf,
-               "the crop (%d, %d, %d) at (%d, %d, %d) overhangs the volume (%d, %d, %d)", Z, Y, X, z0, y0, x0, Zf, Yf, Xf);
-    const uintptr_t emask = dtype == 0 ? 1 : 3;
-    EnsembleMembers mem = {};
-    for (int n = 0; n < n_members; ++n) {                           // HOST array of device pointers
-        CF_REQUIRE(members[n], "member %d is a null pointer", n);
-        CF_REQUIRE((reinterpret_cast<uintptr_t>(members[n]) & emask) == 0, "member %d is not aligned to its element size", n);
-        mem.p[n] = members[n];
-    }
+    EnsembleCall c;
+    unsigned blocks;
+    if (int e = c.check(__func__, members, n_members, dtype, K, Z, Y, X, Zf, Yf, Xf, z0, y0, x0, order)) return e;
     EnsemblePairUsers users = {};
     for (int p = 0; p < n_pairs; ++p) {                             // HOST array of n_pairs (i, j)
         const int i = pairs[2 * p], j = pairs[2 * p + 1];
@@ -470,20 +483,14 @@ extern "C" int cf_ensemble_pairs(const void* const* members, int n_members, int 
         const int a = i < j ? i : j, b = i < j ? j : i;
         users.v[a * n_members - a * (a + 1) / 2 + (b - a - 1)] |= 1u << p;     // (a, b)'s place among the (i < j) in lexicographic order
     }
-    EnsembleOrder ord = {};
-    if (order)
-        for (int k = 0; k < K; ++k) ord.v[k] = order[k];            // HOST array of the regions' label values
-    const long per_row = (x0 + 7) / 8 + (X + 7) / 8 + (Xf - x0 - X + 7) / 8;
-    const long units = (long)Zf * Yf * per_row;
-    CF_REQUIRE(units < (1L << 31) - 1, "output of %ld 8-voxel chunks is too large", units);
+    if (int e = c.grid(__func__, &blocks)) return e;
     hipStream_t s = as_stream(stream);
     if (hipMemsetAsync(hist, 0, (size_t)n_pairs * PAIRS_BINS * sizeof(unsigned long long), s) != hipSuccess) {
         set_error("cf_ensemble_pairs: memset failed");
         return CF_ERR_LAUNCH;
     }
-    long blocks = (units + 255) / 256;
-    const long cap = (long)device_cu_count() * 8;                   // grid-stride, as cf_ensemble_merge
-    if (blocks > cap) blocks = cap;
+    const EnsembleMembers& mem = c.mem;                             // (the names the switch below reads)
+    const EnsembleOrder& ord = c.ord;
     const bool regions = order != nullptr;
 #define CF_PAIRS_CASE(M_)                                                                                                                      \
     case M_:                                                                                                                                   \
