@@ -150,6 +150,9 @@ SIGNATURES = {
     "cf_frame_boxes": [P, I, P, I, I, I, P],
     "cf_crop_windows": [P, P, P, I, I, I, I, I, P],
     "cf_sample_points_2d": [P, P, P, I, I, I, I, I, P],
+    "cf_select_blocks": [L],
+    "cf_select_count": [P, L, P, I, I, P, P, P],
+    "cf_select_rank": [P, L, I, F, P, P, I, P, P, P, I, I, I, P],
     "cf_profile_enable": [I],
     "cf_profile_reset": [],
     "cf_profile_read": [I, P, P, P],

@@ -1419,3 +1419,70 @@ def cc_apply(src, K, do_fg, classes, labels_fg, counts_fg, max_fg, labels_cls, c
                             ptr(labels_cls), ptr(counts_cls), ptr(max_cls), float(volume_per_voxel), None if mv is None else ctypes.cast(mv, ctypes.c_void_p),
                             _stream()), "cf_cc_apply")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ voxels by rank (csrc/dataset.hip)
+class RankIndex(object):
+    """The block prefixes of one count pass over `key` (cf_select_count): what select_coords / select_values search.  values None: the one
+    row of the predicate `key > 0`; else one row per listed value, `key == value`.  totals: numpy int64, one per row (the only read-back)."""
+
+    def __init__(self, key, values=None):
+        import ctypes
+        ptr = _f32(key, "key")
+        self.key, self.n = key, key.numel()
+        self.values = None if values is None else [float(v) for v in values]
+        rows = 1 if values is None else len(self.values)
+        nb = max(lib().cf_select_blocks(self.n), 1)
+        self.prefix = torch.empty((max(rows, 1), nb), dtype=torch.int32, device=key.device)
+        totals = torch.empty(max(rows, 1), dtype=torch.int64, device=key.device)
+        vals = None if values is None else ctypes.cast((ctypes.c_float * max(rows, 1))(*self.values), ctypes.c_void_p)
+        check(lib().cf_select_count(ptr, self.n, vals, rows, int(values is None), self.prefix.data_ptr(), totals.data_ptr(), _stream()), "cf_select_count")
+        self.totals = totals.cpu().numpy()
+
+    def row(self, value):
+        if self.values is None:
+            assert value is None, "this index holds the `> 0` predicate"
+            return 0
+        return self.values.index(float(value))
+
+
+def label_counts(seg, values):
+    """np.array([(seg == v).sum() for v in values]) of a float32 device volume (at most 16 values) -> numpy int64."""
+    return RankIndex(seg, values).totals
+
+
+def _select(key, value, ranks, src, index):
+    index = RankIndex(key, None if value is None else [value]) if index is None else index
+    assert index.key.data_ptr() == key.data_ptr() and index.n == key.numel(), "the index was counted over another volume"
+    row = index.row(value)
+    total = int(index.totals[row])
+    if not torch.is_tensor(ranks):
+        ranks = torch.from_numpy(np.ascontiguousarray(np.asarray(ranks, dtype=np.int64)).reshape(-1))
+    K = ranks.numel()
+    if K and not ranks.is_cuda and (int(ranks.min()) < 0 or int(ranks.max()) >= total):
+        raise IndexError("rank out of bounds: %d voxels match" % total)
+    ranks = ranks.to(key.device, dtype=torch.int64).contiguous()
+    if src is not None:
+        assert src.numel() == key.numel(), "src and key must have the same number of voxels"
+        out = torch.empty(K, dtype=torch.float32, device=key.device)
+        args = (_f32(src, "src"), out.data_ptr(), None, 0, 0, 0)
+    else:
+        assert key.dim() == 3, "select_coords takes a 3-D volume"
+        out = torch.empty((K, 3), dtype=torch.int64, device=key.device)
+        args = (None, None, out.data_ptr()) + tuple(key.shape)
+    if K == 0:              # (an empty tensor has no address to hand over; the call would launch nothing)
+        return out
+    check(lib().cf_select_rank(_f32(key, "key"), key.numel(), int(value is None), 0.0 if value is None else float(value), index.prefix[row].data_ptr(),
+                               ranks.data_ptr() if K else None, K, *args, _stream()), "cf_select_rank")
+    return out
+
+
+def select_coords(seg, value, ranks, index=None):
+    """np.argwhere(seg == value)[ranks] of a float32 device volume [X, Y, Z] -> int64 device tensor [K, 3].  ranks: numpy or tensor, any
+    order, duplicates allowed.  index: a RankIndex over `seg` that lists `value` (saves the count pass when several classes are asked)."""
+    return _select(seg, value, ranks, None, index)
+
+
+def select_values(src, key, ranks, index=None):
+    """src[key > 0][ranks] of two float32 device arrays of the same size -> float32 device tensor [K]."""
+    return _select(key, None, ranks, src, index)

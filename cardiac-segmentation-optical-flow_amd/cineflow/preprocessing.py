@@ -5,8 +5,11 @@ class names, argument meaning and return values; numpy in, numpy out like the re
 `trainer.preprocess_patient` (nnunet/training/network_training/nnUNetTrainer.py:571-597) is a drop-in.  Every number comes from
 libcineflow_hip.so (csrc/preprocess.hip, csrc/postprocess.hip); torch only holds memory, slices and moves it.
 """
+import copy
 import ctypes
 import os
+import pickle
+import shutil
 from collections import OrderedDict
 
 import numpy as np
@@ -123,8 +126,108 @@ def load_case_from_list_of_files(data_files, seg_file=None, info_dict=None):
     return data_npy.astype(np.float32), seg_npy, properties
 
 
+def get_case_identifier(case):
+    """cropping.py:65-68: `<patient>_<frame>` of a case's first image file `<patient>_<frame>_0000.nii.gz`"""
+    return os.path.basename(case[0]).split(".nii.gz")[0][:-5]
+
+
+def get_case_identifier_from_npz(case):
+    return os.path.basename(case)[:-4]
+
+
+def _save_case(folder, case_identifier, all_data, properties):
+    np.savez_compressed(os.path.join(folder, "%s.npz" % case_identifier), data=all_data)
+    with open(os.path.join(folder, "%s.pkl" % case_identifier), "wb") as f:
+        pickle.dump(properties, f)
+
+
 class ImageCropper(object):
-    """cropping.py:145-177 (the test-time entry points)."""
+    """cropping.py:145-335: the test-time entry points (static) and the training-side driver of the fork, which crops the cases of a
+    patient together.  Files are read and compressed by at most 16 threads around the device work; no process pool."""
+
+    def __init__(self, num_threads, output_folder=None):
+        self.output_folder = output_folder
+        self.num_threads = max(1, min(16, int(num_threads)))
+        self.seconds = {"read": 0.0, "device": 0.0, "write": 0.0}      # where run_cropping spent its time (write: summed over the threads)
+        if self.output_folder is not None:
+            os.makedirs(self.output_folder, exist_ok=True)
+
+    get_case_identifier = staticmethod(get_case_identifier)
+
+    def _crop_patient(self, loaded):
+        """loaded: [(data, seg, properties)] of one patient's cases as numpy.  Every case is uploaded once, cropped to its own non-zero
+        box on the device and zero-padded to the union of the patient's boxes -> [(device data, device seg, properties)], the union box."""
+        cropped = [ImageCropper.crop(_to_dev(d), p, _to_dev(s)) for d, s, p in loaded]
+        boxes = np.stack([np.stack([np.array(b) for b in p["crop_bbox"]]) for _, _, p in cropped])       # [cases, 3, 2]
+        lo, hi = np.min(boxes[:, :, 0], axis=0), np.max(boxes[:, :, 1], axis=0)
+        union = [list(x) for x in np.stack([lo, hi], axis=-1)]
+        return cropped, boxes[:, :, 0] - lo[None], tuple(int(v) for v in hi - lo), union
+
+    def load_crop_save(self, case, case_identifier, overwrite_existing=False, info_dict=None, loaded=None, pool=None):
+        """cropping.py:179-236.  case: the patient's cases [[image files ..., label file], ...]; case_identifier / info_dict: one per case.
+        loaded: the cases already read (run_cropping reads ahead); pool: an executor for the compressed writes (their futures are returned)."""
+        import time
+        if loaded is None:
+            loaded = [load_case_from_list_of_files(c[:-1], c[-1], None if info_dict is None else info_dict[i]) for i, c in enumerate(case)]
+        t0 = time.perf_counter()
+        cropped, before, union_size, union = self._crop_patient(loaded)
+        writes = []
+        for i, (d, s, props) in enumerate(cropped):
+            if "Quorum" not in case[i][0]:
+                # np.pad of data and seg to the union box: zeros around the case's own box
+                full = torch.zeros((d.shape[0] + s.shape[0],) + union_size, dtype=torch.float32, device=d.device)
+                sl = (slice(None),) + tuple(slice(int(b), int(b) + n) for b, n in zip(before[i], d.shape[1:]))
+                full[:d.shape[0]][sl] = d
+                full[d.shape[0]:][sl] = s.float()
+            else:
+                full = torch.cat([d, s.float()], 0)
+            props["size_after_cropping"] = tuple(full.shape[1:])
+            props["crop_bbox"] = union
+            npz = os.path.join(self.output_folder, "%s.npz" % case_identifier[i])
+            if overwrite_existing or not os.path.isfile(npz) or not os.path.isfile(npz[:-4] + ".pkl"):
+                args = (self.output_folder, case_identifier[i], full.cpu().numpy(), props)
+                if pool is not None:
+                    writes.append(pool.submit(self._timed_save, *args))
+                else:
+                    self.seconds["write"] += self._timed_save(*args)
+        self.seconds["device"] += time.perf_counter() - t0
+        return writes
+
+    def _timed_save(self, *args):
+        import time
+        t0 = time.perf_counter()
+        _save_case(*args)
+        return time.perf_counter() - t0
+
+    def run_cropping(self, list_of_files, overwrite_existing=False, output_folder=None, info_list=None):
+        """cropping.py:298-334.  list_of_files: patients -> cases -> [image files ..., label file]; info_list: patients -> cases -> the
+        case's dataset.json training entry.  The label files are copied to <output_folder>/gt_segmentations."""
+        import time
+        from concurrent.futures import ThreadPoolExecutor
+        from .folder_io import read_ahead
+        if output_folder is not None:
+            self.output_folder = output_folder
+        output_folder_gt = os.path.join(self.output_folder, "gt_segmentations")
+        os.makedirs(output_folder_gt, exist_ok=True)
+        if info_list is None:
+            info_list = [[None] * len(p) for p in list_of_files]
+        jobs = []
+        for p, patient_info in zip(list_of_files, info_list):
+            for case in p:
+                if case[-1] is not None:
+                    shutil.copy(case[-1], output_folder_gt)
+            jobs.append([(case, info) for case, info in zip(p, patient_info)])
+        writes = []
+        with ThreadPoolExecutor(self.num_threads) as pool:
+            t0 = time.perf_counter()
+            # (half the threads read ahead -- a patient is a few files -- while the others compress what the device has finished)
+            for job, loaded in read_ahead(jobs, lambda ci: load_case_from_list_of_files(ci[0][:-1], ci[0][-1], ci[1]), depth=max(2, self.num_threads // 4),
+                                          pool=pool):
+                self.seconds["read"] += time.perf_counter() - t0           # what the device waited for, not the threads' total
+                p, info = [c for c, _ in job], [i for _, i in job]
+                writes += self.load_crop_save(p, [get_case_identifier(c) for c in p], overwrite_existing, info, loaded=loaded, pool=pool)
+                t0 = time.perf_counter()
+            self.seconds["write"] += sum(w.result() for w in writes)
 
     @staticmethod
     def crop(data, properties, seg=None):
@@ -433,6 +536,89 @@ class GenericPreprocessor(object):
         if seg_prev is not None:
             d = prev_stage_to_input(d, seg_prev, prev_stage_classes)
         return d.cpu().numpy().astype(np.float32, copy=False), (s.cpu().numpy() if need_seg else None), properties
+
+    @staticmethod
+    def load_cropped(cropped_output_dir, case_identifier):
+        """preprocessing.py:219-226 -> (all_data [C + 1, X, Y, Z] as stored, properties)"""
+        from .safe_pickle import load_plain_pickle
+        all_data = np.load(os.path.join(cropped_output_dir, "%s.npz" % case_identifier))["data"]
+        return all_data, load_plain_pickle(os.path.join(cropped_output_dir, "%s.pkl" % case_identifier))
+
+    @staticmethod
+    def class_locations(seg, all_classes, num_samples=10000, min_percent_coverage=0.01, seed=1234):
+        """preprocessing.py:403-421 for a device label volume [X, Y, Z] (float32): per foreground class up to num_samples voxel
+        coordinates (at least min_percent_coverage of the class), drawn without replacement by ONE np.random.RandomState(seed) that the
+        classes consume in all_classes order -- np.argwhere(seg == c)[rndst.choice(n, target, replace=False)] without the argwhere: the
+        counts come from the count pass, the coordinates from the select kernel.  -> {class: int64 [target, 3] or []}"""
+        rndst = np.random.RandomState(seed)
+        class_locs = {}
+        seg = seg.contiguous()
+        for g in range(0, len(all_classes), 16):                    # (a count pass takes 16 values)
+            group = list(all_classes[g:g + 16])
+            index = ops.RankIndex(seg, group)
+            for c, n in zip(group, index.totals.tolist()):
+                if n == 0:
+                    class_locs[c] = []
+                    continue
+                target = max(min(num_samples, n), int(np.ceil(n * min_percent_coverage)))
+                class_locs[c] = ops.select_coords(seg, c, rndst.choice(n, target, replace=False), index).cpu().numpy()
+        return class_locs
+
+    def _run_case(self, all_data, properties, target_spacings, force_separate_z, all_classes, keep_spacing):
+        """preprocessing.py:387-427 for every stage of one labelled case: all_data [C + 1, X, Y, Z] (numpy, the cropped .npz) goes to the
+        device once -> [(all_data float32 numpy, properties)] per stage"""
+        tf = (0, *[i + 1 for i in self.transpose_forward])
+        t = _to_dev(all_data).permute(tf).contiguous()
+        out = []
+        for target_spacing in target_spacings:
+            props = copy.deepcopy(properties)
+            if keep_spacing:
+                target_spacing = props["original_spacing"]
+            d, s, props = self.resample_and_normalize(t[:-1].clone(), target_spacing, props, t[-1:].clone(), force_separate_z)   # (normalised in place)
+            staged = torch.cat([d, s.float()], 0)
+            props["class_locations"] = self.class_locations(staged[-1], all_classes)
+            out.append((staged.cpu().numpy(), props))
+        return out
+
+    def run(self, target_spacings, input_folder_with_cropped_npz, output_folder, data_identifier, num_threads=8, force_separate_z=None,
+            keep_spacing=False):
+        """preprocessing.py:429-467 / :704-730, labelled cases: <output_folder>/<data_identifier>_stage<k>/<case>.npz + .pkl for every
+        cropped case and stage.  Case-major: a case is read once (ahead, by the thread pool), uploaded once and leaves the device once
+        per stage; the compressed writes run on the same pool of at most 16 threads."""
+        import time
+        from concurrent.futures import ThreadPoolExecutor
+        from .folder_io import read_ahead, subfiles
+        from .safe_pickle import load_plain_pickle
+        cases = [get_case_identifier_from_npz(c) for c in subfiles(input_folder_with_cropped_npz, suffix=".npz")]
+        assert len(cases) != 0, "set list of files first"
+        os.makedirs(output_folder, exist_ok=True)
+        all_classes = load_plain_pickle(os.path.join(input_folder_with_cropped_npz, "dataset_properties.pkl"))["all_classes"]
+        stage_folders = [os.path.join(output_folder, data_identifier + "_stage%d" % i) for i in range(len(target_spacings))]
+        for f in stage_folders:
+            os.makedirs(f, exist_ok=True)
+        self.seconds = {"read": 0.0, "device": 0.0, "write": 0.0}
+        threads = max(1, min(16, int(num_threads[-1] if isinstance(num_threads, (list, tuple, np.ndarray)) else num_threads)))
+
+        def save(folder, case, arr, props):
+            t0 = time.perf_counter()
+            _save_case(folder, case, arr, props)
+            return time.perf_counter() - t0
+
+        writes = []
+        with ThreadPoolExecutor(threads) as pool:
+            t0 = time.perf_counter()
+            for (case,), (loaded,) in read_ahead([[c] for c in cases], lambda c: self.load_cropped(input_folder_with_cropped_npz, c), depth=max(2, threads // 2),
+                                                   pool=pool):
+                t1 = time.perf_counter()
+                self.seconds["read"] += t1 - t0
+                if "_u" in case:
+                    raise NotImplementedError("%s: unlabeled cases (`_u`) are not built" % case)
+                for folder, (arr, props) in zip(stage_folders, self._run_case(loaded[0], loaded[1], target_spacings, force_separate_z, all_classes,
+                                                                             keep_spacing)):
+                    writes.append(pool.submit(save, folder, case, arr, props))
+                t0 = time.perf_counter()
+                self.seconds["device"] += t0 - t1
+            self.seconds["write"] += sum(w.result() for w in writes)
 
     def preprocess_arrays(self, data, seg, properties, target_spacing, force_separate_z=None):
         tf = (0, *[i + 1 for i in self.transpose_forward])

@@ -711,6 +711,26 @@ int cf_crop_windows(const uint8_t* labels, int* windows, int* jobs, int N, int H
  * channel 0 is normalised by W - 1 and used as grid x, channel 1 by H - 1 as grid y (the reference's shape[~i]). */
 int cf_sample_points_2d(const float* field, const float* pts, float* out, int B, int C, int H, int W, int P, void* stream);
 
+/* ---------------------------------------------------------------- voxels by rank among the matching voxels (csrc/dataset.hip)
+ * The training-side preprocessing drivers pick voxels by their C-order rank among the voxels that match a predicate:
+ * np.argwhere(seg == c)[idx] (class locations, nnunet/preprocessing/preprocessing.py:387-470) and modality[seg > 0][::10] (foreground
+ * samples, nnunet/experiment_planning/DatasetAnalyzer.py).  key: device fp32 [n] in C order, 0 <= n < 2^31, cut into scan blocks of 256
+ * voxels; cf_select_blocks(n) = their number nb (host arithmetic).
+ * cf_select_count, mode 0: `values` is a HOST array of n_values (1..16) floats; row r counts the voxels with key == values[r].  mode 1:
+ * one row, the voxels with key > 0 (values and n_values are not read).  prefix: device int32 [rows][nb], on return the EXCLUSIVE prefix
+ * over the blocks of every row's per-block counts; totals: device int64 [rows], the rows' sums -- the only numbers a caller reads back
+ * (its random generator needs them).  Two launches (count, one-workgroup scan per row), no atomics.
+ * cf_select_rank: `prefix` is ONE row of cf_select_count's result for the same key and predicate (mode, and `value` in mode 0).  ranks:
+ * device int64 [K], any order, duplicates allowed, each 0 <= rank < that row's total.  One wave per rank: binary search for the block, then
+ * 64-bit ballots and population counts inside it.  Either src (device fp32 [n]) + vals (device fp32 [K]): vals[k] = src at the voxel --
+ * src[key > 0][ranks] -- or coords (device int64 [K][3]) with the key's shape D0 x D1 x D2 (D0 D1 D2 == n): the voxel's index triple --
+ * np.argwhere(key == value)[ranks].  Exactly one of src / coords is non-NULL.  K == 0 launches nothing.  A rank outside the contract
+ * writes -1s / 0 to its own slot and touches nothing else. */
+int cf_select_blocks(long n);
+int cf_select_count(const float* key, long n, const float* values, int n_values, int mode, int* prefix, long long* totals, void* stream);
+int cf_select_rank(const float* key, long n, int mode, float value, const int* prefix, const long long* ranks, int K, const float* src,
+                   float* vals, long long* coords, int D0, int D1, int D2, void* stream);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py only; no reference analogue)
  * cf_profile_enable(n): pre-create n event pairs and time every conv / CorrVolume launch with a (start, stop) pair that
  * brackets exactly that kernel on its own stream (hipExtLaunchKernelGGL); 0 disables.  Kernel ids:

@@ -1,0 +1,170 @@
+"""python -m cineflow.plan_and_preprocess on a synthetic task against the same stage folders computed on CPU processes.
+
+Workload: a seeded cine-like task of `--patients` (24) patients x 2 frames, one MRI modality, arrays of 12 x 256 x 224 voxels with a zero
+frame, in-plane spacings between 1.25 and 1.6 mm (every case is resampled) and 10 mm slices; labels 0-3.  Default planners
+(ExperimentPlanner3D_v21 and ExperimentPlanner2D_v21): two stage folders, 2 x cases stage files.
+
+    (a) device   cineflow.plan_and_preprocess.plan_and_preprocess: crop, fingerprint, plans, both stage folders; 16 reader / writer threads.
+                 Its report splits the two drivers' time into read (what the device loop waited for), device (upload, kernels, read-back)
+                 and compress-write (np.savez_compressed + pickle, summed over the threads: it overlaps the other two).
+    (b) cpu      the stage folders only, from (a)'s cropped folder and plans: oracle.preprocess.resample_and_normalize, class locations by
+                 np.argwhere + RandomState(1234).choice, np.savez_compressed -- the project's CPU restatement of the reference's
+                 _run_internal (the reference itself needs packages the machines lack) -- on 16 spawned worker processes, one case per
+                 task, as the reference's process pool works.  Cropping, fingerprint and planning are NOT in (b)'s time.
+
+(a) is timed by the host clock around calls that end with every file written; (b) by the host clock around the pool's map.  The label
+channels of both trees are compared case by case.  One JSON line.
+
+    python tools/plan_and_preprocess_bench.py [--patients 24] [--small]"""
+import argparse
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "cardiac-segmentation-optical-flow_amd"))
+sys.path.insert(0, ROOT)
+
+TASK = "Task502_BenchCine"
+
+
+def build_task(folder, patients, shape):
+    import numpy as np
+    from cineflow.nifti import write_nifti
+    rng = np.random.default_rng(502)
+    os.makedirs(os.path.join(folder, "imagesTr"))
+    os.makedirs(os.path.join(folder, "labelsTr"))
+    training = []
+    g = np.meshgrid(*[np.linspace(-1, 1, n) for n in shape], indexing="ij")
+    r = np.sqrt(0.3 * g[0] ** 2 + g[1] ** 2 + g[2] ** 2)
+    for p in range(patients):
+        sp = float(np.round(1.25 + 0.35 * rng.random(), 3))
+        for f in range(2):
+            case = "patient%03d_frame%02d" % (p + 1, f + 1)
+            scale = 1.0 + 0.1 * f + 0.05 * rng.random()
+            lab = np.zeros(shape, np.uint8)
+            for c, rad in ((1, 0.5), (2, 0.38), (3, 0.25)):
+                lab[r * scale < rad] = c
+            lo = rng.integers(4, 24, size=2)
+            img = np.round(rng.normal(size=shape) * 60 + 300 + 90.0 * lab).astype(np.float32)
+            img[img == 0] = 1.0
+            keep = np.zeros(shape, bool)
+            keep[:, lo[0]:shape[1] - lo[1], lo[1]:shape[2] - lo[0]] = True
+            img[~keep] = 0
+            lab[~keep] = 0
+            write_nifti(os.path.join(folder, "imagesTr", case + "_0000.nii.gz"), img, (sp, sp, 10.0))
+            write_nifti(os.path.join(folder, "labelsTr", case + ".nii.gz"), lab, (sp, sp, 10.0))
+            training.append({"image": "./imagesTr/%s.nii.gz" % case, "label": "./labelsTr/%s.nii.gz" % case})
+    with open(os.path.join(folder, "dataset.json"), "w") as fh:
+        json.dump({"modality": {"0": "MRI"}, "labels": {"0": "background", "1": "a", "2": "b", "3": "c"}, "training": training, "test": []}, fh)
+
+
+def cpu_case(job):
+    """one (case, stage) of the reference's _run_internal on the CPU -> the label channel's checksum"""
+    import copy
+    import pickle
+    import numpy as np
+    from oracle import preprocess as OP
+    cropped, case, folder, spacing, tf, schemes, use_mask, ip, two_d, all_classes = job
+    all_data = np.load(os.path.join(cropped, case + ".npz"))["data"]
+    with open(os.path.join(cropped, case + ".pkl"), "rb") as f:
+        props = pickle.load(f)
+    axes = (0, *[i + 1 for i in tf])
+    data, seg = all_data[:-1].astype(np.float32).transpose(axes), all_data[-1:].transpose(axes)
+    data, seg, props = OP.resample_and_normalize(data.copy(), spacing, copy.deepcopy(props), seg.copy(), tf, schemes, use_mask, ip, None, two_d)
+    out = np.vstack((data, seg)).astype(np.float32)
+    rnd = np.random.RandomState(1234)
+    locs = {}
+    for c in all_classes:
+        where = np.argwhere(out[-1] == c)
+        if len(where) == 0:
+            locs[c] = []
+            continue
+        n = max(min(10000, len(where)), int(np.ceil(len(where) * 0.01)))
+        locs[c] = where[rnd.choice(len(where), n, replace=False)]
+    props["class_locations"] = locs
+    np.savez_compressed(os.path.join(folder, case + ".npz"), data=out)
+    with open(os.path.join(folder, case + ".pkl"), "wb") as f:
+        pickle.dump(props, f)
+    return case, float(out[-1].sum())
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--patients", type=int, default=24)
+    ap.add_argument("--small", action="store_true", help="a rehearsal of the script at 6 x 48 x 40, not a measurement")
+    a = ap.parse_args()
+    import multiprocessing
+    import numpy as np
+    import torch
+    assert torch.cuda.is_available(), "plan_and_preprocess_bench needs a GPU"
+    from cineflow import plan_and_preprocess as PP
+    from cineflow.safe_pickle import load_plain_pickle
+    shape = (6, 48, 40) if a.small else (12, 256, 224)
+    root = tempfile.mkdtemp(prefix="ppbench_")
+    try:
+        raw, cropped, pre = (os.path.join(root, d, TASK) for d in ("raw", "cropped", "pre"))
+        build_task(raw, a.patients, shape)
+        ncases = 2 * a.patients
+        # warm-up: code objects and the allocator, on a two-patient copy of the task
+        warm = os.path.join(root, "warm")
+        os.makedirs(os.path.join(warm, "raw"))
+        for d in ("imagesTr", "labelsTr"):
+            os.makedirs(os.path.join(warm, "raw", d))
+            for f in sorted(os.listdir(os.path.join(raw, d)))[:4]:
+                shutil.copy(os.path.join(raw, d, f), os.path.join(warm, "raw", d))
+        dj = json.load(open(os.path.join(raw, "dataset.json")))
+        dj["training"] = dj["training"][:4]
+        json.dump(dj, open(os.path.join(warm, "raw", "dataset.json"), "w"))
+        PP.plan_and_preprocess(os.path.join(warm, "raw"), os.path.join(warm, "cropped"), os.path.join(warm, "pre"), tf=16)
+        torch.cuda.synchronize()
+
+        t0 = time.perf_counter()
+        report = PP.plan_and_preprocess(raw, cropped, pre, tf=16)
+        torch.cuda.synchronize()
+        device_total = time.perf_counter() - t0
+        stages = {k: v for k, v in report.items() if k not in ("crop", "fingerprint")}
+        device_stage_seconds = sum(v["total"] for v in stages.values())
+
+        jobs, folders = [], {}
+        for name, two_d in (("nnUNetPlansv2.1_plans_3D.pkl", False), ("nnUNetPlansv2.1_plans_2D.pkl", True)):
+            plans = load_plain_pickle(os.path.join(pre, name))
+            for k, st in plans["plans_per_stage"].items():
+                folder = os.path.join(root, "cpu", plans["data_identifier"] + "_stage%d" % k)
+                os.makedirs(folder)
+                folders[folder] = os.path.join(pre, plans["data_identifier"] + "_stage%d" % k)
+                for f in plans["list_of_npz_files"]:
+                    jobs.append((cropped, os.path.basename(f)[:-4], folder, np.array(st["current_spacing"]), [int(v) for v in plans["transpose_forward"]],
+                                 dict(plans["normalization_schemes"]), dict(plans["use_mask_for_norm"]), plans["dataset_properties"]["intensityproperties"],
+                                 two_d, plans["all_classes"]))
+        with multiprocessing.get_context("spawn").Pool(16) as pool:
+            pool.map(cpu_case, jobs[:16])                                        # the workers' imports are not the measurement
+            t0 = time.perf_counter()
+            pool.map(cpu_case, jobs, chunksize=1)
+            cpu_stage_seconds = time.perf_counter() - t0
+        labels_equal, worst = 0, 0.0
+        for cpu_folder, dev_folder in folders.items():
+            for f in sorted(os.listdir(cpu_folder)):
+                if f.endswith(".npz"):
+                    x, y = np.load(os.path.join(cpu_folder, f))["data"], np.load(os.path.join(dev_folder, f))["data"]
+                    labels_equal += int(x.shape == y.shape and np.array_equal(x[-1], y[-1]))
+                    if x.shape == y.shape:
+                        worst = max(worst, float(np.abs(x[:-1] - y[:-1]).max()))
+        stage_files = len(jobs)
+        print(json.dumps({
+            "task": {"patients": a.patients, "cases": ncases, "array": shape, "modalities": 1, "stage_files": stage_files},
+            "device_total_s": round(device_total, 3), "device_cases_per_s_whole_pipeline": round(ncases / device_total, 2),
+            "device_stage_s": round(device_stage_seconds, 3), "device_stage_files_per_s": round(stage_files / device_stage_seconds, 2),
+            "cpu16_stage_s": round(cpu_stage_seconds, 3), "cpu16_stage_files_per_s": round(stage_files / cpu_stage_seconds, 2),
+            "cpu_over_device_stage_time": round(cpu_stage_seconds / device_stage_seconds, 2),
+            "split_s": {k: {kk: round(vv, 3) for kk, vv in v.items()} for k, v in report.items()},
+            "label_channels_equal": "%d of %d" % (labels_equal, stage_files), "max_abs_image_difference": worst}), flush=True)
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
