@@ -127,6 +127,7 @@ SIGNATURES = {
     "cf_assign_where_ge": [P, P, L, F, F, P],
     "cf_seg_outside_mask": [P, P, I, L, F, P],
     "cf_prev_stage_onehot": [P, I, I, I, P, I, I, I, P, I, P],
+    "cf_resize_labels": [P, P, I, I, I, I, I, I, I, I, I, I, P],
     "cf_ensemble_merge": [P, I, I, I, I, I, I, P, I, I, I, I, I, I, P, P, P],
     "cf_ensemble_pairs": [P, I, I, I, I, I, I, P, I, P, P, I, I, I, I, I, I, P, P, P],
     "cf_confusion_counts": [P, P, L, P, P],

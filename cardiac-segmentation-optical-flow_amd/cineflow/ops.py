@@ -1124,6 +1124,18 @@ def resize3d(src, new_shape, linear=(1, 1, 1)):
     return dst
 
 
+def resize_labels(src, new_shape, linear=(1, 1, 1)):
+    """batchgenerators' resize_segmentation(order=1) of the label maps src [N,X,Y,Z] float32 -> [N,*new_shape]: the largest label whose
+    resized fp64 indicator reaches 0.5, else 0; per axis linear or nearest, as resize3d."""
+    N, X, Y, Z = src.shape
+    X2, Y2, Z2 = (int(v) for v in new_shape)
+    src = src.contiguous()
+    dst = torch.empty((N, X2, Y2, Z2), dtype=torch.float32, device=src.device)
+    check(lib().cf_resize_labels(_f32(src), _f32(dst), N, X, Y, Z, X2, Y2, Z2, int(linear[0]), int(linear[1]), int(linear[2]), _stream()),
+          "cf_resize_labels")
+    return dst
+
+
 def prev_stage_onehot(seg, classes, out):
     """Previous-stage labels -> one-hot network-input planes (nnunet/inference/predict.py:82-85) in one kernel: batchgenerators'
     resize_segmentation(seg, out.shape[1:], order=1) then to_one_hot(., classes).  seg: uint8 [X,Y,Z]; out: float32

@@ -296,12 +296,9 @@ def _resize_cubic(t, new_shape, slab_axis):
 
 def _resize_labels(t, new_shape, lin):
     """batchgenerators' resize_segmentation for order 1: every label's indicator is resized (linear on the axes flagged in `lin`,
-    nearest on the others) and the label assigned where it reaches 0.5, labels ascending."""
-    out = torch.zeros((t.shape[0],) + tuple(int(v) for v in new_shape), dtype=torch.float32, device=t.device)
-    for c in torch.unique(t).tolist():
-        ind = ops.resize3d((t == c).float().contiguous(), new_shape, lin)
-        check(lib().cf_assign_where_ge(_f32(out), _f32(ind), out.numel(), 0.5, float(c), _stream()), "cf_assign_where_ge")
-    return out
+    nearest on the others) and the label assigned where it reaches 0.5, labels ascending.  t [C, x, y, z] fp32 on the device.
+    One kernel (ops.resize_labels): the reference's fp64 indicator chain, so indicators of exactly 0.5 fall on its side."""
+    return ops.resize_labels(t, new_shape, lin)
 
 
 def resize_segmentation(segmentation, new_shape, order=1):

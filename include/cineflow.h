@@ -541,7 +541,8 @@ int cf_masked_moments(const float* x, const float* seg, long n, int use_range, f
 int cf_normalize(float* x, const float* seg, long n, int clip, float lo, float hi, float sub, float div, int zero_outside, void* stream);
 /* preprocessing.py:251 `data[np.isnan(data)] = 0`, in place */
 int cf_nan_to_zero(float* x, long n, void* stream);
-/* batchgenerators resize_segmentation (orders > 0): dst[i] = value where the resized indicator src[i] >= thr */
+/* dst[i] = value where src[i] >= thr (the per-label step of batchgenerators' resize_segmentation; the package's own label route is
+ * cf_resize_labels, which decides on the reference's fp64 indicator instead of a resized fp32 one) */
 int cf_assign_where_ge(float* dst, const float* src, long n, float thr, float value, void* stream);
 /* cropping.py:128-135: seg [C][V] gets `label` where seg == 0 and mask [V] == 0 (a zero-filled seg yields the created one) */
 int cf_seg_outside_mask(float* seg, const uint8_t* mask, int C, long V, float label, void* stream);
@@ -551,9 +552,15 @@ int cf_seg_outside_mask(float* seg, const uint8_t* mask, int C, long V, float la
  * [num_modalities + n_classes][X2][Y2][Z2] at channel num_modalities.  classes: HOST array, the label value of plane j
  * (n_classes <= 255).  Sampling as cf_resize3d (linear on every axis); a voxel gets the largest label whose resized indicator is
  * >= 0.5, else 0; plane j is 1.0f where that label is classes[j], else 0.0f.  Labels outside `classes` compete and get no plane.
- * Indicators that are exactly 0.5 with weights that are not exact in fp32 are implementation-defined ties (csrc/prev_stage.hip). */
+ * The indicator is the reference's fp64 chain (scipy.ndimage.zoom, order 1), product by product and sum by sum, so an indicator
+ * of exactly 0.5 falls on the reference's side (csrc/prev_stage.hip). */
 int cf_prev_stage_onehot(const uint8_t* seg, int X, int Y, int Z, float* dst, int X2, int Y2, int Z2, const uint8_t* classes,
                          int n_classes, void* stream);
+/* batchgenerators resize_segmentation(order=1) of N label maps, src [N][X][Y][Z] -> dst [N][X2][Y2][Z2] (device fp32, label values
+ * of either sign): a voxel gets the largest label whose resized indicator is >= 0.5, else 0.  Per axis linear, or nearest
+ * (linear_* = 0: the separate axis of resample_data_or_seg, order_z 0) as cf_resize3d; the same fp64 chain as cf_prev_stage_onehot. */
+int cf_resize_labels(const float* src, float* dst, int N, int X, int Y, int Z, int X2, int Y2, int Z2, int linear_x, int linear_y,
+                     int linear_z, void* stream);
 /* Ensemble of saved softmax volumes (nnunet/inference/ensemble_predictions.py merge_files + the label step and bounding-box placement of
  * segmentation_export.py) in one launch.  members: HOST array of n_members (1..16) device pointers, each [K][Z][Y][X] of __half (dtype 0)
  * or float (dtype 1).  seg: device uint8 [Zf][Yf][Xf], written everywhere: the labels of the crop at (z0, y0, x0), 0 outside (a crop that

@@ -2,7 +2,9 @@
 window, the Swin window attention, the RAFT all-pairs pyramid and CorrVolume), each a few lines.  The GPU tables test_gpu_preprocess_kernels.py,
 test_gpu_metrics_kernels.py, test_gpu_volume_ops.py, test_gpu_window_attention.py, test_gpu_flow_op_shapes.py and
 test_gpu_corr_volume_routes.py hold the HIP kernels to these; test_kernel_refs_cpu.py pins every restatement
-to the oracle (and through it to the reference's golden vectors) so that helper and kernel cannot be wrong together."""
+to the oracle (and through it to the reference's golden vectors) so that helper and kernel cannot be wrong together.
+The label-resize references (linear_chain_f64, label_resize_exact) are pinned by test_label_resize_refs_cpu.py and describe the
+decision that test_gpu_label_resize.py holds the device to through the oracle."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -123,6 +125,112 @@ def resize_edge(x, new_shape, linear):
             x = np.take(x, i0, ax) * (1.0 - w) + np.take(x, i1, ax) * w
         else:
             x = np.take(x, np.clip(np.floor(s + 0.5).astype(int), 0, n - 1), ax)
+    return x
+
+
+def _chain_axes(shape, new_shape, linear):
+    """per axis the support of one output sample: (indices [taps, n2], fp64 weights [taps, n2]); a linear axis has the two edge-clamped
+    neighbours of s = (n / n2) (o + 0.5) - 0.5 with weights (1 - y, y), y = s - floor(s); a nearest axis has one tap of weight 1"""
+    axes = []
+    for n, n2, lin in zip(shape, new_shape, linear):
+        s = (float(n) / n2) * (np.arange(n2) + 0.5) - 0.5              # numpy rounds every product and sum on its own
+        if lin:
+            f = np.floor(s)
+            y = s - f
+            i = f.astype(np.int64)
+            axes.append((np.stack([np.clip(i, 0, n - 1), np.clip(i + 1, 0, n - 1)]), np.stack([1.0 - y, y])))
+        else:
+            axes.append((np.clip(np.floor(s + 0.5).astype(np.int64), 0, n - 1)[None], np.ones((1, n2))))
+    return axes
+
+
+def linear_chain_f64(x, new_shape, linear):
+    """scipy.ndimage.zoom(order=1, mode='nearest', grid_mode=True) of a 2-D or 3-D array restated as one fp64 chain, bit for bit
+    (test_label_resize_refs_cpu.py): t += ((v * w_a) * w_b) * w_c over the 2^d support points, last axis fastest, every product and
+    sum rounded on its own.  An axis with linear = 0 is nearest (floor(s + 0.5), edge-clamped) as in resize_edge."""
+    import itertools
+    x = np.asarray(x, np.float64)
+    assert x.ndim == len(new_shape) == len(linear) and x.ndim in (2, 3)
+    axes = _chain_axes(x.shape, new_shape, linear)
+    t = np.zeros(tuple(int(v) for v in new_shape))
+    for taps in itertools.product(*[range(len(a[0])) for a in axes]):
+        c = x[np.ix_(*[a[0][k] for a, k in zip(axes, taps)])]
+        for d, (a, k) in enumerate(zip(axes, taps)):
+            c = c * a[1][k].reshape([-1 if e == d else 1 for e in range(x.ndim)])
+        t = t + c
+    return t
+
+
+def labels_from_chain(seg, new_shape, linear):
+    """batchgenerators' resize_segmentation(order=1) on linear_chain_f64: labels ascending, each assigned where its indicator >= 0.5"""
+    seg = np.asarray(seg)
+    out = np.zeros(tuple(int(v) for v in new_shape), seg.dtype)
+    for c in np.unique(seg):
+        out[linear_chain_f64(seg == c, new_shape, linear) >= 0.5] = c
+    return out
+
+
+def label_resize_exact(seg, new_shape, linear):
+    """The same decision in exact integer arithmetic.  s = (n (2o + 1) - n2) / (2 n2), so a linear axis' weights are (2 n2 - r, r) / (2 n2)
+    with r = (n (2o + 1) - n2) mod 2 n2, and indicator * D is an integer for D = prod 2 n2.
+    -> (labels present, sign of indicator - 1/2 per label [L, *new_shape] int8, tie mask (some label's indicator is exactly 1/2),
+    smallest non-zero |indicator - 1/2|).  A nearest axis must not sit on a rounding boundary (asserted)."""
+    import itertools
+    seg = np.asarray(seg)
+    assert seg.ndim == len(new_shape) == len(linear)
+    D, axes = 1, []
+    for n, n2, lin in zip(seg.shape, new_shape, linear):
+        n, n2 = int(n), int(n2)
+        num = n * (2 * np.arange(n2, dtype=np.int64) + 1) - n2           # s = num / (2 n2)
+        if lin:
+            f, r = num // (2 * n2), num % (2 * n2)
+            axes.append((np.stack([np.clip(f, 0, n - 1), np.clip(f + 1, 0, n - 1)]), np.stack([2 * n2 - r, r])))
+            D *= 2 * n2
+        else:
+            i = np.clip((num + n2) // (2 * n2), 0, n - 1)
+            s = (float(n) / n2) * (np.arange(n2) + 0.5) - 0.5
+            assert np.array_equal(i, np.clip(np.floor(s + 0.5).astype(np.int64), 0, n - 1)), "a nearest axis rounds differently in fp64"
+            axes.append((i[None], np.ones((1, n2), np.int64)))
+    assert 2 * D < 2 ** 62, "indicator * D does not fit int64"
+    labels = np.unique(seg)
+    sign = np.zeros((len(labels),) + tuple(int(v) for v in new_shape), np.int8)
+    gap = None
+    for j, c in enumerate(labels):
+        t = np.zeros(sign.shape[1:], np.int64)
+        ind = (seg == c).astype(np.int64)
+        for taps in itertools.product(*[range(len(a[0])) for a in axes]):
+            v = ind[np.ix_(*[a[0][k] for a, k in zip(axes, taps)])]
+            for d, (a, k) in enumerate(zip(axes, taps)):
+                v = v * a[1][k].reshape([-1 if e == d else 1 for e in range(seg.ndim)])
+            t += v
+        diff = 2 * t - D                                                 # (indicator - 1/2) * 2 D
+        sign[j] = np.sign(diff)
+        nz = np.abs(diff[diff != 0])
+        if nz.size:
+            gap = int(nz.min()) if gap is None else min(gap, int(nz.min()))
+    return labels, sign, (sign == 0).any(0), (gap / (2.0 * D) if gap is not None else float("inf"))
+
+
+def resize3d_f32_chain(x, new_shape, linear):
+    """cf_resize3d's arithmetic (postprocess.hip resize3d_kernel) in numpy fp32, without FMA contraction: coordinates in double,
+    weight rounded to fp32, nested lerp u + (v - u) * w along z, then y, then x.  x [X, Y, Z] -> fp32 [*new_shape]."""
+    x = np.asarray(x, np.float32)
+    idx, w = [], []
+    for n, n2, lin in zip(x.shape, new_shape, linear):
+        s = (float(n) / n2) * (np.arange(n2) + 0.5) - 0.5
+        if lin:
+            f = np.floor(s)
+            i = f.astype(np.int64)
+            idx.append((np.clip(i, 0, n - 1), np.clip(i + 1, 0, n - 1)))
+            w.append((s - f).astype(np.float32))
+        else:
+            i = np.clip(np.floor(s + 0.5).astype(np.int64), 0, n - 1)
+            idx.append((i, i))
+            w.append(np.zeros(n2, np.float32))
+    for ax in (2, 1, 0):
+        wa = w[ax].reshape([-1 if e == ax else 1 for e in range(3)])
+        u, v = np.take(x, idx[ax][0], ax), np.take(x, idx[ax][1], ax)
+        x = (u + ((v - u) * wa).astype(np.float32)).astype(np.float32)
     return x
 
 

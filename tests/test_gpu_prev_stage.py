@@ -2,13 +2,13 @@
 straight into the network-input tensor.  Expected planes: oracle.preprocess.resize_segmentation (float64, scipy) plus a three-line
 one-hot, computed once per case on the CPU and shared by the tests.  Every comparison is bit-exact equality of all planes.
 
-Condition on the inputs (asserted below with the oracle alone, before the GPU is touched): over every label present, the resized
-float64 indicator stays at least TIE_MARGIN = 1e-4 away from 0.5.  The kernel's fp32 weights and sums are within a few 1e-7 of the
-float64 ones (at most 8 terms, each a product of three weights in [0, 1]), so under that condition no voxel's label depends on
-rounding.  Maps whose indicators hit 0.5 with weights that are not exact in fp32 (e.g. (6,16,16) -> (8,32,32)) are implementation-
-defined ties and not used.  The cases marked `exact` need no margin: every per-axis weight is a dyadic fraction with at most 3
-fractional bits (shape ratios 2, 1/2), so all products and sums are exact in fp32 and in float64, in any order -- there the `>=`
-itself, indicators of exactly 0.5 included, must agree with the oracle.
+Condition on the inputs of THIS file (asserted below with the oracle alone, before the GPU is touched): over every label present, the
+resized float64 indicator stays at least TIE_MARGIN = 1e-4 away from 0.5, so no voxel's label depends on rounding and the rows test
+the kernel's shape handling (tails, alignment, classes, offsets) whatever its arithmetic.  The cases marked `exact` need no margin:
+every per-axis weight is a dyadic fraction with at most 3 fractional bits (shape ratios 2, 1/2), so all products and sums are exact
+in any precision and order -- there the `>=` itself, indicators of exactly 0.5 included, must agree with the oracle.
+Indicators of exactly 0.5 with weights that round are NOT implementation-defined: the reference's side is that of one fixed float64
+chain, the kernel runs that chain, and tests/test_gpu_label_resize.py holds it to the oracle on maps chosen for such ties.
 
 Label maps: seeded Gaussian-smoothed noise quantised to equal-volume labels; the seeds were picked on the CPU for the margin."""
 import functools
@@ -93,7 +93,7 @@ def test_voxels_without_a_label_at_one_half_are_background():
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_fused_equals_the_unfused_route(dev, name):
-    """to_one_hot(_resize_labels(...)): one cf_resize3d + one cf_assign_where_ge per label, then a compare per class"""
+    """to_one_hot(_resize_labels(...)): one cf_resize_labels launch, then a compare per class"""
     from cineflow import preprocessing as P
     _src, dst, _seed, _n, classes, _exact = CASES[name]
     seg, expected, _m, _t = case(name)

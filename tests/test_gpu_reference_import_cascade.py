@@ -7,8 +7,8 @@ Input: 2 patients x 2 frames of (10, 40, 36) volumes at the full-resolution stag
 non-zero leaves a (10, 32, 32) grid.  The previous stage's label file is UNCROPPED (10, 40, 36) and is resized onto that grid as the
 reference does it: ratios 1, 40/32 = 1.25 and 36/32 = 1.125, so every per-axis weight is a multiple of 1/8 or 1/16 and every product and
 sum is exact in fp32 and in float64, in any order.  That is why the network input can be held to the oracle bit for bit whatever
-labels the lowres network happens to predict (indicators of exactly 0.5 included) -- with inexact weights a tie's side would be
-implementation-defined (tests/test_gpu_prev_stage.py).
+labels the lowres network happens to predict (indicators of exactly 0.5 included) by any arithmetic; ties whose weights round are
+held to the oracle by tests/test_gpu_label_resize.py.
 
 Bars: the generic_unet_3d.npz logits bar (1e-4, as test_gpu_reference_import_3d.py); the exported fp16 softmax against the direct route
 at 2^-10 (one fp16 ulp below 1.0 is 2^-11, doubled for values that straddle a rounding boundary); label files equal wherever the

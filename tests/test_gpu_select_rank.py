@@ -2,7 +2,11 @@
 
 The scan block is 256 voxels.  The volumes (3, 5, 67) = 1005, (9, 70, 66) = 41580 and (2, 1, 4099) = 8198 voxels cross 3, 162 and 32 full
 blocks and end in a partial block of 237, 108 and 6 voxels: the issue's sizes, unchanged.  Ranks: first, last, the last match of every block
-and the first of the next one, duplicates, unsorted."""
+and the first of the next one, duplicates, unsorted.
+
+(3, 151, 149) = 67497 voxels are 264 scan blocks: select_scan_kernel takes a second trip of 256 blocks and carries the first trip's sum
+into it, from flat index 65536 on.  (9, 251, 247) = 557973 voxels are 2180 blocks: select_count_kernel's 2048 workgroups take a second
+grid-stride trip from flat index 524288 on.  The ranks on both sides of each of those two indices are asserted to be among those tested."""
 import numpy as np
 import pytest
 import torch
@@ -10,7 +14,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 SCAN = 256
-SHAPES = [(3, 5, 67), (9, 70, 66), (2, 1, 4099)]
+SHAPES = [(3, 5, 67), (9, 70, 66), (2, 1, 4099), (3, 151, 149), (9, 251, 247)]
+TRIP_EDGES = [SCAN * 256, SCAN * 2048]                          # the scan's second 256-block trip, the count's second grid-stride trip
 
 
 def _labels(shape, seed, nvalues=4):
@@ -28,6 +33,9 @@ def _edge_ranks(match_flat, rng):
     for b in before.tolist():
         ranks += [b - 1, b]
     ranks = np.array([r for r in ranks if 0 <= r < total], dtype=np.int64)
+    for edge in TRIP_EDGES:                                     # the last match before a trip edge and the first at or after it
+        b = int(match_flat[:edge].sum())
+        assert edge >= match_flat.size or not 0 < b < total or {b - 1, b} <= set(ranks.tolist())
     ranks = np.concatenate([ranks, ranks[:3], rng.integers(0, total, size=17)])
     rng.shuffle(ranks)
     return ranks

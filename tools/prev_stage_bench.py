@@ -1,14 +1,14 @@
 """Building the network input of a cascade's full-resolution stage from device-resident data and previous-stage labels, two routes:
 
-    unfused   preprocessing._resize_labels (per label: a compare, one cf_resize3d, one cf_assign_where_ge; a torch.unique().tolist()
-              host round trip first), then a compare per class and torch.cat with the data
+    unfused   preprocessing._resize_labels (one cf_resize_labels launch writing the label volume), then a compare per class and torch.cat
+              with the data
     fused     preprocessing.prev_stage_to_input: the data copied into the result and ONE cf_prev_stage_onehot writing the planes in place
 
 Workloads: a cine-sized volume (10, 256, 216) -> (13, 320, 270) and an isotropic one (80, 160, 160) -> (128, 256, 256), one modality,
 4 labels (smoothed seeded noise), classes [1, 2, 3].  Both routes run in one process, alternating, after warm-up; each sample is a host
 clock around `--calls` back-to-back calls that end in a device synchronise; the fused kernel alone is also timed by device events.  Per route: the median time per call and the bytes of the
 label planes written (3 x voxels x 4 B, the least any route must store) per second against the measured HBM copy rate of the chip.
-The planes of both routes are compared once (indicators of exactly 0.5 whose weights round in fp32 may fall on either side).
+The planes of both routes are compared once (both kernels decide on the reference's fp64 chain: no value may differ).
 
     python tools/prev_stage_bench.py [--calls 20] [--runs 7]        one JSON line per workload, then the clocks rocm-smi reports"""
 import argparse
