@@ -97,6 +97,7 @@ SIGNATURES = {
     "cf_tta_accumulate_3d_nonlin": [P, P, I, I, I, I, I, I, I, I, F, I, P],
     "cf_region_labels": [P, P, I, I, L, P, P],
     "cf_resize3d": [P, P, I, I, I, I, I, I, I, I, I, I, P],
+    "cf_resample_argmax": [P] + [I] * 10 + [P] + [I] * 6 + [P, P, P, P, P],
     "cf_cc_init": [P, P, L, P, I, P],
     "cf_cc_sweep": [P, I, I, I, P, P],
     "cf_cc_count": [P, P, L, P],

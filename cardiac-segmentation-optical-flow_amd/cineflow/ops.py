@@ -1269,6 +1269,52 @@ def ensemble_pairs(members, pairs, gt, bbox_lo=(0, 0, 0), regions_class_order=No
     return seg, hist
 
 
+RESAMPLE_HIST_K = 16
+
+
+def resample_argmax(src, new_shape, linear, full_shape=None, bbox_lo=(0, 0, 0), regions_class_order=None, want_probs=False, gt=None):
+    """The export of one validated case in one kernel (cf_resample_argmax): src, a contiguous float32 CUDA tensor [K,X,Y,Z] (K in 1..255),
+    resampled to new_shape as resize3d(src, new_shape, linear) resamples it, bit for bit (equal sizes copy) -> (seg, probs, hist).
+    seg: uint8 [*full_shape] (default: new_shape), the arg-max over the channels (first maximum) -- or, with a regions_class_order, 0
+    overwritten by regions_class_order[i] where channel i > 0.5, in that order -- placed at bbox_lo inside zeros.  probs (want_probs, else
+    None): float16 [K,*new_shape], export.probabilities_as_stored of the resampled channels.  hist (gt given, else None): int64
+    [16 * 16 + 1], cf_label_confusion(seg, gt) at K = 16 (hist[t * 16 + r]; the last bin counts the voxels with a label >= 16 in either
+    volume); gt: contiguous uint8 [*full_shape] on src's device."""
+    who = "resample_argmax"
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise TypeError("%s: src must be a CUDA/HIP tensor (cineflow has no CPU path)" % who)
+    if src.dtype != torch.float32 or src.dim() != 4:
+        raise ValueError("%s: src must be [K,X,Y,Z] float32, got %s %s" % (who, tuple(src.shape), src.dtype))
+    if not src.is_contiguous():
+        raise ValueError("%s: src must be contiguous" % who)
+    K, X, Y, Z = src.shape
+    if not 1 <= K <= 255:
+        raise ValueError("%s: %d classes (1..255 are supported)" % (who, K))
+    new_shape = tuple(int(v) for v in new_shape)
+    if len(new_shape) != 3 or len(linear) != 3 or min(new_shape) < 1 or min(X, Y, Z) < 1:
+        raise ValueError("%s: cannot resample %s to %s with linear = %r" % (who, (X, Y, Z), new_shape, tuple(linear)))
+    full_shape = tuple(int(v) for v in (new_shape if full_shape is None else full_shape))
+    bbox_lo = _check_placement(who, new_shape, bbox_lo, full_shape)
+    order = None
+    if regions_class_order is not None:
+        regions_class_order = check_regions_class_order(regions_class_order, K, who + ": regions_class_order")
+        order = ctypes.cast((ctypes.c_uint8 * K)(*regions_class_order), ctypes.c_void_p)
+    hist = None
+    if gt is not None:
+        if not isinstance(gt, torch.Tensor) or gt.dtype != torch.uint8 or tuple(gt.shape) != full_shape or gt.device != src.device \
+                or not gt.is_contiguous():
+            raise ValueError("%s: gt must be a contiguous uint8 %s tensor on src's device" % (who, full_shape))
+        hist = torch.empty(RESAMPLE_HIST_K * RESAMPLE_HIST_K + 1, dtype=torch.int64, device=src.device)
+    seg = torch.empty(full_shape, dtype=torch.uint8, device=src.device)
+    probs = torch.empty((K,) + new_shape, dtype=torch.float16, device=src.device) if want_probs else None
+    check(lib().cf_resample_argmax(src.data_ptr(), K, X, Y, Z, new_shape[0], new_shape[1], new_shape[2], int(bool(linear[0])),
+                                   int(bool(linear[1])), int(bool(linear[2])), seg.data_ptr(), full_shape[0], full_shape[1], full_shape[2],
+                                   bbox_lo[0], bbox_lo[1], bbox_lo[2], order, None if probs is None else probs.data_ptr(),
+                                   None if gt is None else gt.data_ptr(), None if hist is None else hist.data_ptr(), _stream()),
+          "cf_resample_argmax")
+    return seg, probs, hist
+
+
 def resample_data_or_seg(data, new_shape, is_seg, axis=None, order=3, do_separate_z=False, order_z=0):
     """nnunet/preprocessing/preprocessing.py:111-200 on the device for the orders the export uses (0 and 1).  data: numpy or
     device tensor (c, x, y, z); returns the same kind.  Segmentations of order 0 are nearest-neighbour in every axis; data is

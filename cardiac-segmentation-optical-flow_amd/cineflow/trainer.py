@@ -288,18 +288,22 @@ class CineTrainer:
     # -- nnUNetTrainer.py:637-679
     def predict_preprocessed_data_return_seg_and_softmax(self, data, do_mirroring=True, mirror_axes=None, use_sliding_window=True,
                                                          step_size=0.5, use_gaussian=True, pad_border_mode="constant", pad_kwargs=None,
-                                                         all_in_gpu=False, verbose=True, mixed_precision=True):
+                                                         all_in_gpu=False, verbose=True, mixed_precision=True, return_device=False):
         """(seg [Z,X,Y], softmax [K,Z,X,Y]) of one preprocessed volume; with several folds resident (load_ensemble) the softmax is the
-        mean over the folds of each fold's flip-TTA sliding-window softmax."""
+        mean over the folds of each fold's flip-TTA sliding-window softmax.  return_device: the same two as device tensors (views of the
+        padded buffers, not necessarily contiguous), nothing copied to the host (cineflow.validate resamples and scores them there)."""
         mirror_axes = self.data_aug_params["mirror_axes"] if mirror_axes is None else mirror_axes
         with ops.conv_terms(1 if (mixed_precision and SEG_MIXED_PRECISION) else 3):
             if self.seg_dim == 3:
                 seg, prob = self._predict_volume_3d(data, step_size, do_mirroring, mirror_axes, use_gaussian, pad_border_mode, pad_kwargs)
-                return seg.cpu().numpy(), prob.cpu().numpy()
+                return (seg, prob) if return_device else (seg.cpu().numpy(), prob.cpu().numpy())
             if len(self.seg_nets) == 1 and self.seg_arch != "mtl":
                 return predict_3D_2Dconv_tiled(self.seg_net, data, self.patch_size, step_size=step_size, do_mirroring=do_mirroring,
                                                mirror_axes=mirror_axes, use_gaussian=use_gaussian, pad_border_mode=pad_border_mode,
-                                               pad_kwargs=pad_kwargs, regions_class_order=self.regions_class_order)
+                                               pad_kwargs=pad_kwargs, return_device=return_device, regions_class_order=self.regions_class_order)
+            if return_device:
+                return _predict_cine_tiled_device(self.seg_nets, [data], self.patch_size, step_size, do_mirroring, mirror_axes, use_gaussian,
+                                                  pad_border_mode, pad_kwargs, None, self.regions_class_order)[0]
             return predict_cine_2Dconv_tiled(self.seg_nets, [data], self.patch_size, step_size=step_size, do_mirroring=do_mirroring,
                                              mirror_axes=mirror_axes, use_gaussian=use_gaussian, pad_border_mode=pad_border_mode,
                                              pad_kwargs=pad_kwargs, regions_class_order=self.regions_class_order)[0]

@@ -469,6 +469,19 @@ int cf_cc_apply(const uint8_t* src, uint8_t* dst, long n, int K, int do_fg, int 
  * map_coordinates mode='nearest'); per axis linear (1) or nearest (0). */
 int cf_resize3d(const float* src, float* dst, int N, int X, int Y, int Z, int X2, int Y2, int Z2, int linear_x, int linear_y,
                 int linear_z, void* stream);
+/* The export of one validated case in one launch (nnUNetTrainer.validate, nnunet/training/network_training/nnUNetTrainer.py:801-868, and
+ * predict_next_stage, nnunet/training/cascade_stuff/predict_next_stage.py:31-87): src, device fp32 [K][X][Y][Z] (K in 1..255), is resampled
+ * to (X2, Y2, Z2) exactly as cf_resize3d resamples each channel (the two kernels share the sampling function; equal sizes copy), and
+ * seg, device uint8 [Xf][Yf][Zf], is written everywhere: the label of the crop at (x0, y0, z0), 0 outside (a crop that overhangs is
+ * refused).  Label: the first maximum over the K resampled channels (numpy's argmax, NaN rule included), or with `order` (HOST array of K
+ * label values, regions_class_order; may be NULL) 0 overwritten by order[k] where channel k > 0.5, in channel order.  probs_out (may be
+ * NULL): device __half [K][X2][Y2][Z2], the resampled values rounded to nearest even; with `order`, a value > 0.5 that rounds to <= 0.5
+ * is stored as the next fp16 above 0.5, so that stored > 0.5 exactly where the value is.  gt with hist (both or neither): gt device uint8
+ * [Xf][Yf][Zf], hist device u64 [16 * 16 + 1] = what cf_label_confusion(seg, gt, ., 16, .) gives, overflow bin included; this call zeroes
+ * hist on `stream` before the launch. */
+int cf_resample_argmax(const float* src, int K, int X, int Y, int Z, int X2, int Y2, int Z2, int linear_x, int linear_y, int linear_z,
+                       uint8_t* seg, int Xf, int Yf, int Zf, int x0, int y0, int z0, const uint8_t* order, void* probs_out, const uint8_t* gt,
+                       unsigned long long* hist, void* stream);
 
 /* Stem convolutions (nn.Conv2d with 1, 2 or 6 input channels, 3x3 pad 1 or 1x1, stride 1, e.g. Generic_UNet's first conv,
  * nnunet/network_architecture/generic_UNet.py:70-86, and the encoders' first DoubleConv, nnunet/lib/utils.py:1175-1210) as a direct
