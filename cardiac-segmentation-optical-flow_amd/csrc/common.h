@@ -78,6 +78,7 @@ __device__ __forceinline__ float act_apply(float v, int act) {
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));      // the accumulator of a 32x32 MFMA
 __device__ __forceinline__ void split2_f16(float x0, float x1, f16x2& hi, f16x2& lo) {
     typedef float f32x2s __attribute__((ext_vector_type(2)));
     hi = __builtin_convertvector((f32x2s){x0, x1}, f16x2);
@@ -157,6 +158,11 @@ __device__ __forceinline__ float sample_taps(const float* __restrict__ plane, co
     return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(a, t.w00), __fmul_rn(b, t.w01)), __fmul_rn(c, t.w10)),
                      __fmul_rn(d, t.w11));
 }
+
+// Division by a launch-constant divisor in the index decodes of the convolution kernels: the host passes m = magic(d) = floor(2^32 / d) + 1
+// beside d, and fdiv(n, d, m) = n / d for every 0 <= n < 2^31 / d (the launch plans check the range).
+__host__ __device__ inline unsigned magic(int d) { return d <= 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)d + 1ull); }
+__device__ __forceinline__ int fdiv(int n, int d, unsigned m) { return d <= 1 ? n : (int)__umulhi((unsigned)n, m); }
 
 // Per-device bookkeeping for the launchers (a process may drive several GPUs): the current device's index (0 when out of the table's range)
 // and its compute-unit count rounded down to whole groups of 8 XCDs (256 on an MI355X in SPX mode; 256 when the query fails).

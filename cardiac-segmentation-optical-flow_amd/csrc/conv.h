@@ -58,4 +58,53 @@ int allpairs_pyramid_fused(const float* f1, const float* f2, float* pyr, int B, 
 // GroupNorm statistics pass (norm.hip): ws[2*(b*groups+g)] = sum, +1 = sum of squares, fp64
 int launch_gn_stats(const float* x, double* ws, int B, int C, int HW, int groups, hipStream_t s);
 
+// ---- host parts that the f16-split launchers share (conv_f16s.hip, conv_wino.hip, conv3d_f16s.hip, conv3d_pw_f16s.hip)
+
+// The statistics request of an exported call: gn_groups < 0 declares gn_ws already zeroed.  P: any of the kernels' parameter structs.
+template <class P>
+inline void set_stats_request(P& p, double* gn_ws, int gn_groups) {
+    p.gn_ws = gn_ws; p.gn_groups = gn_groups < 0 ? -gn_groups : gn_groups; p.gn_prezeroed = gn_groups < 0;
+}
+
+// A batch of which at most `max_per_launch` samples fit one launch (32-bit buffer offsets) is cut into the FEWEST parts that fit and the
+// parts are made equal: n samples each, `last` (at most parts - 1 fewer) in the final one -- a greedy cut could leave a remainder of one
+// sample, for which a plan picks another kernel shape than for the large parts.  n == 0: one sample is already too large.
+struct Parts { long n, last; };
+inline Parts equal_parts(long B, long max_per_launch) {
+    if (max_per_launch < 1) return {0, 0};
+    if (B <= max_per_launch) return {B, B};
+    const long parts = (B + max_per_launch - 1) / max_per_launch;
+    const long n = (B + parts - 1) / parts;
+    return {n, B - (B - 1) / n * n};
+}
+
+// The plan of a whole call (3-D files): the cut and the plans of its two part sizes, or why the call is declined.  for_each_part runs
+// part(first sample, samples, plan) on every part in turn.
+template <class Plan>
+struct CallPlan { Parts parts = {0, 0}; Plan first = {}, last = {}; const char* why = nullptr; };
+template <class Plan, class F>
+inline int for_each_part(long B, const CallPlan<Plan>& c, F part) {
+    for (long b0 = 0; b0 < B; b0 += c.parts.n) {
+        const bool tail = B - b0 < c.parts.n;
+        if (const int rc = part(b0, (int)(tail ? c.parts.last : c.parts.n), tail ? c.last : c.first)) return rc;
+    }
+    return CF_OK;
+}
+
+// The statistics half of a launch.  `launch(ws)` runs the kernel with ws as the workspace of its epilogue: gn_ws when the plan can fuse the
+// statistics -- they accumulate with atomics, so the workspace is zeroed first unless the caller handed out a slice of a pool it zeroed
+// itself -- else null, and norm.hip's pass over the dense output [B, C, HW] follows the kernel.
+template <class Launch>
+inline int launch_with_stats(const char* family, double* gn_ws, int gn_groups, bool prezeroed, bool fusable, const float* out, int B, int C,
+                             int HW, hipStream_t s, Launch launch) {
+    const bool fused = gn_ws && fusable;
+    if (fused && !prezeroed && hipMemsetAsync(gn_ws, 0, sizeof(double) * 2 * (size_t)B * gn_groups, s) != hipSuccess) {
+        set_error(std::string(family) + ": memset failed");
+        return CF_ERR_LAUNCH;
+    }
+    const int rc = launch(fused ? gn_ws : nullptr);
+    if (rc != CF_OK || !gn_ws || fused) return rc;
+    return launch_gn_stats(out, gn_ws, B, C, HW, gn_groups, s);
+}
+
 }  // namespace cf

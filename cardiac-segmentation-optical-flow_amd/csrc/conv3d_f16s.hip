@@ -20,16 +20,16 @@
 //   * Weights: host-packed fragment order [m-tile][chunk][dz][ky*3+kx][hi/lo][lane][8], 1 KiB per fragment, one coalesced dwordx4 per lane
 //     from L1/L2 through a 3-slot register ring prefetched two taps ahead (conv_f16s.hip's register-fragment path).
 // Only the 3-term product is built: under cf_conv_terms(1) cf_conv3d_f16s_ok answers 0 and the caller keeps its 2-D composition.
+// Host half (below the kernel): one plan per launch and one per call, read by the probe and the launcher alike; the epilogue's statistics
+// combine is conv3d.h's, shared with conv3d_pw_f16s.hip.
 #include <hip/hip_fp16.h>
+#include <algorithm>
 
-#include "conv.h"
+#include "conv3d.h"
 #include "profile.h"
 
 namespace cf {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct C3Params {
     const float* x1;      // [B,C1,D,H,W]
@@ -48,9 +48,6 @@ struct C3Geom {
     int tiles_x, tiles_y, bgroups, nchunk, c1_pad;
     unsigned m_tx, m_ty, m_nrec, m_phpw, m_pw, m_thtw, m_tw, m_do;      // floor(2^32 / d) + 1 multipliers of the index decodes
 };
-
-inline unsigned magic(int d) { return d <= 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)d + 1ull); }
-__device__ __forceinline__ int fdiv(int n, int d, unsigned m) { return d <= 1 ? n : (int)__umulhi((unsigned)n, m); }
 
 template <int WM, int NTW, int MAXT, int NW>
 __global__ void __launch_bounds__(64 * NW, (NTW <= 2 && MAXT <= 3) ? 4 : 2)
@@ -261,96 +258,72 @@ conv3d_f16s_kernel(const C3Params p, const C3Geom g, const _Float16* __restrict_
             ssq[r] += m * m;
         }
     }
-    if (do_stats) {       // transpose-reduce as conv_f16s.hip, then a workgroup combine in LDS and one fp64 atomic pair per (group, workgroup)
-        xreduce16(ssum, lane);
-        xreduce16(ssq, lane);
-        // every wave owns a slot per channel and the slots are summed in a fixed order: the fp32 part of the sum does not depend on which
-        // wave arrives first (LDS atomics would make a repeated run differ in the last bit of a mean); the fp64 atomics that follow add
-        // fp32-valued terms, whose sum is exact in fp64 in any order while they span fewer than 29 binary orders of magnitude
-        constexpr int NGRP = NW / WM;
-        float* red = reinterpret_cast<float*>(lds);   // [NGRP][WM*32 channels][2]; the main loop ended on a barrier: the patch buffers are free
-        if ((lane & 1) == 0) {
-            const int r = ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
-            const int cl = (wave % WM) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            red[2 * (ngrp * WM * 32 + cl)] = ssum[0];
-            red[2 * (ngrp * WM * 32 + cl) + 1] = ssq[0];
-        }
-        __syncthreads();
-        if (tid < WM * 32) {
-            const int co = blockIdx.y * WM * 32 + tid;
-            const int cpg = p.Cout / p.gn_groups;
-            if (co < p.Cout && (tid == 0 || co % cpg == 0)) {
-                int n = cpg - co % cpg;
-                if (n > WM * 32 - tid) n = WM * 32 - tid;
-                if (n > p.Cout - co) n = p.Cout - co;
-                float s1 = 0.f, s2 = 0.f;
-                for (int j = 0; j < n; ++j)
-                    for (int q = 0; q < NGRP; ++q) { s1 += red[2 * (q * WM * 32 + tid + j)]; s2 += red[2 * (q * WM * 32 + tid + j) + 1]; }
-                double* w = p.gn_ws + 2L * ((long)fdiv(bz0, p.Do, g.m_do) * p.gn_groups + co / cpg);     // host: one sample per workgroup
-                atomicAdd(w, (double)s1);
-                atomicAdd(w + 1, (double)s2);
-            }
-        }
-    }
+    // the main loop ended on a barrier: the patch buffers are free for the combine; host: one sample per workgroup when gn_ws is set
+    if (do_stats)
+        conv3d_stats_combine<WM, NW>(ssum, ssq, reinterpret_cast<float*>(lds), tid, p.Cout, p.gn_groups,
+                                     p.gn_ws + 2L * (long)fdiv(bz0, p.Do, g.m_do) * p.gn_groups);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Kernel shapes (WM m-tiles x NTW pixel tiles per wave, staging tasks per thread): 64 channels x 128 pixels at in-plane stride 1, 64 x 64 at
-// stride 2 (its patch is four times the tile), 32-channel forms of both for Cout <= 32.
-enum { V_S1 = 0, V_S1_NARROW, V_S2, V_S2_NARROW };
+// Host half: the table of built instantiations (CF_C3_SHAPES), the plan of one launch (c3_plan: pure host arithmetic naming table row,
+// geometry, grid, LDS size and statistics route, or why the shape is declined) and the plan of a call (c3_call: the sub-batch cut and the
+// plans of its two part sizes).  cf_conv3d_f16s_ok and cf_conv3d_f16s both read c3_call; nothing else decides.
+// Every <WM, NTW, MAXT> that is built (WM m-tiles x NTW pixel tiles per wave, staging tasks per thread; four waves each), in the order
+// row = 2 * (in-plane stride 2) + (Cout <= 32): 64 channels x 128 pixels at in-plane stride 1, 64 x 64 at stride 2 (its patch is four times
+// the tile), 32-channel x 128-pixel forms of both for Cout <= 32.  The launch functions are instantiated from this table and from nothing else.
+#define CF_C3_SHAPES(X) X(2, 2, 2) X(1, 1, 2) X(2, 1, 3) X(1, 1, 5)
+constexpr int C3_NW = 4;
+struct C3Shape { int WM, NTW, MAXT; };
+#define CF_C3_ROW(...) {__VA_ARGS__},
+constexpr C3Shape k_c3_shapes[] = {CF_C3_SHAPES(CF_C3_ROW)};
+#undef CF_C3_ROW
+
+// What one launch on a (sub-)batch will be: a pure function of the C3Params (no pointer is read).
+struct C3Plan {
+    int shape = -1;              // row of k_c3_shapes
+    C3Geom g = {};               // the kernel's geometry argument, complete
+    unsigned grid_x = 0, grid_y = 0;
+    size_t lds_bytes = 0;        // dynamic LDS of the launch
+    bool fusable = false;        // the epilogue can accumulate the statistics: every workgroup stays inside one sample
+    const char* why = nullptr;   // declined: the reason
+};
+C3Plan c3_declined(const char* why) { C3Plan pl; pl.why = why; return pl; }
 
 bool shape_ok(const C3Params& p) {
     return (p.KD == 1 || p.KD == 3) && (p.sd == 1 || p.sd == 2) && (p.stride == 1 || p.stride == 2) && p.B > 0 && p.C1 > 0 && p.C2 >= 0 &&
            p.D > 0 && p.H > 0 && p.W > 0 && p.Cout > 0;
 }
 
-// samples per launch: x1, x2 and the output of a launch each stay below 2 GiB (32-bit buffer offsets); 0: one sample is already too large
-long sub_batch(const C3Params& p) {
-    const double dhw = (double)p.D * p.H * p.W, dhwo = (double)p.Do * p.Ho * p.Wo;
-    double per = (double)p.C1 * dhw;
-    if ((double)p.C2 * dhw > per) per = (double)p.C2 * dhw;
-    if ((double)p.Cout * dhwo > per) per = (double)p.Cout * dhwo;
-    per *= 4.0;
-    if (per >= 2147483648.0) return 0;
-    const long nb = (long)(2147483647.0 / per);
-    if (p.B <= nb) return p.B;
-    const long parts = (p.B + nb - 1) / nb;
-    return (p.B + parts - 1) / parts;
-}
-
-bool geometry(const C3Params& p, C3Geom& g, int& variant, int& maxt) {
-    const bool narrow = p.Cout <= 32, s2 = p.stride == 2;
-    variant = s2 ? (narrow ? V_S2_NARROW : V_S2) : (narrow ? V_S1_NARROW : V_S1);
-    maxt = s2 ? (narrow ? 5 : 3) : 2;
-    const int npx = (s2 && !narrow) ? 64 : 128;
+C3Plan c3_plan(const C3Params& p) {
+    C3Plan pl;
+    const bool s2 = p.stride == 2;
+    pl.shape = 2 * s2 + (p.Cout <= 32);
+    const C3Shape t = k_c3_shapes[pl.shape];
+    const int npx = (C3_NW / t.WM) * t.NTW * 32, nstage = 64 * C3_NW;      // output pixels and staging threads of a workgroup
     const int NBZ = p.B * p.Do;
-    g.TW = p.Wo < 32 ? p.Wo : 32;
-    g.TH = npx / g.TW;
-    if (g.TH > p.Ho) g.TH = p.Ho;
-    g.NIMG = 1;
-    if (g.TH == p.Ho && g.TW == p.Wo) {
-        g.NIMG = npx / (g.TH * g.TW);
-        if (g.NIMG > 8) g.NIMG = 8;
-        if (g.NIMG > NBZ) g.NIMG = NBZ;
-        if (g.NIMG < 1) g.NIMG = 1;
-    }
-    g.PH = (g.TH - 1) * p.stride + 3;
-    g.PW = (g.TW - 1) * p.stride + 3;
-    while (g.NIMG > 1 && (g.NIMG * g.PH * g.PW * 2 + 255) / 256 > maxt) --g.NIMG;
-    if ((g.NIMG * g.PH * g.PW * 2 + 255) / 256 > maxt) return false;           // a tall one-column tile: the staging budget does not hold its patch
+    C3Geom& g = pl.g;
+    g.TW = std::min(p.Wo, 32);
+    g.TH = std::min(npx / g.TW, p.Ho);
+    g.NIMG = (g.TH == p.Ho && g.TW == p.Wo) ? std::max(1, std::min(npx / (g.TH * g.TW), std::min(8, NBZ))) : 1;
+    g.PH = (g.TH - 1) * p.stride + 3; g.PW = (g.TW - 1) * p.stride + 3;
+    while (g.NIMG > 1 && (g.NIMG * g.PH * g.PW * 2 + nstage - 1) / nstage > t.MAXT) --g.NIMG;
+    if ((g.NIMG * g.PH * g.PW * 2 + nstage - 1) / nstage > t.MAXT) return c3_declined("a tall one-column tile: the staging budget does not hold its patch");
     g.PWR = g.PW; g.pwh = 0;
     if (s2) { g.pwh = (g.PW + 1) / 2; g.PWR = 2 * g.pwh; }
-    g.tiles_x = (p.Wo + g.TW - 1) / g.TW;
-    g.tiles_y = (p.Ho + g.TH - 1) / g.TH;
+    g.tiles_x = (p.Wo + g.TW - 1) / g.TW; g.tiles_y = (p.Ho + g.TH - 1) / g.TH;
     g.bgroups = (NBZ + g.NIMG - 1) / g.NIMG;
     g.c1_pad = p.C2 > 0 ? ((p.C1 + 15) / 16) * 16 : (1 << 30);
     g.nchunk = p.C2 > 0 ? g.c1_pad / 16 + (p.C2 + 15) / 16 : (p.C1 + 15) / 16;
     const long nwg = (long)g.tiles_x * g.tiles_y * g.bgroups;
-    if (nwg >= (1L << 31) / (g.tiles_x > g.tiles_y ? g.tiles_x : g.tiles_y)) return false;      // index decode by multiplication
-    if ((long)NBZ >= (1L << 31) / p.Do) return false;
+    if (nwg >= (1L << 31) / std::max(g.tiles_x, g.tiles_y) || (long)NBZ >= (1L << 31) / p.Do) return c3_declined("grid too large for the index decode");
     g.m_tx = magic(g.tiles_x); g.m_ty = magic(g.tiles_y); g.m_nrec = magic(g.NIMG * g.PH * g.PW); g.m_phpw = magic(g.PH * g.PW);
     g.m_pw = magic(g.PW); g.m_thtw = magic(g.TH * g.TW); g.m_tw = magic(g.TW); g.m_do = magic(p.Do);
-    return (size_t)2 * g.NIMG * g.PH * g.PWR * 80 <= 160 * 1024;
+    const size_t tile_bytes = (size_t)2 * g.NIMG * g.PH * g.PWR * 80;
+    if (tile_bytes > LDS_LIMIT) return c3_declined("LDS tile too large");
+    pl.lds_bytes = std::max(tile_bytes, (size_t)C3_NW * 64 * sizeof(float));      // at least the statistics combine's slots
+    pl.grid_x = (unsigned)nwg, pl.grid_y = (unsigned)((p.Cout + 32 * t.WM - 1) / (32 * t.WM));
+    pl.fusable = g.NIMG == 1 || p.Do % g.NIMG == 0;
+    return pl;
 }
 
 // Shapes the kernel can run but which the caller's composition of 2-D convolutions was measured to run faster (tools/conv3d_ab.py on the
@@ -361,44 +334,41 @@ bool geometry(const C3Params& p, C3Geom& g, int& variant, int& maxt) {
 //       one-pixel-tile-per-wave stride-2 shape re-reads every weight fragment per 3 MFMAs (64 -> 128 at 20x128x112: 0.25 vs 0.29 ms);
 //   (c) fewer than two workgroups per compute unit with a long K loop: every (chunk, depth tap) step exposes a global-load latency that
 //       nothing else on the CU hides (320 -> 320 at 5x8x7, 60 steps: 0.18 vs 0.23 ms; 512 -> 256 at 10x32x28, 96 steps: 0.35 vs 0.39 ms).
-bool composition_is_faster(const C3Params& p, const C3Geom& g, int variant) {
+bool composition_is_faster(const C3Params& p, const C3Plan& pl) {
     const long out_px = (long)p.Do * p.Ho * p.Wo;
-    const int wm = (variant == V_S1 || variant == V_S2) ? 2 : 1;
-    const long nwg = (long)g.tiles_x * g.tiles_y * g.bgroups * ((p.Cout + 32 * wm - 1) / (32 * wm));
     if (p.KD == 1 && out_px >= 65536) return true;
     if (p.stride == 2 && p.sd == 1 && out_px >= 65536) return true;
-    return nwg < 512 && g.nchunk * p.KD > 24;
+    return (long)pl.grid_x * pl.grid_y < 512 && pl.g.nchunk * p.KD > 24;
+}
+
+// The plan of a call.  Samples per launch: x1, x2 and the output of a launch each stay below 2 GiB (32-bit buffer offsets).
+CallPlan<C3Plan> c3_call(C3Params p) {
+    CallPlan<C3Plan> c;
+    if (!shape_ok(p)) { c.why = "kernel (1|3,3,3) and strides 1|2 only"; return c; }
+    if (conv_terms() != 3) { c.why = "only the three-term product is built"; return c; }
+    const double dhw = (double)p.D * p.H * p.W, per = 4.0 * std::max({p.C1 * dhw, p.C2 * dhw, (double)p.Cout * p.Do * p.Ho * p.Wo});
+    c.parts = equal_parts(p.B, per >= 2147483648.0 ? 0 : (long)(2147483647.0 / per));
+    if (c.parts.n < 1) { c.why = "one sample of a tensor exceeds 2 GiB"; return c; }
+    p.B = (int)c.parts.n;
+    c.first = c.last = c3_plan(p);
+    if (c.parts.last != c.parts.n) { p.B = (int)c.parts.last; c.last = c3_plan(p); }
+    c.why = c.first.why ? c.first.why : c.last.why;
+    return c;
+}
+
+// the probe's answer: null when the call has a plan and the composition is not the faster route for its first part, else the reason
+const char* declined(const C3Params& p, const CallPlan<C3Plan>& c) {
+    if (c.why) return c.why;
+    return composition_is_faster(p, c.first) ? "the composition of 2-D convolutions is the faster route" : nullptr;
 }
 
 template <int WM, int NTW, int MAXT>
-int launch_variant(const C3Params& p, const C3Geom& g, const _Float16* wpk, hipStream_t s) {
-    constexpr int NW = 4;
-    size_t lds_bytes = (size_t)2 * g.NIMG * g.PH * g.PWR * 80;
-    if (lds_bytes < (size_t)NW * 64 * sizeof(float)) lds_bytes = (size_t)NW * 64 * sizeof(float);     // the statistics combine
-    dim3 grid((unsigned)(g.tiles_x * g.tiles_y * g.bgroups), (unsigned)((p.Cout + 32 * WM - 1) / (32 * WM)));
-    return launch_lds<conv3d_f16s_kernel<WM, NTW, MAXT, NW>>("conv3d_f16s", -1, 0.0, grid, dim3(64 * NW), lds_bytes, s, p, g, wpk);      // not among the timed kernels
+int launch_c3_shape(const C3Params& p, const C3Plan& pl, const _Float16* wpk, hipStream_t s) {      // not among the timed kernels
+    return launch_lds<conv3d_f16s_kernel<WM, NTW, MAXT, C3_NW>>("conv3d_f16s", -1, 0.0, dim3(pl.grid_x, pl.grid_y), dim3(64 * C3_NW), pl.lds_bytes, s, p, pl.g, wpk);
 }
-
-// one launch on a (sub-)batch; the statistics come from the fused epilogue when every workgroup stays inside one sample, else from norm.hip's pass
-int launch_part(const C3Params& p, const _Float16* wpk, hipStream_t s) {
-    C3Geom g;
-    int variant, maxt;
-    if (!geometry(p, g, variant, maxt)) { set_error("conv3d_f16s: shape not taken (ask cf_conv3d_f16s_ok first)"); return CF_ERR_ARG; }
-    C3Params q = p;
-    const bool fused = p.gn_ws && (g.NIMG == 1 || p.Do % g.NIMG == 0);
-    if (p.gn_ws && !fused) q.gn_ws = nullptr;
-    if (fused && !p.gn_prezeroed &&
-        hipMemsetAsync(p.gn_ws, 0, sizeof(double) * 2 * (size_t)p.B * p.gn_groups, s) != hipSuccess) { set_error("conv3d_f16s: memset failed"); return CF_ERR_LAUNCH; }
-    int rc;
-    switch (variant) {
-        case V_S1: rc = launch_variant<2, 2, 2>(q, g, wpk, s); break;
-        case V_S1_NARROW: rc = launch_variant<1, 1, 2>(q, g, wpk, s); break;
-        case V_S2: rc = launch_variant<2, 1, 3>(q, g, wpk, s); break;
-        default: rc = launch_variant<1, 1, 5>(q, g, wpk, s); break;
-    }
-    if (rc != CF_OK || !p.gn_ws || fused) return rc;
-    return launch_gn_stats(p.out, p.gn_ws, p.B, p.Cout, p.Do * p.Ho * p.Wo, p.gn_groups, s);
-}
+#define CF_C3_ROW(...) launch_c3_shape<__VA_ARGS__>,
+int (*const k_c3_launch[])(const C3Params&, const C3Plan&, const _Float16*, hipStream_t) = {CF_C3_SHAPES(CF_C3_ROW)};
+#undef CF_C3_ROW
 
 void fill(C3Params& p, int B, int C1, int C2, int D, int H, int W, int Cout, int KD, int sd, int st) {
     p.x1 = p.x2 = p.bias = nullptr; p.out = nullptr; p.gn_ws = nullptr;
@@ -410,21 +380,6 @@ void fill(C3Params& p, int B, int C1, int C2, int D, int H, int W, int Cout, int
     p.Wo = (W - 1) / st + 1;
 }
 
-// does the kernel take the shape?  Every sub-batch size the launcher would use must have a geometry.
-bool taken(const C3Params& p0) {
-    if (!shape_ok(p0) || conv_terms() != 3) return false;
-    const long nb = sub_batch(p0);
-    if (nb < 1) return false;
-    C3Params p = p0;
-    C3Geom g;
-    int variant, maxt;
-    p.B = (int)nb;
-    if (!geometry(p, g, variant, maxt) || composition_is_faster(p, g, variant)) return false;
-    const long last = p0.B - (p0.B - 1) / nb * nb;
-    p.B = (int)last;
-    return last == nb || geometry(p, g, variant, maxt);
-}
-
 }  // namespace
 }  // namespace cf
 
@@ -434,7 +389,7 @@ extern "C" int cf_conv3d_f16s_ok(int B, int C1, int C2, int D, int H, int W, int
     if (KH != 3) return 0;
     C3Params p;
     fill(p, B, C1, C2, D, H, W, Cout, KD, stride_d, stride_hw);
-    return taken(p) ? 1 : 0;
+    return declined(p, c3_call(p)) ? 0 : 1;
 }
 
 extern "C" int cf_conv3d_f16s(const float* x1, int C1, const float* x2, int C2, const void* wpk, const float* bias, float* out, int B, int D, int H,
@@ -446,22 +401,25 @@ extern "C" int cf_conv3d_f16s(const float* x1, int C1, const float* x2, int C2, 
     CF_REQUIRE(KH == 3 && KW == 3, "in-plane kernel %dx%d: only 3x3 is built", KH, KW);
     C3Params p;
     fill(p, B, C1, C2, D, H, W, Cout, KD, stride_d, stride_hw);
-    CF_REQUIRE(taken(p), "unsupported configuration B=%d C=%d+%d D=%d H=%d W=%d Cout=%d kernel (%d,3,3) stride (%d,%d,%d): kernel (1|3,3,3), strides 1|2, "
-                         "one sample of every tensor < 2 GiB, three-term product mode (cf_conv3d_f16s_ok)", B, C1, C2, D, H, W, Cout, KD, stride_d, stride_hw, stride_hw);
+    const CallPlan<C3Plan> call = c3_call(p);
+    const char* why = declined(p, call);
+    CF_REQUIRE(!why, "unsupported configuration B=%d C=%d+%d D=%d H=%d W=%d Cout=%d kernel (%d,3,3) stride (%d,%d,%d): %s (cf_conv3d_f16s_ok)", B, C1, C2, D,
+               H, W, Cout, KD, stride_d, stride_hw, stride_hw, why);
     p.x1 = x1; p.x2 = C2 ? x2 : nullptr; p.bias = bias; p.out = out; p.alpha = alpha;
-    p.gn_ws = gn_ws; p.gn_groups = gn_groups < 0 ? -gn_groups : gn_groups; p.gn_prezeroed = gn_groups < 0;
+    set_stats_request(p, gn_ws, gn_groups);
     CF_REQUIRE(!gn_ws || (p.gn_groups > 0 && Cout % p.gn_groups == 0), "bad GroupNorm statistics request");
-    const long nb = sub_batch(p);
     const long DHW = (long)D * H * W, DHWo = (long)p.Do * p.Ho * p.Wo;
-    for (long b0 = 0; b0 < B; b0 += nb) {
+    const hipStream_t s = as_stream(stream);
+    // every part executes its plan; the statistics come from the fused epilogue where the plan can fuse them, else from norm.hip's pass
+    return for_each_part(B, call, [&](long b0, int nb, const C3Plan& pl) {
         C3Params q = p;
-        q.B = (int)(B - b0 < nb ? B - b0 : nb);
-        q.x1 = x1 + b0 * C1 * DHW;
+        q.B = nb; q.x1 = x1 + b0 * C1 * DHW;
         if (q.x2) q.x2 = x2 + b0 * C2 * DHW;
         q.out = out + b0 * Cout * DHWo;
         if (gn_ws) q.gn_ws = gn_ws + 2 * b0 * p.gn_groups;
-        const int rc = launch_part(q, reinterpret_cast<const _Float16*>(wpk), as_stream(stream));
-        if (rc != CF_OK) return rc;
-    }
-    return CF_OK;
+        return launch_with_stats("conv3d_f16s", q.gn_ws, q.gn_groups, q.gn_prezeroed, pl.fusable, q.out, nb, Cout, (int)DHWo, s, [&](double* ws) {
+            q.gn_ws = ws;
+            return k_c3_launch[pl.shape](q, pl, reinterpret_cast<const _Float16*>(wpk), s);
+        });
+    });
 }

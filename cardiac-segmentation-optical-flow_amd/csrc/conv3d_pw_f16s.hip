@@ -14,19 +14,19 @@
 //     conv3d_f16s.hip, double-buffered with one barrier per step, and runs 3 MFMAs per (k-step, pixel tile) on it.
 //   * Small maps: when two or more whole samples fit a tile, a workgroup holds up to 128 / (Do*Ho*Wo) of them; the statistics then come
 //     from the statistics pass of norm.hip after the kernel.  Otherwise a workgroup stays inside one sample and the fused statistics are
-//     summed in a fixed order as in conv3d_f16s.hip.
+//     summed in a fixed order (conv3d.h).
 //   * Weights: cineflow.ops.pack_conv_weight_f16s' 1x1 order [m-tile][chunk of 32][k-step][hi/lo][lane][8], 1 KiB per fragment, one
 //     coalesced dwordx4 per lane from L1/L2, the next step's four fragments prefetched while the current step multiplies.
 // Only the 3-term product is built: under cf_conv_terms(1) cf_conv3d_pw_f16s_ok answers 0 and the caller keeps its 2-D composition.
+// Host half (below the kernel): one plan per launch and one per call, read by the probe and the launcher alike; the epilogue's statistics
+// combine is conv3d.h's, shared with conv3d_f16s.hip.
 #include <hip/hip_fp16.h>
+#include <algorithm>
 
-#include "conv.h"
+#include "conv3d.h"
 
 namespace cf {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 struct PwParams {
     const float* x;       // [B,Cin,D,H,W]
@@ -47,42 +47,6 @@ __device__ __forceinline__ bool decode(const PwParams& p, int b0, int q0, int P,
     b = b0 + img;
     q = q0 + pidx - img * P;
     return img < p.nimg && b < p.B && q < P;
-}
-
-// The fused-statistics combine of the epilogue (the scheme of conv3d_f16s.hip).  ssum / ssq: the 16 per-register sums of this lane over its pixels.  Waves are laid out as wave = ngrp * WM + (m-tile within the
-// workgroup); `red` is LDS that no wave still reads ([NW / WM][WM * 32 channels][2] floats), `ws` the statistics of the workgroup's sample.
-// Every wave owns a slot per channel and the slots are summed in a fixed order: the fp32 part of the sum does not depend on which wave
-// arrives first (LDS atomics would make a repeated run differ in the last bit of a mean); the fp64 atomics that follow add fp32-valued
-// terms, whose sum is exact in fp64 in any order while they span fewer than 29 binary orders of magnitude.
-template <int WM, int NW>
-__device__ __forceinline__ void conv3d_stats_combine(float (&ssum)[16], float (&ssq)[16], float* red, int tid, int cout, int gn_groups, double* ws) {
-    constexpr int NGRP = NW / WM;
-    const int lane = tid & 63, wave = tid >> 6, half = lane >> 5;
-    const int ngrp = wave / WM;
-    xreduce16(ssum, lane);      // transpose-reduce as conv_f16s.hip: lane 2k holds channel register r(k)
-    xreduce16(ssq, lane);
-    if ((lane & 1) == 0) {
-        const int r = ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
-        const int cl = (wave % WM) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        red[2 * (ngrp * WM * 32 + cl)] = ssum[0];
-        red[2 * (ngrp * WM * 32 + cl) + 1] = ssq[0];
-    }
-    __syncthreads();
-    if (tid < WM * 32) {
-        const int co = blockIdx.y * WM * 32 + tid;
-        const int cpg = cout / gn_groups;
-        if (co < cout && (tid == 0 || co % cpg == 0)) {      // one thread per (group, workgroup): the first channel of the group in this block
-            int n = cpg - co % cpg;
-            if (n > WM * 32 - tid) n = WM * 32 - tid;
-            if (n > cout - co) n = cout - co;
-            float s1 = 0.f, s2 = 0.f;
-            for (int j = 0; j < n; ++j)
-                for (int q = 0; q < NGRP; ++q) { s1 += red[2 * (q * WM * 32 + tid + j)]; s2 += red[2 * (q * WM * 32 + tid + j) + 1]; }
-            double* w = ws + 2L * (co / cpg);
-            atomicAdd(w, (double)s1);
-            atomicAdd(w + 1, (double)s2);
-        }
-    }
 }
 
 template <int WM, int NTW, int NW>
@@ -248,56 +212,55 @@ void fill(PwParams& p, int B, int Cin, int D, int H, int W, int Cout, int sd, in
     p.Wo = (W - 1) / st + 1;
 }
 
-// samples per launch: x and the output of a launch each stay below 2 GiB (32-bit buffer offsets); 0: one sample is already too large
-long sub_batch(const PwParams& p) {
-    double per = (double)p.Cin * p.D * p.H * p.W;
-    const double po = (double)p.Cout * p.Do * p.Ho * p.Wo;
-    if (po > per) per = po;
-    per *= 4.0;
-    if (per >= 2147483648.0) return 0;
-    const long nb = (long)(2147483647.0 / per);
-    if (p.B <= nb) return p.B;
-    const long parts = (p.B + nb - 1) / nb;
-    return (p.B + parts - 1) / parts;
+// ---------------------------------------------------------------------------------------------------------------------
+// Host half: the plan of one launch (pw_plan: pure host arithmetic naming the kernel variant, samples per workgroup, tiles per sample,
+// grid and statistics route) and the plan of a call (pw_call: the sub-batch cut and the plans of its two part sizes, or why the call is
+// declined).  cf_conv3d_pw_f16s_ok and cf_conv3d_pw_f16s both read pw_call; nothing else decides.
+constexpr int PW_NW = 4;
+
+// What one launch on a (sub-)batch will be: a pure function of the PwParams (no pointer is read); only a whole call is ever declined.
+struct PwPlan {
+    int wm;                      // the built variants: <WM, NTW> = <1, 1> for Cout <= 32, else <2, 2>
+    int nimg, tiles;             // the kernel arguments of the same names
+    unsigned grid_x, grid_y;
+    bool fusable;                // the epilogue can accumulate the statistics: one sample per workgroup
+};
+
+PwPlan pw_plan(const PwParams& p) {
+    PwPlan pl;
+    const long P = (long)p.Do * p.Ho * p.Wo;
+    pl.wm = p.Cout <= 32 ? 1 : 2;
+    pl.nimg = 1; pl.tiles = (int)((P + NPX - 1) / NPX);
+    if (2 * P <= NPX && p.B > 1) { pl.nimg = (int)std::min((long)p.B, NPX / P); pl.tiles = 1; }
+    pl.grid_x = (unsigned)(pl.nimg > 1 ? (p.B + pl.nimg - 1) / pl.nimg : (long)p.B * pl.tiles);
+    pl.grid_y = (unsigned)((p.Cout + 32 * pl.wm - 1) / (32 * pl.wm));
+    pl.fusable = pl.nimg == 1;
+    return pl;
 }
 
+// The plan of a call.  Samples per launch: x and the output of a launch each stay below 2 GiB (32-bit buffer offsets).
 // A shape class on which the caller's composition measures faster would be declined here by a size threshold, as cf_conv3d_f16s_ok does.
 // None is: on every trainer-width projection (32 -> 64 at 128^3 down to 320 -> 320 at 8^3, strides (2,2,2) and (1,2,2)) the kernel's
 // median is 1.18x to 2.40x below the composition's (tools/resenc_bench.py, profiles/resenc_pw3d.txt).
-bool taken(const PwParams& p) { return shape_ok(p) && conv_terms() == 3 && sub_batch(p) >= 1; }
-
-template <int WM, int NTW>
-int launch_variant(const PwParams& p, const _Float16* wpk, hipStream_t s) {
-    constexpr int NW = 4;
-    const long nwg = p.nimg > 1 ? (p.B + p.nimg - 1) / p.nimg : (long)p.B * p.tiles;
-    dim3 grid((unsigned)nwg, (unsigned)((p.Cout + 32 * WM - 1) / (32 * WM)));
-    hipLaunchKernelGGL((conv3d_pw_f16s_kernel<WM, NTW, NW>), grid, dim3(64 * NW), 0, s, p, wpk);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error(std::string("conv3d_pw_f16s launch failed: ") + hipGetErrorString(e));
-        return CF_ERR_LAUNCH;
-    }
-    return CF_OK;
+CallPlan<PwPlan> pw_call(PwParams p) {
+    CallPlan<PwPlan> c;
+    if (!shape_ok(p)) { c.why = "strides 1|2 only"; return c; }
+    if (conv_terms() != 3) { c.why = "only the three-term product is built"; return c; }
+    const double per = 4.0 * std::max((double)p.Cin * p.D * p.H * p.W, (double)p.Cout * p.Do * p.Ho * p.Wo);
+    c.parts = equal_parts(p.B, per >= 2147483648.0 ? 0 : (long)(2147483647.0 / per));
+    if (c.parts.n < 1) { c.why = "one sample of x or out exceeds 2 GiB"; return c; }
+    p.B = (int)c.parts.n;
+    c.first = c.last = pw_plan(p);
+    if (c.parts.last != c.parts.n) { p.B = (int)c.parts.last; c.last = pw_plan(p); }
+    return c;
 }
 
-// one launch on a (sub-)batch; the statistics come from the fused epilogue when every workgroup stays inside one sample, else from norm.hip's pass
-int launch_part(const PwParams& p0, const _Float16* wpk, hipStream_t s) {
-    PwParams p = p0;
-    const long P = (long)p.Do * p.Ho * p.Wo;
-    p.nimg = 1;
-    p.tiles = (int)((P + NPX - 1) / NPX);
-    if (2 * P <= NPX && p.B > 1) {
-        p.nimg = (int)(NPX / P);
-        if (p.nimg > p.B) p.nimg = p.B;
-        p.tiles = 1;
-    }
-    const bool fused = p.gn_ws && p.nimg == 1;
-    if (p.gn_ws && !fused) p.gn_ws = nullptr;
-    if (fused && !p.gn_prezeroed &&
-        hipMemsetAsync(p.gn_ws, 0, sizeof(double) * 2 * (size_t)p.B * p.gn_groups, s) != hipSuccess) { set_error("conv3d_pw_f16s: memset failed"); return CF_ERR_LAUNCH; }
-    const int rc = p.Cout <= 32 ? launch_variant<1, 1>(p, wpk, s) : launch_variant<2, 2>(p, wpk, s);
-    if (rc != CF_OK || !p0.gn_ws || fused) return rc;
-    return launch_gn_stats(p0.out, p0.gn_ws, p0.B, p0.Cout, (int)P, p0.gn_groups, s);
+template <int WM, int NTW>
+int launch_pw_shape(const PwParams& p, const PwPlan& pl, const void* wpk, hipStream_t s) {
+    hipLaunchKernelGGL((conv3d_pw_f16s_kernel<WM, NTW, PW_NW>), dim3(pl.grid_x, pl.grid_y), dim3(64 * PW_NW), 0, s, p, reinterpret_cast<const _Float16*>(wpk));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error(std::string("conv3d_pw_f16s launch failed: ") + hipGetErrorString(e)); return CF_ERR_LAUNCH; }
+    return CF_OK;
 }
 
 }  // namespace
@@ -308,7 +271,7 @@ using namespace cf;
 extern "C" int cf_conv3d_pw_f16s_ok(int B, int Cin, int D, int H, int W, int Cout, int stride_d, int stride_hw) {
     PwParams p;
     fill(p, B, Cin, D, H, W, Cout, stride_d, stride_hw);
-    return taken(p) ? 1 : 0;
+    return pw_call(p).why ? 0 : 1;
 }
 
 extern "C" int cf_conv3d_pw_f16s(const float* x, const void* wpk, const float* bias, float* out, int B, int Cin, int D, int H, int W, int Cout,
@@ -317,21 +280,24 @@ extern "C" int cf_conv3d_pw_f16s(const float* x, const void* wpk, const float* b
     CF_REQUIRE((reinterpret_cast<uintptr_t>(wpk) & 15) == 0, "packed weights must be 16-byte aligned");
     PwParams p;
     fill(p, B, Cin, D, H, W, Cout, stride_d, stride_hw);
-    CF_REQUIRE(taken(p), "unsupported configuration B=%d Cin=%d D=%d H=%d W=%d Cout=%d stride (%d,%d,%d): strides 1|2, one sample of x and out "
-                         "< 2 GiB, three-term product mode (cf_conv3d_pw_f16s_ok)", B, Cin, D, H, W, Cout, stride_d, stride_hw, stride_hw);
+    const CallPlan<PwPlan> call = pw_call(p);
+    CF_REQUIRE(!call.why, "unsupported configuration B=%d Cin=%d D=%d H=%d W=%d Cout=%d stride (%d,%d,%d): %s (cf_conv3d_pw_f16s_ok)", B, Cin, D, H, W, Cout,
+               stride_d, stride_hw, stride_hw, call.why);
     p.x = x; p.bias = bias; p.out = out; p.alpha = alpha;
-    p.gn_ws = gn_ws; p.gn_groups = gn_groups < 0 ? -gn_groups : gn_groups; p.gn_prezeroed = gn_groups < 0;
+    set_stats_request(p, gn_ws, gn_groups);
     CF_REQUIRE(!gn_ws || (p.gn_groups > 0 && Cout % p.gn_groups == 0), "bad GroupNorm statistics request");
-    const long nb = sub_batch(p);
     const long DHW = (long)D * H * W, DHWo = (long)p.Do * p.Ho * p.Wo;
-    for (long b0 = 0; b0 < B; b0 += nb) {
+    const hipStream_t s = as_stream(stream);
+    // every part executes its plan; the statistics come from the fused epilogue where the plan can fuse them, else from norm.hip's pass
+    return for_each_part(B, call, [&](long b0, int nb, const PwPlan& pl) {
         PwParams q = p;
-        q.B = (int)(B - b0 < nb ? B - b0 : nb);
+        q.B = nb; q.nimg = pl.nimg; q.tiles = pl.tiles;
         q.x = x + b0 * Cin * DHW;
         q.out = out + b0 * Cout * DHWo;
         if (gn_ws) q.gn_ws = gn_ws + 2 * b0 * p.gn_groups;
-        const int rc = launch_part(q, reinterpret_cast<const _Float16*>(wpk), as_stream(stream));
-        if (rc != CF_OK) return rc;
-    }
-    return CF_OK;
+        return launch_with_stats("conv3d_pw_f16s", q.gn_ws, q.gn_groups, q.gn_prezeroed, pl.fusable, q.out, nb, Cout, (int)DHWo, s, [&](double* ws) {
+            q.gn_ws = ws;
+            return pl.wm == 1 ? launch_pw_shape<1, 1>(q, pl, wpk, s) : launch_pw_shape<2, 2>(q, pl, wpk, s);
+        });
+    });
 }

@@ -35,9 +35,6 @@
 
 namespace cf {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 CF_CLOCK_DECL(g_clock_f16s)
 
 struct F16sGeom {
@@ -55,9 +52,6 @@ struct F16sGeom {
     int PWR, pwh, kx1, kx2;  // LDS row pitch in records and the record offsets of taps kx = 1, 2 (stride 2: columns de-interleaved by parity)
     unsigned m_tx, m_ty, m_percg, m_phnq, m_nq, m_nrec, m_phpw, m_pw, m_thtw, m_tw;
 };
-
-__host__ __device__ inline unsigned f16s_magic(int d) { return d <= 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)d + 1ull); }
-__device__ __forceinline__ int fdiv(int n, int d, unsigned m) { return d <= 1 ? n : (int)__umulhi((unsigned)n, m); }
 
 // No range clamp: an activation beyond fp16's range (|x| >= 65520) becomes hi = inf, lo = NaN and poisons the output loudly, NaN and
 // Inf inputs propagate as they do through an fp32 convolution (a clamp here saturated them silently and cost one VALU per element).
@@ -801,16 +795,16 @@ static F16sPlan f16s_finish(const ConvParams& p, const F16sShape& t, F16sGeom g)
     const int WGRP = (t.KH * t.KW == 9) ? 3 : ((t.KH * t.KW == 1) ? t.CK / 16 : 5);      // k-steps per LDS weight slot (kernel: G)
     const int NSTAGE = 64 * t.NW;
     const int nrec = g.NIMG * g.PH * g.PW;
-    g.m_tx = f16s_magic(g.tiles_x);
-    g.m_ty = f16s_magic(g.tiles_y);
-    g.m_percg = f16s_magic(g.NIMG * g.PH * g.NQ);
-    g.m_phnq = f16s_magic(g.PH * g.NQ);
-    g.m_nq = f16s_magic(g.NQ);
-    g.m_nrec = f16s_magic(nrec);
-    g.m_phpw = f16s_magic(g.PH * g.PW);
-    g.m_pw = f16s_magic(g.PW);
-    g.m_thtw = f16s_magic(g.TH * g.TW);
-    g.m_tw = f16s_magic(g.TW);
+    g.m_tx = magic(g.tiles_x);
+    g.m_ty = magic(g.tiles_y);
+    g.m_percg = magic(g.NIMG * g.PH * g.NQ);
+    g.m_phnq = magic(g.PH * g.NQ);
+    g.m_nq = magic(g.NQ);
+    g.m_nrec = magic(nrec);
+    g.m_phpw = magic(g.PH * g.PW);
+    g.m_pw = magic(g.PW);
+    g.m_thtw = magic(g.TH * g.TW);
+    g.m_tw = magic(g.TW);
     if ((long)g.tiles_x * g.tiles_y * g.bgroups >= (1L << 31) / (g.tiles_x > g.tiles_y ? g.tiles_x : g.tiles_y))
         return f16s_declined("conv_f16s: grid too large for the index decode");
     if (!t.VEC && (nrec * (t.CK / 8) + NSTAGE - 1) / NSTAGE > t.MAXT) return f16s_declined("conv_f16s: staging tasks exceed MAXT");
@@ -962,44 +956,28 @@ static int (*const k_f16s_launch[])(const ConvParams&, const F16sPlan&, const _F
 static int launch_conv_f16s_part(const ConvParams& p, const _Float16* wpk, hipStream_t s) {
     const F16sPlan pl = f16s_plan(p);
     if (pl.route == F16S_DECLINED) { set_error(pl.why); return CF_ERR_ARG; }
-    const bool fused = p.gn_ws && pl.fusable;
-    // the fused statistics accumulate with atomics: the workspace must start at zero (gn_prezeroed: the caller hands out slices
-    // of a pool it zeroed with ONE memset -- the per-launch memsets were 1.2 % of the step)
-    const bool zero = fused && !p.gn_prezeroed;
-    const size_t ws_bytes = sizeof(double) * 2 * (size_t)p.B * p.gn_groups;
-    if (zero && hipMemsetAsync(p.gn_ws, 0, ws_bytes, s) != hipSuccess) {
-        set_error(pl.route == F16S_STREAM ? "conv_stream: memset failed" : "conv_f16s: memset failed");
-        return CF_ERR_LAUNCH;
-    }
-    if (pl.route == F16S_STREAM) return launch_conv_stream(p, wpk, s);
-    ConvParams q = p;
-    if (!fused) q.gn_ws = nullptr;
-    const int rc = k_f16s_launch[pl.shape](q, pl, wpk, s);
-    if (rc != CF_OK || !p.gn_ws || fused) return rc;
     const int up = p.scatter2x2 ? 2 : 1;
     const int cout = p.scatter2x2 ? p.Cout / 4 : p.Cout;
-    if (p.out_coff != 0 || p.out_ctotal != cout) { set_error("conv_f16s: GroupNorm statistics need a dense output tensor"); return CF_ERR_ARG; }
-    return launch_gn_stats(p.out, p.gn_ws, p.B, cout, p.Ho * up * p.Wo * up, p.gn_groups, s);
+    return launch_with_stats(pl.route == F16S_STREAM ? "conv_stream" : "conv_f16s", p.gn_ws, p.gn_groups, p.gn_prezeroed, pl.fusable, p.out, p.B, cout,
+                             p.Ho * up * p.Wo * up, s, [&](double* ws) -> int {
+        if (pl.route == F16S_STREAM) return launch_conv_stream(p, wpk, s);
+        ConvParams q = p; q.gn_ws = ws;
+        const int rc = k_f16s_launch[pl.shape](q, pl, wpk, s);
+        if (rc != CF_OK || !p.gn_ws || ws) return rc;
+        if (p.out_coff != 0 || p.out_ctotal != cout) { set_error("conv_f16s: GroupNorm statistics need a dense output tensor"); return CF_ERR_ARG; }
+        return CF_OK;
+    });
 }
 
 // The kernel addresses its inputs with 32-bit buffer offsets (< 2 GiB per descriptor).  A batch whose input tensors are larger is
 // cut into sub-batches HERE (same kernel, same numbers, a few more launches) instead of being handed to another kernel: the batch
 // axis is the outermost one of every operand, so a sub-batch is a pointer offset.
-// Samples per sub-batch: the batch is cut into the FEWEST parts that fit and the parts are made equal (the last one at most parts - 1
-// samples smaller) -- a greedy cut could leave a remainder of one sample, for which the plan picks another kernel shape than for the
-// large parts (e.g. one without the deferred input normalisation).  Plans are made per part: n samples, `last` in the remainder; n == 0:
-// one sample of an input exceeds 2 GiB.
-struct F16sParts { long n, last; };
-static F16sParts f16s_parts(const ConvParams& p) {
+// Plans are made per part of equal_parts' cut (conv.h): n samples, `last` in the remainder; n == 0: one sample of an input exceeds 2 GiB.
+static Parts f16s_parts(const ConvParams& p) {
     if (conv_stream_applicable(p)) return {p.B, p.B};      // per-sample buffer resources: no 2 GiB limit on the batch
     const long HW = (long)p.H * p.W;
     const long per1 = (long)p.C1 * HW * 4, per2 = (long)p.C2 * HW * 4;
-    const long nb = ((1L << 31) - 1) / (per1 > per2 ? per1 : per2);
-    if (nb < 1) return {0, 0};
-    if (p.B <= nb) return {p.B, p.B};
-    const long parts = (p.B + nb - 1) / nb;
-    const long n = (p.B + parts - 1) / parts;
-    return {n, p.B - (p.B - 1) / n * n};
+    return equal_parts(p.B, ((1L << 31) - 1) / (per1 > per2 ? per1 : per2));
 }
 
 int launch_conv_f16s(const ConvParams& p, const _Float16* wpk, hipStream_t s) {
@@ -1032,10 +1010,6 @@ static ConvParams f16s_layer(int B, int C1, int C2, int H, int W, int Cout, int 
     p.gn_ws = nullptr; p.gn_groups = 0; p.gn_prezeroed = 0;
     p.terms = conv_terms();
     return p;
-}
-// gn_groups < 0 declares gn_ws already zeroed
-static void f16s_stats(ConvParams& p, double* gn_ws, int gn_groups) {
-    p.gn_ws = gn_ws; p.gn_groups = gn_groups < 0 ? -gn_groups : gn_groups; p.gn_prezeroed = gn_groups < 0;
 }
 // the transposed 2x2 / stride 2 convolution as the kernel sees it: a 1x1 GEMM to 4 * Cout rows (co, dy, dx), scattered by the epilogue
 static ConvParams f16s_layer_transposed(int B, int Cin, int H, int W, int Cout) {
@@ -1076,7 +1050,7 @@ extern "C" int cf_conv2d_f16s(const float* x1, int C1, const float* x2, int C2, 
     ConvParams p = f16s_layer(B, C1, C2, H, W, Cout, KH, KW, stride, pad_h, pad_w);
     p.x1 = x1; p.x2 = C2 ? x2 : nullptr; p.bias = bias; p.res = res; p.out = out;
     p.out_ctotal = out_ctotal; p.out_coff = out_coff; p.act = act; p.alpha = alpha;
-    f16s_stats(p, gn_ws, gn_groups);
+    set_stats_request(p, gn_ws, gn_groups);
     CF_REQUIRE(!gn_ws || (p.gn_groups > 0 && Cout % p.gn_groups == 0 && out_coff == 0 && out_ctotal == Cout), "bad GroupNorm statistics request");
     CF_REQUIRE(p.Ho > 0 && p.Wo > 0, "empty output");
     CF_REQUIRE(conv_f16s_supported(p), "%s", k_f16s_unsupported);
@@ -1093,7 +1067,7 @@ extern "C" int cf_conv2d_f16s_prenorm_ok(int B, int C, int H, int W, int Cout) {
     ConvParams p = f16s_layer(B, C, 0, H, W, Cout, 3, 3, 1, 1, 1);
     p.x1 = p.in_norm = f16s_address(0);
     if (!conv_f16s_supported(p)) return 0;
-    const F16sParts parts = f16s_parts(p);
+    const Parts parts = f16s_parts(p);
     if (parts.n < 1) return 0;
     for (const long b : {parts.n, parts.last}) {
         p.B = (int)b;
@@ -1110,7 +1084,7 @@ extern "C" int cf_conv2d_f16s_prenorm(const float* x, int C, const float* in_nor
     CF_REQUIRE((reinterpret_cast<uintptr_t>(wpk) & 15) == 0, "packed weights must be 16-byte aligned");
     ConvParams p = f16s_layer(B, C, 0, H, W, Cout, 3, 3, 1, 1, 1);
     p.x1 = x; p.bias = bias; p.out = out; p.alpha = alpha; p.in_norm = in_norm; p.in_slope = in_slope;
-    f16s_stats(p, gn_ws, gn_groups);
+    set_stats_request(p, gn_ws, gn_groups);
     CF_REQUIRE(!gn_ws || (p.gn_groups > 0 && Cout % p.gn_groups == 0), "bad GroupNorm statistics request");
     CF_REQUIRE(conv_f16s_supported(p), "unsupported configuration for the f16-split kernel");
     return launch_conv_f16s(p, reinterpret_cast<const _Float16*>(wpk), as_stream(stream));
@@ -1125,7 +1099,7 @@ extern "C" int cf_conv_transpose2d_k2s2_f16s(const float* x, const void* wpk, co
     CF_REQUIRE((reinterpret_cast<uintptr_t>(wpk) & 15) == 0, "packed weights must be 16-byte aligned");
     ConvParams p = f16s_layer_transposed(B, Cin, H, W, Cout);
     p.x1 = x; p.bias = bias; p.out = out; p.out_ctotal = out_ctotal; p.out_coff = out_coff; p.alpha = alpha;
-    f16s_stats(p, gn_ws, gn_groups);
+    set_stats_request(p, gn_ws, gn_groups);
     CF_REQUIRE(!gn_ws || (p.gn_groups > 0 && Cout % p.gn_groups == 0 && out_coff == 0 && out_ctotal == Cout), "bad GroupNorm statistics request");
     CF_REQUIRE(conv_f16s_supported(p), "unsupported configuration for the f16-split kernel (one sample of the input must stay below 2 GiB)");
     return launch_conv_f16s(p, reinterpret_cast<const _Float16*>(wpk), as_stream(stream));
@@ -1142,10 +1116,10 @@ extern "C" int cf_conv2d_f16s_route(int B, int C1, int C2, int H, int W, int Cou
     if (p.C2) p.x2 = f16s_address(x2_low4);
     if (prenorm && !transposed) { p.in_norm = f16s_address(0); p.in_slope = 0.01f; }
     static double stats;      // stands for a workspace: the plan asks only whether there is one
-    if (stats_groups) f16s_stats(p, &stats, stats_groups);
+    if (stats_groups) set_stats_request(p, &stats, stats_groups);
     CF_REQUIRE(p.Ho > 0 && p.Wo > 0, "empty output");
     F16sPlan pl;
-    F16sParts parts = {0, 0};
+    Parts parts = {0, 0};
     if (!conv_f16s_supported(p)) {
         pl = f16s_declined(k_f16s_unsupported);
     } else {

@@ -41,11 +41,9 @@
 namespace cf {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 struct WinoGeom {
@@ -1189,16 +1187,16 @@ int wino_run(const char* family, const ConvParams& p, const WinoPlan& pl, const 
 
 int launch_plan(const ConvParams& p, const WinoPlan& pl, const _Float16* wpk, hipStream_t s) {
     if (!pl.form) { set_error(pl.why); return CF_ERR_ARG; }
-    if (p.gn_ws && !p.gn_prezeroed &&
-        hipMemsetAsync(p.gn_ws, 0, sizeof(double) * 2 * (size_t)p.B * p.gn_groups, s) != hipSuccess) { set_error("conv_wino: memset failed"); return CF_ERR_LAUNCH; }
     const bool pre = p.in_norm != nullptr;
-    if (pl.form == 8) {
-        const char* ps = "conv_wino (persistent)";
-        if (pl.m16) return pre ? wino_run<conv_wino_ps_kernel<1, 1>>(ps, p, pl, wpk, s) : wino_run<conv_wino_ps_kernel<0, 1>>(ps, p, pl, wpk, s);
-        return pre ? wino_run<conv_wino_ps_kernel<1, 0>>(ps, p, pl, wpk, s) : wino_run<conv_wino_ps_kernel<0, 0>>(ps, p, pl, wpk, s);
-    }
-    if (pl.form == 4) return pre ? wino_run<conv_wino_kernel<4, 1>>("conv_wino", p, pl, wpk, s) : wino_run<conv_wino_kernel<4, 0>>("conv_wino", p, pl, wpk, s);
-    return pre ? wino_run<conv_wino_kernel<2, 1>>("conv_wino", p, pl, wpk, s) : wino_run<conv_wino_kernel<2, 0>>("conv_wino", p, pl, wpk, s);
+    return launch_with_stats("conv_wino", p.gn_ws, p.gn_groups, p.gn_prezeroed, true, p.out, p.B, p.Cout, p.Ho * p.Wo, s, [&](double*) {      // every form fuses
+        if (pl.form == 8) {
+            const char* ps = "conv_wino (persistent)";
+            if (pl.m16) return pre ? wino_run<conv_wino_ps_kernel<1, 1>>(ps, p, pl, wpk, s) : wino_run<conv_wino_ps_kernel<0, 1>>(ps, p, pl, wpk, s);
+            return pre ? wino_run<conv_wino_ps_kernel<1, 0>>(ps, p, pl, wpk, s) : wino_run<conv_wino_ps_kernel<0, 0>>(ps, p, pl, wpk, s);
+        }
+        if (pl.form == 4) return pre ? wino_run<conv_wino_kernel<4, 1>>("conv_wino", p, pl, wpk, s) : wino_run<conv_wino_kernel<4, 0>>("conv_wino", p, pl, wpk, s);
+        return pre ? wino_run<conv_wino_kernel<2, 1>>("conv_wino", p, pl, wpk, s) : wino_run<conv_wino_kernel<2, 0>>("conv_wino", p, pl, wpk, s);
+    });
 }
 
 }  // namespace
@@ -1216,7 +1214,7 @@ static void wino_params(ConvParams& p, const float* x1, int C1, const float* x2,
     p.x1 = x1; p.x2 = C2 ? x2 : nullptr; p.wt = nullptr; p.bias = bias; p.res = res; p.out = out; p.w_bstride = 0;
     p.C1 = C1; p.C2 = C2; p.B = B; p.H = H; p.W = W; p.Cout = Cout; p.KH = 3; p.KW = 3; p.stride = 1;
     p.pad_h = 1; p.pad_w = 1; p.Ho = H; p.Wo = W; p.out_ctotal = out_ctotal; p.out_coff = out_coff; p.act = act; p.alpha = alpha; p.scatter2x2 = 0;
-    p.gn_ws = gn_ws; p.gn_groups = gn_groups < 0 ? -gn_groups : gn_groups; p.gn_prezeroed = gn_groups < 0;
+    set_stats_request(p, gn_ws, gn_groups);
 }
 
 // the plan of a shape query (no tensors: an aligned dummy address, never dereferenced).  prenorm: 0 = none, 1 = deferred norm + LeakyReLU,

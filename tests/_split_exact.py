@@ -1,7 +1,8 @@
 """Split-exact fp64 references of the f16-split convolution kernels, shared by the GPU route tables (test_gpu_conv_f16s_routes.py,
-test_gpu_wino_stream_routes.py) and checked on the CPU by test_split_exact_reference.py.  A plain helper module: no tests live here.
+test_gpu_wino_stream_routes.py, test_gpu_conv3d_routes.py, test_gpu_conv3d_pw_routes.py) and checked on the CPU by test_split_exact_reference.py.  A plain helper module: no tests live here.
 
-Direct form (conv_f16s.hip, conv_stream.hip): split_reference, derived in test_gpu_conv_f16s_routes.py.
+Direct form (conv_f16s.hip, conv_stream.hip): split_reference, derived in test_gpu_conv_f16s_routes.py; split_reference_3d is the same for
+the 5-D operands of conv3d_f16s.hip and conv3d_pw_f16s.hip.
 Row-Winograd form (conv_wino.hip): wino_split_reference, derived in test_gpu_wino_stream_routes.py."""
 import torch
 import torch.nn.functional as F
@@ -60,6 +61,26 @@ def split_reference(x, w, b, s, conv):
     one = lambda a, m: conv(a[:, c:c + 1], m[:, c:c + 1])   # weights: input channels on dim 1 (conv2d layout and the GEMM layout of convT)
     r["d1"] = sc * one(xh, wh)
     r["d3"] = sc * (one(xh, wh) + one(xh, wl) + one(xl, wh))
+    return r
+
+
+def split_reference_3d(x, w, b, s, conv):
+    """split_reference for 5-D operands: fp64 {y3, y1, true, A, d3 = split-exact contribution of the last input channel} and, when the
+    kernel has three depth taps, z3 = that of the depth tap dz = 0"""
+    xh, xl = split_x(x)
+    wh, wl = split_w(w, s)
+    sc = 2.0 ** -s
+    three = lambda ah, al, mh, ml: conv(ah, mh) + conv(ah, ml) + conv(al, mh)
+    bb = b.double().view(1, -1, 1, 1, 1)
+    hh = conv(xh, wh)
+    r = dict(y3=sc * (conv(xh, wl) + conv(xl, wh) + hh) + bb, y1=sc * hh + bb, true=conv(x.double(), w.double()) + bb,
+             A=sc * conv(xh.abs() + xl.abs(), wh.abs() + wl.abs()) + bb.abs())
+    c = x.shape[1] - 1
+    r["d3"] = sc * three(xh[:, c:c + 1], xl[:, c:c + 1], wh[:, c:c + 1], wl[:, c:c + 1])
+    if w.shape[2] == 3:
+        m = torch.zeros_like(wh)
+        m[:, :, 0] = 1.0
+        r["z3"] = sc * three(xh, xl, wh * m, wl * m)
     return r
 
 

@@ -793,6 +793,87 @@ def test_wino_plan_declines_a_norm_table_past_the_lds():
         h.cf_conv_wino_enable(prev)
 
 
+CONV3D_PROBE_TABLE = os.path.join(ROOT, "tests", "golden", "conv3d_probe_table.json")
+
+
+def _conv3d_probe_rows(lists, pointwise):
+    import itertools
+    keys = ("B", "C1", "D", "HW", "Cout", "sd", "s") if pointwise else ("B", "C1", "C2", "D", "HW", "Cout", "KD", "sd", "s")
+    for v in itertools.product(*(lists[k] for k in keys)):
+        r = dict(zip(keys, v))
+        yield r if not pointwise else dict(r, C2=0, KD=1)
+
+
+def _conv3d_probe_answers(h, lists, pointwise):
+    bits = []
+    for r in _conv3d_probe_rows(lists, pointwise):
+        (H, W) = r["HW"]
+        if pointwise:
+            a = h.cf_conv3d_pw_f16s_ok(r["B"], r["C1"], r["D"], H, W, r["Cout"], r["sd"], r["s"])
+        else:
+            a = h.cf_conv3d_f16s_ok(r["B"], r["C1"], r["C2"], r["D"], H, W, r["Cout"], r["KD"], 3, r["sd"], r["s"])
+        assert a in (0, 1), (r, a)
+        bits.append(a)
+    return bits
+
+
+def _bits_to_hex(bits):
+    return "%0*x" % ((len(bits) + 3) // 4, int("".join(map(str, bits)), 2))
+
+
+def _hex_to_bits(s, n):
+    return [int(c) for c in bin(int(s, 16))[2:].zfill(n)]
+
+
+def test_conv3d_probe_table():
+    """cf_conv3d_f16s_ok and cf_conv3d_pw_f16s_ok answer every row of a grid as the library did before the two files planned each launch
+    once: tests/golden/conv3d_probe_table.json holds the grid's lists and, per probe, the recorded answers as one hex bit string in
+    itertools.product order.  (CINEFLOW_WRITE_PROBE_TABLE=1 with CINEFLOW_LIB naming the library to record rewrites the file instead.)
+    The grid reaches both answers often, every class of decline of the native probe -- one sample of 2 GiB or more; (a) no depth taps on a
+    large map; (b) in-plane stride 2 at depth stride 1 on a large map; (c) few workgroups with a long K loop, or no geometry -- and
+    B = 40 rows cut into sub-batches (40 is no multiple of most part counts), so the plan of a shorter last part is in the table.  The
+    counts are the recorded library's."""
+    import json
+    from cineflow import _lib, ops
+    h = _lib.lib()
+    if os.environ.get("CINEFLOW_WRITE_PROBE_TABLE") == "1":
+        lists = dict(B=[1, 2, 3, 40], C1=[1, 32, 40, 320], C2=[0, 16], D=[1, 2, 5, 20],
+                     HW=[[4, 5], [8, 7], [12, 20], [32, 28], [128, 112], [256, 224], [512, 448]], Cout=[8, 32, 48, 320], KD=[1, 3], sd=[1, 2], s=[1, 2])
+        table = dict(lists=lists, native=_bits_to_hex(_conv3d_probe_answers(h, lists, False)), pointwise=_bits_to_hex(_conv3d_probe_answers(h, lists, True)))
+        with open(CONV3D_PROBE_TABLE, "w") as f:
+            json.dump(table, f, indent=1)
+            f.write("\n")
+    table = json.load(open(CONV3D_PROBE_TABLE))
+    lists = table["lists"]
+    for pointwise, name, n_rows, n_taken in ((False, "native", 28672, 22390), (True, "pointwise", 7168, 7080)):
+        rows = list(_conv3d_probe_rows(lists, pointwise))
+        want = _hex_to_bits(table[name], len(rows))
+        assert len(rows) == n_rows and len(want) == n_rows and sum(want) == n_taken, (name, len(rows), sum(want))
+        got = _conv3d_probe_answers(h, lists, pointwise)
+        wrong = [(r, g, w) for r, g, w in zip(rows, got, want) if g != w]
+        assert not wrong, (name, len(wrong), wrong[:5])
+        if pointwise:
+            continue
+        assert 10 * sum(want) >= n_rows and 10 * (n_rows - sum(want)) >= n_rows
+        classes = {"2gib": 0, "a": 0, "b": 0, "c": 0}
+        cut = cut_taken = 0
+        for r, w in zip(rows, want):
+            (H, W), pd = r["HW"], r["KD"] // 2
+            Do, Ho, Wo = (r["D"] + 2 * pd - r["KD"]) // r["sd"] + 1, (H - 1) // r["s"] + 1, (W - 1) // r["s"] + 1
+            per = 4 * max(max(r["C1"], r["C2"]) * r["D"] * H * W, r["Cout"] * Do * Ho * Wo)      # bytes of the largest tensor's sample
+            if r["B"] == 40 and per < 2 ** 31 and r["B"] > (2 ** 31 - 1) // per:
+                cut, cut_taken = cut + 1, cut_taken + w
+            if not w:
+                large = Do * Ho * Wo >= 65536
+                cls = "2gib" if per >= 2 ** 31 else "a" if r["KD"] == 1 and large else "b" if r["s"] == 2 and r["sd"] == 1 and large else "c"
+                classes[cls] += 1
+        assert classes == {"2gib": 352, "a": 3024, "b": 736, "c": 2170}, classes
+        assert (cut, cut_taken) == (1476, 781), (cut, cut_taken)
+    assert ops.conv3d_f16s_ok(2, 32, 16, 5, 32, 28, 48, (3, 3, 3), (1, 1, 1)) and ops.conv3d_pw_f16s_ok(2, 32, 5, 32, 28, 48, (2, 2, 2))
+    with ops.conv_terms(1):      # only the three-term product is built
+        assert not ops.conv3d_f16s_ok(2, 32, 16, 5, 32, 28, 48, (3, 3, 3), (1, 1, 1)) and not ops.conv3d_pw_f16s_ok(2, 32, 5, 32, 28, 48, (2, 2, 2))
+
+
 class _FakeTensor:
     """what the route decisions read of a tensor: its shape, its element count and an aligned address"""
 

@@ -26,7 +26,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _split_exact import SPLIT_BAR, check_stats, device_input, randn, ratio, split_w, split_x
+from _split_exact import SPLIT_BAR, check_stats, device_input, randn, ratio
+from _split_exact import split_reference_3d as split_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -52,25 +53,6 @@ ROWS = [
 
 def row_id(r):
     return "row%d_k%d_s%d%d%s" % (r.n, r.k[0], r.stride[0], r.stride[1], "_view" if r.view else "")
-
-
-def split_reference(x, w, b, s, conv):
-    """fp64 {y3, y1, true, A, d3 = split-exact contribution of the last input channel, z3 = that of the depth tap dz = 0} for 5-D operands"""
-    xh, xl = split_x(x)
-    wh, wl = split_w(w, s)
-    sc = 2.0 ** -s
-    three = lambda ah, al, mh, ml: conv(ah, mh) + conv(ah, ml) + conv(al, mh)
-    bb = b.double().view(1, -1, 1, 1, 1)
-    hh = conv(xh, wh)
-    r = dict(y3=sc * (conv(xh, wl) + conv(xl, wh) + hh) + bb, y1=sc * hh + bb, true=conv(x.double(), w.double()) + bb,
-             A=sc * conv(xh.abs() + xl.abs(), wh.abs() + wl.abs()) + bb.abs())
-    c = x.shape[1] - 1
-    r["d3"] = sc * three(xh[:, c:c + 1], xl[:, c:c + 1], wh[:, c:c + 1], wl[:, c:c + 1])
-    if w.shape[2] == 3:
-        m = torch.zeros_like(wh)
-        m[:, :, 0] = 1.0
-        r["z3"] = sc * three(xh, xl, wh * m, wl * m)
-    return r
 
 
 @pytest.mark.parametrize("row", ROWS, ids=row_id)
