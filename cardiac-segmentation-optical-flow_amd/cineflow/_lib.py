@@ -155,6 +155,10 @@ SIGNATURES = {
     "cf_select_blocks": [L],
     "cf_select_count": [P, L, P, I, I, P, P, P],
     "cf_select_rank": [P, L, I, F, P, P, I, P, P, P, I, I, I, P],
+    "cf_deflate_chunk_bytes": [],
+    "cf_deflate": [P, L, P, L, P, L, P, P],
+    "cf_crc32": [P, L, P, L, P, P],
+    "cf_huffman_code_lengths": [P, I, I, P, P],
     "cf_profile_enable": [I],
     "cf_profile_reset": [],
     "cf_profile_read": [I, P, P, P],
@@ -187,6 +191,9 @@ def lib():
     h.cf_last_error.argtypes = []
     h.cf_edt_workspace_bytes.restype = ctypes.c_long       # a size, not a status: declared `long` in the header
     h.cf_edt_workspace_bytes.argtypes = [I, I, I]
+    for name in ("cf_deflate_bound", "cf_deflate_workspace_bytes", "cf_crc32_workspace_bytes"):   # sizes too
+        getattr(h, name).restype = ctypes.c_long
+        getattr(h, name).argtypes = [L]
     h.cf_version.restype = ctypes.c_int
     h.cf_version.argtypes = []
     _lib = h

@@ -95,8 +95,18 @@ def _write_labels(seg, props, out_file):
     write_nifti(out_file, seg, first["itk_spacing"], first["itk_origin"], first["itk_direction"])
 
 
-def _write_npz(mean, props, out_file):
-    np.savez_compressed(out_file[:-7] + ".npz", softmax=mean)
+# who deflates the mean softmax's .npz: "zlib" (np.savez_compressed), or "device" (cineflow.deflate).  merge and merge_files keep the
+# reference's argument lists, so the choice is this module attribute; _write_npz itself takes it as a keyword.
+NPZ_COMPRESS = "zlib"
+
+
+def _write_npz(mean, props, out_file, compress="zlib"):
+    if compress == "zlib":
+        np.savez_compressed(out_file[:-7] + ".npz", softmax=mean)
+    else:
+        from . import deflate
+        deflate.check_compress(compress)
+        deflate.savez_compressed(out_file[:-7] + ".npz", softmax=mean)
     with open(out_file[:-7] + ".pkl", "wb") as f:
         pickle.dump(props, f)
 
@@ -113,7 +123,7 @@ def merge_files(files, properties_files, out_file, override, store_npz):
     t2 = time.perf_counter()
     _write_labels(seg, props, out_file)
     if store_npz:
-        _write_npz(mean, props, out_file)
+        _write_npz(mean, props, out_file, NPZ_COMPRESS)
     t3 = time.perf_counter()
     LAST_TIMING.clear()
     LAST_TIMING.update(load_s=t1 - t0, device_s=t2 - t1, write_s=t3 - t2)
@@ -153,7 +163,7 @@ def merge(folders, output_folder, threads, override=True, postprocessing_file=No
             os.makedirs(os.path.dirname(out_file), exist_ok=True)
             writes.append(pool.submit(_write_labels, seg, props, out_file))
             if store_npz:
-                writes.append(pool.submit(_write_npz, mean, props, out_file))
+                writes.append(pool.submit(_write_npz, mean, props, out_file, NPZ_COMPRESS))
         for w in writes:
             w.result()
 

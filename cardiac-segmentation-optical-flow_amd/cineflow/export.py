@@ -45,7 +45,7 @@ def save_segmentation_nifti_from_softmax(segmentation_softmax, out_fname, proper
                                          seg_postprogess_fn=None, seg_postprocess_args=None, resampled_npz_fname=None,
                                          non_postprocessed_fname=None, force_separate_z=None, interpolation_order_z=0, verbose=True,
                                          flow=None, flow_path=None, registered=None, registered_path=None, seg_precomputed=None,
-                                         properties_pkl=False):
+                                         properties_pkl=False, compress="zlib"):
     """segmentation_export.py:29-223: resample softmax / flow / registered labels back to the size before resampling (device
     kernels, cineflow.ops.resample_data_or_seg), rescale the flow to the new pixel grid, argmax, place into the crop bounding
     box, write uint8 NIfTI with the case's geometry; flow [2,Z,Y,X] -> npz `flow` [Y,X,Z,2] float32 + `spacing`.
@@ -97,7 +97,12 @@ def save_segmentation_nifti_from_softmax(segmentation_softmax, out_fname, proper
             print("no resampling necessary")
         seg_old_spacing = segmentation_softmax
     if resampled_npz_fname is not None:
-        np.savez_compressed(resampled_npz_fname, softmax=probabilities_as_stored(seg_old_spacing, region_class_order))
+        if compress == "zlib":
+            np.savez_compressed(resampled_npz_fname, softmax=probabilities_as_stored(seg_old_spacing, region_class_order))
+        else:                                                                    # (the device deflates; the file holds the same array)
+            from . import deflate
+            deflate.check_compress(compress)
+            deflate.savez_compressed(resampled_npz_fname, softmax=probabilities_as_stored(seg_old_spacing, region_class_order))
         if region_class_order is not None:                                       # segmentation_export.py:141-142: an ensemble member says so itself
             properties_dict["regions_class_order"] = region_class_order
         if properties_pkl:

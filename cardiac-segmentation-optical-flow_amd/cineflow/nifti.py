@@ -54,15 +54,10 @@ def _write_all(path, data):
         f.write(_gzip(data, GZIP_LEVEL) if str(path).endswith(".gz") else data)
 
 
-def write_nifti(path, array, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), direction=(1, 0, 0, 0, 1, 0, 0, 0, 1)):
-    """array [Z,Y,X] (or [Y,X]); spacing/origin/direction in ITK (x,y,z / LPS) convention."""
-    a = np.asarray(array)
-    if a.ndim == 2:
-        a = a[None]
-    assert a.ndim == 3, "only 3-D volumes"
-    if a.dtype not in _CODES:
-        a = a.astype(np.float32)
-    nz, ny, nx = a.shape
+def nifti_header(shape, dtype, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), direction=(1, 0, 0, 0, 1, 0, 0, 0, 1)):
+    """The 352 bytes in front of the voxels of a [Z,Y,X] volume of one of the dtypes of _CODES."""
+    nz, ny, nx = shape
+    dtype = np.dtype(dtype)
     D = np.asarray(direction, dtype=np.float64).reshape(3, 3)
     lps2ras = np.diag([-1.0, -1.0, 1.0])
     A = lps2ras @ D @ np.diag(np.asarray(spacing, dtype=np.float64))
@@ -70,8 +65,8 @@ def write_nifti(path, array, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), di
     hdr = bytearray(348)
     struct.pack_into("<i", hdr, 0, 348)
     struct.pack_into("<8h", hdr, 40, 3, nx, ny, nz, 1, 1, 1, 1)
-    struct.pack_into("<h", hdr, 70, _CODES[a.dtype])
-    struct.pack_into("<h", hdr, 72, a.dtype.itemsize * 8)
+    struct.pack_into("<h", hdr, 70, _CODES[dtype])
+    struct.pack_into("<h", hdr, 72, dtype.itemsize * 8)
     struct.pack_into("<8f", hdr, 76, 1.0, float(spacing[0]), float(spacing[1]), float(spacing[2]), 1.0, 1.0, 1.0, 1.0)
     struct.pack_into("<f", hdr, 108, 352.0)          # vox_offset
     struct.pack_into("<f", hdr, 112, 1.0)            # scl_slope
@@ -81,7 +76,54 @@ def write_nifti(path, array, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), di
     for r in range(3):
         struct.pack_into("<4f", hdr, 280 + 16 * r, float(A[r, 0]), float(A[r, 1]), float(A[r, 2]), float(t[r]))
     hdr[344:348] = b"n+1\0"
-    _write_all(path, bytes(hdr) + b"\0\0\0\0" + np.ascontiguousarray(a).tobytes())
+    return bytes(hdr) + b"\0\0\0\0"
+
+
+def _device_volume(array):
+    """array (a device tensor, or numpy, whose bytes are uploaded as they are) -> (3-D payload of a NIfTI dtype, that numpy dtype)"""
+    import torch
+    from .deflate import numpy_dtype
+    if not torch.is_tensor(array):
+        a = np.asarray(array)
+        a = a[None] if a.ndim == 2 else a
+        assert a.ndim == 3, "only 3-D volumes"
+        a = np.ascontiguousarray(a if a.dtype in _CODES else a.astype(np.float32))
+        return a, a.dtype
+    array = array[None] if array.dim() == 2 else array
+    assert array.dim() == 3, "only 3-D volumes"
+    if str(array.dtype) not in ("torch.uint8", "torch.int8", "torch.int16", "torch.int32", "torch.float32", "torch.float64"):
+        array = array.float()
+    return array.contiguous(), numpy_dtype(array)
+
+
+def nifti_device_bytes(path, array, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), direction=(1, 0, 0, 0, 1, 0, 0, 0, 1)):
+    """The file bytes of write_nifti(..., compress="device"): the voxels are compressed and checksummed on the device (this is the device
+    visit), the header joins them on the host.  A path without .gz gives the plain file."""
+    import torch
+    from . import deflate
+    t, dtype = _device_volume(array)
+    hdr = nifti_header(tuple(t.shape), dtype, spacing, origin, direction)
+    if not str(path).endswith(".gz"):
+        return hdr + (t.cpu().numpy() if torch.is_tensor(t) else t).tobytes()
+    return deflate.gzip_member(hdr, t)
+
+
+def write_nifti(path, array, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0), direction=(1, 0, 0, 0, 1, 0, 0, 0, 1), compress="zlib"):
+    """array [Z,Y,X] (or [Y,X]); spacing/origin/direction in ITK (x,y,z / LPS) convention.  compress="device": the .gz stream is made on
+    the device (cineflow.deflate) and `array` may be a device tensor; the voxels a reader gets back are the same."""
+    if compress != "zlib":
+        from .deflate import check_compress
+        check_compress(compress)
+        with open(path, "wb") as f:
+            f.write(nifti_device_bytes(path, array, spacing, origin, direction))
+        return
+    a = np.asarray(array)
+    if a.ndim == 2:
+        a = a[None]
+    assert a.ndim == 3, "only 3-D volumes"
+    if a.dtype not in _CODES:
+        a = a.astype(np.float32)
+    _write_all(path, nifti_header(a.shape, a.dtype, spacing, origin, direction) + np.ascontiguousarray(a).tobytes())
 
 
 def read_nifti(path):

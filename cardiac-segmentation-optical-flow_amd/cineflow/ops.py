@@ -1544,3 +1544,54 @@ def select_coords(seg, value, ranks, index=None):
 def select_values(src, key, ranks, index=None):
     """src[key > 0][ranks] of two float32 device arrays of the same size -> float32 device tensor [K]."""
     return _select(key, None, ranks, src, index)
+
+
+# ---------------------------------------------------------------- DEFLATE and CRC-32 of a device buffer (csrc/deflate.hip)
+def deflate_chunk_bytes():
+    """Bytes of input that cf_deflate compresses on their own (one workgroup, one run of non-final blocks)."""
+    return int(lib().cf_deflate_chunk_bytes())
+
+
+def deflate_bound(n):
+    """Bytes that the stream of n input bytes never exceeds: n + 5 ceil(n / chunk)."""
+    size = int(lib().cf_deflate_bound(int(n)))
+    if size < 0:
+        check(size, "cf_deflate_bound")
+    return size
+
+
+def _as_bytes(t, name):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise ValueError("%s must be a device tensor" % name)
+    return t.contiguous().reshape(-1).view(torch.uint8)
+
+
+def deflate(t, out=None, ws=None, out_bytes=None):
+    """RFC 1951 blocks of a device tensor's bytes (C order), without the final block: -> (out uint8 [deflate_bound(n)], out_bytes int64 [1]),
+    both on the device; the stream is out[:out_bytes].  Nothing is read back and nothing synchronises.  out / ws / out_bytes: the
+    caller's buffers (tests pass guarded ones); by default they are allocated here."""
+    b = _as_bytes(t, "deflate: t")
+    n = b.numel()
+    h = lib()
+    out = torch.empty(max(deflate_bound(n), 1), dtype=torch.uint8, device=b.device) if out is None else out
+    out_bytes = torch.empty(1, dtype=torch.int64, device=b.device) if out_bytes is None else out_bytes
+    ws = torch.empty(int(h.cf_deflate_workspace_bytes(n)), dtype=torch.uint8, device=b.device) if ws is None else ws
+    if n == 0:              # (an empty tensor has no address to hand over)
+        out_bytes.zero_()
+        return out, out_bytes
+    check(h.cf_deflate(b.data_ptr(), n, out.data_ptr(), out.numel(), ws.data_ptr(), ws.numel(), out_bytes.data_ptr(), _stream()), "cf_deflate")
+    return out, out_bytes
+
+
+def crc32(t, ws=None, crc=None):
+    """zlib.crc32 of a device tensor's bytes -> int64 device tensor [1] (the low 32 bits; nothing is read back)."""
+    b = _as_bytes(t, "crc32: t")
+    n = b.numel()
+    h = lib()
+    crc = torch.zeros(1, dtype=torch.int64, device=b.device) if crc is None else crc
+    if n == 0:
+        crc.zero_()
+        return crc
+    ws = torch.empty(int(h.cf_crc32_workspace_bytes(n)), dtype=torch.uint8, device=b.device) if ws is None else ws
+    check(h.cf_crc32(b.data_ptr(), n, ws.data_ptr(), ws.numel(), crc.data_ptr(), _stream()), "cf_crc32")
+    return crc

@@ -37,14 +37,14 @@ def create_lists_from_splitted_dataset(base_folder_splitted):
     return lists, {int(i): d["modality"][str(i)] for i in d["modality"].keys()}, info_list
 
 
-def crop(raw_task_folder, cropped_out_dir, override=False, num_threads=EP.default_num_threads):
+def crop(raw_task_folder, cropped_out_dir, override=False, num_threads=EP.default_num_threads, compress="zlib"):
     """experiment_planning/utils.py:207-222 -> the ImageCropper that ran (its `seconds` say where the time went)"""
     from .preprocessing import ImageCropper
     if override and os.path.isdir(cropped_out_dir):
         shutil.rmtree(cropped_out_dir)
     os.makedirs(cropped_out_dir, exist_ok=True)
     lists, _, info_list = create_lists_from_splitted_dataset(raw_task_folder)
-    imgcrop = ImageCropper(num_threads, cropped_out_dir)
+    imgcrop = ImageCropper(num_threads, cropped_out_dir, compress)
     imgcrop.run_cropping(lists, overwrite_existing=override, info_list=info_list)
     shutil.copy(join(raw_task_folder, "dataset.json"), cropped_out_dir)
     return imgcrop
@@ -60,13 +60,16 @@ def convert_id_to_task_name(task_id, folders):
 
 
 def plan_and_preprocess(raw, cropped, preprocessed, planner3d="ExperimentPlanner3D_v21", planner2d="ExperimentPlanner2D_v21", planner_config=None,
-                        no_pp=False, tf=8, report=None):
-    """One task.  report: a dict that receives the seconds per step (tools/plan_and_preprocess_bench.py)."""
+                        no_pp=False, tf=8, report=None, compress="zlib"):
+    """One task.  report: a dict that receives the seconds per step (tools/plan_and_preprocess_bench.py).  compress="device": every .npz
+    (cropped cases, stage folders) is deflated and checksummed on the device (cineflow.deflate); the arrays inside are the same."""
+    from .deflate import check_compress
+    check_compress(compress)
     tf = max(1, min(16, int(tf)))
     planners = [EP.find_planner(planner3d), EP.find_planner(planner2d)]           # an unknown name raises before any work
     report = {} if report is None else report
     t0 = time.perf_counter()
-    report["crop"] = dict(crop(raw, cropped, False, tf).seconds)
+    report["crop"] = dict(crop(raw, cropped, False, tf, compress).seconds)
     report["crop"]["total"] = time.perf_counter() - t0
 
     t0 = time.perf_counter()
@@ -88,6 +91,7 @@ def plan_and_preprocess(raw, cropped, preprocessed, planner3d="ExperimentPlanner
         if not no_pp:
             t0 = time.perf_counter()
             pre = planner._preprocessor()
+            pre.compress = compress
             planner.run_preprocessing(tf, preprocessor=pre)
             report[planner.data_identifier] = dict(pre.seconds, total=time.perf_counter() - t0, stages=len(planner.plans_per_stage))
     return report
@@ -105,6 +109,8 @@ def main(argv=None):
     ap.add_argument("--planner_config", default=None, help="the model's YAML for CustomExperimentPlanner")
     ap.add_argument("-no_pp", action="store_true", help="plan only: write the plans files and no stage folder")
     ap.add_argument("-tf", type=int, default=8, help="reader / writer threads (at most 16)")
+    ap.add_argument("--compress", choices=("zlib", "device"), default="zlib", help="who deflates the .npz files: zlib on the writer threads "
+                    "(default) or the device, which then hands back compressed bytes only; the arrays inside are identical")
     a = ap.parse_args(argv)
     if a.task_ids:
         base, pre = os.environ.get("nnUNet_raw_data_base"), os.environ.get("nnUNet_preprocessed")
@@ -120,7 +126,7 @@ def main(argv=None):
             ap.error("give --raw, --cropped and --preprocessed, or -t with the reference's environment variables")
         jobs = [(a.raw, a.cropped, a.preprocessed)]
     for raw, cropped, preprocessed in jobs:
-        report = plan_and_preprocess(raw, cropped, preprocessed, a.planner3d, a.planner2d, a.planner_config, a.no_pp, a.tf)
+        report = plan_and_preprocess(raw, cropped, preprocessed, a.planner3d, a.planner2d, a.planner_config, a.no_pp, a.tf, compress=a.compress)
         print("%s: %s" % (preprocessed, {k: round(v["total"], 3) for k, v in report.items()}))
     return 0
 

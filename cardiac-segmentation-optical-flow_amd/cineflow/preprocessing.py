@@ -135,8 +135,16 @@ def get_case_identifier_from_npz(case):
     return os.path.basename(case)[:-4]
 
 
-def _save_case(folder, case_identifier, all_data, properties):
-    np.savez_compressed(os.path.join(folder, "%s.npz" % case_identifier), data=all_data)
+def _save_case(folder, case_identifier, all_data, properties, compress="zlib"):
+    """compress="device": all_data is a deflate.Member whose bytes the device loop has already compressed (the writer thread only puts the
+    zip container around them), or an array / device tensor that is compressed now."""
+    if compress == "zlib":
+        np.savez_compressed(os.path.join(folder, "%s.npz" % case_identifier), data=all_data)
+    else:
+        from . import deflate
+        deflate.check_compress(compress)
+        member = all_data if isinstance(all_data, deflate.Member) else deflate.npy_member(all_data)
+        deflate.write_npz(os.path.join(folder, "%s.npz" % case_identifier), {"data": member})
     with open(os.path.join(folder, "%s.pkl" % case_identifier), "wb") as f:
         pickle.dump(properties, f)
 
@@ -145,8 +153,10 @@ class ImageCropper(object):
     """cropping.py:145-335: the test-time entry points (static) and the training-side driver of the fork, which crops the cases of a
     patient together.  Files are read and compressed by at most 16 threads around the device work; no process pool."""
 
-    def __init__(self, num_threads, output_folder=None):
+    def __init__(self, num_threads, output_folder=None, compress="zlib"):
+        from .deflate import check_compress
         self.output_folder = output_folder
+        self.compress = check_compress(compress)          # "device": the cropped cases are deflated on the device, only the compressed bytes come back
         self.num_threads = max(1, min(16, int(num_threads)))
         self.seconds = {"read": 0.0, "device": 0.0, "write": 0.0}      # where run_cropping spent its time (write: summed over the threads)
         if self.output_folder is not None:
@@ -185,7 +195,11 @@ class ImageCropper(object):
             props["crop_bbox"] = union
             npz = os.path.join(self.output_folder, "%s.npz" % case_identifier[i])
             if overwrite_existing or not os.path.isfile(npz) or not os.path.isfile(npz[:-4] + ".pkl"):
-                args = (self.output_folder, case_identifier[i], full.cpu().numpy(), props)
+                if self.compress == "zlib":
+                    args = (self.output_folder, case_identifier[i], full.cpu().numpy(), props)
+                else:
+                    from .deflate import npy_member
+                    args = (self.output_folder, case_identifier[i], npy_member(full), props, self.compress)
                 if pool is not None:
                     writes.append(pool.submit(self._timed_save, *args))
                 else:
@@ -447,6 +461,7 @@ class GenericPreprocessor(object):
     """preprocessing.py:202-331 (test-time methods)."""
 
     resample_order_seg_test = 1
+    compress = "zlib"          # "device": run() deflates the stage folders' .npz on the device (an attribute, so that planners need no new argument)
 
     def __init__(self, normalization_scheme_per_modality, use_nonzero_mask, transpose_forward, intensityproperties=None):
         self.transpose_forward = transpose_forward
@@ -561,9 +576,10 @@ class GenericPreprocessor(object):
                 class_locs[c] = ops.select_coords(seg, c, rndst.choice(n, target, replace=False), index).cpu().numpy()
         return class_locs
 
-    def _run_case(self, all_data, properties, target_spacings, force_separate_z, all_classes, keep_spacing):
+    def _run_case(self, all_data, properties, target_spacings, force_separate_z, all_classes, keep_spacing, compress="zlib"):
         """preprocessing.py:387-427 for every stage of one labelled case: all_data [C + 1, X, Y, Z] (numpy, the cropped .npz) goes to the
-        device once -> [(all_data float32 numpy, properties)] per stage"""
+        device once -> [(all_data float32 numpy, properties)] per stage; compress="device": the stage's array as a deflate.Member, compressed
+        and checksummed before it leaves the device"""
         tf = (0, *[i + 1 for i in self.transpose_forward])
         t = _to_dev(all_data).permute(tf).contiguous()
         out = []
@@ -574,11 +590,15 @@ class GenericPreprocessor(object):
             d, s, props = self.resample_and_normalize(t[:-1].clone(), target_spacing, props, t[-1:].clone(), force_separate_z)   # (normalised in place)
             staged = torch.cat([d, s.float()], 0)
             props["class_locations"] = self.class_locations(staged[-1], all_classes)
-            out.append((staged.cpu().numpy(), props))
+            if compress == "zlib":
+                out.append((staged.cpu().numpy(), props))
+            else:
+                from .deflate import npy_member
+                out.append((npy_member(staged), props))
         return out
 
     def run(self, target_spacings, input_folder_with_cropped_npz, output_folder, data_identifier, num_threads=8, force_separate_z=None,
-            keep_spacing=False):
+            keep_spacing=False, compress=None):
         """preprocessing.py:429-467 / :704-730, labelled cases: <output_folder>/<data_identifier>_stage<k>/<case>.npz + .pkl for every
         cropped case and stage.  Case-major: a case is read once (ahead, by the thread pool), uploaded once and leaves the device once
         per stage; the compressed writes run on the same pool of at most 16 threads."""
@@ -596,9 +616,12 @@ class GenericPreprocessor(object):
         self.seconds = {"read": 0.0, "device": 0.0, "write": 0.0}
         threads = max(1, min(16, int(num_threads[-1] if isinstance(num_threads, (list, tuple, np.ndarray)) else num_threads)))
 
+        from .deflate import check_compress
+        compress = check_compress(compress or self.compress)
+
         def save(folder, case, arr, props):
             t0 = time.perf_counter()
-            _save_case(folder, case, arr, props)
+            _save_case(folder, case, arr, props, compress)
             return time.perf_counter() - t0
 
         writes = []
@@ -611,7 +634,7 @@ class GenericPreprocessor(object):
                 if "_u" in case:
                     raise NotImplementedError("%s: unlabeled cases (`_u`) are not built" % case)
                 for folder, (arr, props) in zip(stage_folders, self._run_case(loaded[0], loaded[1], target_spacings, force_separate_z, all_classes,
-                                                                             keep_spacing)):
+                                                                             keep_spacing, compress)):
                     writes.append(pool.submit(save, folder, case, arr, props))
                 t0 = time.perf_counter()
                 self.seconds["device"] += t0 - t1

@@ -216,7 +216,7 @@ def _with_prev_stage(trainer, data, prev, case):
     return np.concatenate([np.asarray(data, dtype=np.float32), onehot.cpu().numpy()], axis=0)
 
 
-def export_case(softmax, properties, transpose_backward, force_separate_z, order, order_z, regions_class_order, want_probs, gt):
+def export_case(softmax, properties, transpose_backward, force_separate_z, order, order_z, regions_class_order, want_probs, gt, on_device=False):
     """The one-visit export: softmax, a device tensor [K, *stage shape] in the network's axis order -> (labels uint8 numpy at the size before
     cropping, stored fp16 probabilities numpy [K, *size_after_cropping] or None, hist int64 numpy [257] or None).  gt: the case's ground
     truth (numpy, the size before cropping) or None."""
@@ -235,12 +235,38 @@ def export_case(softmax, properties, transpose_backward, force_separate_z, order
         gt_t = label_volume_u8(gt, case_name(properties))
     seg, probs, hist = ops.resample_argmax(softmax, crop, lin, full_shape=full, bbox_lo=lo, regions_class_order=regions_class_order,
                                            want_probs=want_probs, gt=gt_t)
+    if on_device:               # (compress="device": labels and probabilities stay where they are compressed)
+        return seg, probs, None if hist is None else hist.cpu().numpy()
     return seg.cpu().numpy(), None if probs is None else probs.cpu().numpy(), None if hist is None else hist.cpu().numpy()
 
 
-def _write_case(out_file, seg, probs, properties, regions_class_order):
-    """the files save_segmentation_nifti_from_softmax(..., resampled_npz_fname=<case>.npz, properties_pkl=True) writes"""
+def _pack_case(out_file, seg, probs, properties):
+    """compress="device", in the device loop: device labels and probabilities -> (the .nii.gz file's bytes, the softmax's deflate.Member or
+    None); the raw arrays are not read back"""
+    from . import deflate
+    from .nifti import nifti_device_bytes
+    return (nifti_device_bytes(out_file, seg, properties["itk_spacing"], properties["itk_origin"], properties["itk_direction"]),
+            None if probs is None else deflate.npy_member(probs))
+
+
+def _write_case(out_file, seg, probs, properties, regions_class_order, compress="zlib"):
+    """the files save_segmentation_nifti_from_softmax(..., resampled_npz_fname=<case>.npz, properties_pkl=True) writes.  compress="device":
+    seg and probs are what _pack_case made of them (finished bytes), or arrays that are packed now."""
     from .nifti import write_nifti
+    if compress != "zlib":
+        from . import deflate
+        deflate.check_compress(compress)
+        if not isinstance(seg, bytes):
+            seg, probs = _pack_case(out_file, seg, probs, properties)
+        if probs is not None:
+            deflate.write_npz(out_file[:-7] + ".npz", {"softmax": probs})
+            if regions_class_order is not None:
+                properties["regions_class_order"] = regions_class_order
+            with open(out_file[:-7] + ".pkl", "wb") as f:
+                pickle.dump(properties, f)
+        with open(out_file, "wb") as f:
+            f.write(seg)
+        return
     if probs is not None:
         np.savez_compressed(out_file[:-7] + ".npz", softmax=probs)
         if regions_class_order is not None:
@@ -250,9 +276,11 @@ def _write_case(out_file, seg, probs, properties, regions_class_order):
     write_nifti(out_file, seg, properties["itk_spacing"], properties["itk_origin"], properties["itk_direction"])
 
 
-def resample_and_save(predicted, target_shape, output_file, force_separate_z=False, interpolation_order=1, interpolation_order_z=0):
+def resample_and_save(predicted, target_shape, output_file, force_separate_z=False, interpolation_order=1, interpolation_order_z=0,
+                      compress="zlib"):
     """predict_next_stage.py:31-43: predicted, the device softmax [K,X,Y,Z] of the lower stage, at the next stage's shape as uint8 labels
-    in `output_file` (`data=`); resampling and arg-max are one ops.resample_argmax launch."""
+    in `output_file` (`data=`); resampling and arg-max are one ops.resample_argmax launch.  compress="device": the labels are deflated
+    where they are and returned as a device tensor."""
     import torch
     from . import ops
     _check_orders(interpolation_order, interpolation_order_z)
@@ -260,7 +288,13 @@ def resample_and_save(predicted, target_shape, output_file, force_separate_z=Fal
         raise ValueError("predict_next_stage: force_separate_z needs an anisotropic axis, which the stage folders do not name")
     if not torch.is_tensor(predicted):
         predicted = torch.from_numpy(np.ascontiguousarray(predicted, dtype=np.float32)).to(torch.device("cuda", torch.cuda.current_device()))
-    seg = ops.resample_argmax(predicted.contiguous(), target_shape, (int(interpolation_order),) * 3)[0].cpu().numpy()
+    seg = ops.resample_argmax(predicted.contiguous(), target_shape, (int(interpolation_order),) * 3)[0]
+    if compress != "zlib":
+        from . import deflate
+        deflate.check_compress(compress)
+        deflate.savez_compressed(output_file, data=seg)
+        return seg
+    seg = seg.cpu().numpy()
     np.savez_compressed(output_file, data=seg)
     return seg
 
@@ -284,13 +318,16 @@ def _copy_shared(dataset, gt_folder, output_folder_base, plans_pkl):
 def validate(trainer, params, fold, data_folder, gt_folder, output_folder_base, do_mirroring=True, use_sliding_window=True, step_size=0.5,
              save_softmax=True, use_gaussian=True, overwrite=True, validation_folder_name="validation_raw", debug=False,
              segmentation_export_kwargs=None, run_postprocessing_on_folds=True, splits_file=None, plans_pkl=None, task=None,
-             next_stage_folder=None, prev_stage_folder=None, num_threads=default_num_threads):
+             next_stage_folder=None, prev_stage_folder=None, num_threads=default_num_threads, compress="zlib"):
     """nnUNetTrainer.validate for one fold: trainer / params as load_model_and_checkpoint_files(MODEL_FOLDER, [fold]) gives them (params: that
     fold's checkpoint dict).  Writes output_folder_base/fold_<fold>/<validation_folder_name>/ and what goes with it (module docstring) and
     returns that folder.  next_stage_folder: also predict_next_stage into output_folder_base/pred_next_stage; prev_stage_folder: where a
-    cascade model finds <case>_segFromPrevStage.npz."""
+    cascade model finds <case>_segFromPrevStage.npz.  compress="device": validation_raw's .nii.gz / .npz and pred_next_stage's .npz are
+    deflated and checksummed on the device in the case loop (cineflow.deflate); the writer threads get finished bytes."""
     import torch
+    from .deflate import check_compress
     from .evaluation import Counted, HIST_K, aggregate_scores, evaluate_regions
+    check_compress(compress)
     from .postprocessing import determine_postprocessing
     if trainer.flow_net is not None:
         raise ValueError("the model folder holds 'flow_net': cineflow.validate validates segmentation-only model folders")
@@ -345,13 +382,17 @@ def validate(trainer, params, fold, data_folder, gt_folder, output_folder_base, 
             softmax = trainer.predict_preprocessed_data_return_seg_and_softmax(
                 data, do_mirroring=do_mirroring, mirror_axes=mirror_axes, use_sliding_window=use_sliding_window, step_size=step_size,
                 use_gaussian=use_gaussian, verbose=False, mixed_precision=trainer.mixed_precision, return_device=True)[1]
-            seg, probs, hist = export_case(softmax, properties, tb, force_separate_z, order, order_z, regions_class_order, save_softmax, gt)
+            seg, probs, hist = export_case(softmax, properties, tb, force_separate_z, order, order_z, regions_class_order, save_softmax, gt,
+                                           on_device=compress != "zlib")
             out_file = join(output_folder, name + ".nii.gz")
-            written.append(writers.submit(_write_case, out_file, seg, probs, properties, regions_class_order))
+            n_voxels = int(seg.numel() if torch.is_tensor(seg) else seg.size)
+            if compress != "zlib":
+                seg, probs = _pack_case(out_file, seg, probs, properties)
+            written.append(writers.submit(_write_case, out_file, seg, probs, properties, regions_class_order, compress))
             if in_histogram and not hist[-1]:                           # every voxel of both volumes is below 16
-                counted[name] = Counted(out_file, hist[:-1].reshape(HIST_K, HIST_K), int(seg.size))
+                counted[name] = Counted(out_file, hist[:-1].reshape(HIST_K, HIST_K), n_voxels)
             if next_out is not None:
-                resample_and_save(softmax, next_shape, join(next_out, case + NEXT_STAGE_SUFFIX), force_separate_z, order, order_z)
+                resample_and_save(softmax, next_shape, join(next_out, case + NEXT_STAGE_SUFFIX), force_separate_z, order, order_z, compress)
             del softmax
         for w in written:
             w.result()
@@ -376,7 +417,7 @@ def validate(trainer, params, fold, data_folder, gt_folder, output_folder_base, 
 
 
 def predict_next_stage(trainer, params, fold, data_folder, stage_to_be_predicted_folder, output_folder_base, splits_file=None,
-                       do_mirroring=True, step_size=0.5, num_threads=default_num_threads):
+                       do_mirroring=True, step_size=0.5, num_threads=default_num_threads, compress="zlib"):
     """predict_next_stage.py:46-87 on its own: the validation cases of `fold` predicted by the lower stage and written at the next stage's
     shape to output_folder_base/pred_next_stage/<case>_segFromPrevStage.npz.  (validate(..., next_stage_folder=...) writes the same files
     from the softmax it already holds.)  Returns the folder."""
@@ -395,7 +436,7 @@ def predict_next_stage(trainer, params, fold, data_folder, stage_to_be_predicted
         softmax = trainer.predict_preprocessed_data_return_seg_and_softmax(
             data, do_mirroring=do_mirroring, mirror_axes=trainer.data_aug_params["mirror_axes"] if do_mirroring else (), step_size=step_size,
             verbose=False, mixed_precision=trainer.mixed_precision, return_device=True)[1]
-        resample_and_save(softmax, next_shape, join(out, job[0] + NEXT_STAGE_SUFFIX), force_separate_z, order, order_z)
+        resample_and_save(softmax, next_shape, join(out, job[0] + NEXT_STAGE_SUFFIX), force_separate_z, order, order_z, compress)
     return out
 
 
@@ -420,6 +461,8 @@ def build_parser():
     parser.add_argument("--prev_stage", default=None, help="folder with <case>_segFromPrevStage.npz (a cascade model)")
     parser.add_argument("-t", "--task", default=None, help="task name of summary.json (default: the preprocessed task folder's name)")
     parser.add_argument("-chk", default="model_final_checkpoint")
+    parser.add_argument("--compress", choices=("zlib", "device"), default="zlib", help="who deflates the .nii.gz / .npz files: zlib on the writer "
+                        "threads (default) or the device, which hands back compressed bytes only; the contents are identical")
     return parser
 
 
@@ -444,7 +487,7 @@ def main(argv=None):
         out.append(validate(trainer, params[0], fold, a.data, a.gt_folder, a.output_folder, do_mirroring=not a.disable_tta, step_size=a.step_size,
                             save_softmax=not a.no_softmax, overwrite=bool(a.overwrite), validation_folder_name=a.val, debug=a.debug,
                             run_postprocessing_on_folds=not a.disable_postprocessing, splits_file=a.splits, plans_pkl=a.plans, task=a.task,
-                            next_stage_folder=a.next_stage, prev_stage_folder=a.prev_stage))
+                            next_stage_folder=a.next_stage, prev_stage_folder=a.prev_stage, compress=a.compress))
     return out
 
 

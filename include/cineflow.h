@@ -751,6 +751,31 @@ int cf_select_count(const float* key, long n, const float* values, int n_values,
 int cf_select_rank(const float* key, long n, int mode, float value, const int* prefix, const long long* ranks, int K, const float* src,
                    float* vals, long long* coords, int D0, int D1, int D2, void* stream);
 
+/* ---------------------------------------------------------------- DEFLATE and CRC-32 of a device buffer (csrc/deflate.hip)
+ * cf_deflate writes the RFC 1951 blocks of src[0..n) (device bytes of any dtype) to out: the input is cut into chunks of
+ * cf_deflate_chunk_bytes() = 32768 bytes, every chunk is compressed on its own (matches of 4..258 bytes at distances inside the chunk,
+ * dynamic Huffman codes; a stored block when that is not smaller) and ends on a byte boundary as NON-final blocks, the chunks' streams
+ * stand back to back.  There is no final block: the caller appends the two bytes 03 00 (an empty final fixed-Huffman block) and has a
+ * complete raw-deflate stream that zlib, zipfile and gzip readers inflate.  *out_bytes_dev (device int64) = the stream's length, at most
+ * cf_deflate_bound(n) = n + 5 ceil(n / chunk) -- out_cap must be at least that, and nothing past it is written.  n == 0 writes nothing
+ * and sets the length to 0.  ws: cf_deflate_workspace_bytes(n) bytes, 16-byte aligned, caller-owned (per-chunk output slots, 128 KiB of
+ * match state for each of at most 512 workgroups, the slot sizes and offsets).  Three launches on the caller's stream, no allocation,
+ * no synchronisation.  The same input gives the same bytes on every run, whatever ws and out held before.
+ * cf_crc32: *crc_dev (device uint32) = zlib's crc32 of src[0..n) (0 for n == 0).  ws: cf_crc32_workspace_bytes(n) bytes (4 per 256 KiB of
+ * input plus 256), 4-byte aligned.  Two launches.
+ * The three size queries are host arithmetic and return CF_ERR_ARG for a negative n.  Null pointers, a negative n, a short out_cap or
+ * workspace and a misaligned workspace are refused on the host before any launch. */
+int cf_deflate_chunk_bytes(void);
+long cf_deflate_bound(long n);
+long cf_deflate_workspace_bytes(long n);
+int cf_deflate(const void* src, long n, void* out, long out_cap, void* ws, long ws_bytes, long long* out_bytes_dev, void* stream);
+/* cf_huffman_code_lengths -- a TEST HOOK, not part of what callers need: the code lengths cf_deflate gives a histogram -- freq device uint32 [n], 2 <= n <= 286, lens device uint8 [n]:
+ * Huffman lengths when none exceeds max_bits (1..15, 2^max_bits >= n), else folded to max_bits and repaired to a complete code with the
+ * heaviest symbols on the shortest codes; weight 0 gives length 0, and fewer than two used symbols are made two.  One small launch. */
+int cf_huffman_code_lengths(const unsigned* freq, int n, int max_bits, unsigned char* lens, void* stream);
+long cf_crc32_workspace_bytes(long n);
+int cf_crc32(const void* src, long n, void* ws, long ws_bytes, unsigned* crc_dev, void* stream);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py only; no reference analogue)
  * cf_profile_enable(n): pre-create n event pairs and time every conv / CorrVolume launch with a (start, stop) pair that
  * brackets exactly that kernel on its own stream (hipExtLaunchKernelGGL); 0 disables.  Kernel ids:

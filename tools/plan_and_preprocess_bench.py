@@ -15,7 +15,10 @@ frame, in-plane spacings between 1.25 and 1.6 mm (every case is resampled) and 1
 (a) is timed by the host clock around calls that end with every file written; (b) by the host clock around the pool's map.  The label
 channels of both trees are compared case by case.  One JSON line.
 
-    python tools/plan_and_preprocess_bench.py [--patients 24] [--small]"""
+--compress device runs (a) with the .npz files deflated on the device (cineflow.deflate); --skip_cpu leaves (b) and the comparison out (an
+A/B of (a) between two trees or two --compress values needs neither).  The bytes of the written folders are reported either way.
+
+    python tools/plan_and_preprocess_bench.py [--patients 24] [--small] [--compress {zlib,device}] [--skip_cpu]"""
 import argparse
 import json
 import os
@@ -96,7 +99,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--patients", type=int, default=24)
     ap.add_argument("--small", action="store_true", help="a rehearsal of the script at 6 x 48 x 40, not a measurement")
+    ap.add_argument("--compress", choices=("zlib", "device"), default="zlib")
+    ap.add_argument("--skip_cpu", action="store_true", help="time the device pipeline only")
     a = ap.parse_args()
+    kw = {} if a.compress == "zlib" else {"compress": a.compress}          # (the default call is the one older trees take too)
     import multiprocessing
     import numpy as np
     import torch
@@ -119,16 +125,27 @@ def main():
         dj = json.load(open(os.path.join(raw, "dataset.json")))
         dj["training"] = dj["training"][:4]
         json.dump(dj, open(os.path.join(warm, "raw", "dataset.json"), "w"))
-        PP.plan_and_preprocess(os.path.join(warm, "raw"), os.path.join(warm, "cropped"), os.path.join(warm, "pre"), tf=16)
+        PP.plan_and_preprocess(os.path.join(warm, "raw"), os.path.join(warm, "cropped"), os.path.join(warm, "pre"), tf=16, **kw)
         torch.cuda.synchronize()
 
         t0 = time.perf_counter()
-        report = PP.plan_and_preprocess(raw, cropped, pre, tf=16)
+        report = PP.plan_and_preprocess(raw, cropped, pre, tf=16, **kw)
         torch.cuda.synchronize()
         device_total = time.perf_counter() - t0
         stages = {k: v for k, v in report.items() if k not in ("crop", "fingerprint")}
         device_stage_seconds = sum(v["total"] for v in stages.values())
 
+        def npz_bytes(folder):
+            return sum(os.path.getsize(os.path.join(folder, f)) for f in os.listdir(folder) if f.endswith(".npz"))
+
+        written = {"cropped": npz_bytes(cropped)}
+        written.update({d: npz_bytes(os.path.join(pre, d)) for d in sorted(os.listdir(pre)) if "_stage" in d})
+        if a.skip_cpu:
+            print(json.dumps({
+                "task": {"patients": a.patients, "cases": ncases, "array": shape, "modalities": 1}, "compress": a.compress,
+                "device_total_s": round(device_total, 3), "device_stage_s": round(device_stage_seconds, 3),
+                "split_s": {k: {kk: round(vv, 3) for kk, vv in v.items()} for k, v in report.items()}, "npz_bytes": written}), flush=True)
+            return
         jobs, folders = [], {}
         for name, two_d in (("nnUNetPlansv2.1_plans_3D.pkl", False), ("nnUNetPlansv2.1_plans_2D.pkl", True)):
             plans = load_plain_pickle(os.path.join(pre, name))
@@ -156,6 +173,7 @@ def main():
         stage_files = len(jobs)
         print(json.dumps({
             "task": {"patients": a.patients, "cases": ncases, "array": shape, "modalities": 1, "stage_files": stage_files},
+            "compress": a.compress, "npz_bytes": written,
             "device_total_s": round(device_total, 3), "device_cases_per_s_whole_pipeline": round(ncases / device_total, 2),
             "device_stage_s": round(device_stage_seconds, 3), "device_stage_files_per_s": round(stage_files / device_stage_seconds, 2),
             "cpu16_stage_s": round(cpu_stage_seconds, 3), "cpu16_stage_files_per_s": round(stage_files / cpu_stage_seconds, 2),

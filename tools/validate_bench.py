@@ -16,7 +16,12 @@ Workloads, K = 4, seeded blocky softmaxes (tools/ensemble_bench.py's):
 A sample is the wall time of one case (device synchronised before and after); the routes alternate and take turns to go first, `--runs`
 samples each after one warm-up round; medians and every sample are printed.  The results of the two routes are compared before timing.
 
-    python tools/validate_bench.py [--runs 7] [--small]      one JSON line per workload, between the clocks rocm-smi reports"""
+--compress adds a second line per workload: the case's FILES (validation_raw's <case>.nii.gz, .npz and .pkl) written by the default
+route (read back, np.savez_compressed at zlib level 6 and the .nii.gz at level 2, on the calling thread) against compress="device"
+(cf_deflate + cf_crc32 on the tensors, compressed bytes read back, containers written by hand), alternating like the routes above; wall
+time of one case on one thread, and the bytes of the files.
+
+    python tools/validate_bench.py [--runs 7] [--small] [--compress]      JSON lines per workload, between the clocks rocm-smi reports"""
 import argparse
 import json
 import os
@@ -40,6 +45,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--small", action="store_true")
+    ap.add_argument("--compress", action="store_true", help="also time the case's files under both compress settings")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -89,6 +95,38 @@ def main():
                           "fused_ms": round(ma * 1e3, 3), "fused_samples_ms": [round(t * 1e3, 3) for t in ta],
                           "composed_ms": round(mb * 1e3, 3), "composed_samples_ms": [round(t * 1e3, 3) for t in tb],
                           "composed_over_fused": round(mb / ma, 2)}), flush=True)
+        if a.compress:
+            import tempfile
+            from cineflow import validate as V
+            from cineflow.nifti import read_nifti
+            props = {"itk_spacing": (1.4, 1.4, 10.0), "itk_origin": (0.0, 0.0, 0.0), "itk_direction": (1, 0, 0, 0, 1, 0, 0, 0, 1)}
+            with tempfile.TemporaryDirectory(prefix="valbench_") as tmp:
+                files = {c: os.path.join(tmp, c + ".nii.gz") for c in ("zlib", "device")}
+
+                def write_zlib():
+                    seg, probs, _hist = fused()
+                    V._write_case(files["zlib"], seg, probs, dict(props), None)
+
+                def write_device():
+                    seg, probs, hist = ops.resample_argmax(softmax, crop, lin, full_shape=full, bbox_lo=lo, want_probs=True, gt=gt)
+                    hist.cpu()
+                    packed = V._pack_case(files["device"], seg, probs, props)
+                    V._write_case(files["device"], packed[0], packed[1], dict(props), None, "device")
+
+                tz, td = [], []
+                for r in range(a.runs + 1):
+                    first, second = (write_zlib, write_device) if r % 2 == 0 else (write_device, write_zlib)
+                    x, y = sample(first), sample(second)
+                    if r:
+                        tz.append(x if first is write_zlib else y)
+                        td.append(y if first is write_zlib else x)
+                same = np.array_equal(read_nifti(files["zlib"])[0], read_nifti(files["device"])[0]) and \
+                    np.array_equal(np.load(files["zlib"][:-7] + ".npz")["softmax"], np.load(files["device"][:-7] + ".npz")["softmax"])
+                size = {c: {e: os.path.getsize(f[:-7] + e) for e in (".nii.gz", ".npz")} for c, f in files.items()}
+            print(json.dumps({"workload": name, "files": True, "contents_equal": bool(same), "zlib_ms": round(statistics.median(tz) * 1e3, 3),
+                              "zlib_samples_ms": [round(t * 1e3, 3) for t in tz], "device_ms": round(statistics.median(td) * 1e3, 3),
+                              "device_samples_ms": [round(t * 1e3, 3) for t in td], "zlib_over_device": round(statistics.median(tz) / statistics.median(td), 2),
+                              "file_bytes": size}), flush=True)
     print(json.dumps({"clocks_after": smi()}), flush=True)
 
 
