@@ -159,6 +159,14 @@ SIGNATURES = {
     "cf_deflate": [P, L, P, L, P, L, P, P],
     "cf_crc32": [P, L, P, L, P, P],
     "cf_huffman_code_lengths": [P, I, I, P, P],
+    "cf_conv2d_wgrad_splits": [I] * 7,
+    "cf_conv2d_wgrad": [P, I, P, I, P, P, P, P, L] + [I] * 7 + [P],
+    "cf_conv2d_dgrad": [P, P, P] + [I] * 13 + [P],
+    "cf_norm_act_bwd": [P] * 9 + [I, I, I, F, F, P],
+    "cf_dc_ce_loss_blocks": [L],
+    "cf_dc_ce_loss": [P] * 7 + [I, I, I, F, F, P],
+    "cf_grad_norm": [P, P, I, F, P, P, P],
+    "cf_sgd_nesterov": [P, P, P, P, I, L, P, F, F, F, I, P],
     "cf_profile_enable": [I],
     "cf_profile_reset": [],
     "cf_profile_read": [I, P, P, P],

@@ -776,6 +776,46 @@ int cf_huffman_code_lengths(const unsigned* freq, int n, int max_bits, unsigned 
 long cf_crc32_workspace_bytes(long n);
 int cf_crc32(const void* src, long n, void* ws, long ws_bytes, unsigned* crc_dev, void* stream);
 
+/* ---------------------------------------------------------------- training: nnUNetTrainerV2_noDataAugmentation on the 2-D Generic_UNet
+ * The backward of cf_conv2d, of InstanceNorm + LeakyReLU, the deep-supervision DC + CE loss (loss_functions/dice_loss.py:201-237,436-497,
+ * deep_supervision.py), clip_grad_norm_ and torch.optim.SGD(nesterov) (nnUNetTrainerV2.py:231-279).  No floating-point atomics and no
+ * workgroup that waits on another: every cross-workgroup sum is a second launch adding partials in a fixed order, so the same inputs give
+ * the same bits on every call.
+ *
+ * cf_conv2d_wgrad: dw[(C1+C2)*KH*KW][Cout] (the layout cf_conv2d reads) and, when db is not null, db[Cout], from the layer input cat[x1, x2]
+ * [B,C1|C2,H,W] and dy [B,Cout,Ho,Wo].  Kernels 3x3 pad 1 and 1x1 pad 0, stride 1 or 2.  Exact fp32 products on v_mfma_f32_32x32x2_f32; the
+ * pixel axis is cut into cf_conv2d_wgrad_splits(...) chunks (a function of the shape alone; > 0, or CF_ERR_ARG), one partial tile each in
+ * ws, added in split order in fp64.  ws: 8-byte aligned, at least round8(splits * Cin*KH*KW * Cout * 4) + splits * Cout * 8 bytes.
+ * cf_conv2d_dgrad: the adjoint of the same convolution in gather form (no zero-stuffed map at stride 2), for the input channels
+ * [ci_off, ci_off + Cn) of the layer's Cin, written to channels [dx_coff, dx_coff + Cn) of dx [B,dx_ctotal,H,W]; accumulate != 0 adds to
+ * what dx holds (a skip map's second gradient). */
+int cf_conv2d_wgrad_splits(int Cin, int Cout, int KH, int KW, int B, int Ho, int Wo);
+int cf_conv2d_wgrad(const float* x1, int C1, const float* x2, int C2, const float* dy, float* dw, float* db, void* ws, long ws_bytes, int B,
+                    int H, int W, int Cout, int KH, int KW, int stride, void* stream);
+int cf_conv2d_dgrad(const float* dy, const float* wt, float* dx, int dx_ctotal, int dx_coff, int ci_off, int Cn, int Cin, int B, int H, int W,
+                    int Cout, int KH, int KW, int stride, int accumulate, void* stream);
+/* cf_norm_act_bwd: y = leaky(gamma * xhat + beta, slope) per (b, c) plane of the raw map x [B,C,HW], ws = cf_group_norm_stats' {sum, sum of
+ * squares} with groups == C.  dy = dL/dy -> dx = dL/dx, dgamma[C], dbeta[C].  The LeakyReLU derivative is taken on the recomputed z
+ * (z > 0 ? 1 : slope).  bws: B*C*2 doubles (the planes' {sum dz, sum dz * xhat}, statistics launch); the apply launch adds them over the
+ * batch in batch order. */
+int cf_norm_act_bwd(const float* x, const float* dy, const double* ws, const float* gamma, const float* beta, float* dx, float* dgamma,
+                    float* dbeta, double* bws, int B, int C, int HW, float eps, float slope, void* stream);
+/* cf_dc_ce_loss: l = CE(mean over pixels) + 1 - mean over classes 1..K-1 of (2tp + smooth) / (2tp + fp + fn + smooth + 1e-8), tp/fp/fn summed
+ * over batch and space (batch_dice, do_bg = False) of softmax(logits [B,K,HW]); target int32 [B,HW].  *loss += weight * l (a device scalar
+ * that collects a step's outputs in call order), *loss_out = l when not null, dlogits = weight * dl/dlogits when not null.  coef: 2*K
+ * floats, part: cf_dc_ce_loss_blocks(B*HW) * (1 + 3K) doubles.  2 <= K <= 16.  Three launches, no host read. */
+int cf_dc_ce_loss_blocks(long N);
+int cf_dc_ce_loss(const float* logits, const int* target, float* dlogits, float* loss, float* loss_out, float* coef, double* part, int B, int K,
+                  int HW, float smooth, float weight, void* stream);
+/* The optimizer works on flat fp32 arenas; table (device int64 [T][3]) = {offset, size, has_grad} per tensor.
+ * cf_grad_norm: out[0] = torch's total_norm over the tensors with a gradient (the 2-norm of the per-tensor 2-norms), out[1] =
+ * min(1, max_norm / (out[0] + 1e-6)); tnorm: T floats.
+ * cf_sgd_nesterov, per element of every tensor with has_grad: g = grad * clip[1]; g += wd * p; buf = first ? g : mu * buf + g; g += mu * buf;
+ * p -= lr * g.  Tensors without a gradient keep parameter and buffer bit for bit (no weight decay either).  max_size: the largest tensor. */
+int cf_grad_norm(const float* grad, const long* table, int T, float max_norm, float* tnorm, float* out, void* stream);
+int cf_sgd_nesterov(float* param, const float* grad, float* mom, const long* table, int T, long max_size, const float* clip, float lr,
+                    float wd, float mu, int first, void* stream);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py only; no reference analogue)
  * cf_profile_enable(n): pre-create n event pairs and time every conv / CorrVolume launch with a (start, stop) pair that
  * brackets exactly that kernel on its own stream (hipExtLaunchKernelGGL); 0 disables.  Kernel ids:
